@@ -14,12 +14,16 @@ One step = one pass of the hot path over one synthetic minibatch that is already
   workload "teacher"  : BASELINE config 3 (SE-ResNet50 teacher forward, batch 128, 1 GPU)
   workload "joint"    : BASELINE config 5 shard (SE-ResNet50 fwd+bwd + student fwd+bwd, 64 / GPU)
 
-Prints ONE JSON line on rank 0 (contract in the task statement), with two extra objects:
-  roofline     -- dominant convolution kernel: algorithmic FLOPs of its launches / their summed
-                  durations, measured with HIP events on the launch stream in a second pass of
-                  the same K steps (the first pass, without events, gives `value`);
-  cpu_baseline -- the CPU oracle (oracle/, "port" of MatConvNet's CPU algorithm) timed on the
-                  host cores over a bounded sample of the same workload (rank 0, N = 1 only).
+Prints ONE JSON line on rank 0 (metric, value, unit, higher_is_better, dtype, ms_per_step, ...).  A plain run sets
+up, warms up, times the K steps and prints it; with --full the line also carries what takes runs of its own after the
+timed steps:
+  roofline        -- dominant convolution kernel: algorithmic FLOPs of its launches / their summed
+                     durations, measured with HIP events on the launch stream in a second pass of
+                     the same K steps (the first pass, without events, gives `value`);
+  cpu_baseline    -- the CPU oracle (oracle/, "port" of MatConvNet's CPU algorithm) timed on the
+                     host cores over a bounded sample of the same workload (rank 0, N = 1 only);
+  north_star_b256 -- north_star's own configuration timed in a child process (default single-GPU line only).
+Without --full, `roofline` and `cpu_baseline` are null.  --dump-outputs DIR writes what the last timed step computed.
 """
 import argparse
 import ctypes as C
@@ -39,6 +43,10 @@ PEAK_FP32_MFMA_TFLOPS = 157.3  # MI355X_MICROARCH.md: v_mfma_f32_32x32x2_f32, de
 GFLOP = {"student_fwd_bwd_300": 16.633, "resnet50_fwd": 7.712, "senet50_fwd": 7.717,
          "senet50_fwd_bwd": 22.915}
 
+# --dump-outputs: entries sampled from each flat parameter / derivative / momentum buffer (8 MB each; the joint workload's
+# six buffers stay under 64 MB in all)
+DUMP_SAMPLE = 1 << 21
+
 
 def parse():
     ap = argparse.ArgumentParser()
@@ -48,7 +56,7 @@ def parse():
     ap.add_argument("--steps", type=int, default=0,
                     help="timed steps K (exactly K are timed).  0 = as many as fill --min-seconds, estimated from the "
                          "warm-up (the clocks of this part need ~0.3 s of sustained load to settle: a 0.2 s timed "
-                         "region under-reports by 5-10 %)")
+                         "region under-reports by 5-10 %%)")
     ap.add_argument("--warmup", type=int, default=0,
                     help="untimed steps W; 0 = 10.  Untimed 'settle' steps follow until 1.5 s of load have passed")
     ap.add_argument("--min-seconds", type=float, default=2.0)
@@ -56,6 +64,13 @@ def parse():
                     choices=["distill", "student", "teacher", "joint", "cpu-teacher"])
     ap.add_argument("--per-gpu-batch", type=int, default=0)
     ap.add_argument("--width", type=int, default=300, help="spectrogram width (3 s clips)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also measure what the headline figure does not need: the roofline leg, "
+                         "the CPU baseline and the north_star pass (each can still be left out with its own option)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default="",
+                    help="write what the last timed step computed to DIR/<name>.npy (float32; rank 0): the teacher "
+                         "logits, the trained networks' output variables, and a fixed seeded sample of at most %d "
+                         "entries of their parameters, derivatives and momenta" % DUMP_SAMPLE)
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-roofline", action="store_true")
     ap.add_argument("--cpu-pairs", type=int, default=0, help="CPU baseline sample size (0 = scaled to the host: ~cores/16, "
@@ -97,9 +112,9 @@ def parse():
                          "its stream (samples are independent in test mode; a slice's activations stay in the 256 MB "
                          "Infinity Cache between layers).  0 = the whole batch in one pass")
     ap.add_argument("--north-star", type=int, default=-1,
-                    help="1: after the main measurement, time north_star's own configuration (SE-ResNet50 teacher + "
-                         "VGGVox student, 256 pairs on this GPU) for a bounded number of steps in a child process and "
-                         "attach it as `north_star_b256`.  -1 = on for the default single-GPU distill line only")
+                    help="with --full, 1: after the main measurement, time north_star's own configuration (SE-ResNet50 "
+                         "teacher + VGGVox student, 256 pairs on this GPU) for a bounded number of steps in a child "
+                         "process and attach it as `north_star_b256`.  -1 = on for the default single-GPU distill line only")
     ap.add_argument("--teacher-prefetch", type=int, default=1,
                     help="1: the teacher stream works one batch ahead of the student (needs --overlap-teacher 1)")
     ap.add_argument("--teacher-gate", default="",
@@ -146,10 +161,13 @@ def host_info():
 
 
 def launch_ranks(args):
-    """`python bench.py --gpus N` with N > 1 and no launcher around it: become `python -m torch.distributed.run
-    --nnodes=1 --nproc-per-node N ... bench.py <same arguments>` (one process per GPU, cnn_train_dag's
-    numel(opts.gpus) workers, run_distillation.m:71,77,179-181).  Refuses -- never runs fewer ranks than asked for --
-    when the node shows fewer than N devices, unless XM_DEBUG_DIST=gloo0 (functional run of the N-rank path on one GPU)."""
+    """`python bench.py --gpus N` with N > 1 and no launcher around it: run `python -m torch.distributed.run
+    --nnodes=1 --nproc-per-node N ... bench.py <same arguments>` as a child and exit with its status (one process per
+    GPU, cnn_train_dag's numel(opts.gpus) workers, run_distillation.m:71,77,179-181).  A child, not an exec: counting the
+    devices has initialised the GPU in this process, and replacing such a process's program is not safe.  Refuses --
+    never runs fewer ranks than asked for -- when the node shows fewer than N devices, unless XM_DEBUG_DIST=gloo0
+    (functional run of the N-rank path on one GPU)."""
+    import subprocess
     import socket
     import torch
     have = torch.cuda.device_count() if torch.cuda.is_available() else 0
@@ -164,7 +182,8 @@ def launch_ranks(args):
            "--master-addr", "127.0.0.1", "--master-port", str(port), os.path.abspath(__file__)] + sys.argv[1:]
     sys.stdout.flush()
     sys.stderr.flush()
-    os.execve(sys.executable, cmd, dict(os.environ))
+    rc = subprocess.call(cmd)
+    sys.exit(rc if rc >= 0 else 128 - rc)     # killed by a signal: the shell's status for it
 
 
 def main():
@@ -349,13 +368,12 @@ def main():
         if wl == "teacher":
             if mode["serial"]:
                 teacher.eval(["data", faces])
-            else:
-                frozen.logits(faces)   # fetch_emovoxceleb_imdb.m:129-130
-            return
+                return teacher.vars["prediction"].value
+            return frozen.logits(faces)   # fetch_emovoxceleb_imdb.m:129-130
         if wl == "student":
             train.train_step(student, ["data", spec, "logitTarget", lgo, "maxLabel", lab], opts, it,
                              parserv, nb * world)
-            return
+            return None
         if wl == "distill" and F > 1:
             # multi-frame pair: teacher over all nb*F frames (two stream lanes), per-pair max over the
             # window's frames (getBatchEmoVoxCeleb.m:179-185), then the student step
@@ -368,13 +386,13 @@ def main():
             tl, ml = vl.aggregate_logits(fl, first, last, "max")
             train.train_step(student, ["data", spec, "logitTarget", tl, "maxLabel", ml], opts, it,
                              parserv, nb * world)
-            return
+            return tl
         if wl == "distill" and (tstream is None or mode["serial"]):
             tl = teacher_logits(faces if tmult == 1 else faces[..., :nb])      # 1 x 1 x 8 x nb teacher logits
             ml = vl.max_label(tl)                       # getBatchEmoVoxCeleb.m:32
             train.train_step(student, ["data", spec, "logitTarget", tl, "maxLabel", ml], opts, it,
                              parserv, nb * world)
-            return
+            return tl
         if wl == "distill":
             # the frozen teacher runs on its own HIP stream; only the loss / metric layers of the
             # student wait for its logits (input_events).  With --teacher-prefetch the teacher works
@@ -429,7 +447,7 @@ def main():
                     if "ev" not in gate:
                         raise SystemExit("--teacher-gate %r: no such layer in the student's backward pass" % args.teacher_gate)
                     refill(gate["ev"])
-                    return
+                    return tl
                 if len(q) == 0:
                     refill()
             else:
@@ -438,7 +456,7 @@ def main():
                     tl, ml = tl[..., :nb], ml[..., :nb]
             train.train_step(student, ["data", spec, "logitTarget", tl, "maxLabel", ml], opts, it,
                              parserv, nb * world, input_events={"logitTarget": ev, "maxLabel": ev})
-            return
+            return tl
         # joint: teacher fwd+bwd (hard-label CE head, ferPlusZoo.m:240-249) + student distillation
         teacher.vars["prediction"].precious = True
         train.train_step(teacher, ["data", faces, "label", flab], opts, it, parserv, nb * world)
@@ -446,6 +464,7 @@ def main():
         ml = vl.max_label(tl)
         train.train_step(student, ["data", spec, "logitTarget", tl, "maxLabel", ml], opts, it, parserv,
                          nb * world)
+        return tl
 
     def barrier():
         torch.cuda.synchronize()
@@ -460,10 +479,13 @@ def main():
     inflight = []
 
     host_t = [0.0, 0]
+    last_out = {}      # --dump-outputs: the teacher logits of the latest step
 
     def throttled_step(it):
         th = time.perf_counter()
-        step(it)
+        tl = step(it)
+        if args.dump_outputs:
+            last_out["teacher_logits"] = tl
         host_t[0] += time.perf_counter() - th
         host_t[1] += 1
         ev = torch.cuda.Event()
@@ -488,6 +510,12 @@ def main():
     # warm-up: Wm steps (default 10) and at least 1.5 s -- tile tuning happens here, and the shader clock of this
     # part takes ~0.3 s of sustained load to reach its steady state (tools/power_probe.py)
     Wm = args.warmup or 10
+    # --dump-outputs: the timed region starts again from the initial parameters, at step counter W (the learning-rate
+    # schedule), so that what it computes does not depend on how many settle steps the clock needed -- two builds then
+    # compare output for output on the same seeded inputs
+    trained = {"student": student, "teacher": teacher if wl == "joint" else None}
+    initial = {k: (n._flat.val.clone(), n._flat.mom.clone()) for k, n in trained.items() if n is not None} \
+        if args.dump_outputs else None
     tw = time.perf_counter()
     for it in range(Wm):
         throttled_step(it)
@@ -516,7 +544,16 @@ def main():
         if world > 1:   # every rank must time the same K
             K = int(ctl_max(K, torch.int64))
     args.steps, args.warmup = K, Wm
-    Wm = Wm + settle   # step counter offset only
+    if initial is None:
+        Wm = Wm + settle   # step counter offset only
+    else:
+        for k, (val, mom) in initial.items():
+            net = trained[k]
+            net._flat.val.copy_(val)
+            net._flat.mom.copy_(mom)
+            net._flat.der.zero_()
+            net.paramGeneration = getattr(net, "paramGeneration", 0) + 1   # as after an update: cached views are stale
+        del initial
     # the timed region: exactly K steps between barrier + synchronize on both sides.  Window marks are HIP events
     # recorded on the main stream every K/8 steps (no host synchronisation): min / median / max window rate show
     # the spread inside the region.
@@ -560,9 +597,12 @@ def main():
                    "rates": [round(r, 1) for r in rates],
                    "note": "rank-0 stream time between event marks inside the timed region (value uses the wall clock)"}
 
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, last_out.get("teacher_logits"), trained)
+
     # ---- roofline leg: same K steps again with HIP events around every conv launch ---------
     roofline = None
-    if not args.no_roofline:
+    if args.full and not args.no_roofline:
         # serial: with the overlap streams on, kernels share the chip and a launch's duration is
         # not the kernel's own speed
         was_serial = mode["serial"]
@@ -622,7 +662,7 @@ def main():
 
     # ---- CPU baseline leg (rank 0, N = 1): the oracle on a bounded sample ------------------
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline and F == 1:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline and F == 1:
         cpu = cpu_baseline(wl, args.cpu_pairs, W)
 
     # ---- north_star configuration (bounded second pass, child process: its own nets and tuning lookups) --------
@@ -630,7 +670,7 @@ def main():
     want_ns = args.north_star == 1 or (args.north_star < 0 and wl == "distill" and world == 1 and F == 1 and
                                        not args.per_gpu_batch and args.teacher == "resnet50" and not args.serial
                                        and W == 300 and not args.teacher_batch)
-    if rank == 0 and world == 1 and want_ns:
+    if args.full and rank == 0 and world == 1 and want_ns:
         north = north_star_pass()
 
     # student FLOPs scale with the spectrogram width (16.633 GFLOP at W = 300, 22.33 at the reference's default W = 400)
@@ -701,6 +741,37 @@ def main():
             time.sleep(1.0)              # let the other ranks finish their teardown output
         sys.stdout.flush()
         print(json.dumps(out), flush=True)
+
+
+def dump_outputs(path, teacher_logits, nets):
+    """--dump-outputs: what a caller of the timed step receives after its last step, as float32 .npy files -- the teacher
+    logits, every output variable a trained network still holds (its objective), and for each trained network a fixed
+    seeded sample of the flat parameter, derivative and momentum buffers (whole when they are smaller; the same entries
+    of all three)"""
+    import torch
+    torch.cuda.synchronize()
+    os.makedirs(path, exist_ok=True)
+
+    def save(name, t):
+        np.save(os.path.join(path, name + ".npy"), np.ascontiguousarray(t.detach().float().cpu().numpy()))
+
+    if teacher_logits is not None:
+        save("teacher_logits", teacher_logits)
+    for tag, net in nets.items():
+        if net is None:
+            continue
+        for name in net.getOutputs():
+            v = net.vars[name].value
+            if isinstance(v, torch.Tensor):
+                save("%s_%s" % (tag, name), v)
+        flat = net._flat
+        n = int(flat.val.numel())
+        idx = None
+        if n > DUMP_SAMPLE:
+            idx = np.sort(np.random.default_rng(0).choice(n, DUMP_SAMPLE, replace=False))
+            idx = torch.from_numpy(idx).to(flat.val.device)
+        for what, buf in (("params", flat.val), ("grads", flat.der), ("momentum", flat.mom)):
+            save("%s_%s" % (tag, what), buf if idx is None else buf[idx])
 
 
 def north_star_pass(steps=12, warmup=3):

@@ -1,7 +1,7 @@
 """bench.py --gpus N is the command the driver runs: it must produce an N-rank line by itself, or refuse.
 
 cnn_train_dag starts numel(opts.gpus) workers (run_distillation.m:71,77,88,179-181); here one process per GPU under
-torch.distributed.run, which `bench.py --gpus N` execs itself into when no launcher is around it."""
+torch.distributed.run, which `bench.py --gpus N` starts as a child process when no launcher is around it."""
 import json
 import os
 import subprocess
@@ -71,6 +71,32 @@ def test_gpus_8_functional_run_on_one_gpu(gpu):
     assert d["control_group"] == "gloo" and d["scaling"] == "weak"
     assert d["config"]["parallelism"] == "dp8" and d["config"]["global_batch"] == 8 * d["config"]["per_gpu_batch"] == 32
     assert d["value"] > 0
+
+
+@pytest.mark.gpu
+def test_plain_line_times_exactly_k_steps_and_dumps_outputs(gpu, tmp_path):
+    """`bench.py --steps K --warmup W` without --full: exactly K timed steps, ms_per_step of one of them, none of the
+    --full legs; --dump-outputs writes the last timed step's outputs as float32 .npy files, 64 MB at most."""
+    import numpy as np
+    out = tmp_path / "dump"
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "2",
+                        "--dump-outputs", str(out)], stdout=subprocess.PIPE, stderr=subprocess.PIPE, env=_env(), timeout=900)
+    assert r.returncode == 0, r.stderr.decode()[-3000:]
+    d = json.loads([ln for ln in r.stdout.decode().splitlines() if ln.startswith("{")][-1])
+    assert d["steps"] == 3 and d["warmup"] == 2 and d["unit"] == "pairs/s" and d["dtype"] == "f32"
+    assert abs(d["ms_per_step"] * 1e-3 * d["value"] - d["config"]["global_batch"]) < 0.01 * d["config"]["global_batch"]
+    assert d["roofline"] is None and d["cpu_baseline"] is None and "north_star_b256" not in d
+    files = sorted(out.glob("*.npy"))
+    names = {f.stem for f in files}
+    assert {"teacher_logits", "student_params", "student_grads", "student_momentum"} <= names, names
+    assert sum(f.stat().st_size for f in files) <= 64 << 20
+    arrs = {f.stem: np.load(f) for f in files}
+    assert all(a.dtype == np.float32 and np.isfinite(a).all() for a in arrs.values())
+    assert arrs["teacher_logits"].size == 8 * d["config"]["per_gpu_batch"]
+    sys.path.insert(0, ROOT)
+    import bench
+    assert arrs["student_params"].size == arrs["student_grads"].size == bench.DUMP_SAMPLE
+    assert np.abs(arrs["student_grads"]).max() > 0
 
 
 def test_imdb_windows_are_time2idx_ranges():

@@ -10,18 +10,18 @@ mkdir -p $O
 B="python bench.py"
 ( time python -m pytest tests -q -m gpu --durations=8 ) 2>&1 | grep -E "passed|failed|error|^real|s call" | tail -14 > $O/pytest_gpu.txt
 python __graft_entry__.py smoke 2>&1 | grep smoke >> $O/pytest_gpu.txt
-$B                                                          | tail -1 > $O/bench_distill_n1.json
-$B --steps 20 --warmup 5 --no-cpu-baseline                  | tail -1 > $O/bench_distill_driver_flags_n1.json   # the driver's command line
-$B --serial --exec-hint 0 --no-cpu-baseline                 | tail -1 > $O/bench_distill_serial_n1.json   # the timed region's kernels on one stream
-$B --workload student --no-cpu-baseline                     | tail -1 > $O/bench_student_n1.json
-$B --workload teacher --no-cpu-baseline                     | tail -1 > $O/bench_teacher_n1.json
-$B --workload joint --no-cpu-baseline                       | tail -1 > $O/bench_joint_n1.json
-$B --teacher senet50 --no-cpu-baseline                      | tail -1 > $O/bench_distill_senet50_n1.json          # run_distillation.m:82 default teacher, F = 1
-$B --teacher senet50 --per-gpu-batch 256 --no-cpu-baseline  | tail -1 > $O/bench_distill_senet50_b256_n1.json     # north_star: batch 256 on one GPU
-$B --per-gpu-batch 256 --no-cpu-baseline                    | tail -1 > $O/bench_distill_b256_n1.json
-$B --frames 13 --no-cpu-baseline --teacher senet50          | tail -1 > $O/bench_distill_13frames_senet50_n1.json
-$B --imdb-windows 1 --no-cpu-baseline --teacher senet50     | tail -1 > $O/bench_distill_imdb_windows_senet50_n1.json
-$B --workload cpu-teacher                                   | tail -1 > $O/bench_cpu_teacher.json                  # BASELINE config 1 (host cores only)
+$B --full                                                          | tail -1 > $O/bench_distill_n1.json
+$B --full --steps 20 --warmup 5 --no-cpu-baseline                  | tail -1 > $O/bench_distill_driver_flags_n1.json   # the driver's command line
+$B --full --serial --exec-hint 0 --no-cpu-baseline                 | tail -1 > $O/bench_distill_serial_n1.json   # the timed region's kernels on one stream
+$B --full --workload student --no-cpu-baseline                     | tail -1 > $O/bench_student_n1.json
+$B --full --workload teacher --no-cpu-baseline                     | tail -1 > $O/bench_teacher_n1.json
+$B --full --workload joint --no-cpu-baseline                       | tail -1 > $O/bench_joint_n1.json
+$B --full --teacher senet50 --no-cpu-baseline                      | tail -1 > $O/bench_distill_senet50_n1.json          # run_distillation.m:82 default teacher, F = 1
+$B --full --teacher senet50 --per-gpu-batch 256 --no-cpu-baseline  | tail -1 > $O/bench_distill_senet50_b256_n1.json     # north_star: batch 256 on one GPU
+$B --full --per-gpu-batch 256 --no-cpu-baseline                    | tail -1 > $O/bench_distill_b256_n1.json
+$B --full --frames 13 --no-cpu-baseline --teacher senet50          | tail -1 > $O/bench_distill_13frames_senet50_n1.json
+$B --full --imdb-windows 1 --no-cpu-baseline --teacher senet50     | tail -1 > $O/bench_distill_imdb_windows_senet50_n1.json
+$B --workload cpu-teacher                                          | tail -1 > $O/bench_cpu_teacher.json                  # BASELINE config 1 (host cores only)
 XM_DEBUG_DIST=1 $B --parserv rccl-capi --no-cpu-baseline --no-roofline --north-star 0 | tail -1 > $O/bench_distill_capi_1rank.json
 XM_DEBUG_DIST=1 $B --parserv torch --no-cpu-baseline --no-roofline --north-star 0 | tail -1 > $O/bench_distill_torch_1rank.json
 XM_DEBUG_DIST=1 XM_PS_LATE=1 $B --parserv rccl-capi --no-cpu-baseline --no-roofline --north-star 0 | tail -1 > $O/bench_distill_capi_late_init.json   # communicator created AFTER the nets: the 12 % trap (xmodal.h CALL ORDER)
@@ -29,8 +29,8 @@ XM_DEBUG_DIST=1 XM_PS_LATE=1 $B --parserv rccl-capi --no-cpu-baseline --no-roofl
 # GPU, exchange over gloo -- a functional run of the N > 1 path; the throughput means nothing)
 XM_DEBUG_DIST=gloo0 $B --gpus 2 --steps 5 --warmup 2 --no-cpu-baseline --no-roofline 2>/dev/null | grep "^{" | tail -1 > $O/bench_distill_gpus2_gloo0.json
 # round 5: the reference's real default shape (numSeconds = 4 -> 512 x 400 spectrograms, run_distillation.m:74)
-$B --workload student --width 400 --no-cpu-baseline        | tail -1 > $O/bench_student_w400_n1.json
-$B --teacher senet50 --width 400 --no-cpu-baseline --north-star 0 | tail -1 > $O/bench_distill_senet50_w400_n1.json
+$B --full --workload student --width 400 --no-cpu-baseline        | tail -1 > $O/bench_student_w400_n1.json
+$B --full --teacher senet50 --width 400 --no-cpu-baseline --north-star 0 | tail -1 > $O/bench_distill_senet50_w400_n1.json
 # one stream + the host's XM_EXEC_SINGLE_STREAM hint (what a MATLAB / MEX host runs) at the north_star batch
 $B --serial --teacher senet50 --per-gpu-batch 256 --no-cpu-baseline --no-roofline | tail -1 > $O/bench_distill_senet50_b256_serial_hint1.json
 # (the schedule / priority / variant A/Bs of rounds 3-4 are not repeated: profiles/r03, profiles/r04 hold them; this
@@ -40,7 +40,7 @@ for n in 32 64 256; do python tools/stem_chain_bench.py $n 2>&1 | grep -v amdgpu
 XM_NO_STEM_FWD=1 XM_NO_STEM_GRAM=1 $B --teacher senet50 --per-gpu-batch 256 --no-cpu-baseline --no-roofline | tail -1 > $O/bench_distill_senet50_b256_round5_stem.json   # the other arm: round-5 stem kernels
 XM_NO_STEM_FWD=1 XM_NO_STEM_GRAM=1 $B --no-cpu-baseline --no-roofline --north-star 0 | tail -1 > $O/bench_distill_round5_stem.json
 # per-kernel durations of the serial pass (what roofline.avg_launch_ms is compared with)
-timeout 600 rocprofv3 --kernel-trace --stats -d $O/kt -o run -- $B --serial --exec-hint 0 --no-cpu-baseline --steps 60 --warmup 10 \
+timeout 600 rocprofv3 --kernel-trace --stats -d $O/kt -o run -- $B --full --serial --exec-hint 0 --no-cpu-baseline --steps 60 --warmup 10 \
     > $O/bench_under_rocprof.json 2> $O/rocprof_kt.log
 DB=$(find $O/kt -name "*.db" | head -1)
 STEPS=$(python - <<PY

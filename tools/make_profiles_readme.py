@@ -52,10 +52,10 @@ round's first collection at `e4e1a38`, 4344 in round 5's collection); every comp
 | file | what |
 |---|---|
 | `{R}/pytest_gpu.txt` | `python -m pytest tests -q -m gpu` on that box ({tests}) |
-| `{R}/bench_distill_n1.json` | `python bench.py` — default line: distillation step, 32 pairs/GPU, K chosen for a >= 2 s timed region, incl. `roofline`, `cpu_baseline`, `windows` |
+| `{R}/bench_distill_n1.json` | `python bench.py --full` — default line: distillation step, 32 pairs/GPU, K chosen for a >= 2 s timed region, incl. `roofline`, `cpu_baseline`, `windows` |
 | `{R}/bench_distill_driver_flags_n1.json` | `python bench.py --steps 20 --warmup 5` — the driver's command line (settle phase in front of the 20 timed steps: `settle_steps` in the line) |
 | `{R}/bench_distill_serial_n1.json` | `python bench.py --serial --exec-hint 0` — same step, same kernels, on ONE HIP stream (no overlap): the mode the roofline leg and the profiles below use |
-| `{R}/bench_under_rocprof.json`, `{R}/kernel_stats.txt` | `rocprofv3 --kernel-trace --stats -- python bench.py --serial --exec-hint 0 --no-cpu-baseline --steps 60 --warmup 10` and its per-kernel summary (`tools/prof_summary.py`): the kernels of the timed region, one after the other |
+| `{R}/bench_under_rocprof.json`, `{R}/kernel_stats.txt` | `rocprofv3 --kernel-trace --stats -- python bench.py --full --serial --exec-hint 0 --no-cpu-baseline --steps 60 --warmup 10` and its per-kernel summary (`tools/prof_summary.py`): the kernels of the timed region, one after the other |
 | `{R}/bench_student_n1.json`, `bench_teacher_n1.json`, `bench_joint_n1.json` | BASELINE configs 2, 3 and the config-5 shard (`--workload student|teacher|joint`) |
 | `{R}/kernel_stats_student.txt`, `kernel_stats_teacher.txt`, `kernel_stats_joint.txt`, `kernel_stats_senet50.txt`, `kernel_stats_b256.txt` | the same rocprofv3 per-kernel summary (serial mode, 20 timed steps) for configs 2, 3, the config-5 shard, the SE-ResNet50 distillation step and the batch-256 step |
 | `{R}/bench_distill_senet50_n1.json` | the reference's default teacher (`run_distillation.m:82`): `--teacher senet50`, one face per pair |
@@ -126,8 +126,8 @@ changed); config 3 {te['value']} img/s (no kernel of that path changed).
 
 ## How the numbers were taken
 ```
-python bench.py                                           # value, roofline (2nd, serial pass with HIP events), cpu_baseline
-rocprofv3 --kernel-trace --stats -d ... -- python bench.py --serial --exec-hint 0 --no-cpu-baseline --steps 60 --warmup 10
+python bench.py --full                                    # value, roofline (2nd, serial pass with HIP events), cpu_baseline
+rocprofv3 --kernel-trace --stats -d ... -- python bench.py --full --serial --exec-hint 0 --no-cpu-baseline --steps 60 --warmup 10
 rocprofv3 --kernel-trace --pmc SQ_WAVE_CYCLES SQ_BUSY_CU_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY \\
           SQ_VALU_MFMA_BUSY_CYCLES SQ_INSTS_VALU SQ_INSTS_MFMA --output-format csv -- python bench.py --serial --steps 3 ...
 rocprofv3 --kernel-trace --pmc FETCH_SIZE  ...            # separate pass
