@@ -53,7 +53,7 @@ enum { XM_FUSE_RELU = 1, XM_BN_BATCH_MOMENTS = 2, XM_FUSE_SIGMOID = 4 };
 
 /* ABI revision: 100 = round 1; 101 = xm_nnbnorm_relu_pool_backward gained `y_pool`, exchange entry points return
  * XM_EINVAL without a communicator; 102 = + xm_nnconv_forward_moments, xm_nnbnorm_backward_dxsum, xm_nnconv_forward_gated;
- * 103 = + xm_nnpool_global_avg_backward_accum; 104 = + xm_nnconv_backward_filter_bnrelupool, xm_nndropout_forward / _apply, xm_resample, xm_se_tail_backward_reduce / _apply, xm_se_squeeze_bn, xm_scale_axpy_bn; 105 = + xm_set_exec_hint / xm_get_exec_hint; 106 = + xm_nnconv_bnorm_relu_pool_forward, xm_stem_gram, xm_stem_gram_moments, xm_nnconv_backward_filter_bnrelupool_gram (additions never change the revision's meaning for older bindings).  A binding checks xm_version() >= the revision it was written against. */
+ * 103 = + xm_nnpool_global_avg_backward_accum; 104 = + xm_nnconv_backward_filter_bnrelupool, xm_nndropout_forward / _apply, xm_resample, xm_se_tail_backward_reduce / _apply, xm_se_squeeze_bn, xm_scale_axpy_bn; 105 = + xm_set_exec_hint / xm_get_exec_hint; 106 = + xm_nnconv_bnorm_relu_pool_forward, xm_stem_gram, xm_stem_gram_moments, xm_nnconv_backward_filter_bnrelupool_gram; 107 = + xm_nnaffinegrid / _backward, xm_nnbilinearsampler / _backward, xm_ferplus_batch (additions never change the revision's meaning for older bindings).  A binding checks xm_version() >= the revision it was written against. */
 int xm_version(void);
 const char *xm_last_error(void);
 /* Device memory for hosts that have no device-array type of their own (MATLAB's gpuArray is CUDA-only: on an
@@ -73,7 +73,10 @@ int xm_device_synchronize(void);
  * written by xm_tune_save.  With the shipped table the kernel and tile choice -- hence the summation order and the bits of
  * every result -- is a function of (shape, table, execution hint below) and of NOTHING else: the same in every process,
  * whatever it called before, on whatever streams; known shapes cost no timed launches on first use
- * (external/compute_audio_feats.m:116-136 walks ten width buckets).  XM_AUTOTUNE=0 uses the analytic model instead. */
+ * (external/compute_audio_feats.m:116-136 walks ten width buckets).  XM_AUTOTUNE=0 uses the analytic model instead.
+ * One exception to "the same bits": the dX of xm_nnbilinearsampler_backward is scattered with float atomics (overlapping
+ * grids add into the same pixels), so its last bits depend on the order the adds arrive in; every other output of the
+ * library, the sampler's dGrid included, is a function of the inputs alone. */
 /* Execution hint, an explicit statement of the host about HOW it calls (process-wide; default 0):
  *   XM_EXEC_SINGLE_STREAM  every operator call of this process arrives on ONE stream (MatConvNet's own sequence:
  *                          cnn_train_dag -> net.eval -> vl_nn* one after the other, run_distillation.m:170-182; what the
@@ -444,6 +447,45 @@ int xm_normalize_face(const float *rgb, int H, int W, int N, const float *avg3, 
  * src: Hin x Win x 3 x N with values 0..255 (single holding the decoded uint8); avg3: HOST pointer. */
 int xm_crop_resize_face(const float *src, int Hin, int Win, int N, float crop, int Ho, int Wo,
                         const float *avg3, float *out, void *stream);
+
+/* ---- vl_nnaffinegrid / vl_nnbilinearsampler  (MatConvNet; getBatchFerPlus, teacher/ferplus_baselines.m:209-213) ------
+ * PARITY UNPINNED: MatConvNet is not available to compare against; the formulas below restate its documented
+ * behaviour.  FINITE INPUTS: results are specified for finite A, X, GRID, DY; a non-finite grid
+ * coordinate samples nothing (output 0), as a coordinate far outside the image does.
+ *
+ * GRID = vl_nnaffinegrid(A, [Ho Wo]):  A is 1 x 1 x 6 x N (c1..c6 per sample), GRID is 2 x Ho x Wo x N with
+ *   GRID(1, i, j, n) = c1 y_i + c3 x_j + c5  (the Y coordinate),  GRID(2, i, j, n) = c2 y_i + c4 x_j + c6  (X),
+ *   y = linspace(-1, 1, Ho), x = linspace(-1, 1, Wo), linspace(-1, 1, 1) = 1 as in MATLAB: A reshaped column-major to
+ *   2 x 3 is [c1 c3 c5; c2 c4 c6] applied to (y, x, 1).
+ * DA = vl_nnaffinegrid(A, [Ho Wo], DGRID): dA (1 x 1 x 6 x N) = sums over Ho x Wo of [dG1 y, dG2 y, dG1 x, dG2 x, dG1,
+ *   dG2]; wave-shuffle reductions in a fixed order, no atomics (fixed bits).  A itself is not read. */
+int xm_nnaffinegrid(const float *A, int N, int Ho, int Wo, float *grid, void *stream);
+int xm_nnaffinegrid_backward(const float *dgrid, int N, int Ho, int Wo, float *dA, void *stream);
+/* Y = vl_nnbilinearsampler(X, GRID):  X is H x W x C x N, GRID 2 x Ho x Wo x No with No = k N (k >= 1 integer, else
+ * XM_EINVAL), Y is Ho x Wo x C x No; output image m (0-based) reads input image floor(m / k).
+ *   py = (gy + 1)(H - 1) / 2, px = (gx + 1)(W - 1) / 2 (in double from the fp32 grid value; a position within
+ *   (H - 1) 2^-25 resp. (W - 1) 2^-25 of an integer is that integer, so that an identity grid returns X bit for bit);
+ *   sy = floor(py), sx = floor(px), wy = py - sy, wx = px - sx;
+ *   Y = sum over a, b in {0, 1} of (a ? wy : 1 - wy)(b ? wx : 1 - wx) X(sy + a, sx + b); a tap outside the image adds 0
+ *   (zero padding, no clamping).  The grid is read once per output pixel for all C channels.
+ * [DX, DGRID] = vl_nnbilinearsampler(X, GRID, DY):  either output may be NULL (not computed).
+ *   DX (H x W x C x N, overwritten) receives w DY in each tap through no-return float atomic adds: overlapping grids add
+ *   into the same pixels, so THE LAST BITS OF DX DEPEND ON SCHEDULING (see the determinism note of the tile table).
+ *   DGRID (2 x Ho x Wo x No) is the derivative of the formula above with sy, sx held fixed (the one-sided derivative
+ *   from above at integer coordinates), summed over C inside one thread: fixed bits. */
+int xm_nnbilinearsampler(const float *x, int H, int W, int C, int N, const float *grid, int Ho, int Wo, int No,
+                         float *y, void *stream);
+int xm_nnbilinearsampler_backward(const float *x, int H, int W, int C, int N, const float *grid, int Ho, int Wo,
+                                  int No, const float *dy, float *dx, float *dgrid, void *stream);
+/* Extension: the whole data path of getBatchFerPlus (ferplus_baselines.m:182-213) in one launch -- grey H x W x 1 x N
+ * (single, 0..255) -> fliplr where flip[n] != 0 (device int array of N, NULL = none) -> replicate x3 minus averageImage
+ * (avg3: HOST pointer, as xm_crop_resize_face) -> affine grid of A (device, 1 x 1 x 6 x N) at Ho x Wo -> bilinear
+ * sampler; out is Ho x Wo x 3 x N.  The normalisation comes BEFORE the zero padding, as in the reference: from the
+ * in-bounds taps S = sum w g and Omega = sum w, out_c = S - avg_c Omega.  Neither the RGB tensor nor the grid is ever
+ * written.  Equal to xm_nnaffinegrid + xm_nnbilinearsampler on the normalised image up to fp32 rounding (the grid
+ * coordinates are the same bits). */
+int xm_ferplus_batch(const float *grey, int H, int W, int N, const int *flip, const float *A, int Ho, int Wo,
+                     const float *avg3, float *out, void *stream);
 
 #ifdef __cplusplus
 }

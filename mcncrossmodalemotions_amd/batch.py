@@ -13,6 +13,8 @@ shapes the tensors the hot path consumes, fed from seeded synthetic sources:
     additive noise ('N')         getBatchEmoVoxCeleb.m:123-135      -> HIP xm_scale_axpy (z + Nratio * y)
     target selection + maxLabel  getBatchEmoVoxCeleb.m:30-32
     face normalisation           fetch_emovoxceleb_imdb.m:176-193   -> HIP xm_normalize_face
+    FER+ batch (getBatchFerPlus) ferplus_baselines.m:153-268        -> HIP xm_ferplus_batch (grey -> flip -> x3 minus
+                                                                       averageImage -> affine grid -> bilinear sampler)
 """
 import math
 
@@ -310,3 +312,167 @@ def getImageBatch(num, imageSize=(224, 224), averageImage=(131.0912, 103.8827, 9
     rgb = torch.randint(0, 256, (num, 3, imageSize[1], imageSize[0]), generator=g, device=device)
     rgb = rgb.to(torch.float32).permute(3, 2, 1, 0)
     return vl.normalize_face(rgb, averageImage)
+
+
+# ---------------------------------------------------------------------------------------------
+# FER+ (teacher training): getBatchFerPlus / computeAugs of teacher/ferplus_baselines.m
+# ---------------------------------------------------------------------------------------------
+FERPLUS_CLASSES = ["neutral", "happiness", "surprise", "sadness", "anger", "disgust", "fear", "contempt", "unknown",
+                   "NF"]
+
+
+def ferplus_num_classes(dataType):
+    """ferplus_baselines.m:88-93,160-165: 'CNTK' / 'clean' -> 8, 'full' -> 10."""
+    if dataType in ("CNTK", "clean"):
+        return 8
+    if dataType == "full":
+        return 10
+    raise ValueError("%s uknown number of classes" % dataType)
+
+
+class SyntheticFerPlusImdb:
+    """Stand-in for the FER+ imdb (getFerPlusImdb is not part of the reference and the FER2013 / FER+ CSVs cannot be
+    read here): seeded 48 x 48 greyscale faces (single, integer values 0..255, smooth blobs on a noisy background),
+    ten vote columns per image in the FER+ order (the eight emotions, 'unknown', 'NF'; ten annotators, at least one
+    vote among the first eight), hardLabels = 1-based argmax over the eight emotions, set 1 / 2 / 3 = train / val / test.
+    Fields as the reference reads them: images.data (H x W x 1 x N), images.votes (N x 10), images.hardLabels (1 x N),
+    images.set (N), meta.classes."""
+
+    def __init__(self, num_images=256, seed=0, size=48, val_fraction=0.25, test_fraction=0.0):
+        rng = np.random.default_rng(seed)
+        N = int(num_images)
+        yy, xx = np.meshgrid(np.arange(size), np.arange(size), indexing="ij")
+        data = np.zeros((size, size, 1, N), np.float32, order="F")
+        for n in range(N):
+            cy, cx = rng.uniform(0.3, 0.7, 2) * size
+            r = rng.uniform(0.15, 0.35) * size
+            face = 200 * np.exp(-((yy - cy) ** 2 + (xx - cx) ** 2) / (2 * r * r)) + rng.normal(40, 15, (size, size))
+            data[:, :, 0, n] = np.clip(np.round(face), 0, 255)
+        votes = np.zeros((N, 10))
+        for n in range(N):
+            votes[n] = rng.multinomial(10, rng.dirichlet(np.full(10, 0.3)))
+            if votes[n, :8].sum() == 0:
+                votes[n, rng.integers(0, 8)] += 1
+        sets = np.ones(N, int)
+        perm = rng.permutation(N)
+        nv, nt = int(round(N * val_fraction)), int(round(N * test_fraction))
+        sets[perm[:nv]] = 2
+        sets[perm[nv:nv + nt]] = 3
+        self.images = {"data": data, "votes": votes, "set": sets,
+                       "hardLabels": (votes[:, :8].argmax(1) + 1).reshape(1, N).astype(np.float64)}
+        self.meta = {"classes": list(FERPLUS_CLASSES)}
+        self._dev = {}
+
+    @property
+    def set(self):
+        return self.images["set"]
+
+    def device_arrays(self, numClasses, device):
+        """device-resident copies, made once: the images (storage N x 1 x W x H: the MATLAB array H x W x 1 x N),
+        the vote distributions over the first numClasses columns (N x numClasses) and the hard labels (N)."""
+        key = (int(numClasses), str(device))
+        if key not in self._dev:
+            d = self.images["data"]
+            data = torch.from_numpy(np.ascontiguousarray(d.transpose(3, 2, 1, 0))).to(device)
+            v = self.images["votes"][:, :numClasses]
+            probs = torch.from_numpy((v / v.sum(1, keepdims=True)).astype(np.float32)).to(device)   # :167-168
+            hard = torch.from_numpy(self.images["hardLabels"].reshape(-1).astype(np.float32)).to(device)
+            self._dev[key] = (data, probs, hard)
+        return self._dev[key]
+
+
+def zoomOut(zoomScale, minYX):
+    """ferplus_baselines.m:271-278 (the whole 3 x 3 matrix is scaled, its last row included)."""
+    zs = (zoomScale - 1) / zoomScale
+    tx = zs - 2 * zs * minYX[1]
+    ty = zs - 2 * zs * minYX[0]
+    return np.array([[1, 0, tx], [0, 1, ty], [0, 0, 1]], np.float64) * zoomScale
+
+
+def rotate(theta):
+    """ferplus_baselines.m:281-286."""
+    return np.array([[np.cos(theta), -np.sin(theta), 0], [np.sin(theta), np.cos(theta), 0], [0, 0, 1]])
+
+
+def skew(s1, s2):
+    """ferplus_baselines.m:289-294."""
+    return np.array([[1, s1, 0], [s2, 1, 0], [0, 0, 1]], np.float64)
+
+
+def _randi(rng, imax, shape):
+    """randi(imax, shape...) drawn in MATLAB's column-major order from `rng`."""
+    return rng.integers(1, int(imax) + 1, size=int(np.prod(shape))).reshape(shape, order="F")
+
+
+def computeAugs(batchSize, rng):
+    """affs = computeAugs(batchSize) -- ferplus_baselines.m:224-268: 3 x 3 x B affine matrices acting on (x, y, 1),
+    zoom * rotate * skew, then about half of them replaced by eye(3).  Draw order as the reference: minXY =
+    randi(maxOffset, B, 2) (maxOffset = round(224 / 25) = 9), zoomSc = 0.96 + 0.08 rand(1, B), thetas = randi(3, B) --
+    a B x B matrix of which the first B values (column-major) are used, the rest only advances the stream --,
+    skews = randi(3, B, 2), drop = rand(1, B) > 0.5.  `rng` is a numpy Generator standing in for MATLAB's."""
+    B = int(batchSize)
+    ratio = 1 / 25
+    maxOffset = int(np.floor(ratio * 224 + 0.5))                     # round(): 8.96 -> 9
+    minXY = _randi(rng, maxOffset, (B, 2))
+    zoomSc = (1 - ratio) + (ratio * 2) * rng.random(B)
+    vals = [-np.pi / 18, 0, np.pi / 18]
+    thetas = _randi(rng, 3, (B, B)).reshape(-1, order="F")[:B]       # randi(3, batchSize): B x B
+    svals = [-0.1, 0, 0.1]
+    skews = _randi(rng, 3, (B, 2))
+    affs = np.zeros((3, 3, B))
+    for ii in range(B):
+        affs[:, :, ii] = (zoomOut(zoomSc[ii], minXY[ii]) @ rotate(vals[thetas[ii] - 1]) @
+                          skew(svals[skews[ii, 0] - 1], svals[skews[ii, 1] - 1]))
+    drop = np.nonzero(rng.random(B) > 0.5)[0]
+    for ii in drop:
+        affs[:, :, ii] = np.eye(3)
+    return affs
+
+
+# tmp([5 4 2 1 8 7]) of ferplus_baselines.m:207, 0-based column-major positions of the 3 x 3 matrix
+AFFINE_REORDER = [4, 3, 1, 0, 7, 6]
+
+
+def affine_params(aff):
+    """the six vl_nnaffinegrid parameters of a 3 x 3 matrix acting on (x, y, 1): tmp([5 4 2 1 8 7])
+    = [a22 a12 a21 a11 a23 a13] -> grid Y = a22 y + a21 x + a23 = y', grid X = a12 y + a11 x + a13 = x'."""
+    return np.asarray(aff, np.float64).reshape(-1, order="F")[AFFINE_REORDER]
+
+
+def getBatchFerPlus(imdb, batch, dataType="CNTK", lossType="distributions", dataAug=True, imageSize=(224, 224),
+                    averageImage=(131.0912, 103.8827, 91.4953), rng=None, device=None):
+    """inputs = getBatchFerPlus(imdb, batch, opts, dag) -- ferplus_baselines.m:153-221.  Vote distributions over the
+    first numClasses columns (1 x 1 x C x N), the single-set assertion, a flip draw per sample in train mode BEFORE
+    computeAugs (which is always called: it advances the stream in validation too), identity transforms when dataAug
+    is off or outside the training set, the [5 4 2 1 8 7] reorder, and the whole image path -- grey -> flip -> x3 minus
+    averageImage -> affine grid -> bilinear sampler at imageSize -- in ONE xm_ferplus_batch launch.  The host draws the
+    numbers and uploads two small arrays (int32 [batch indices | flips], float transforms); images, vote
+    distributions and hard labels are gathered from the imdb's device-resident copies.
+    Returns ['data', data, 'label', votes, 'hardlabel', hardlabel] ('distributions') or ['data', data, 'label',
+    hardlabel] ('softmaxlog')."""
+    rng = rng or np.random.default_rng(0)
+    batch = [int(b) for b in batch]
+    N = len(batch)
+    numClasses = ferplus_num_classes(dataType)
+    setIdx = np.unique(np.asarray(imdb.images["set"])[batch])
+    assert setIdx.size == 1, "training/val/test sets have gotten mixed together!"     # :173-174
+    device = device or torch.device("cuda", torch.cuda.current_device())
+    trainMode = bool(setIdx[0] == 1)
+    flips = (rng.random(N) > 0.5).astype(np.int32) if trainMode else np.zeros(N, np.int32)   # :180-186
+    augs = computeAugs(N, rng)                                                                # :189
+    transforms = np.zeros((6, N), np.float32)
+    for i in range(N):
+        transforms[:, i] = affine_params(augs[:, :, i] if (dataAug and trainMode) else np.eye(3))   # :190-207
+    data_all, probs_all, hard_all = imdb.device_arrays(numClasses, device)
+    ints = torch.from_numpy(np.concatenate([np.asarray(batch, np.int32), flips])).to(device)
+    tr = torch.from_numpy(transforms.reshape(-1, order="F").copy()).to(device)
+    idx = ints[:N].long()
+    grey = data_all.index_select(0, idx).permute(3, 2, 1, 0)                     # H x W x 1 x N
+    data = vl.ferplus_batch(grey, tr.reshape(N, 6, 1, 1).permute(3, 2, 1, 0), ints[N:], averageImage, imageSize)
+    hardlabel = hard_all.index_select(0, idx).reshape(N, 1, 1, 1).permute(3, 2, 1, 0)
+    if lossType == "distributions":
+        votes = probs_all.index_select(0, idx).reshape(N, numClasses, 1, 1).permute(3, 2, 1, 0)
+        return ["data", data, "label", votes, "hardlabel", hardlabel]
+    if lossType == "softmaxlog":
+        return ["data", data, "label", hardlabel]
+    raise ValueError("unknown loss type: %s" % lossType)

@@ -873,3 +873,77 @@ def normalize_face(rgb, average_image):
     out = mat_empty(H, W, 3, N, device=rgb.device)
     _lib.check(_L().xm_normalize_face(_ptr(rgb), H, W, N, avg, _ptr(out), _stream()))
     return out
+
+
+# --------------------------------------------------------------------------------------------
+# vl_nnaffinegrid / vl_nnbilinearsampler and the fused FER+ batch (getBatchFerPlus, ferplus_baselines.m:153-221)
+# --------------------------------------------------------------------------------------------
+
+
+def vl_nnaffinegrid(A, sz, dzdy=None):
+    """GRID = vl_nnaffinegrid(A, [Ho Wo]) / DA = vl_nnaffinegrid(A, [Ho Wo], DZDY).  A is 1 x 1 x 6 x N, GRID
+    2 x Ho x Wo x N: GRID(1) = c1 y + c3 x + c5, GRID(2) = c2 y + c4 x + c6 over linspace(-1, 1, Ho / Wo)
+    (include/xmodal.h; parity with MatConvNet unpinned)."""
+    A = _chk(A, "A")
+    Ho, Wo = _pair(sz, "SZ")
+    N = int(A.numel()) // 6
+    if A.numel() != 6 * N or N < 1:
+        raise ValueError("vl_nnaffinegrid: A must be 1 x 1 x 6 x N")
+    if dzdy is not None:
+        d = _chk(dzdy, "DZDY")
+        if d.numel() != 2 * Ho * Wo * N:
+            raise ValueError("vl_nnaffinegrid: DZDY must be 2 x Ho x Wo x N")
+        dA = mat_empty(1, 1, 6, N, device=A.device)
+        _lib.check(_L().xm_nnaffinegrid_backward(_ptr(d), N, Ho, Wo, _ptr(dA), _stream()))
+        return dA
+    grid = mat_empty(2, Ho, Wo, N, device=A.device)
+    _lib.check(_L().xm_nnaffinegrid(_ptr(A), N, Ho, Wo, _ptr(grid), _stream()))
+    return grid
+
+
+def vl_nnbilinearsampler(X, grid, dzdy=None):
+    """Y = vl_nnbilinearsampler(X, GRID) / [DX, DGRID] = vl_nnbilinearsampler(X, GRID, DZDY).  X is H x W x C x N,
+    GRID 2 x Ho x Wo x No with No a multiple of N (output image m reads input image m // (No / N)); zero padding.
+    DX is accumulated with float atomics (its last bits depend on scheduling); DGRID has fixed bits."""
+    X, grid = _chk(X, "X"), _chk(grid, "GRID")
+    H, W, Cc, N = _shape4(X)
+    two, Ho, Wo, No = _shape4(grid)
+    if two != 2:
+        raise ValueError("vl_nnbilinearsampler: GRID must be 2 x Ho x Wo x No")
+    if No % N:
+        raise ValueError("vl_nnbilinearsampler: %d grids for %d images (must be a multiple)" % (No, N))
+    if dzdy is not None:
+        d = _chk(dzdy, "DZDY")
+        if tuple(_shape4(d)) != (Ho, Wo, Cc, No):
+            raise ValueError("vl_nnbilinearsampler: DZDY must be Ho x Wo x C x No")
+        dX = mat_empty(H, W, Cc, N, device=X.device)
+        dG = mat_empty(2, Ho, Wo, No, device=X.device)
+        _lib.check(_L().xm_nnbilinearsampler_backward(_ptr(X), H, W, Cc, N, _ptr(grid), Ho, Wo, No, _ptr(d), _ptr(dX),
+                                                      _ptr(dG), _stream()))
+        return dX, dG
+    Y = mat_empty(Ho, Wo, Cc, No, device=X.device)
+    _lib.check(_L().xm_nnbilinearsampler(_ptr(X), H, W, Cc, N, _ptr(grid), Ho, Wo, No, _ptr(Y), _stream()))
+    return Y
+
+
+def ferplus_batch(grey, transforms, flips, average_image, image_size=(224, 224)):
+    """the data path of getBatchFerPlus (ferplus_baselines.m:182-213) in one kernel: grey H x W x 1 x N (0..255) ->
+    fliplr where flips[n] -> x3 minus averageImage -> affine grid of `transforms` (1 x 1 x 6 x N) -> bilinear sampler
+    at image_size.  `flips`: int32 device tensor of N entries, or None.  Returns Ho x Wo x 3 x N."""
+    grey, transforms = _chk(grey, "GREY"), _chk(transforms, "TRANSFORMS")
+    H, W, c1, N = _shape4(grey)
+    if c1 != 1:
+        raise ValueError("ferplus_batch: expected H x W x 1 x N greyscale images")
+    if transforms.numel() != 6 * N:
+        raise ValueError("ferplus_batch: TRANSFORMS must be 1 x 1 x 6 x N")
+    if flips is not None:
+        if not (isinstance(flips, torch.Tensor) and flips.is_cuda):
+            raise RuntimeError("FLIPS: tensor is not on the GPU; this build has no CPU path")
+        if flips.dtype != torch.int32 or flips.numel() != N or not flips.is_contiguous():
+            raise ValueError("ferplus_batch: FLIPS must be a contiguous int32 tensor of N entries")
+    Ho, Wo = _pair(image_size, "IMAGE_SIZE")
+    avg = (C.c_float * 3)(*[float(v) for v in np.ravel(average_image)[:3]])
+    out = mat_empty(Ho, Wo, 3, N, device=grey.device)
+    _lib.check(_L().xm_ferplus_batch(_ptr(grey), H, W, N, _ptr(flips), _ptr(transforms), Ho, Wo, avg, _ptr(out),
+                                     _stream()))
+    return out

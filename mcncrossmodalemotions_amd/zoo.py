@@ -179,9 +179,38 @@ def calibrate_moments(net, inputs):
 # ---------------------------------------------------------------------------------------------
 # ferPlusZoo (teacher)  -- teacher/ferPlusZoo.m:93-114,127-133
 # ---------------------------------------------------------------------------------------------
-def ferPlusZoo(modelName, seed=100, width_mult=1.0, blocks=(3, 4, 6, 3)):
-    """dag = ferPlusZoo(modelName): pretrained branch only (the non-pretrained branch of the
-    reference is unreachable as shipped -- SURVEY Appendix C)."""
+FERPLUS_TRAINABLE = {"resnet50_ft-dag": False, "senet50_ft-dag": True}     # VGGFace2 imports -> SE or not
+
+
+def ferPlusZoo(modelName, seed=100, width_mult=1.0, blocks=(3, 4, 6, 3), *, useBnorm=False, finetuneLR=1,
+               dropoutRate=0, lossType="distributions", numOutputs=7):
+    """dag = ferPlusZoo(modelName, 'useBnorm', .., 'finetuneLR', .., 'dropoutRate', .., 'lossType', ..,
+    'numOutputs', ..) -- teacher/ferPlusZoo.m (option defaults :30-36).
+
+    'resnet50-ferplus' / 'senet50-ferplus': the pretrained FER+ teachers, returned as loaded (:93-114, :127-133).
+    'resnet50_ft-dag' / 'senet50_ft-dag': the VGGFace2 networks configured for FER+ training (:116-124), as
+    ferplus_baselines.m calls it.  That branch is broken as shipped; what is built is its evident
+    intent, and these are the deviations:
+      * `numOutputs` is undefined at :116 -- opts.numOutputs is used;
+      * `opts.dropoout` at :119 does not exist (opts.dropooutRate is a typo'd second default) -- opts.dropoutRate is used;
+      * `insertBNLayers` (:122) is not in the reference; both architectures carry batch norm after every convolution
+        already, so useBnorm changes nothing (as ferplus_baselines.m:14-17 documents for such models);
+      * fixInputVarnames (:127-133) renames the input to 'input' although getBatchFerPlus feeds 'data'; it is 'data'
+        here, as in the pretrained branch;
+      * MATLAB's addLayer APPENDS the dropout layers, so layers(1:end-2) at :236 would be every layer but the two
+        dropouts and the classifier would get finetuneLR too; the dropouts sit behind their convolutions here and
+        layers(1:end-2) are all layers but pool5 and the classifier, which keeps its own rates ("except those used in
+        the classifier", :12-14);
+      * with lossType 'softmaxlog' getBatchFerPlus provides no 'hardlabel' (:215-220): the classerror head reads
+        'label' then.
+    Weights are seeded synthetic ones, as elsewhere (the VGGFace2 .mat files are not available)."""
+    if modelName in FERPLUS_TRAINABLE:
+        net = resnet50(FERPLUS_TRAINABLE[modelName], numOutputs, width_mult, blocks)
+        synthetic_pretrained(net, seed)
+        prepareFromDagNN(net, numOutputs, seed)                                    # :116
+        configureForClassification(net, finetuneLR, dropoutRate, lossType)         # :118-119
+        net.meta["modelName"] = modelName
+        return net
     if modelName == "resnet50-ferplus":
         net = resnet50(False, 8, width_mult, blocks)
     elif modelName == "senet50-ferplus":
@@ -194,6 +223,29 @@ def ferPlusZoo(modelName, seed=100, width_mult=1.0, blocks=(3, 4, 6, 3)):
         if old in net.vars:
             net.renameVar(old, "data")
     net.meta["modelName"] = modelName
+    return net
+
+
+def configureForClassification(net, finetuneLR, dropout, lossType):
+    """ferPlusZoo.m:202-263: dropout behind convLayers(end-2:end-1) when dropout > 0 and the net has none, finetuneLR
+    on every parameter of layers(1:end-2) (BatchNorm moments included, as `deal` sets them all), then the loss heads
+    {'prediction', 'label'} -> 'objective' (vl_nnsoftmaxceloss with T = 1 on probability targets for 'distributions',
+    vl_nnloss softmaxlog otherwise) and classerror {'prediction', 'hardlabel'} -> 'classerror', and meta.classes."""
+    if dropout and dropout > 0 and not any(isinstance(l.block, dagnn.DropOut) for l in net.layers):
+        _dropout_after_last_convs(net, float(dropout))
+    for l in net.layers[:-2]:
+        for pname in l.params:
+            net.params[pname].learningRate = float(finetuneLR)
+    if lossType == "softmaxlog":
+        layer, hard = dagnn.Loss("softmaxlog"), "label"
+    elif lossType == "distributions":
+        layer, hard = dagnn.SoftmaxCELoss(temperature=1, logitTargets=False), "hardlabel"
+    else:
+        raise ValueError("unrecognised loss: %s" % lossType)
+    net.addLayer("loss", layer, ["prediction", "label"], "objective")
+    net.addLayer("classerror", dagnn.Loss("classerror"), ["prediction", hard], "classerror")
+    net.meta["classes"] = {"name": list(EMOTIONS), "description": list(EMOTIONS)}
+    net._flat = None
     return net
 
 
@@ -279,14 +331,20 @@ def insert_dropout(net, prev, nxt, rate):
     return net
 
 
+def _dropout_after_last_convs(net, rate):
+    """emoVoxZoo.m:116-135 / ferPlusZoo.m:213-232: a dropout layer behind each of convLayers(end-2:end-1)."""
+    convs = [l for l in net.layers if isinstance(l.block, dagnn.Conv)]
+    for sel in convs[-3:-1]:                      # convLayers(end-2:end-1): "reduce aggression"
+        nxt = [l.name for l in net.layers if sel.outputs[0] in l.inputs]
+        assert nxt, "target layer was not found"
+        insert_dropout(net, sel.name, nxt[0], rate)
+    return net
+
+
 def configureForRegression(net, lossType, numOutputs, dropout=0):
     """emoVoxZoo.m:105-177 (the dropout layers of :116-135 first, then the loss heads)."""
     if dropout and dropout > 0 and not any(isinstance(l.block, dagnn.DropOut) for l in net.layers):
-        convs = [l for l in net.layers if isinstance(l.block, dagnn.Conv)]
-        for sel in convs[-3:-1]:                      # convLayers(end-2:end-1): "reduce aggression" (:120)
-            nxt = [l.name for l in net.layers if sel.outputs[0] in l.inputs]
-            assert nxt, "target layer was not found"  # :132
-            insert_dropout(net, sel.name, nxt[0], float(dropout))
+        _dropout_after_last_convs(net, float(dropout))
     if lossType == "softmaxlog":
         layer, inputs = dagnn.Loss("softmaxlog"), ["prediction", "maxLabel"]
     elif lossType == "hot-cross-ent":
