@@ -46,14 +46,16 @@ enum {
 
 enum { XM_POOL_MAX = 0, XM_POOL_AVG = 1 };
 enum { XM_LOSS_SOFTMAXLOG = 0, XM_LOSS_CLASSERROR = 1 };
-enum { XM_AGG_MAX = 0, XM_AGG_MEAN = 1 };
+enum { XM_AGG_MAX = 0, XM_AGG_MEAN = 1, XM_AGG_PEAK = 2 };
+/* xm_mnrfit status per problem */
+enum { XM_MNR_CONVERGED = 0, XM_MNR_ITERLIMIT = 1, XM_MNR_NOTPD = 2, XM_MNR_BADINPUT = 3 };
 
 /* fused-epilogue flags for xm_nnconv_forward_fused / xm_nnbnorm_forward_fused */
 enum { XM_FUSE_RELU = 1, XM_BN_BATCH_MOMENTS = 2, XM_FUSE_SIGMOID = 4 };
 
 /* ABI revision: 100 = round 1; 101 = xm_nnbnorm_relu_pool_backward gained `y_pool`, exchange entry points return
  * XM_EINVAL without a communicator; 102 = + xm_nnconv_forward_moments, xm_nnbnorm_backward_dxsum, xm_nnconv_forward_gated;
- * 103 = + xm_nnpool_global_avg_backward_accum; 104 = + xm_nnconv_backward_filter_bnrelupool, xm_nndropout_forward / _apply, xm_resample, xm_se_tail_backward_reduce / _apply, xm_se_squeeze_bn, xm_scale_axpy_bn; 105 = + xm_set_exec_hint / xm_get_exec_hint; 106 = + xm_nnconv_bnorm_relu_pool_forward, xm_stem_gram, xm_stem_gram_moments, xm_nnconv_backward_filter_bnrelupool_gram; 107 = + xm_nnaffinegrid / _backward, xm_nnbilinearsampler / _backward, xm_ferplus_batch (additions never change the revision's meaning for older bindings).  A binding checks xm_version() >= the revision it was written against. */
+ * 103 = + xm_nnpool_global_avg_backward_accum; 104 = + xm_nnconv_backward_filter_bnrelupool, xm_nndropout_forward / _apply, xm_resample, xm_se_tail_backward_reduce / _apply, xm_se_squeeze_bn, xm_scale_axpy_bn; 105 = + xm_set_exec_hint / xm_get_exec_hint; 106 = + xm_nnconv_bnorm_relu_pool_forward, xm_stem_gram, xm_stem_gram_moments, xm_nnconv_backward_filter_bnrelupool_gram; 107 = + xm_nnaffinegrid / _backward, xm_nnbilinearsampler / _backward, xm_ferplus_batch; 108 = + XM_AGG_PEAK, xm_mnrfit, xm_mnrval (additions never change the revision's meaning for older bindings).  A binding checks xm_version() >= the revision it was written against. */
 int xm_version(void);
 const char *xm_last_error(void);
 /* Device memory for hosts that have no device-array type of their own (MATLAB's gpuArray is CUDA-only: on an
@@ -425,7 +427,10 @@ int xm_resample(const float *x, int Lx, const float *h, int Lh, int p, int q, in
 int xm_spec_magnitude(const float *reim, int Wo, int B, int N, float *out, void *stream);
 /* getBatchEmoVoxCeleb.m:145-158,179-188: for sample n aggregate frame logits (F_total x E,
  * column-major, all wavs concatenated) over rows [first[n], last[n]] (1-based, inclusive)
- * -> out 1 x 1 x E x N and maxLabel (1-based argmax, getBatchEmoVoxCeleb.m:32) */
+ * -> out 1 x 1 x E x N and maxLabel (1-based argmax, getBatchEmoVoxCeleb.m:32).
+ * agg = XM_AGG_MAX | XM_AGG_MEAN, or XM_AGG_PEAK (ABI 108; selectPeakLogit, external/run_cross_val.m:149-155): the
+ * whole row of the block that holds its largest entry, the first one in column-major order as max(logits(:)) finds
+ * it (lowest e, then lowest row); an empty range gives -Inf as XM_AGG_MAX does. */
 int xm_aggregate_logits(const float *frame_logits, int F_total, int E, const int *first,
                         const int *last, int N, int agg, float *out, float *max_label,
                         void *stream);
@@ -447,6 +452,34 @@ int xm_normalize_face(const float *rgb, int H, int W, int N, const float *avg3, 
  * src: Hin x Win x 3 x N with values 0..255 (single holding the decoded uint8); avg3: HOST pointer. */
 int xm_crop_resize_face(const float *src, int Hin, int Win, int N, float crop, int Ho, int Wo,
                         const float *avg3, float *out, void *stream);
+
+/* ---- mnrfit / mnrval (Statistics Toolbox; external/run_cross_val.m:138-145, external/emo_benchmarks.m:90-100) --------
+ * Extensions, not MatConvNet operators.  G independent problems per call, one workgroup each; every sum runs in a fixed
+ * order without float atomics, so a problem's outputs are the same bits whatever G is and whatever else shares the call.
+ * X is p x n single with each sample's features contiguous (the 1 x 1 x p x n output of xm_aggregate_logits), labels n
+ * int32 in 1..k, problem g owns rows[offsets[g] .. offsets[g+1]) (int32, 1-based sample indices; nnz = size of rows).
+ * B (per problem (p+1) x (k-1) doubles, column-major, problems one after another) is MATLAB's nominal model
+ *     log(pi_j / pi_k) = B(1, j) + x * B(2:end, j),  j < k  (the last category is the reference),
+ * i.e. what mnrfit returns and mnrval takes.  D = (p+1)(k-1) <= 64, p >= 1, k >= 2, else XM_EINVAL before any launch.
+ *
+ * coefficients = mnrfit(double(X(:, rows)'), labels(rows)): Newton-Raphson from B = 0 in fp64; the information matrix
+ * is accumulated per entry in row order and solved by Cholesky in LDS; a step whose log-likelihood is lower than the
+ * current one is halved (at most 30 times); stop when a step that raised it has max|dB| <= tol_x * max(1, max|B|)
+ * (statset('mnrfit'): 100 iterations, 1e-6) or after max_iter iterations.  Per problem: B, deviance = -2 log-likelihood, the iteration count
+ * and status_out = XM_MNR_CONVERGED | XM_MNR_ITERLIMIT (separable data ends here with finite B) | XM_MNR_NOTPD (a
+ * Cholesky pivot <= 1e-14 x the largest diagonal entry; B = the last accepted iterate) | XM_MNR_BADINPUT (a label
+ * outside 1..k, a row outside 1..n, bad offsets, or a class absent from the training rows -- where mnrfit would drop
+ * the category and shift the columns; B = 0, deviance NaN). */
+int xm_mnrfit(const float *x, int p, int n, const int *labels, int k, const int *offsets, const int *rows, int nnz,
+              int G, int max_iter, double tol_x, double *b_out, double *dev_out, int *iters_out, int *status_out,
+              void *stream);
+/* preds = mnrval(B, double(X(:, rows)')); [~, cls] = max(preds, [], 2); confusionmat(labels, cls, 'Order', 1:k).
+ * probs_out (optional): k doubles per listed row, contiguous (the transpose of mnrval's n x k), in the order of rows;
+ * preds_out: the 1-based class per row, the first maximum winning ties; conf_out (optional, with labels): k x k int32
+ * per problem, column-major, (true label, predicted class), exact counts, overwritten.  A row index outside 1..n gets
+ * NaN probabilities and class 0 and is not counted; neither is a label outside 1..k. */
+int xm_mnrval(const double *b, const float *x, int p, int n, int k, const int *offsets, const int *rows, int nnz, int G,
+              const int *labels, double *probs_out, int *preds_out, int *conf_out, void *stream);
 
 /* ---- vl_nnaffinegrid / vl_nnbilinearsampler  (MatConvNet; getBatchFerPlus, teacher/ferplus_baselines.m:209-213) ------
  * PARITY UNPINNED: MatConvNet is not available to compare against; the formulas below restate its documented

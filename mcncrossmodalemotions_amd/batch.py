@@ -314,6 +314,47 @@ def getImageBatch(num, imageSize=(224, 224), averageImage=(131.0912, 103.8827, 9
     return vl.normalize_face(rgb, averageImage)
 
 
+class SyntheticBenchmarkImdb:
+    """Stand-in for the imdb of an external benchmark (RML, eNTERFACE, AFEW: getRmlImdb & co. are not in the reference
+    and the media cannot be decoded here) as external/run_cross_val.m reads it: tracks.set (1 = train, 2 = val, the
+    split the AFEW branch uses), tracks.labels (1-based, the classes dealt out evenly in seeded order) and tracks.id
+    (1..N); per track a 512 x T spectrogram magnitude (audio, T in [min_frames, max_frames]) or F_i normalised face
+    frames of face_size x face_size x 3 (visual, F_i in [min_faces, max_faces]), made on the device from seeded noise
+    when first asked for.  Every size is a parameter; the defaults make no claim about the real datasets."""
+
+    def __init__(self, num_tracks=120, num_classes=6, modality="audio", seed=0, val_fraction=0.0, min_frames=100,
+                 max_frames=400, min_faces=1, max_faces=6, face_size=224, averageImage=(131.0912, 103.8827, 91.4953)):
+        if modality not in ("audio", "visual"):
+            raise ValueError("unknown modality %s" % modality)
+        rng = np.random.default_rng(seed)
+        N = int(num_tracks)
+        self.modality, self.seed, self.face_size, self.averageImage = modality, int(seed), int(face_size), averageImage
+        labels = rng.permutation(np.arange(N) % int(num_classes)) + 1
+        sets = np.ones(N, int)
+        sets[rng.permutation(N)[:int(round(N * val_fraction))]] = 2
+        self.tracks = {"set": sets, "labels": labels.astype(int), "id": np.arange(1, N + 1)}
+        if modality == "audio":
+            self.frames = rng.integers(int(min_frames), int(max_frames) + 1, N)
+        else:
+            self.frames = rng.integers(int(min_faces), int(max_faces) + 1, N)
+        self._dev = {}
+
+    def __len__(self):
+        return len(self.tracks["set"])
+
+    def device_spec(self, ii, device):
+        """512 x T spectrogram magnitude of track ii (MATLAB layout)."""
+        g = torch.Generator(device=device)
+        g.manual_seed(self.seed * 100003 + 17 + int(ii))
+        T = int(self.frames[ii])
+        return torch.randn(T, 512, generator=g, device=device, dtype=torch.float32).abs_().t()
+
+    def device_faces(self, ii, device):
+        """face_size x face_size x 3 x F_i normalised face frames of track ii (getImageBatch's arithmetic)."""
+        return getImageBatch(int(self.frames[ii]), imageSize=(self.face_size, self.face_size),
+                             averageImage=self.averageImage, seed=self.seed * 100003 + 29 + int(ii), device=device)
+
+
 # ---------------------------------------------------------------------------------------------
 # FER+ (teacher training): getBatchFerPlus / computeAugs of teacher/ferplus_baselines.m
 # ---------------------------------------------------------------------------------------------

@@ -550,15 +550,34 @@ __global__ void aggregate_logits_kernel(const float *__restrict__ lg, int F, int
   int n = blockIdx.x * blockDim.x + threadIdx.x;
   if (n >= N) return;
   int f0 = first[n] - 1, f1 = min(last[n], F);
+  // XM_AGG_PEAK (selectPeakLogit, run_cross_val.m:149-155): the row holding the block's largest entry, the first one in
+  // column-major order as max(logits(:)) finds it -- lowest e, then lowest row
+  int peak = f0;
+  if (agg == XM_AGG_PEAK) {
+    float top = -INFINITY;
+    for (int e = 0; e < E; ++e)
+      for (int fr = f0; fr < f1; ++fr) {
+        float v = lg[fr + (size_t)F * e];
+        if (v > top) {
+          top = v;
+          peak = fr;
+        }
+      }
+  }
   float best = -INFINITY;
   int arg = 0;
   for (int e = 0; e < E; ++e) {
-    float a = agg == XM_AGG_MAX ? -INFINITY : 0.f;
-    for (int fr = f0; fr < f1; ++fr) {
-      float v = lg[fr + (size_t)F * e];
-      a = agg == XM_AGG_MAX ? fmaxf(a, v) : a + v;
+    float a;
+    if (agg == XM_AGG_PEAK) {
+      a = f1 > f0 ? lg[peak + (size_t)F * e] : -INFINITY;
+    } else {
+      a = agg == XM_AGG_MAX ? -INFINITY : 0.f;
+      for (int fr = f0; fr < f1; ++fr) {
+        float v = lg[fr + (size_t)F * e];
+        a = agg == XM_AGG_MAX ? fmaxf(a, v) : a + v;
+      }
+      if (agg == XM_AGG_MEAN) a /= (float)(f1 - f0);
     }
-    if (agg == XM_AGG_MEAN) a /= (float)(f1 - f0);
     out[(size_t)E * n + e] = a;
     if (a > best) {
       best = a;
@@ -937,7 +956,7 @@ int xm_aggregate_logits(const float *frame_logits, int F_total, int E, const int
                         const int *last, int N, int agg, float *out, float *max_label,
                         void *stream) {
   if (F_total <= 0 || E <= 0 || N <= 0) return fail(XM_EINVAL, "aggregate_logits: empty input");
-  if (agg != XM_AGG_MAX && agg != XM_AGG_MEAN)
+  if (agg != XM_AGG_MAX && agg != XM_AGG_MEAN && agg != XM_AGG_PEAK)
     return fail(XM_EINVAL, "unrecognised aggregator %d", agg);
   hipLaunchKernelGGL(aggregate_logits_kernel, dim3((N + 63) / 64), dim3(64), 0, (hipStream_t)stream,
                      frame_logits, F_total, E, first, last, N, agg, out, max_label);

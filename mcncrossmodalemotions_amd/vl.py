@@ -812,20 +812,104 @@ def resample(x, h, p, q, delay, Ly):
     return y
 
 
+_AGG = {"max": 0, "mean": 1, "peak": 2}   # XM_AGG_MAX / XM_AGG_MEAN / XM_AGG_PEAK
+
+
 def aggregate_logits(frame_logits, first, last, agg="max"):
     """frame_logits F x E (column-major), first/last int32 device vectors (1-based, inclusive).
-    Returns (logitTarget 1 x 1 x E x N, maxLabel 1 x 1 x 1 x N)."""
+    agg: "max" | "mean" (getBatchEmoVoxCeleb.m:179-188) | "peak" (selectPeakLogit, run_cross_val.m:149-155: the row
+    of the block holding its largest entry).  Returns (logitTarget 1 x 1 x E x N, maxLabel 1 x 1 x 1 x N)."""
     fl = _chk(frame_logits, "LOGITS")
     Fr, E = int(fl.shape[0]), int(fl.shape[1])
     N = int(first.numel())
     out = mat_empty(1, 1, E, N, device=fl.device)
     lab = mat_empty(1, 1, 1, N, device=fl.device)
-    if agg not in ("max", "mean"):
+    if agg not in _AGG:
         raise ValueError("unreccognised aggregator %s" % agg)
     _lib.check(_L().xm_aggregate_logits(_ptr(fl), Fr, E, C.c_void_p(first.data_ptr()),
-                                        C.c_void_p(last.data_ptr()), N, 0 if agg == "max" else 1,
+                                        C.c_void_p(last.data_ptr()), N, _AGG[agg],
                                         _ptr(out), _ptr(lab), _stream()))
     return out, lab
+
+
+# xm_mnrfit status codes (include/xmodal.h)
+MNR_CONVERGED, MNR_ITERLIMIT, MNR_NOTPD, MNR_BADINPUT = 0, 1, 2, 3
+
+
+def _features(X):
+    """p x n single features in MATLAB layout (p x n, or the 1 x 1 x p x n output of aggregate_logits) -> (p, n)."""
+    X = _chk(X, "X")
+    if X.dim() < 2 or any(int(d) != 1 for d in X.shape[:-2]):
+        raise ValueError("X: expected p x n (or 1 x 1 x p x n) features")
+    return int(X.shape[-2]), int(X.shape[-1])
+
+
+def _labels(labels, n, device):
+    if not isinstance(labels, torch.Tensor):
+        raise TypeError("LABELS: expected a torch tensor")
+    if not labels.is_cuda:
+        raise RuntimeError("LABELS: tensor is not on the GPU; this build has no CPU path")
+    if labels.numel() != n:
+        raise ValueError("LABELS: %d labels for %d samples" % (labels.numel(), n))
+    return labels.reshape(-1).to(device=device, dtype=torch.int32).contiguous()
+
+
+def _csr(sets, device):
+    """list of 1-based index lists -> (offsets int32[G+1], rows int32[nnz]) on the device, offsets on the host."""
+    sets = [np.asarray(s, dtype=np.int64).reshape(-1) for s in sets]
+    offs = np.concatenate([[0], np.cumsum([len(s) for s in sets])]).astype(np.int64)
+    if offs[-1] >= 2 ** 31:
+        raise ValueError("too many rows")
+    rows = np.concatenate(sets).astype(np.int32) if offs[-1] else np.zeros(1, np.int32)
+    return (torch.from_numpy(offs.astype(np.int32)).to(device), torch.from_numpy(rows).to(device), offs)
+
+
+def mnrfit(X, labels, train_sets, k, maxIter=100, tolX=1e-6):
+    """coefficients = mnrfit(double(X(:, train)'), labels(train)) for every index set in `train_sets` (1-based sample
+    indices), one launch (xm_mnrfit, fp64 Newton-Raphson).  X: p x n single device features, labels: n device labels
+    in 1..k.  Returns device tensors (B, status, iters, dev): B is (p+1) x (k-1) x G double in MATLAB layout (B[:, :, g]
+    is the problem's `coefficients`), status (MNR_*), iters int32 and the deviance double, G each."""
+    p, n = _features(X)
+    lab = _labels(labels, n, X.device)
+    k, G = int(k), len(train_sets)
+    offs, rows, h_offs = _csr(train_sets, X.device)
+    B = torch.empty(G, k - 1, p + 1, dtype=torch.float64, device=X.device).permute(2, 1, 0)
+    status = torch.empty(G, dtype=torch.int32, device=X.device)
+    iters = torch.empty(G, dtype=torch.int32, device=X.device)
+    dev = torch.empty(G, dtype=torch.float64, device=X.device)
+    _lib.check(_L().xm_mnrfit(_ptr(X), p, n, _ptr(lab), k, _ptr(offs), _ptr(rows), int(h_offs[-1]), G, int(maxIter),
+                              float(tolX), _ptr(B), _ptr(dev), _ptr(iters), _ptr(status), _stream()))
+    return B, status, iters, dev
+
+
+def mnrval(B, X, val_sets, labels=None):
+    """preds = mnrval(B(:, :, g), double(X(:, val)')) for every index set of `val_sets`, one launch (xm_mnrval).
+    B: (p+1) x (k-1) x G double device coefficients (what mnrfit returns), X: p x n single device features,
+    labels (optional): n device labels.  Returns (probs, preds, conf): per problem an n_g x k double tensor and an
+    n_g int32 tensor of 1-based classes (first maximum wins), and conf = G x k x k int32 counts
+    [true label - 1, predicted - 1] as confusionmat(..., 'Order', 1:k) (None without labels)."""
+    p, n = _features(X)
+    if not isinstance(B, torch.Tensor) or B.dtype != torch.float64:
+        raise TypeError("B: expected a double-precision torch tensor")
+    if not B.is_cuda:
+        raise RuntimeError("B: tensor is not on the GPU; this build has no CPU path")
+    Bm = B.reshape(B.shape[0], B.shape[1], -1) if B.dim() >= 2 else B
+    if Bm.dim() != 3 or int(Bm.shape[0]) != p + 1 or not Bm.permute(2, 1, 0).is_contiguous():
+        raise ValueError("B: expected (p+1) x (k-1) x G coefficients in MATLAB layout")
+    k, G = int(Bm.shape[1]) + 1, int(Bm.shape[2])
+    if G != len(val_sets):
+        raise ValueError("mnrval: %d coefficient sets for %d index sets" % (G, len(val_sets)))
+    lab = None if labels is None else _labels(labels, n, X.device)
+    offs, rows, h_offs = _csr(val_sets, X.device)
+    nnz = int(h_offs[-1])
+    probs = torch.empty(max(nnz, 1), k, dtype=torch.float64, device=X.device)
+    preds = torch.empty(max(nnz, 1), dtype=torch.int32, device=X.device)
+    conf = None if lab is None else torch.empty(G, k, k, dtype=torch.int32, device=X.device)
+    _lib.check(_L().xm_mnrval(_ptr(Bm), _ptr(X), p, n, k, _ptr(offs), _ptr(rows), nnz, G, _ptr(lab), _ptr(probs),
+                              _ptr(preds), _ptr(conf), _stream()))
+    sl = [slice(int(h_offs[g]), int(h_offs[g + 1])) for g in range(G)]
+    return ([probs[s] for s in sl], [preds[s] for s in sl],
+            None if conf is None else conf.transpose(1, 2))
 
 
 def max_label(lgo):
