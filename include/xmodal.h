@@ -49,13 +49,15 @@ enum { XM_LOSS_SOFTMAXLOG = 0, XM_LOSS_CLASSERROR = 1 };
 enum { XM_AGG_MAX = 0, XM_AGG_MEAN = 1, XM_AGG_PEAK = 2 };
 /* xm_mnrfit status per problem */
 enum { XM_MNR_CONVERGED = 0, XM_MNR_ITERLIMIT = 1, XM_MNR_NOTPD = 2, XM_MNR_BADINPUT = 3 };
+/* xm_roc status per problem */
+enum { XM_ROC_OK = 0, XM_ROC_NAN = 1, XM_ROC_BADINPUT = 2 };
 
 /* fused-epilogue flags for xm_nnconv_forward_fused / xm_nnbnorm_forward_fused */
 enum { XM_FUSE_RELU = 1, XM_BN_BATCH_MOMENTS = 2, XM_FUSE_SIGMOID = 4 };
 
 /* ABI revision: 100 = round 1; 101 = xm_nnbnorm_relu_pool_backward gained `y_pool`, exchange entry points return
  * XM_EINVAL without a communicator; 102 = + xm_nnconv_forward_moments, xm_nnbnorm_backward_dxsum, xm_nnconv_forward_gated;
- * 103 = + xm_nnpool_global_avg_backward_accum; 104 = + xm_nnconv_backward_filter_bnrelupool, xm_nndropout_forward / _apply, xm_resample, xm_se_tail_backward_reduce / _apply, xm_se_squeeze_bn, xm_scale_axpy_bn; 105 = + xm_set_exec_hint / xm_get_exec_hint; 106 = + xm_nnconv_bnorm_relu_pool_forward, xm_stem_gram, xm_stem_gram_moments, xm_nnconv_backward_filter_bnrelupool_gram; 107 = + xm_nnaffinegrid / _backward, xm_nnbilinearsampler / _backward, xm_ferplus_batch; 108 = + XM_AGG_PEAK, xm_mnrfit, xm_mnrval (additions never change the revision's meaning for older bindings).  A binding checks xm_version() >= the revision it was written against. */
+ * 103 = + xm_nnpool_global_avg_backward_accum; 104 = + xm_nnconv_backward_filter_bnrelupool, xm_nndropout_forward / _apply, xm_resample, xm_se_tail_backward_reduce / _apply, xm_se_squeeze_bn, xm_scale_axpy_bn; 105 = + xm_set_exec_hint / xm_get_exec_hint; 106 = + xm_nnconv_bnorm_relu_pool_forward, xm_stem_gram, xm_stem_gram_moments, xm_nnconv_backward_filter_bnrelupool_gram; 107 = + xm_nnaffinegrid / _backward, xm_nnbilinearsampler / _backward, xm_ferplus_batch; 108 = + XM_AGG_PEAK, xm_mnrfit, xm_mnrval; 109 = + xm_roc, xm_roc_launches, xm_label_hist (additions never change the revision's meaning for older bindings).  A binding checks xm_version() >= the revision it was written against. */
 int xm_version(void);
 const char *xm_last_error(void);
 /* Device memory for hosts that have no device-array type of their own (MATLAB's gpuArray is CUDA-only: on an
@@ -480,6 +482,47 @@ int xm_mnrfit(const float *x, int p, int n, const int *labels, int k, const int 
  * NaN probabilities and class 0 and is not counted; neither is a label outside 1..k. */
 int xm_mnrval(const double *b, const float *x, int p, int n, int k, const int *offsets, const int *rows, int nnz, int G,
               const int *labels, double *probs_out, int *preds_out, int *conf_out, void *stream);
+
+/* ---- vl_roc / histcounts (vlfeat [EXT]; emoVoxCeleb/student_stats.m:65-68,97-125, emoVoxCeleb/teacher_stats.m:28-29,57)
+ * Extensions, not MatConvNet operators (ABI 109).
+ *
+ * xm_roc: [~, ~, info] = vl_roc(labels, scores) with vlfeat's default options for G x E problems in one call.
+ * scores is n x E single, column-major (column c = the scores of emotion c + 1); cls holds n int32 classes (1-based, the
+ * teacher's label of each row); set g owns rows[offsets[g] .. offsets[g+1]) (int32, 1-based rows, nnz = size of rows,
+ * as xm_mnrfit).  Problem (g, c): the rows of set g, label +1 where cls == c + 1 and -1 elsewhere, score scores[row, c].
+ *   - p / n = the number of +1 / -1 labels over ALL rows of the set;
+ *   - the rows are ranked by score, descending and stable: equal scores (-0.0 == +0.0) keep the order of `rows`, as
+ *     MATLAB's sort(..., 'descend'); ties are not grouped, every row is a curve point;
+ *   - rows scoring -Inf are never retrieved: they count in p / n, the curve stops before them
+ *     (retrieved = the number of rows with score > -Inf);
+ *   - tp = [0 cumsum(label > 0)], fp = [0 cumsum(label < 0)] over the retrieved rows, tpr = tp / max(p, 1e-10),
+ *     fpr = fp / max(n, 1e-10), auc = the trapezoid sum of tpr over fpr.  A positive step adds no area and a negative
+ *     step adds tp / (p n), so with S = sum over retrieved negatives of the positives ranked before them (an exact
+ *     64-bit integer)  auc = (double)S / ((double)p * (double)n), one division; auc = 0 when p == 0 or n == 0.
+ * Outputs, all overwritten: auc (E x G doubles, column-major: entry c + E g), area (E x G, S), counts (3 x E x G:
+ * p, n, retrieved), status (E x G): XM_ROC_OK; XM_ROC_NAN = a NaN score in the problem (auc = NaN, the other problems
+ * of the call are unaffected); XM_ROC_BADINPUT = a row outside 1..n in the set, or offsets that are not 0 <= ascending
+ * <= nnz (then every problem; auc = NaN; no row is read through a bad index).  A host that has the index sets checks
+ * them before the call (vl.roc does).  An empty set gives p = n = 0, auc = 0, XM_ROC_OK.
+ * perm_out / tp_out (optional, both or neither; E x nnz int32 each, entry c nnz + offsets[g] + i): the row (1-based)
+ * ranked i-th in problem (g, c) and the positives among the first i + 1 rows, over all rows of the set, not only the
+ * retrieved ones; fp = i + 1 - tp.  With `retrieved` this is the whole curve.  For a problem whose status is not
+ * XM_ROC_OK they hold a permutation of the set in an unspecified order.
+ * Only integers are accumulated (integer atomics), there are no float atomics: every output bit is a function of the
+ * problem's own rows -- independent of G, of the order of the sets, of the launch shape and of scheduling.  A problem is
+ * spread over workgroups of 2048 entries; the number of launches (xm_roc_launches(): four 8-bit passes of a stable
+ * radix sort, three launches each, plus six) does not depend on n, nnz, G or E.  Scratch (16 nnz E bytes plus the tile
+ * tables) comes from the stream's workspace.  XM_EINVAL before any device work: E < 1, G < 0, n < 1, nnz < 0, a NULL
+ * required pointer, one of perm_out / tp_out without the other.  Supported: nnz E < 2^31, E <= 65535, 3 E G < 2^31;
+ * XM_ENOTSUP beyond. */
+int xm_roc(const float *scores, int n, int E, const int *cls, const int *offsets, const int *rows, int nnz, int G,
+           double *auc, long long *area, int *counts, int *status, int *perm_out, int *tp_out, void *stream);
+int xm_roc_launches(void);
+/* histcounts(labels, 0.5:E+0.5) of [~, labels] = max(x, [], 2): the first maximum per sample (as xm_max_label) counted
+ * into E 64-bit integer bins, one launch, exact in any order.  x holds N samples of E logits: sample_major = 0 is
+ * E x N (a sample's logits contiguous, the 1 x 1 x E x N layout of xm_max_label), sample_major = 1 is N x E column-major
+ * (vertcat(imdb.wavLogits{:})).  ADDS to bins (zero them before the first block of a stream of blocks).  E <= 4096. */
+int xm_label_hist(const float *x, int N, int E, int sample_major, long long *bins, void *stream);
 
 /* ---- vl_nnaffinegrid / vl_nnbilinearsampler  (MatConvNet; getBatchFerPlus, teacher/ferplus_baselines.m:209-213) ------
  * PARITY UNPINNED: MatConvNet is not available to compare against; the formulas below restate its documented

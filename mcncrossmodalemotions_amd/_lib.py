@@ -117,6 +117,9 @@ SIGNATURES = {
     "xm_ferplus_batch": [c_fp, _i, _i, _i, c_fp, c_fp, _i, _i, C.POINTER(C.c_float), c_fp, _vp],
     "xm_mnrfit": [c_fp, _i, _i, c_fp, _i, c_fp, c_fp, _i, _i, _i, C.c_double, c_fp, c_fp, c_fp, c_fp, _vp],
     "xm_mnrval": [c_fp, c_fp, _i, _i, _i, c_fp, c_fp, _i, _i, c_fp, c_fp, c_fp, c_fp, _vp],
+    "xm_roc": [c_fp, _i, _i, c_fp, c_fp, c_fp, _i, _i, c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, _vp],
+    "xm_roc_launches": [],
+    "xm_label_hist": [c_fp, _i, _i, _i, c_fp, _vp],
 }
 _RESTYPES = {"xm_get_exec_hint": C.c_uint, "xm_last_error": C.c_char_p, "xm_workspace_bytes": C.c_size_t,
              "xm_workspace_generation": C.c_ulonglong}

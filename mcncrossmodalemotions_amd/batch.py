@@ -127,7 +127,7 @@ class SyntheticEmoVoxImdb:
     cached teacher logits imdb.wavLogits{i} (F_i x 8 single, one row per sampled face frame)."""
 
     def __init__(self, num_tracks=64, seed=0, min_seconds=4.5, max_seconds=9.0, num_emotions=8, fs=16000,
-                 val_fraction=0.0):
+                 val_fraction=0.0, heard_fraction=0.0):
         rng = np.random.default_rng(seed)
         self.fs = fs
         self.num_samples = rng.integers(int(min_seconds * fs), int(max_seconds * fs), num_tracks)
@@ -135,9 +135,12 @@ class SyntheticEmoVoxImdb:
         for n in self.num_samples:
             frames = time2idx(n / fs)
             self.wavLogits.append(np.asfortranarray(rng.standard_normal((frames, num_emotions)).astype(np.float32) * 3))
-        self.set = np.ones(num_tracks, int)       # imdb.images.set: 1 = train, 2 = val
+        self.set = np.ones(num_tracks, int)       # imdb.images.set: 1 = train, 2 = val (unheardVal), 3 = heardVal
         if val_fraction > 0:
             self.set[rng.permutation(num_tracks)[:int(round(num_tracks * val_fraction))]] = 2
+        if heard_fraction > 0:   # 3 = heardVal (student_stats.m:79-81), drawn after everything else from the other tracks
+            rest = np.nonzero(self.set == 1)[0]
+            self.set[rng.permutation(rest)[:int(round(num_tracks * heard_fraction))]] = 3
         self.seed = seed
         self._dev = None
 

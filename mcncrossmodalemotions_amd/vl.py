@@ -912,6 +912,105 @@ def mnrval(B, X, val_sets, labels=None):
             None if conf is None else conf.transpose(1, 2))
 
 
+# xm_roc status codes (include/xmodal.h)
+ROC_OK, ROC_NAN, ROC_BADINPUT = 0, 1, 2
+
+
+def roc_sets(sets, n, device):
+    """index sets (1-based rows of an n-row score matrix) checked on the host and uploaded once: the tuple can be
+    passed to roc() as `sets` any number of times."""
+    sets = [np.asarray(s, dtype=np.int64).reshape(-1) for s in sets]
+    for g, s in enumerate(sets):
+        if s.size and (s.min() < 1 or s.max() > n):
+            raise ValueError("roc: set %d holds a row outside 1..%d" % (g + 1, n))
+    return _csr(sets, device)
+
+
+def roc(scores, cls, sets, want_curve=False):
+    """[~, ~, info] = vl_roc(labels, scores) (vlfeat, default options; student_stats.m:109-115) for every index set of
+    `sets` (1-based rows, or the tuple roc_sets() made of them) and every column of `scores`, one call of xm_roc.
+    scores: n x E single device scores, cls: n device classes (1-based); problem (g, c) labels a row +1 where cls == c + 1 and -1 elsewhere.
+    Returns a dict of device tensors: auc (G x E double), area (G x E int64: S, auc = S / (p n)), p, n, retrieved and
+    status (G x E int32, ROC_*), offsets (the host CSR offsets of the sets) and, with want_curve, perm and tp
+    (E x nnz int32: row c holds, set after set, the rows by descending score and the positives among the first
+    i + 1 of them)."""
+    scores = _chk(scores, "SCORES")
+    if scores.dim() != 2:
+        raise ValueError("SCORES: expected n x E scores")
+    n, E = int(scores.shape[0]), int(scores.shape[1])
+    lab = _labels(cls, n, scores.device)
+    offs, rows, h_offs = sets if isinstance(sets, tuple) else roc_sets(sets, n, scores.device)
+    G, nnz = len(h_offs) - 1, int(h_offs[-1])
+    dev = scores.device
+    auc = torch.empty(G, E, dtype=torch.float64, device=dev)
+    area = torch.empty(G, E, dtype=torch.int64, device=dev)
+    counts = torch.empty(G, E, 3, dtype=torch.int32, device=dev)
+    status = torch.empty(G, E, dtype=torch.int32, device=dev)
+    perm = tp = None
+    if want_curve:
+        perm = torch.empty(E, max(nnz, 1), dtype=torch.int32, device=dev)
+        tp = torch.empty(E, max(nnz, 1), dtype=torch.int32, device=dev)
+    _lib.check(_L().xm_roc(_ptr(scores), n, E, _ptr(lab), _ptr(offs), _ptr(rows), nnz, G, _ptr(auc), _ptr(area),
+                           _ptr(counts), _ptr(status), _ptr(perm), _ptr(tp), _stream()))
+    out = {"auc": auc, "area": area, "p": counts[:, :, 0], "n": counts[:, :, 1], "retrieved": counts[:, :, 2],
+           "status": status, "offsets": h_offs}
+    if want_curve:
+        out["perm"], out["tp"] = perm[:, :nnz], tp[:, :nnz]
+    return out
+
+
+def vl_roc(labels, scores):
+    """[TPR, TNR, INFO] = VL_ROC(LABELS, SCORES) of vlfeat for one problem (default options): labels in {-1, 0, +1}
+    (host or device), scores a device vector.  A 0 label is ignored: counted in neither p nor n and it advances
+    neither cumulative sum -- those rows are left out of the index set, the others keep their relative order.
+    Returns (tpr, tnr, info) as numpy doubles of retrieved + 1 points and info = {'auc', 'p', 'n', 'status'};
+    info.eer and the plotting branch are not provided (student_stats.m reads info.auc only)."""
+    if not isinstance(scores, torch.Tensor):
+        raise TypeError("SCORES: expected a torch tensor")
+    if not scores.is_cuda:
+        raise RuntimeError("SCORES: tensor is not on the GPU; this build has no CPU path")
+    lab = labels.detach().cpu().numpy() if isinstance(labels, torch.Tensor) else np.asarray(labels)
+    lab = lab.reshape(-1)
+    s = scores.reshape(-1).to(torch.float32).contiguous()[:, None]
+    if lab.size != s.shape[0]:
+        raise ValueError("vl_roc: %d labels for %d scores" % (lab.size, s.shape[0]))
+    if lab.size == 0:
+        z = np.zeros(1)
+        return z, 1 - z, {"auc": 0.0, "p": 0, "n": 0, "status": ROC_OK}
+    cls = torch.from_numpy(np.where(lab > 0, 1, 2).astype(np.int32)).to(s.device)
+    r = roc(s, cls, [np.nonzero(lab != 0)[0] + 1], want_curve=True)
+    p, n, ret = (int(r[k][0, 0]) for k in ("p", "n", "retrieved"))
+    tp = np.concatenate([[0], r["tp"][0, :ret].cpu().numpy().astype(np.float64)])
+    fp = np.arange(ret + 1, dtype=np.float64) - tp
+    tpr, fpr = tp / max(p, 1e-10), fp / max(n, 1e-10)
+    return tpr, 1 - fpr, {"auc": float(r["auc"][0, 0]), "p": p, "n": n, "status": int(r["status"][0, 0])}
+
+
+def label_hist(x, dim=None, bins=None):
+    """histcounts(labels, 0.5:E+0.5) with [~, labels] = max(x, [], dim): exact int64 counts of the first maximum per
+    sample, one launch (xm_label_hist).  x: N x E (dim = 2, the default for 2-D input: vertcat(wavLogits{:}),
+    student_stats.m:65, teacher_stats.m:28-29) or 1 x 1 x E x N (dim = 3, as max_label).  `bins` (E int64 device
+    counts) is added to when given, so blocks of frames can be streamed through."""
+    x = _chk(x, "X")
+    if dim is None:
+        dim = 2 if x.dim() == 2 else 3
+    if dim == 2 and x.dim() == 2:
+        N, E, sample_major = int(x.shape[0]), int(x.shape[1]), 1
+    elif dim == 3:
+        H, W, E, N = _shape4(x)
+        if H != 1 or W != 1:
+            raise ValueError("label_hist: X must be 1 x 1 x E x N for dim = 3")
+        sample_major = 0
+    else:
+        raise ValueError("label_hist: dim = 2 needs an N x E array, dim = 3 a 1 x 1 x E x N array")
+    if bins is None:
+        bins = torch.zeros(E, dtype=torch.int64, device=x.device)
+    elif bins.dtype != torch.int64 or not bins.is_cuda or bins.numel() != E or not bins.is_contiguous():
+        raise ValueError("label_hist: bins must be E contiguous int64 device counts")
+    _lib.check(_L().xm_label_hist(_ptr(x), N, E, sample_major, _ptr(bins), _stream()))
+    return bins
+
+
 def max_label(lgo):
     """[~, maxLabel] = max(lgo, [], 3) -- getBatchEmoVoxCeleb.m:32; lgo is 1 x 1 x C x N."""
     lgo = _chk(lgo, "LGO")
