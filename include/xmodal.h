@@ -57,7 +57,7 @@ enum { XM_FUSE_RELU = 1, XM_BN_BATCH_MOMENTS = 2, XM_FUSE_SIGMOID = 4 };
 
 /* ABI revision: 100 = round 1; 101 = xm_nnbnorm_relu_pool_backward gained `y_pool`, exchange entry points return
  * XM_EINVAL without a communicator; 102 = + xm_nnconv_forward_moments, xm_nnbnorm_backward_dxsum, xm_nnconv_forward_gated;
- * 103 = + xm_nnpool_global_avg_backward_accum; 104 = + xm_nnconv_backward_filter_bnrelupool, xm_nndropout_forward / _apply, xm_resample, xm_se_tail_backward_reduce / _apply, xm_se_squeeze_bn, xm_scale_axpy_bn; 105 = + xm_set_exec_hint / xm_get_exec_hint; 106 = + xm_nnconv_bnorm_relu_pool_forward, xm_stem_gram, xm_stem_gram_moments, xm_nnconv_backward_filter_bnrelupool_gram; 107 = + xm_nnaffinegrid / _backward, xm_nnbilinearsampler / _backward, xm_ferplus_batch; 108 = + XM_AGG_PEAK, xm_mnrfit, xm_mnrval; 109 = + xm_roc, xm_roc_launches, xm_label_hist (additions never change the revision's meaning for older bindings).  A binding checks xm_version() >= the revision it was written against. */
+ * 103 = + xm_nnpool_global_avg_backward_accum; 104 = + xm_nnconv_backward_filter_bnrelupool, xm_nndropout_forward / _apply, xm_resample, xm_se_tail_backward_reduce / _apply, xm_se_squeeze_bn, xm_scale_axpy_bn; 105 = + xm_set_exec_hint / xm_get_exec_hint; 106 = + xm_nnconv_bnorm_relu_pool_forward, xm_stem_gram, xm_stem_gram_moments, xm_nnconv_backward_filter_bnrelupool_gram; 107 = + xm_nnaffinegrid / _backward, xm_nnbilinearsampler / _backward, xm_ferplus_batch; 108 = + XM_AGG_PEAK, xm_mnrfit, xm_mnrval; 109 = + xm_roc, xm_roc_launches, xm_label_hist; 110 = + xm_group_rows, xm_gather_rows, xm_scatter_rows, xm_track_peaks (additions never change the revision's meaning for older bindings).  A binding checks xm_version() >= the revision it was written against. */
 int xm_version(void);
 const char *xm_last_error(void);
 /* Device memory for hosts that have no device-array type of their own (MATLAB's gpuArray is CUDA-only: on an
@@ -523,6 +523,53 @@ int xm_roc_launches(void);
  * E x N (a sample's logits contiguous, the 1 x 1 x E x N layout of xm_max_label), sample_major = 1 is N x E column-major
  * (vertcat(imdb.wavLogits{:})).  ADDS to bins (zero them before the first block of a stream of blocks).  E <= 4096. */
 int xm_label_hist(const float *x, int N, int E, int sample_major, long long *bins, void *stream);
+
+/* ---- teacher logits per track (emoVoxCeleb/fetch_emovoxceleb_imdb.m:119-148, emoVoxCeleb/sample_audio.m:69-74) -------
+ * Extensions, not MatConvNet operators (ABI 110).  Index sets as xm_roc / xm_mnrfit: `offsets` holds G + 1 0-based
+ * positions, `rows` 1-based rows.  No float atomics, every output bit is a function of the inputs alone, the number of
+ * launches does not depend on the sizes, scratch comes from the stream's workspace.  XM_EINVAL (a NULL required pointer,
+ * a negative count) and XM_ENOTSUP (a size past 2^31) are returned before any device work.
+ *
+ * xm_group_rows: wavLogits{ii} = logits(denseFramesWavIds == images.id(ii), :) for all ii at once
+ * (fetch_emovoxceleb_imdb.m:140-148), as index sets.  ids: the int32 wav id of each of n frames, in any order; keys:
+ * T DISTINCT ids in 0 < key <= key_max (a key outside that range claims nothing; duplicate keys are the caller's
+ * error -- which of them receives the rows is unspecified --, the host wrapper refuses them).  Group t receives the
+ * 1-based rows i + 1 with ids[i] == keys[t] in ascending order (the grouping is stable):
+ *   offsets_out (T + 1 int32), rows_out (n int32: the first nnz entries are the groups one after another, the rest is
+ *   0), nnz_out (one int32: the number of rows kept = offsets_out[T]).
+ * A row whose id is in no key is dropped: the "unclaimed" id 0, the tracks past `limit`, ids <= 0 or > key_max.
+ * A table of key_max + 1 slots maps id -> group, the rows are sorted by group with the stable 8-bit LSD radix passes of
+ * xm_roc (four passes, dropped rows carry the largest key), the offsets are lower bounds in the sorted keys.  16 launches
+ * whatever n, T and key_max are (one when n == 0 or T == 0).  Scratch: 16 n + 4 (key_max + 1) bytes plus the tile
+ * histograms.  Supported: key_max < 2^28; XM_ENOTSUP beyond. */
+int xm_group_rows(const int *ids, int n, const int *keys, int T, int key_max, int *offsets_out, int *rows_out,
+                  int *nnz_out, void *stream);
+/* The `out'` store of fetch_emovoxceleb_imdb.m:130-131 and its inverse: E-wide rows between the 1 x 1 x E x n layout a
+ * network emits (`packed`, sample i at packed[E i .. E i + E)) and an F x E column-major matrix (`mat`).  Row i of the
+ * packed side is matrix row rows[i] (1-based) when rows != NULL, else row0 + i + 1 (row0 0-based).
+ *   xm_gather_rows:   packed[e + E i] = mat[row + F e];  a row outside 1..F gives NaN
+ *   xm_scatter_rows:  mat[row + F e] = packed[e + E i];  a row outside 1..F is skipped; the other rows of mat are left
+ *                     as they were; the listed rows must be distinct
+ * One launch each.  XM_EINVAL: n < 0, E < 1, F < 1, row0 < 0, a NULL tensor (n > 0); without a row list also
+ * row0 + n > F.  XM_ENOTSUP: F E >= 2^31 or n E >= 2^31. */
+int xm_gather_rows(const float *mat, int F, int E, int row0, const int *rows, int n, float *packed, void *stream);
+int xm_scatter_rows(const float *packed, int n, int E, float *mat, int F, int row0, const int *rows, void *stream);
+/* sample_audio.m:69-74 for all tracks in one launch.  logits: F x E column-major; group t = the rows
+ * rows[offsets[t] .. offsets[t+1]) (1-based), or, with rows == NULL, the contiguous rows offsets[t] + 1 .. offsets[t+1].
+ *   [~, m] = max(x(:)); [frameIdx, tag] = ind2sub(size(x), m)  -> frame_idx[t], tag[t] (int32, both 1-based; frame_idx is
+ *                        the position within the group, not the matrix row)
+ *   max(x, [], 1)       -> maxed, 1 x 1 x E x T
+ * Ties go to the first entry in column-major order: lowest emotion, then lowest position.  NaN as XM_AGG_PEAK /
+ * XM_AGG_MAX of xm_aggregate_logits: a NaN never wins (v > best is false) and fmaxf drops it, so a group without any
+ * entry > -Inf gives frame_idx = tag = 1 and a column of NaN gives -Inf.  An empty group (or offsets that descend)
+ * gives 0, 0 and -Inf.  A listed row outside 1..F is passed over like a NaN; contiguous groups are cut to 0..F.  With a
+ * row list the caller guarantees offsets[T] <= the length of rows (the host wrapper checks).
+ * One wave per group: lane l reads positions l, l + 64, ... of every column (consecutive lanes read consecutive floats
+ * when the rows are contiguous), the column maxima are reduced with wave shuffles and the peak with a shuffle reduction
+ * on (value, then lower emotion, then lower position).  Comparisons only: the result does not depend on the order of
+ * the reduction.  One launch.  XM_EINVAL: F < 1, E < 1, T < 0, a NULL tensor (T > 0).  XM_ENOTSUP: F E or T E >= 2^31. */
+int xm_track_peaks(const float *logits, int F, int E, const int *offsets, const int *rows, int T, int *frame_idx,
+                   int *tag, float *maxed, void *stream);
 
 /* ---- vl_nnaffinegrid / vl_nnbilinearsampler  (MatConvNet; getBatchFerPlus, teacher/ferplus_baselines.m:209-213) ------
  * PARITY UNPINNED: MatConvNet is not available to compare against; the formulas below restate its documented

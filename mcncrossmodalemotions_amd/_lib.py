@@ -120,6 +120,10 @@ SIGNATURES = {
     "xm_roc": [c_fp, _i, _i, c_fp, c_fp, c_fp, _i, _i, c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, _vp],
     "xm_roc_launches": [],
     "xm_label_hist": [c_fp, _i, _i, _i, c_fp, _vp],
+    "xm_group_rows": [c_fp, _i, c_fp, _i, _i, c_fp, c_fp, c_fp, _vp],
+    "xm_gather_rows": [c_fp, _i, _i, _i, c_fp, _i, c_fp, _vp],
+    "xm_scatter_rows": [c_fp, _i, _i, c_fp, _i, _i, c_fp, _vp],
+    "xm_track_peaks": [c_fp, _i, _i, c_fp, c_fp, _i, c_fp, c_fp, c_fp, _vp],
 }
 _RESTYPES = {"xm_get_exec_hint": C.c_uint, "xm_last_error": C.c_char_p, "xm_workspace_bytes": C.c_size_t,
              "xm_workspace_generation": C.c_ulonglong}

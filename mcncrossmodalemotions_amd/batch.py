@@ -13,6 +13,7 @@ shapes the tensors the hot path consumes, fed from seeded synthetic sources:
     additive noise ('N')         getBatchEmoVoxCeleb.m:123-135      -> HIP xm_scale_axpy (z + Nratio * y)
     target selection + maxLabel  getBatchEmoVoxCeleb.m:30-32
     face normalisation           fetch_emovoxceleb_imdb.m:176-193   -> HIP xm_normalize_face
+    dense face frames            fetch_emovoxceleb_imdb.m:127,196-285 -> SyntheticDenseFrames (lister, find, decoded frames)
     FER+ batch (getBatchFerPlus) ferplus_baselines.m:153-268        -> HIP xm_ferplus_batch (grey -> flip -> x3 minus
                                                                        averageImage -> affine grid -> bilinear sampler)
 """
@@ -172,6 +173,60 @@ class SyntheticEmoVoxImdb:
             cat = np.asfortranarray(np.concatenate(self.wavLogits, 0))
             self._dev = (vl.from_numpy(cat, device), offs)
         return self._dev
+
+
+class SyntheticDenseFrames:
+    """Stand-in for the unpacked dense face frames (opts.faceDir of fetch_emovoxceleb_imdb.m:69,127,246-247): which
+    frame files each track has, what `find` reports, and the decoded pixels of a list of frames.
+      lister(track)   the relative frame paths of one track, <celeb>/1.6/<video>/<track>/<00001..>.jpg (:246-247);
+                      `track` is a dict with at least 'name', 'video', 'track' and 'id'.  A track has the frame count
+                      SyntheticEmoVoxImdb assumes, time2idx(seconds), except the ids in `frameless`, which have none
+                      (the 134 tracks of :231,264);
+      find()          every frame file under faceDir (:209-222): the listed ones and `unclaimed` more that belong to no
+                      track (the 1217 frames of :232-233);
+      frames(paths, device)  the decoded frames, Hin x Win x 3 x n single with values 0..255.  The pixels of a frame are
+                      a hash of (seed, its path, the pixel position): they do not depend on what else is in the batch, on
+                      the batch size or on the order of the calls."""
+
+    def __init__(self, imdb, seed=0, frameSize=(96, 96), frameless=(), unclaimed=0):
+        ids = np.asarray(imdb.images["id"] if hasattr(imdb, "images") else np.arange(1, len(imdb.num_samples) + 1))
+        self.counts = {int(i): time2idx(int(n) / imdb.fs) for i, n in zip(ids, imdb.num_samples)}
+        for i in frameless:
+            self.counts[int(i)] = 0
+        self.seed, self.frameSize, self.unclaimed = int(seed), (int(frameSize[0]), int(frameSize[1])), int(unclaimed)
+        self._tracks = {}
+
+    def lister(self, track):
+        celeb = str(track["name"]).split("/")[0]                                        # :244-246
+        d = "%s/1.6/%s/%d" % (celeb, track["video"], int(track["track"]))
+        paths = ["%s/%05d.jpg" % (d, j + 1) for j in range(self.counts.get(int(track["id"]), 0))]
+        self._tracks[int(track["id"])] = paths
+        return paths
+
+    def find(self):
+        """needs the tracks to have been listed once; the unclaimed files come last"""
+        return [p for t in self._tracks.values() for p in t] + ["unclaimed/1.6/none/0/%05d.jpg" % (j + 1)
+                                                       for j in range(self.unclaimed)]
+
+    def frame_key(self, path):
+        import zlib
+        return zlib.crc32(str(path).encode())
+
+    def __call__(self, paths, device=None):
+        device = device or torch.device("cuda", torch.cuda.current_device())
+        Hin, Win = self.frameSize
+        # the keys go up through pinned memory without blocking: a pageable upload would make the host wait for the
+        # device once per batch (buildImdb's loop only enqueues)
+        k = torch.tensor([self.frame_key(p) for p in paths], dtype=torch.int64).pin_memory()
+        k = k.to(device, non_blocking=True)[:, None]
+        i = torch.arange(3 * Win * Hin, dtype=torch.int64, device=device)[None, :]
+        M = 0xFFFFFFFF
+        x = (k * 0x9E3779B1 + i * 0x85EBCA77 + (self.seed & M) * 0xC2B2AE3D) & M       # 32-bit integer hash, in int64
+        x = ((x ^ (x >> 15)) * 0x2C1B3C6D) & M
+        x = ((x ^ (x >> 12)) * 0x297A2D39) & M
+        x = x ^ (x >> 15)
+        raw = (x & 255).to(torch.float32).reshape(len(paths), 3, Win, Hin)
+        return raw.permute(3, 2, 1, 0)
 
 
 def crop_window(total_samples, audSamp, fs, num_logit_rows, rng, fixedSegments=False, timeOffset=None):

@@ -13,6 +13,10 @@
 // 18 launches whatever G and E are.  Only integers are accumulated, so every output bit is a function of the problem's
 // own rows: independent of G, of the order of the sets and of how the tiles are scheduled.  The sort is stable because
 // an LSD pass keeps the order of equal digits and the initial order is the order of `rows`.
+//
+// xm_group_rows (fetch_emovoxceleb_imdb.m:140-148) sorts the frames by the group their wav id belongs to with the same
+// passes, as one problem: id -> group through a slot table, (group, position) through the four passes, offsets as lower
+// bounds in the sorted keys.  16 launches; no float atomics, integer LDS atomics only (the tile histograms).
 #include "xm_common.h"
 
 namespace xm {
@@ -401,6 +405,63 @@ label_hist_kernel(const float *__restrict__ x, int N, int E, int sample_major, u
     if (hbins[c]) atomicAdd(&bins[c], (unsigned long long)hbins[c]);
 }
 
+// ---- xm_group_rows: rows grouped by wav id (fetch_emovoxceleb_imdb.m:140-148) with the radix passes above ----------
+constexpr unsigned kGroupDropped = 0xFFFFFFFFu;           // the key of a row no group claims: sorts after every group
+
+// slot[id] = 0 for every id, and the one-problem tile table the radix kernels read: set 0 = entries [0, n)
+__global__ void __launch_bounds__(kRocThreads)
+group_clear_kernel(int *__restrict__ slot, int slots, int n, int Tc, int *__restrict__ tile_start,
+                   int *__restrict__ offsets1) {
+  const size_t i = blockIdx.x * (size_t)kRocThreads + threadIdx.x;
+  if (i < (size_t)slots) slot[i] = 0;
+  if (i == 0) {
+    tile_start[0] = 0;
+    tile_start[1] = Tc;
+    tile_start[2] = 0;
+    offsets1[0] = 0;
+    offsets1[1] = n;
+  }
+}
+
+// slot[key] = group + 1
+__global__ void __launch_bounds__(kRocThreads)
+group_slots_kernel(const int *__restrict__ keys, int T, int key_max, int *__restrict__ slot) {
+  const size_t t = blockIdx.x * (size_t)kRocThreads + threadIdx.x;
+  if (t >= (size_t)T) return;
+  const int k = keys[t];
+  if (k > 0 && k <= key_max) slot[k] = (int)t + 1;
+}
+
+__global__ void __launch_bounds__(kRocThreads)
+group_keys_kernel(const int *__restrict__ ids, int n, int key_max, const int *__restrict__ slot,
+                  unsigned *__restrict__ key, unsigned *__restrict__ pos) {
+  const size_t i = blockIdx.x * (size_t)kRocThreads + threadIdx.x;
+  if (i >= (size_t)n) return;
+  const int id = ids[i];
+  const int g = (id > 0 && id <= key_max) ? slot[id] : 0;
+  key[i] = g ? (unsigned)(g - 1) : kGroupDropped;
+  pos[i] = (unsigned)i;
+}
+
+// offsets[t] = the number of sorted keys below t (t = 0 .. T; keys are group numbers, dropped rows sort last), rows_out =
+// the sorted positions + 1 up to nnz = offsets[T] and 0 behind; key == NULL: nothing is claimed
+__global__ void __launch_bounds__(kRocThreads)
+group_finish_kernel(const unsigned *__restrict__ key, const unsigned *__restrict__ pos, int n, int T,
+                    int *__restrict__ offsets_out, int *__restrict__ rows_out, int *__restrict__ nnz_out) {
+  const size_t i = blockIdx.x * (size_t)kRocThreads + threadIdx.x;
+  if (i < (size_t)n) rows_out[i] = (key && key[i] != kGroupDropped) ? (int)pos[i] + 1 : 0;
+  if (i <= (size_t)T) {
+    int lo = 0, hi = key ? n : 0;   // first entry with key >= i
+    while (lo < hi) {
+      const int mid = lo + ((hi - lo) >> 1);
+      if (key[mid] < (unsigned)i) lo = mid + 1;
+      else hi = mid;
+    }
+    offsets_out[i] = lo;
+    if (i == (size_t)T) *nnz_out = lo;
+  }
+}
+
 }  // namespace xm
 
 using namespace xm;
@@ -464,6 +525,56 @@ int xm_label_hist(const float *x, int N, int E, int sample_major, long long *bin
   const int blocks = (int)(((size_t)N + 255) / 256 < 2048 ? ((size_t)N + 255) / 256 : 2048);
   hipLaunchKernelGGL(label_hist_kernel, dim3(blocks), dim3(256), sizeof(unsigned) * E, (hipStream_t)stream, x, N, E,
                      sample_major ? 1 : 0, (unsigned long long *)bins);
+  XM_LAUNCH_CHECK();
+  return XM_OK;
+}
+
+int xm_group_rows(const int *ids, int n, const int *keys, int T, int key_max, int *offsets_out, int *rows_out,
+                  int *nnz_out, void *stream) {
+  if (n < 0 || T < 0 || key_max < 0)
+    return fail(XM_EINVAL, "group_rows: need n >= 0, T >= 0, key_max >= 0 (got n=%d T=%d key_max=%d)", n, T, key_max);
+  if ((n > 0 && (!ids || !rows_out)) || (T > 0 && !keys) || !offsets_out || !nnz_out)
+    return fail(XM_EINVAL, "group_rows: NULL tensor");
+  const long long Tc = ((long long)n + kTile - 1) / kTile;
+  if (key_max >= (1 << 28) || too_big(Tc, 256))
+    return fail(XM_ENOTSUP, "group_rows: supported up to key_max < 2^28 and n < 2^31 (got n=%d key_max=%d)", n, key_max);
+  hipStream_t st = (hipStream_t)stream;
+  const dim3 blk(kRocThreads);
+  const size_t fin = ((size_t)(n > T + 1 ? n : T + 1) + kRocThreads - 1) / kRocThreads;
+  if (n == 0 || T == 0) {
+    hipLaunchKernelGGL(group_finish_kernel, dim3((unsigned)fin), blk, 0, st, (const unsigned *)nullptr,
+                       (const unsigned *)nullptr, n, T, offsets_out, rows_out, nnz_out);
+    XM_LAUNCH_CHECK();
+    return XM_OK;
+  }
+  const size_t slots = (size_t)key_max + 1;
+  const size_t bytes = WsCarver::need(slots, 4) + 2 * WsCarver::need(4, 4) + 4 * WsCarver::need((size_t)n, 4) +
+                       WsCarver::need((size_t)Tc * 256, 4);
+  WsCarver ws;
+  int rc = ws.init(bytes, st);
+  if (rc) return rc;
+  int *slot = ws.take<int>(slots);
+  int *tile_start = ws.take<int>(4);
+  int *offsets1 = ws.take<int>(4);
+  unsigned *key[2] = {ws.take<unsigned>(n), ws.take<unsigned>(n)};
+  unsigned *pos[2] = {ws.take<unsigned>(n), ws.take<unsigned>(n)};
+  unsigned *hist = ws.take<unsigned>((size_t)Tc * 256);
+  const dim3 tiles((unsigned)Tc, 1), one(1, 1);
+  hipLaunchKernelGGL(group_clear_kernel, dim3((unsigned)((slots + kRocThreads - 1) / kRocThreads)), blk, 0, st, slot,
+                     (int)slots, n, (int)Tc, tile_start, offsets1);
+  hipLaunchKernelGGL(group_slots_kernel, dim3((unsigned)(((size_t)T + kRocThreads - 1) / kRocThreads)), blk, 0, st, keys,
+                     T, key_max, slot);
+  hipLaunchKernelGGL(group_keys_kernel, dim3((unsigned)(((size_t)n + kRocThreads - 1) / kRocThreads)), blk, 0, st, ids, n,
+                     key_max, slot, key[0], pos[0]);
+  int cur = 0;
+  for (int shift = 0; shift < 32; shift += 8, cur ^= 1) {
+    hipLaunchKernelGGL(roc_hist_kernel, tiles, blk, 0, st, key[cur], offsets1, n, 1, tile_start, (int)Tc, shift, hist);
+    hipLaunchKernelGGL(roc_scan_kernel, one, blk, 0, st, tile_start, (int)Tc, hist);
+    hipLaunchKernelGGL(roc_scatter_kernel, tiles, blk, 0, st, key[cur], pos[cur], key[cur ^ 1], pos[cur ^ 1], offsets1, n,
+                       1, tile_start, (int)Tc, shift, hist);
+  }
+  hipLaunchKernelGGL(group_finish_kernel, dim3((unsigned)fin), blk, 0, st, key[cur], pos[cur], n, T, offsets_out,
+                     rows_out, nnz_out);
   XM_LAUNCH_CHECK();
   return XM_OK;
 }

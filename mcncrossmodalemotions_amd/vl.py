@@ -1032,6 +1032,110 @@ def class_stats(x, labels, correct, population):
     _lib.check(_L().xm_class_stats(_ptr(x), _ptr(labels), Cc, N, _ptr(correct), _ptr(population), _stream()))
 
 
+# --------------------------------------------------------------------------------------------
+# teacher logits per track (fetch_emovoxceleb_imdb.m:119-148, sample_audio.m:69-74)
+# --------------------------------------------------------------------------------------------
+
+
+def _ivec(t, name, count=None):
+    """contiguous int32 device vector (no CPU path, as _chk)"""
+    if not isinstance(t, torch.Tensor):
+        raise TypeError("%s: expected a torch tensor" % name)
+    if not t.is_cuda:
+        raise RuntimeError("%s: tensor is not on the GPU; this build has no CPU path" % name)
+    if t.dtype != torch.int32 or not t.is_contiguous():
+        raise TypeError("%s: expected a contiguous int32 tensor" % name)
+    if count is not None and t.numel() != count:
+        raise ValueError("%s: %d entries, expected %d" % (name, t.numel(), count))
+    return t.reshape(-1)
+
+
+def group_rows(ids, keys, key_max=None):
+    """wavLogits{ii} = logits(denseFramesWavIds == images.id(ii), :) for every ii at once, as index sets
+    (fetch_emovoxceleb_imdb.m:140-148; xm_group_rows).  ids: int32 device vector, the wav id of each frame, in any
+    order; keys: the T distinct ids (host sequence) that own a group, each in 0 < key <= key_max (default max(keys)).
+    Returns device tensors (offsets int32[T + 1], rows int32[n] -- 1-based, stable, the first nnz entries --, nnz
+    int32[1]); no result is downloaded.  The keys are uploaded from pageable memory on every call, a copy that makes
+    the host wait for the stream: call it after a loop, not inside one.  Duplicate keys raise XmError(XM_EINVAL)."""
+    keys = np.asarray(keys, dtype=np.int64).reshape(-1)
+    T = int(keys.size)
+    if key_max is None:
+        key_max = int(keys.max()) if T else 0
+    if T and (keys.min() < 1 or keys.max() > key_max):
+        raise _lib.XmError(1, "group_rows: keys must lie in 1..key_max")
+    if np.unique(keys).size != T:
+        raise _lib.XmError(1, "group_rows: duplicate keys")
+    ids = _ivec(ids, "IDS")
+    n = int(ids.numel())
+    dkeys = torch.from_numpy(keys.astype(np.int32)).to(ids.device)
+    offsets = torch.empty(T + 1, dtype=torch.int32, device=ids.device)
+    rows = torch.empty(max(n, 1), dtype=torch.int32, device=ids.device)
+    nnz = torch.empty(1, dtype=torch.int32, device=ids.device)
+    _lib.check(_L().xm_group_rows(_ptr(ids), n, _ptr(dkeys), T, int(key_max), _ptr(offsets), _ptr(rows), _ptr(nnz),
+                                  _stream()))
+    return offsets, rows[:n], nnz
+
+
+def _logit_matrix(mat, name):
+    mat = _chk(mat, name)
+    if mat.dim() != 2:
+        raise ValueError("%s: expected an F x E matrix" % name)
+    return mat, int(mat.shape[0]), int(mat.shape[1])
+
+
+def gather_rows(mat, rows=None, row0=0, n=None):
+    """F x E column-major matrix -> 1 x 1 x E x n (xm_gather_rows): sample i is matrix row rows[i] (1-based int32 device
+    list) or, without a list, row row0 + i + 1 for i < n."""
+    mat, F, E = _logit_matrix(mat, "MAT")
+    if rows is not None:
+        rows = _ivec(rows, "ROWS")
+        n = int(rows.numel())
+    elif n is None:
+        n = F - int(row0)
+    out = mat_empty(1, 1, E, max(int(n), 0), device=mat.device)
+    _lib.check(_L().xm_gather_rows(_ptr(mat), F, E, int(row0), _ptr(rows), int(n), _ptr(out), _stream()))
+    return out
+
+
+def scatter_rows(packed, mat, rows=None, row0=0):
+    """logits(batch, :) = out' (fetch_emovoxceleb_imdb.m:130-131; xm_scatter_rows): the 1 x 1 x E x n output of a network
+    into rows row0 + 1 .. row0 + n of the F x E column-major matrix `mat` (in place), or into the rows of a 1-based int32
+    device list.  Returns mat."""
+    packed = _chk(packed, "PACKED")
+    mat, F, E = _logit_matrix(mat, "MAT")
+    H, W, Cc, n = _shape4(packed)
+    if H != 1 or W != 1 or Cc != E:
+        raise ValueError("scatter_rows: PACKED must be 1 x 1 x %d x n" % E)
+    if rows is not None:
+        rows = _ivec(rows, "ROWS", n)
+    _lib.check(_L().xm_scatter_rows(_ptr(packed), n, E, _ptr(mat), F, int(row0), _ptr(rows), _stream()))
+    return mat
+
+
+def track_peaks(logits, offsets, rows=None):
+    """sample_audio.m:69-74 for every track in one launch (xm_track_peaks): [~, m] = max(x(:)), [frameIdx, tag] =
+    ind2sub(size(x), m) and max(x, [], 1) of the groups rows[offsets[t] : offsets[t + 1]] (1-based rows; rows = None:
+    the contiguous rows offsets[t] + 1 .. offsets[t + 1]) of the F x E matrix.  offsets: int32 device vector of T + 1.
+    Returns (frame_idx int32[T], tag int32[T], maxed 1 x 1 x E x T), all on the device; ties go to the lowest emotion,
+    then the lowest position; an empty group gives 0, 0, -Inf.  With a row list the largest offset is read back to
+    check it against the list (one device synchronisation); without one nothing is synchronised."""
+    logits, F, E = _logit_matrix(logits, "LOGITS")
+    offsets = _ivec(offsets, "OFFSETS")
+    T = int(offsets.numel()) - 1
+    if T < 0:
+        raise ValueError("track_peaks: OFFSETS needs at least one entry")
+    if rows is not None:
+        rows = _ivec(rows, "ROWS")
+        if T and int(offsets.max()) > int(rows.numel()):
+            raise ValueError("track_peaks: OFFSETS reach past the %d listed rows" % int(rows.numel()))
+    frame_idx = torch.empty(max(T, 1), dtype=torch.int32, device=logits.device)
+    tag = torch.empty(max(T, 1), dtype=torch.int32, device=logits.device)
+    maxed = mat_empty(1, 1, E, T, device=logits.device)
+    _lib.check(_L().xm_track_peaks(_ptr(logits), F, E, _ptr(offsets), _ptr(rows), T, _ptr(frame_idx), _ptr(tag),
+                                   _ptr(maxed), _stream()))
+    return frame_idx[:T], tag[:T], maxed
+
+
 def crop_resize_face(src, average_image, image_size=(224, 224), crop=1 / 1.6):
     """getImageBatch of fetch_emovoxceleb_imdb.m:152-193 from decoded frames (Hin x Win x 3 x N, values
     0..255): centre crop 1/1.6 -> bilinear resize -> uint8 -> grey -> x3 -> minus averageImage, fused."""
