@@ -57,7 +57,7 @@ enum { XM_FUSE_RELU = 1, XM_BN_BATCH_MOMENTS = 2, XM_FUSE_SIGMOID = 4 };
 
 /* ABI revision: 100 = round 1; 101 = xm_nnbnorm_relu_pool_backward gained `y_pool`, exchange entry points return
  * XM_EINVAL without a communicator; 102 = + xm_nnconv_forward_moments, xm_nnbnorm_backward_dxsum, xm_nnconv_forward_gated;
- * 103 = + xm_nnpool_global_avg_backward_accum; 104 = + xm_nnconv_backward_filter_bnrelupool, xm_nndropout_forward / _apply, xm_resample, xm_se_tail_backward_reduce / _apply, xm_se_squeeze_bn, xm_scale_axpy_bn; 105 = + xm_set_exec_hint / xm_get_exec_hint; 106 = + xm_nnconv_bnorm_relu_pool_forward, xm_stem_gram, xm_stem_gram_moments, xm_nnconv_backward_filter_bnrelupool_gram; 107 = + xm_nnaffinegrid / _backward, xm_nnbilinearsampler / _backward, xm_ferplus_batch; 108 = + XM_AGG_PEAK, xm_mnrfit, xm_mnrval; 109 = + xm_roc, xm_roc_launches, xm_label_hist; 110 = + xm_group_rows, xm_gather_rows, xm_scatter_rows, xm_track_peaks (additions never change the revision's meaning for older bindings).  A binding checks xm_version() >= the revision it was written against. */
+ * 103 = + xm_nnpool_global_avg_backward_accum; 104 = + xm_nnconv_backward_filter_bnrelupool, xm_nndropout_forward / _apply, xm_resample, xm_se_tail_backward_reduce / _apply, xm_se_squeeze_bn, xm_scale_axpy_bn; 105 = + xm_set_exec_hint / xm_get_exec_hint; 106 = + xm_nnconv_bnorm_relu_pool_forward, xm_stem_gram, xm_stem_gram_moments, xm_nnconv_backward_filter_bnrelupool_gram; 107 = + xm_nnaffinegrid / _backward, xm_nnbilinearsampler / _backward, xm_ferplus_batch; 108 = + XM_AGG_PEAK, xm_mnrfit, xm_mnrval; 109 = + xm_roc, xm_roc_launches, xm_label_hist; 110 = + xm_group_rows, xm_gather_rows, xm_scatter_rows, xm_track_peaks; 111 = + xm_wav_batch (additions never change the revision's meaning for older bindings).  A binding checks xm_version() >= the revision it was written against. */
 int xm_version(void);
 const char *xm_last_error(void);
 /* Device memory for hosts that have no device-array type of their own (MATLAB's gpuArray is CUDA-only: on an
@@ -422,6 +422,22 @@ int xm_spec_rownorm(const float *spec, int H, int W, int N, float *out, void *st
  * with the filter delay removed.  The host designs h (Kaiser-windowed ideal low-pass, batch.resample_design restates
  * the toolbox's recipe) and passes it with p, q already reduced by their gcd. */
 int xm_resample(const float *x, int Lx, const float *h, int Lh, int p, int q, int delay, float *y, int Ly, void *stream);
+/* The waveform front-end of a whole batch (ABI 111; getBatchEmoVoxCeleb.m:102-135): crop or speed-perturb, zero-pad and
+ * mix noise into the L x N sample matrix runSpec takes, clip n at z + n L.  wav / noise are device banks (all tracks /
+ * all noise files concatenated, wav_len / noise_len samples); desc holds {src, len, p, q, nsrc, nlen} per clip (device,
+ * contiguous), ratio one float per clip (device).  Every z(j, n), j = 0 .. L-1, is written exactly once:
+ *   p == q   v = j < len ? wav[src + j] : 0                          (audioread window, zero padded when short, :109-119)
+ *   p != q   v = sample j of resample(wav[src .. src + len), p, q) for j < min(ceil(len p / q), L), 0 behind   (:102-108)
+ *   nlen > 0 for j < nlen: v += ratio[n] noise[nsrc + j]                                        (z + y .* Nratio, :123-135)
+ * resample is the recipe of xm_resample's host design (batch.resample_design) with no filter in memory: p, q are
+ * reduced by their gcd here, the 2 * 10 * max(p, q) + 1 Kaiser(5)-windowed sinc taps are evaluated where they are
+ * used (~21 per output; the sine from m mod max(p, q) in integers, I0 by its power series) and the gain p / sum(h) of
+ * each clip is summed in fp64 by a first kernel into the stream's workspace.  Two launches whatever N is, no atomics;
+ * clip n depends on its own descriptor only.  A read outside [0, wav_len) / [0, noise_len) yields 0 and never reaches
+ * memory; a descriptor with p or q outside 1 .. 2^20 resamples to zeros.  XM_EINVAL: N < 0, L <= 0, a negative bank
+ * length, a NULL tensor with N > 0 (noise may be NULL when noise_len == 0); XM_ETOOBIG: N > 65535; N == 0: XM_OK. */
+int xm_wav_batch(const float *wav, long long wav_len, const float *noise, long long noise_len, const long long *desc,
+                 const float *ratio, int N, float *z, int L, void *stream);
 /* |STFT| from the output of the framing convolution (runSpec of getBatchEmoVoxCeleb.m:162 [EXT VGGVox]):
  * reim is 1 x Wo x 2B x N (channel b = Re of bin b, channel B+b = Im), out is B x Wo x 1 x N with
  * out(b, j, 1, n) = sqrt(Re^2 + Im^2).  The framing/windowing/pre-emphasis/DFT itself is one

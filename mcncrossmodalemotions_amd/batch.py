@@ -11,6 +11,8 @@ shapes the tensors the hot path consumes, fed from seeded synthetic sources:
     per-row normalisation ('I')  getBatchEmoVoxCeleb.m:164-169      -> HIP xm_spec_rownorm
     speed perturbation ('S')     getBatchEmoVoxCeleb.m:102-108,217-245 -> HIP xm_resample (filter designed on the host)
     additive noise ('N')         getBatchEmoVoxCeleb.m:123-135      -> HIP xm_scale_axpy (z + Nratio * y)
+    the three above, batched     getBatchEmoVoxCeleb.m:102-135      -> HIP xm_wav_batch (wavBatch: one descriptor table per
+                                                                       batch, the resampling taps evaluated in the kernel)
     target selection + maxLabel  getBatchEmoVoxCeleb.m:30-32
     face normalisation           fetch_emovoxceleb_imdb.m:176-193   -> HIP xm_normalize_face
     dense face frames            fetch_emovoxceleb_imdb.m:127,196-285 -> SyntheticDenseFrames (lister, find, decoded frames)
@@ -166,6 +168,29 @@ class SyntheticEmoVoxImdb:
             cache[ir] = torch.randn(self.noiselen, generator=g, device=device, dtype=torch.float32) * 0.05
         return cache[ir]
 
+    def wav_offsets(self):
+        """first sample of every track in the waveform bank (num_tracks + 1 values; host only)."""
+        return np.concatenate([[0], np.cumsum(np.asarray(self.num_samples, np.int64))]).astype(np.int64)
+
+    def noise_offsets(self):
+        return np.arange(self.noisenum + 1, dtype=np.int64) * self.noiselen
+
+    def logit_offsets(self):
+        """row offsets of device_logits (host only)."""
+        return np.cumsum([0] + [l.shape[0] for l in self.wavLogits])
+
+    def device_wav_bank(self, device):
+        """(bank, offsets): every track's device_wav concatenated, built once -- the samples the per-clip path reads."""
+        if "_wav_bank" not in self.__dict__:
+            self._wav_bank = torch.cat([self.device_wav(ii, device) for ii in range(len(self.num_samples))])
+        return self._wav_bank, self.wav_offsets()
+
+    def device_noise_bank(self, device):
+        """(bank, offsets): the noise files device_noise(1 .. noisenum) concatenated, built once."""
+        if "_noise_bank" not in self.__dict__:
+            self._noise_bank = torch.cat([self.device_noise(ir, device) for ir in range(1, self.noisenum + 1)])
+        return self._noise_bank, self.noise_offsets()
+
     def device_logits(self, device):
         """all tracks' logits concatenated (F_total x E) on the device + row offsets."""
         if self._dev is None:
@@ -248,14 +273,97 @@ def crop_window(total_samples, audSamp, fs, num_logit_rows, rng, fixedSegments=F
     return wr, s, min(e, int(num_logit_rows))
 
 
+def wav_batch_plan(imdb, batch, W, transformation, rng, fixedSegments=False, timeOffsets=None):
+    """The host side of one batch of cnn_get_batch_wav_emo (getBatchEmoVoxCeleb.m:76-158): every random draw, in the
+    reference's order per clip -- speedR (:103), the crop offset wr (:106 | :111), then Nir, Nwr, Nratio (:125-133) --
+    turned into the descriptor table of vl.wav_batch.  Touches no device.  Returns (desc, ratio, first, last):
+      desc   N x 6 int64 {src, len, p, q, nsrc, nlen}: src / nsrc index the banks of imdb.device_wav_bank /
+             device_noise_bank; a plain crop has p == q == fs and len = the samples the track has in [wr, wr + L);
+             'S' has len = audSampR, p = round(fs / speedR), q = fs, and noise over its resampled length cut to L
+             (nlen = min(ceil(len p / q), L)); a zero-padded crop gets noise over all L samples (:117 pads before :134)
+      ratio  N float32, Nratio
+      first, last  rows of imdb.device_logits that are aggregated (1-based, inclusive)."""
+    batch = list(batch)
+    N, fs = len(batch), int(imdb.fs)
+    audSamp = aud_samples(W)
+    L = int(round(audSamp))
+    chspeed, _, noisy = findSettings(transformation)
+    woffs, noffs, loffs = imdb.wav_offsets(), imdb.noise_offsets(), imdb.logit_offsets()
+    desc = np.zeros((N, 6), np.int64)
+    ratio = np.zeros(N, np.float32)
+    first = np.zeros(N, np.int32)
+    last = np.zeros(N, np.int32)
+    for k, ii in enumerate(batch):
+        total, rows = int(imdb.num_samples[ii]), imdb.wavLogits[ii].shape[0]
+        p = q = fs
+        if chspeed and not fixedSegments:
+            # :102-108 -- draw order as upstream: speed first, then the crop offset; the window read is audSampR long
+            # while the logit rows still follow [wr, wr + audSamp) (:141-142 use audSamp)
+            total = min(total, int(19.9 * fs))
+            speedR = 0.95 + float(rng.random()) * 0.1
+            audSampR = int(round(audSamp * speedR))
+            wd = total - audSampR
+            if wd < 1:
+                raise ValueError("clip %d is shorter than the speed-perturbed window (randi(wd) fails upstream, :106)" % ii)
+            wr = int(rng.integers(1, wd + 1))
+            s = time2idx(wr / fs)
+            e = min(time2idx((wr + audSamp - 1) / fs), int(rows))
+            p, ln = int(round(fs / speedR)), audSampR        # z = resample(zo, round(fs / speedR), fs)
+            nz = -(-ln * p // q)
+            if abs(nz - L) > 160:
+                raise RuntimeError("resample produced %d samples for a window of %d" % (nz, L))
+        else:
+            # getBatchEmoVoxCeleb.m:81-89: no clip of the dataset is longer than DATASET_LIMIT = 19.9 s; the sample
+            # count is thresholded accordingly (the cached teacher logits end there too)
+            wr, s, e = crop_window(total, audSamp, fs, rows, rng, fixedSegments,
+                                   None if timeOffsets is None else timeOffsets[k])
+            ln = max(0, min(L, int(imdb.num_samples[ii]) - (wr - 1)))
+            nz = L
+        start = min(wr - 1, int(imdb.num_samples[ii]))      # 0-based slice start of audioread(audfile, [wr ...])
+        desc[k, :4] = woffs[ii] + start, ln, p, q
+        if noisy:                                                       # :123-135, draw order Nir, Nwr, Nratio
+            nir, nwr = int(rng.integers(1, imdb.noisenum + 1)), int(rng.integers(1, imdb.noiselen - nz + 1))
+            ratio[k] = float(rng.random()) * imdb.noisevol
+            # z + y .* Nratio runs over numel(z) (:128-134): a short clip was zero-padded to audSamp BEFORE the mix, so
+            # its padded tail receives noise too; the resampled window of 'S' is not padded (its own length, cut to L)
+            desc[k, 4:] = noffs[nir - 1] + nwr - 1, min(nz, L)
+        first[k], last[k] = loffs[ii] + s, loffs[ii] + e
+    return desc, ratio, first, last
+
+
+def wav_clips(imdb, batch, desc, ratio, L, device):
+    """The L x N sample matrix of a planned batch, clip by clip: a slice of the track, for 'S' a float64 filter design on
+    the host + xm_resample, for 'N' xm_scale_axpy on a one-clip view.  What vl.wav_batch does in one call."""
+    woffs, noffs = imdb.wav_offsets(), imdb.noise_offsets()
+    z = torch.zeros((len(batch), L), dtype=torch.float32, device=device)      # storage of the L x N mat
+    for k, ii in enumerate(batch):
+        src, ln, p, q, nsrc, nlen = (int(v) for v in desc[k])
+        zo = imdb.device_wav(ii, device)[src - woffs[ii]:src - woffs[ii] + ln]
+        # (the spectrogram width only depends on floor((len - 400) / 160): +-1 sample of 'S' is immaterial)
+        w = resample(zo, p, q)[:L] if p != q else zo
+        z[k, :w.numel()].copy_(w)                                    # zero padding when short (:117)
+        if nlen:
+            nir = int(np.searchsorted(noffs, nsrc, side="right"))    # 1-based noise file
+            y = imdb.device_noise(nir, device)[nsrc - noffs[nir - 1]:nsrc - noffs[nir - 1] + nlen]
+            a = vl.mat_empty(1, 1, 1, 1, device=device)
+            a.fill_(float(ratio[k]))
+            zk = z[k, :nlen]
+            col = lambda t: t.reshape(1, 1, 1, -1).permute(3, 2, 1, 0)     # noqa: E731  (L x 1 x 1 x 1 mat view)
+            zk.copy_(vl.scale_axpy(col(y), a, col(zk)).permute(3, 2, 1, 0).reshape(-1))   # z = z + y .* Nratio (:134)
+    return z.t()
+
+
 def getBatchEmoVoxCeleb(imdb, batch, imageSize=(512, 300), numPredEmotions=8, logitAggregator="max",
                         lossType="hot-cross-ent", transformation="I", rng=None, spec_source=None,
-                        device=None, use_wav=False, fixedSegments=False, timeOffsets=None):
+                        device=None, use_wav=False, fixedSegments=False, timeOffsets=None, wavBatch=False):
     """inputs = getBatchEmoVoxCeleb(imdb, batch, ...) -> ['data', im, 'logitTarget', lgo,
     'maxLabel', maxLabel] (getBatchEmoVoxCeleb.m:31-43).  Spectrogram magnitudes come from
     `spec_source` (H x W x 1 x N device tensor), from the imdb's waveforms through the device
     front-end (`use_wav`: crop [wr, wr+audSamp) with zero padding of short clips :109-119, runSpec
     :162), or from a seeded half-normal generator.
+    `wavBatch` (with `use_wav`): the L x N sample matrix comes from ONE vl.wav_batch call on the imdb's device banks
+    instead of the per-clip loop (slice, host-designed filter + xm_resample, xm_scale_axpy); the draws, and
+    everything behind the matrix, are the same.
     `fixedSegments` (:91-101, :136-137; off upstream, run_distillation.m:86): the crop of clip k starts at
     timeOffsets[k] seconds, clips are not thresholded to DATASET_LIMIT, and ALL cached logit rows of the clip are
     aggregated.  (Upstream always passes timeOffsets = [] (:15), so the branch cannot run there; an offset list is
@@ -269,64 +377,17 @@ def getBatchEmoVoxCeleb(imdb, batch, imageSize=(512, 300), numPredEmotions=8, lo
     chspeed, _, noisy = findSettings(transformation)
     if (chspeed or noisy) and not (use_wav and spec_source is None):
         raise ValueError("transformations 'S' / 'N' act on the waveform: they need use_wav=True")
-    logits, offs = imdb.device_logits(device)
-    first = np.zeros(N, np.int32)
-    last = np.zeros(N, np.int32)
-    crops = []
-    for k, ii in enumerate(batch):
-        total, rows = int(imdb.num_samples[ii]), imdb.wavLogits[ii].shape[0]
-        speedR = audSampR = None
-        if chspeed and not fixedSegments:
-            # :102-108 -- draw order as upstream: speed first, then the crop offset; the window read is audSampR long
-            # while the logit rows still follow [wr, wr + audSamp) (:141-142 use audSamp)
-            total = min(total, int(19.9 * imdb.fs))
-            speedR = 0.95 + float(rng.random()) * 0.1
-            audSampR = int(round(audSamp * speedR))
-            wd = total - audSampR
-            if wd < 1:
-                raise ValueError("clip %d is shorter than the speed-perturbed window (randi(wd) fails upstream, :106)" % ii)
-            wr = int(rng.integers(1, wd + 1))
-            s = time2idx(wr / imdb.fs)
-            e = min(time2idx((wr + audSamp - 1) / imdb.fs), int(rows))
-        else:
-            # getBatchEmoVoxCeleb.m:81-89: no clip of the dataset is longer than DATASET_LIMIT = 19.9 s; the sample
-            # count is thresholded accordingly (the cached teacher logits end there too)
-            wr, s, e = crop_window(total, audSamp, imdb.fs, rows, rng, fixedSegments,
-                                   None if timeOffsets is None else timeOffsets[k])
-        mix = None
-        if noisy:                                                       # :123-135, draw order Nir, Nwr, Nratio
-            nz = (-(-audSampR * int(round(imdb.fs / speedR)) // imdb.fs)) if speedR else int(round(audSamp))
-            mix = (int(rng.integers(1, imdb.noisenum + 1)), int(rng.integers(1, imdb.noiselen - nz + 1)),
-                   float(rng.random()) * imdb.noisevol)
-        crops.append((ii, wr - 1, speedR, audSampR, mix))   # 0-based slice start of audioread(audfile, [wr ...])
-        first[k], last[k] = offs[ii] + s, offs[ii] + e
-    if spec_source is None and use_wav:
-        L = int(round(audSamp))
-        z = torch.zeros((N, L), dtype=torch.float32, device=device)      # storage of the L x N mat
-        for k, (ii, wr, speedR, audSampR, mix) in enumerate(crops):
-            if speedR is not None:
-                zo = imdb.device_wav(ii, device)[wr:wr + audSampR]
-                w = resample(zo, int(round(imdb.fs / speedR)), imdb.fs)   # z = resample(zo, round(fs / speedR), fs)
-                if abs(int(w.numel()) - L) > 160:
-                    raise RuntimeError("resample produced %d samples for a window of %d" % (int(w.numel()), L))
-                w = w[:L]        # (the spectrogram width only depends on floor((len - 400) / 160): +-1 sample is immaterial)
-            else:
-                w = imdb.device_wav(ii, device)[wr:wr + L]
-            z[k, :w.numel()].copy_(w)                                    # zero padding when short (:117)
-            if mix is not None:
-                nir, nwr, ratio = mix
-                # z + y .* Nratio runs over numel(z) (:128-134): a short clip was zero-padded to audSamp BEFORE the mix, so
-                # its padded tail receives noise too; the resampled window of 'S' is not padded (its own length, cut to L)
-                nzlen = int(w.numel()) if speedR is not None else L
-                y = imdb.device_noise(nir, device)[nwr - 1:nwr - 1 + nzlen]
-                a = vl.mat_empty(1, 1, 1, 1, device=device)
-                a.fill_(ratio)
-                zk = z[k, :nzlen]
-                col = lambda t: t.reshape(1, 1, 1, -1).permute(3, 2, 1, 0)     # noqa: E731  (L x 1 x 1 x 1 mat view)
-                zk.copy_(vl.scale_axpy(col(y), a, col(zk)).permute(3, 2, 1, 0).reshape(-1))   # z = z + y .* Nratio (:134)
-        spec_source = runSpec(z.t(), {"fs": imdb.fs})
-        if int(spec_source.shape[1]) != W:
-            raise RuntimeError("runSpec produced %d frames, expected %d" % (int(spec_source.shape[1]), W))
+    logits, _ = imdb.device_logits(device)
+    from_wav = spec_source is None and use_wav
+    desc, ratio, first, last = wav_batch_plan(imdb, batch, W, transformation, rng, fixedSegments, timeOffsets)
+    if from_wav and wavBatch:
+        wav, _ = imdb.device_wav_bank(device)
+        noise = imdb.device_noise_bank(device)[0] if noisy else None
+        spec_source = runSpec(vl.wav_batch(wav, noise, desc, ratio, int(round(audSamp))), {"fs": imdb.fs})
+    elif from_wav:
+        spec_source = runSpec(wav_clips(imdb, batch, desc, ratio, int(round(audSamp)), device), {"fs": imdb.fs})
+    if from_wav and int(spec_source.shape[1]) != W:
+        raise RuntimeError("runSpec produced %d frames, expected %d" % (int(spec_source.shape[1]), W))
     if spec_source is None:
         g = torch.Generator(device=device)
         g.manual_seed(int(rng.integers(0, 2 ** 31)))

@@ -942,6 +942,152 @@ int xm_resample(const float *x, int Lx, const float *h, int Lh, int p, int q, in
   return XM_OK;
 }
 
+// ---- wav_batch: crop | resample, zero padding and noise mix of a whole batch (getBatchEmoVoxCeleb.m:102-135) --------
+// The filter of resample(x, p, q) is never stored: with P = max(p, q), half = 10 P and the delay removed, output j is
+//   y[j] = g sum_k u(j q - k p) x[k],  |j q - k p| <= half,  u(m) = sinc(m / P) I0(beta sqrt(1 - (m / half)^2)),
+// g = p / sum_m u(m) (the constant 1 / (P I0(beta)) of the toolbox's taps cancels in p h / sum(h)).  sin(pi m / P)
+// comes from r = m mod P and the parity of floor(m / P), both carried along the tap loop in integers (m moves by p per
+// tap), so the argument of the sine is exact at every |m|; I0(beta sqrt(s)) is its power series in beta^2 s / 4, which
+// needs no square root.  wav_gain_kernel (one workgroup per clip) reduces p, q by their gcd and sums u in fp64;
+// wav_batch_kernel is one thread per output sample.
+struct WavClip {
+  int p, q;     // reduced ratio; p == 0: the clip has nothing to resample (a crop, or an unusable descriptor)
+  float gain;   // p / sum(u)
+  float pad;
+};
+constexpr int kWavMaxRatio = 1 << 20;
+constexpr float kWavBeta2Over4 = 6.25f;   // kaiser(L, 5): beta^2 / 4
+
+// I0(2 sqrt(y)) = sum_k y^k / (k!)^2 on 0 <= y <= 6.25: the first dropped term is below 2e-11 of the sum
+__device__ __forceinline__ float wav_i0(float y) {
+  const float c[15] = {1.000000000e+00f, 1.000000000e+00f, 2.500000000e-01f, 2.777777778e-02f, 1.736111111e-03f,
+                       6.944444444e-05f, 1.929012346e-06f, 3.936759889e-08f, 6.151187327e-10f, 7.594058428e-12f,
+                       7.594058428e-14f, 6.276081346e-16f, 4.358389823e-18f, 2.578928890e-20f, 1.315780046e-22f};
+  float s = c[14];
+#pragma unroll
+  for (int k = 13; k >= 0; --k) s = fmaf(s, y, c[k]);
+  return s;
+}
+
+// u(m) for |m| <= half, given r = m mod P in [0, P) and odd = parity of floor(m / P)
+__device__ __forceinline__ float wav_tap(int m, int r, int odd, int P, float invP, float P_over_pi, int half, float kb) {
+  const int rr = 2 * r > P ? P - r : r;              // sin(pi r / P) = sin(pi (P - r) / P): argument in [0, pi / 2]
+  float s = sinpif((float)rr * invP);
+  s = odd ? -s : s;
+  const float w = wav_i0((float)(half - m) * (float)(half + m) * kb);
+  return m == 0 ? w : s * P_over_pi * __builtin_amdgcn_rcpf((float)m) * w;
+}
+
+__global__ void __launch_bounds__(1024)
+wav_gain_kernel(const long long *__restrict__ desc, WavClip *__restrict__ clip) {
+  __shared__ double part[16];
+  const int n = blockIdx.x, tid = threadIdx.x;
+  long long p = desc[6 * (size_t)n + 2], q = desc[6 * (size_t)n + 3];
+  if (p < 1 || q < 1 || p > kWavMaxRatio || q > kWavMaxRatio || p == q) {   // the same for every thread of the block
+    if (tid == 0) clip[n] = WavClip{0, 0, 0.f, 0.f};
+    return;
+  }
+  long long a = p, b = q;
+  while (b) {
+    long long t = a % b;
+    a = b;
+    b = t;
+  }
+  p /= a;
+  q /= a;
+  const int P = (int)(p > q ? p : q), half = 10 * P;
+  const float invP = 1.f / (float)P, P_over_pi = (float)P * 0.318309886f, kb = kWavBeta2Over4 / ((float)half * (float)half);
+  double acc = 0.0;
+  for (int m = 1 + tid; m < half; m += 1024) {   // u(-m) = u(m), u(half) = 0
+    const int qd = m / P;
+    acc += (double)wav_tap(m, m - qd * P, qd & 1, P, invP, P_over_pi, half, kb);
+  }
+  acc = xm_wave_sum_d(acc);
+  if ((tid & 63) == 0) part[tid >> 6] = acc;
+  __syncthreads();
+  if (tid == 0) {
+    double s = 0.0;
+    for (int w = 0; w < 16; ++w) s += part[w];
+    s = 2.0 * s + (double)wav_tap(0, 0, 0, P, invP, P_over_pi, half, kb);
+    clip[n] = WavClip{(int)p, (int)q, (float)((double)p / s), 0.f};
+  }
+}
+
+__global__ void __launch_bounds__(256)
+wav_batch_kernel(const float *__restrict__ wav, long long wav_len, const float *__restrict__ noise, long long noise_len,
+                 const long long *__restrict__ desc, const float *__restrict__ ratio, const WavClip *__restrict__ clip,
+                 float *__restrict__ z, int L) {
+  const int n = blockIdx.y, j = blockIdx.x * 256 + threadIdx.x;
+  if (j >= L) return;
+  const long long *d = desc + 6 * (size_t)n;
+  const long long src = d[0], nsrc = d[4], nlen = d[5];
+  long long len = d[1];
+  float v = 0.f;
+  if (len > 0 && d[2] == d[3]) {                                   // crop, zero padded behind len (.m:109-119)
+    const unsigned long long i = (unsigned long long)src + (unsigned long long)j;
+    if (j < len && i < (unsigned long long)wav_len) v = wav[i];
+  } else if (len > 0) {
+    const WavClip c = clip[n];
+    if (len > (1LL << 31)) len = 1LL << 31;
+    // k such that src + k is a sample of the bank: every read below is inside [0, wav_len)
+    long long lo = 0, hi = len - 1;
+    if (src < -(1LL << 32)) {
+      hi = -1;
+    } else {
+      if (src < 0) lo = -src;
+      if (hi > wav_len - 1 - src) hi = wav_len - 1 - src;
+    }
+    if (c.p > 0 && (long long)j * c.q < len * c.p) {               // j < ceil(len p / q)
+      const int P = c.p > c.q ? c.p : c.q, half = 10 * P;
+      const unsigned long long top = (unsigned long long)j * (unsigned)c.q + (unsigned)half;
+      const long long khi = (long long)(top / (unsigned)c.p);      // largest k with j q - k p >= -half
+      const int rem = (int)(top - (unsigned long long)khi * (unsigned)c.p);
+      const long long klo = khi - (2 * half - rem) / c.p;          // smallest k with j q - k p <= half
+      const long long k1 = khi < hi ? khi : hi, k0 = klo > lo ? klo : lo;
+      if (k1 >= k0) {
+        int m = rem - half + (int)((khi - k1) * c.p);              // j q - k1 p
+        const int qd = (m + half) / P;                             // floor(m / P) + 10
+        int r = m + half - qd * P, odd = qd & 1;
+        const float invP = 1.f / (float)P, P_over_pi = (float)P * 0.318309886f,
+                    kb = kWavBeta2Over4 / ((float)half * (float)half);
+        float acc = 0.f;
+        for (long long k = k1; k >= k0; --k) {
+          acc = fmaf(wav_tap(m, r, odd, P, invP, P_over_pi, half, kb), wav[src + k], acc);
+          m += c.p;
+          r += c.p;
+          if (r >= P) {
+            r -= P;
+            odd ^= 1;
+          }
+        }
+        v = acc * c.gain;
+      }
+    }
+  }
+  if (j < nlen) {                                                  // z + y .* Nratio (.m:123-135)
+    const unsigned long long i = (unsigned long long)nsrc + (unsigned long long)j;
+    if (i < (unsigned long long)noise_len) v = fmaf(ratio[n], noise[i], v);
+  }
+  z[(size_t)n * L + j] = v;
+}
+
+int xm_wav_batch(const float *wav, long long wav_len, const float *noise, long long noise_len, const long long *desc,
+                 const float *ratio, int N, float *z, int L, void *stream) {
+  if (N < 0 || L <= 0 || wav_len < 0 || noise_len < 0) return fail(XM_EINVAL, "wav_batch: bad sizes");
+  if (N == 0) return XM_OK;
+  if (!wav || !desc || !ratio || !z || (!noise && noise_len > 0)) return fail(XM_EINVAL, "wav_batch: NULL tensor");
+  if (N > 65535) return fail(XM_ETOOBIG, "wav_batch: more than 65535 clips per call");
+  void *ws = nullptr;
+  int rc = ws_get((size_t)N * sizeof(WavClip), &ws, (hipStream_t)stream);
+  if (rc != XM_OK) return rc;
+  hipLaunchKernelGGL(wav_gain_kernel, dim3(N), dim3(1024), 0, (hipStream_t)stream, desc, (WavClip *)ws);
+  XM_LAUNCH_CHECK();
+  hipLaunchKernelGGL(wav_batch_kernel, dim3((L + 255) / 256, N), dim3(256), 0, (hipStream_t)stream, wav, wav_len, noise,
+                     noise_len, desc, ratio, (const WavClip *)ws, z, L);
+  XM_LAUNCH_CHECK();
+  return XM_OK;
+}
+
 int xm_spec_rownorm(const float *spec, int H, int W, int N, float *out, void *stream) {
   if (H <= 0 || W <= 1 || N <= 0) return fail(XM_EINVAL, "spec_rownorm: need H>0, W>1, N>0");
   if (!spec || !out) return fail(XM_EINVAL, "spec_rownorm: NULL tensor");

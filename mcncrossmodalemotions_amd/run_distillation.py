@@ -6,7 +6,8 @@ Same option names, defaults and flow as the reference entry point: build the imd
 experiment directory, build the student with emoVoxZoo, bind getBatchEmoVoxCeleb, call cnn_train_dag
 with the reference's arguments (run_distillation.m:170-182).  What differs, because there is no
 VoxCeleb / MatConvNet here: the imdb is the seeded synthetic stand-in of batch.SyntheticEmoVoxImdb
-(teacher logits per track, wav lengths), spectrogram magnitudes come from a seeded generator, and
+(teacher logits per track, wav lengths), spectrogram magnitudes come from a seeded generator (or, with `useWav`,
+from the imdb's seeded waveforms through crop / resample / noise mix / runSpec on the device), and
 `gpus` is the torchrun world (one process per GPU).  Extensions are keyword-only and marked.
 """
 import os
@@ -22,10 +23,13 @@ def run_distillation(gpus=(2,), cont=True, miniVal=0.2, numSeconds=4, batchSize=
                      datasetName="voxceleb", teacher="senet50-ferplus", student="emovoxceleb-student",
                      lossType="hot-cross-ent", temperature=2, fixedSegments=False, learningRate=None,
                      parameterServer="tmove", wavDir=None,
-                     *, imdb=None, dataDir="data/xEmo18", numTracks=256, widthMult=1.0, seed=0, verbose=False):
+                     *, imdb=None, dataDir="data/xEmo18", numTracks=256, widthMult=1.0, seed=0, verbose=False,
+                     useWav=False, transformation="I"):
     """Options as in run_distillation.m:72-90.  Extensions (keyword-only): `imdb` (a prepared imdb),
     `dataDir` (root of the experiment directories), `numTracks` / `seed` (synthetic imdb), `widthMult`
-    (narrow student for tests)."""
+    (narrow student for tests), `useWav` (the batches come from the imdb's waveforms through the batched device
+    front-end, batch.getBatchEmoVoxCeleb(use_wav, wavBatch), instead of the seeded spectrogram generator) and
+    `transformation` (net.meta.augmentation.transformation, :130: 'I', 'IS', 'ISN' ...; 'S' / 'N' need useWav)."""
     gpus = list(np.atleast_1d(gpus))
     if miniEpochRatio is None:
         miniEpochRatio = 0.05 * len(gpus)                      # :77
@@ -60,7 +64,7 @@ def run_distillation(gpus=(2,), cont=True, miniVal=0.2, numSeconds=4, batchSize=
         parserv = train.ParameterServer.start_agreed(parameterServer)
     net = zoo.emoVoxZoo(student, scratch=1 if fromScratch else 0, lossType=lossType, numSeconds=numSeconds,
                         numOutputs=numPredEmotions, width_mult=widthMult)             # :125-129
-    net.meta.setdefault("augmentation", {})["transformation"] = "I"                  # :130
+    net.meta.setdefault("augmentation", {})["transformation"] = transformation       # :130
     trainSamples = [i for i in range(len(imdb.set)) if imdb.set[i] == 1]              # :137-138
     valSamples = [i for i in range(len(imdb.set)) if imdb.set[i] == 2]
     if miniVal < 1 and valSamples:                                                    # :141-146
@@ -71,10 +75,14 @@ def run_distillation(gpus=(2,), cont=True, miniVal=0.2, numSeconds=4, batchSize=
     brng = np.random.default_rng(seed + 17)
 
     def getBatch(imdb_, batch):                                                       # getBatchFn, :210-224
+        tr = net.meta["augmentation"]["transformation"]
+        if len(batch) and imdb_.set[batch[0]] != 1:      # validation: 'S' and 'N' off (getBatchEmoVoxCeleb.m:14-25)
+            tr = "v" + tr
         return xbatch.getBatchEmoVoxCeleb(imdb_, batch, imageSize=(512, int(round(numSeconds * 100))),
                                           numPredEmotions=numPredEmotions, logitAggregator=logitAggregator,
-                                          lossType=lossType, transformation=net.meta["augmentation"]["transformation"],
-                                          rng=brng, fixedSegments=fixedSegments)   # bopts.fixedSegments, :220
+                                          lossType=lossType, transformation=tr, rng=brng,
+                                          fixedSegments=fixedSegments,             # bopts.fixedSegments, :220
+                                          use_wav=useWav, wavBatch=useWav)
         # (fixedSegments = true fails upstream as well: getBatchEmoVoxCeleb.m:15 passes timeOffsets = [])
 
     return train.cnn_train_dag(net, imdb, getBatch, learningRate=learningRate, batchSize=batchSize,

@@ -812,6 +812,49 @@ def resample(x, h, p, q, delay, Ly):
     return y
 
 
+WAV_MAX_RATIO = 1 << 20   # p, q of a wav_batch descriptor (xm_wav_batch resamples anything beyond to zeros)
+
+
+def wav_batch(wav, noise, desc, ratio, L):
+    """The L x N sample matrix of a batch (xm_wav_batch; getBatchEmoVoxCeleb.m:102-135) from the device banks `wav` /
+    `noise` (1-D; `noise` may be None when no clip mixes any).  desc: N x 6 int64 HOST array {src, len, p, q, nsrc, nlen}
+    per clip, ratio: N float32 HOST array -- checked here (ranges inside the banks, len >= 0, p, q in 1 .. 2^20,
+    0 <= nlen <= L; ValueError otherwise) and sent up in ONE pinned, non-blocking upload."""
+    desc = np.ascontiguousarray(desc, dtype=np.int64)
+    ratio = np.ascontiguousarray(ratio, dtype=np.float32).reshape(-1)
+    L = int(L)
+    if desc.ndim != 2 or desc.shape[1] != 6 or ratio.size != desc.shape[0]:
+        raise ValueError("wav_batch: DESC must be N x 6 and RATIO must have N elements")
+    if L <= 0:
+        raise ValueError("wav_batch: L must be positive")
+    for t, name in ((wav, "WAV"), (noise, "NOISE")):
+        if t is not None and (_chk(t, name).dim() != 1 or not t.is_contiguous()):
+            raise ValueError("wav_batch: %s must be a contiguous 1-D bank" % name)
+    if wav is None:
+        raise ValueError("wav_batch: WAV is required")
+    N, wav_len, noise_len = int(desc.shape[0]), int(wav.numel()), 0 if noise is None else int(noise.numel())
+    src, ln, p, q, nsrc, nlen = (desc[:, i] for i in range(6))
+    if N and not ((ln >= 0).all() and (src >= 0).all() and (src + ln <= wav_len).all()):
+        raise ValueError("wav_batch: a clip's [src, src + len) leaves the waveform bank")
+    if N and not ((p >= 1).all() and (q >= 1).all() and (p <= WAV_MAX_RATIO).all() and (q <= WAV_MAX_RATIO).all()):
+        raise ValueError("wav_batch: p, q must be in 1 .. 2^20")
+    if N and not ((nlen >= 0).all() and (nlen <= L).all()):
+        raise ValueError("wav_batch: nlen must be in 0 .. L")
+    mixed = nlen > 0
+    if N and not ((nsrc[mixed] >= 0).all() and (nsrc[mixed] + nlen[mixed] <= noise_len).all()):
+        raise ValueError("wav_batch: a clip's [nsrc, nsrc + nlen) leaves the noise bank")
+    z = torch.empty((N, L), dtype=torch.float32, device=wav.device)      # storage of the L x N mat
+    if N:
+        host = torch.empty(52 * N, dtype=torch.uint8, pin_memory=True)   # [desc | ratio]
+        raw = host.numpy()
+        raw[:48 * N].view(np.int64)[:] = desc.reshape(-1)
+        raw[48 * N:].view(np.float32)[:] = ratio
+        up = host.to(wav.device, non_blocking=True)
+        _lib.check(_L().xm_wav_batch(_ptr(wav), wav_len, _ptr(noise), noise_len, C.c_void_p(up.data_ptr()),
+                                     C.c_void_p(up.data_ptr() + 48 * N), N, _ptr(z), L, _stream()))
+    return z.t()
+
+
 _AGG = {"max": 0, "mean": 1, "peak": 2}   # XM_AGG_MAX / XM_AGG_MEAN / XM_AGG_PEAK
 
 
