@@ -57,7 +57,7 @@ enum { XM_FUSE_RELU = 1, XM_BN_BATCH_MOMENTS = 2, XM_FUSE_SIGMOID = 4 };
 
 /* ABI revision: 100 = round 1; 101 = xm_nnbnorm_relu_pool_backward gained `y_pool`, exchange entry points return
  * XM_EINVAL without a communicator; 102 = + xm_nnconv_forward_moments, xm_nnbnorm_backward_dxsum, xm_nnconv_forward_gated;
- * 103 = + xm_nnpool_global_avg_backward_accum; 104 = + xm_nnconv_backward_filter_bnrelupool, xm_nndropout_forward / _apply, xm_resample, xm_se_tail_backward_reduce / _apply, xm_se_squeeze_bn, xm_scale_axpy_bn; 105 = + xm_set_exec_hint / xm_get_exec_hint; 106 = + xm_nnconv_bnorm_relu_pool_forward, xm_stem_gram, xm_stem_gram_moments, xm_nnconv_backward_filter_bnrelupool_gram; 107 = + xm_nnaffinegrid / _backward, xm_nnbilinearsampler / _backward, xm_ferplus_batch; 108 = + XM_AGG_PEAK, xm_mnrfit, xm_mnrval; 109 = + xm_roc, xm_roc_launches, xm_label_hist; 110 = + xm_group_rows, xm_gather_rows, xm_scatter_rows, xm_track_peaks; 111 = + xm_wav_batch (additions never change the revision's meaning for older bindings).  A binding checks xm_version() >= the revision it was written against. */
+ * 103 = + xm_nnpool_global_avg_backward_accum; 104 = + xm_nnconv_backward_filter_bnrelupool, xm_nndropout_forward / _apply, xm_resample, xm_se_tail_backward_reduce / _apply, xm_se_squeeze_bn, xm_scale_axpy_bn; 105 = + xm_set_exec_hint / xm_get_exec_hint; 106 = + xm_nnconv_bnorm_relu_pool_forward, xm_stem_gram, xm_stem_gram_moments, xm_nnconv_backward_filter_bnrelupool_gram; 107 = + xm_nnaffinegrid / _backward, xm_nnbilinearsampler / _backward, xm_ferplus_batch; 108 = + XM_AGG_PEAK, xm_mnrfit, xm_mnrval; 109 = + xm_roc, xm_roc_launches, xm_label_hist; 110 = + xm_group_rows, xm_gather_rows, xm_scatter_rows, xm_track_peaks; 111 = + xm_wav_batch; 112 = + xm_spec_bucket_batch (additions never change the revision's meaning for older bindings).  A binding checks xm_version() >= the revision it was written against. */
 int xm_version(void);
 const char *xm_last_error(void);
 /* Device memory for hosts that have no device-array type of their own (MATLAB's gpuArray is CUDA-only: on an
@@ -438,6 +438,26 @@ int xm_resample(const float *x, int Lx, const float *h, int Lh, int p, int q, in
  * length, a NULL tensor with N > 0 (noise may be NULL when noise_len == 0); XM_ETOOBIG: N > 65535; N == 0: XM_OK. */
 int xm_wav_batch(const float *wav, long long wav_len, const float *noise, long long noise_len, const long long *desc,
                  const float *ratio, int N, float *z, int L, void *stream);
+/* The whole-clip front-end of external/compute_audio_feats.m:160-185 for N clips of different lengths (ABI 112): runSpec,
+ * mean / unbiased std of every frequency row over ALL frames of the clip, centre crop to the bucket width.  wav is the
+ * device bank of xm_wav_batch (wav_len samples); desc holds {src, len, f0} per clip (int64, device, contiguous); bank is
+ * the device filter bank of batch.runSpec, taps x 2B with the tap fastest (taps = Nw + 1: pre-emphasis * Hamming window
+ * * DFT, column b = Re of bin b, column B + b = Im), hop = Ns.  With T = floor((len - Nw) / hop) + 1:
+ *   frame j covers samples src + hop j - 1 .. src + hop j + Nw - 1; the sample in front of src is ZERO (filter([1 -a],
+ *   1, z) starts from rest), samples at or beyond src + len are never read;
+ *   mag(b, j) = |sum_k bank(k, b) s(k) + i sum_k bank(k, B + b) s(k)|, j = 0 .. T - 1;
+ *   mu(b), sd(b) = mean and unbiased std of mag(b, :) over all T frames;
+ *   out(b, i, 1, n) = (mag(b, f0 + i) - mu(b)) / sd(b), i = 0 .. rsize - 1; out is B x rsize x 1 x N.
+ * Every output element is written exactly once; clip n depends on its own descriptor only (the grouping of its partial
+ * statistics follows the tile list of the call: they are merged in fp64, so the output moves by less than fp32
+ * resolves).  Four launches whatever N and the lengths are, no tuning entries, no atomics, scratch from the stream's
+ * workspace (transposed bank, tile list, partial statistics, the N rsize B magnitudes of the crops).  A read outside
+ * [0, wav_len) yields 0 and never reaches memory; frames of the crop outside [0, T) count as magnitude 0; T < 2 gives
+ * NaN as std() of one sample does; len is cut at 2^31.  XM_EINVAL: N < 0, rsize <= 0, a negative bank length, taps < 2,
+ * hop < 2, B <= 0, a NULL tensor with N > 0; XM_ETOOBIG: N > 65535; XM_ENOTSUP: B != 512 or a 64-frame sample span
+ * beyond 64 KB; N == 0: XM_OK. */
+int xm_spec_bucket_batch(const float *wav, long long wav_len, const long long *desc, int N, int rsize, const float *bank,
+                         int taps, int hop, int B, float *out, void *stream);
 /* |STFT| from the output of the framing convolution (runSpec of getBatchEmoVoxCeleb.m:162 [EXT VGGVox]):
  * reim is 1 x Wo x 2B x N (channel b = Re of bin b, channel B+b = Im), out is B x Wo x 1 x N with
  * out(b, j, 1, n) = sqrt(Re^2 + Im^2).  The framing/windowing/pre-emphasis/DFT itself is one

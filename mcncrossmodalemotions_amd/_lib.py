@@ -106,6 +106,7 @@ SIGNATURES = {
     "xm_spec_magnitude": [c_fp, _i, _i, _i, c_fp, _vp],
     "xm_resample": [c_fp, _i, c_fp, _i, _i, _i, _i, c_fp, _i, _vp],
     "xm_wav_batch": [c_fp, C.c_longlong, c_fp, C.c_longlong, c_fp, c_fp, _i, c_fp, _i, _vp],
+    "xm_spec_bucket_batch": [c_fp, C.c_longlong, c_fp, _i, _i, c_fp, _i, _i, _i, c_fp, _vp],
     "xm_aggregate_logits": [c_fp, _i, _i, c_fp, c_fp, _i, _i, c_fp, c_fp, _vp],
     "xm_max_label": [c_fp, _i, _i, c_fp, _vp],
     "xm_class_stats": [c_fp, c_fp, _i, _i, c_fp, c_fp, _vp],

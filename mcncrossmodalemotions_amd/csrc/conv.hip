@@ -426,6 +426,9 @@ struct ProfScope {
     g_prof.push_back(r);
   }
 };
+// the same scope for launches of the other translation units (spec.hip); nullptr while the profiler is off
+void *prof_open(int key, double flops, hipStream_t st) { return g_prof_on ? new ProfScope(key, flops, st) : nullptr; }
+void prof_close(void *scope) { delete (ProfScope *)scope; }
 
 
 // co-resident blocks per CU of the register-staged configurations (VGPR-limited: 222 / 232 / 186 / 140 / 116 / 134 / 122 /
@@ -2439,6 +2442,11 @@ int xm_prof_collect_bytes(int cap, int *keys, double *total_bytes) {
 // human-readable kernel name of a profiler key, matching the rocprofv3 kernel-trace name
 int xm_prof_kernel_name(int key, char *buf, int len) {
   int kind = key / 100;
+  if (kind == 20) {   // spec.hip
+    static const char *const names[4] = {"spec_bank_kernel", "spec_plan_kernel", "spec_gemm_kernel", "spec_finish_kernel"};
+    snprintf(buf, len, "%s", names[key % 100 < 4 ? key % 100 : 0]);
+    return XM_OK;
+  }
   if (kind == 3 || kind == 4) {
     const int v = key % 100;
     snprintf(buf, len, "%s<%s, %d>", kind == 3 ? "conv_halo_kernel" : "conv_halo_multi_kernel",

@@ -3,6 +3,8 @@
     compute_audio_feats   external/compute_audio_feats.m:96-136,160-185
         variable-width student inference: per clip, row-normalise the whole spectrogram, centre-crop to
         the largest bucket width <= T, resize `pool6` to that bucket, one test-mode forward.
+    compute_audio_feats_wav  the same from the waveform bank: audio_feats_plan on the host, then per bucket one
+        xm_spec_bucket_batch call (whole-clip STFT, row statistics, crop) and one forward.
     compute_visual_feats  external/compute_visual_feats.m:60-116
         frozen teacher over the flattened frames of all tracks in minibatches, logits split per track.
 
@@ -152,6 +154,66 @@ def compute_audio_feats(dag, specs, numEmotions=8, batch_by_bucket=False, use_gr
             continue
         dag.eval([inp, x])
         pending.append((idx, dag.vars[out_name].value))
+    for idx, val in pending:
+        out = vl.to_numpy(val).reshape(-1, len(idx), order="F")   # squeeze: E x N
+        logits[idx, :] = out.T[:, :numEmotions]
+    return logits
+
+
+def audio_feats_plan(lengths, offsets, fs=16000, Tw=25, Ts=10):
+    """The host side of compute_audio_feats_wav; touches no device.  lengths / offsets: samples and first sample in the
+    waveform bank of every clip.  Per clip T = floor((len - Nw) / Ns) + 1, the bucket (largest BUCKETS_WIDTH <= T;
+    compute_audio_feats.m:181) and the first frame of the centre crop f0 = rstart - 1, rstart = round((T - rsize) / 2)
+    with halves rounded away from zero and 0 turned into 1 (:182-183).  Returns (T, rsize, f0, groups): three int64
+    arrays and groups = [(rsize, clip indices, desc)] in ascending bucket order, clip order kept inside a bucket, desc
+    the N x 3 {src, len, f0} table of vl.spec_bucket_batch.  A clip with fewer frames than the smallest bucket raises
+    the ValueError of test_getinput."""
+    lengths = np.asarray(lengths, np.int64).reshape(-1)
+    offsets = np.asarray(offsets, np.int64).reshape(-1)[:lengths.size]
+    if offsets.size != lengths.size:
+        raise ValueError("audio_feats_plan: one offset per clip is required")
+    Nw, Ns = int(round(1e-3 * Tw * fs)), int(round(1e-3 * Ts * fs))
+    T = np.where(lengths >= Nw, (lengths - Nw) // Ns + 1, 0).astype(np.int64)
+    widths = np.asarray(BUCKETS_WIDTH, np.int64)
+    if T.size and T.min() < widths[0]:
+        raise ValueError("empty audio clip: %d frames, the smallest bucket needs %d" % (int(T.min()), int(widths[0])))
+    rsize = widths[np.searchsorted(widths, T, side="right") - 1] if T.size else np.zeros(0, np.int64)
+    rstart = (T - rsize + 1) // 2
+    f0 = np.maximum(rstart, 1) - 1
+    groups = []
+    for w in np.unique(rsize):
+        idx = np.nonzero(rsize == w)[0]
+        groups.append((int(w), idx, np.stack([offsets[idx], lengths[idx], f0[idx]], 1)))
+    return T, rsize, f0, groups
+
+
+def compute_audio_feats_wav(dag, wav, offsets, numEmotions=8, limit=float("inf"), maxBatch=64):
+    """logits = compute_audio_feats from the waveforms (compute_audio_feats.m:91-136,160-185): `wav` is the device bank
+    of all clips back to back, `offsets` their first samples plus the bank's length (imdb.device_wav_bank).  The clips
+    are planned on the host (audio_feats_plan); per bucket and chunk of `maxBatch` clips ONE vl.spec_bucket_batch call
+    makes the normalised, cropped 512 x rsize x 1 x n input and ONE test-mode forward with pool6 resized follows.  The
+    logits are read back once at the end.  `limit`: only the clips with id <= firstId + limit are processed (:91-93;
+    ids 1, 2, ...: the first limit + 1 clips)."""
+    inp, ind1 = _prepare(dag)
+    if ind1 is None:
+        raise ValueError("the audio model has no pool6 layer")
+    out_name = list(dag.vars)[-1]                    # "risky use of end variable", :127
+    dag.vars[out_name].precious = True
+    offsets = np.asarray(offsets, np.int64).reshape(-1)
+    numKeep = offsets.size - 1
+    if limit != float("inf"):
+        numKeep = max(0, min(numKeep, int(limit) + 1))
+    lengths = np.diff(offsets)[:numKeep]
+    _, _, _, groups = audio_feats_plan(lengths, offsets[:numKeep])
+    logits = np.zeros((numKeep, numEmotions), np.float32)
+    pending = []                                     # (clip indices, device logits) -- read back once
+    maxBatch = max(1, int(maxBatch))
+    for rsize, idx, desc in groups:
+        dag.layers[ind1].block.poolSize = [1, BUCKETS_POOL[BUCKETS_WIDTH.index(rsize)]]    # :119
+        for s in range(0, len(idx), maxBatch):
+            x = vl.spec_bucket_batch(wav, desc[s:s + maxBatch], rsize)
+            dag.eval([inp, x])
+            pending.append((idx[s:s + maxBatch], dag.vars[out_name].value))
     for idx, val in pending:
         out = vl.to_numpy(val).reshape(-1, len(idx), order="F")   # squeeze: E x N
         logits[idx, :] = out.T[:, :numEmotions]

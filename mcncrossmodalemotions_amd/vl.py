@@ -855,6 +855,44 @@ def wav_batch(wav, noise, desc, ratio, L):
     return z.t()
 
 
+def spec_bucket_batch(wav, desc, rsize, audio=None):
+    """The 512 x rsize x 1 x N input of the student for N whole clips of one width bucket (xm_spec_bucket_batch;
+    compute_audio_feats.m:160-185): runSpec of every clip, its rows normalised by their mean / std over ALL T frames of
+    the clip, the rsize frames from f0 on.  wav: the 1-D device bank; desc: N x 3 int64 HOST array {src, len, f0} per
+    clip -- checked here ([src, src + len) inside the bank, 0 <= f0, f0 + rsize <= T = floor((len - Nw) / Ns) + 1;
+    ValueError otherwise) and sent up in ONE pinned, non-blocking upload.  `audio` as for batch.runSpec; both use the
+    same device filter bank."""
+    from . import batch as xbatch
+    a = dict(fs=16000, Tw=25, Ts=10, alpha=0.97)
+    a.update({k: v for k, v in (audio or {}).items() if k in a})
+    Nw, Ns = int(round(1e-3 * a["Tw"] * a["fs"])), int(round(1e-3 * a["Ts"] * a["fs"]))
+    desc = np.ascontiguousarray(desc, dtype=np.int64)
+    rsize = int(rsize)
+    if desc.ndim != 2 or desc.shape[1] != 3:
+        raise ValueError("spec_bucket_batch: DESC must be N x 3")
+    if rsize <= 0:
+        raise ValueError("spec_bucket_batch: RSIZE must be positive")
+    if wav is None or _chk(wav, "WAV").dim() != 1 or not wav.is_contiguous():
+        raise ValueError("spec_bucket_batch: WAV must be a contiguous 1-D bank")
+    N, wav_len = int(desc.shape[0]), int(wav.numel())
+    src, ln, f0 = (desc[:, i] for i in range(3))
+    if N and not ((ln >= 0).all() and (src >= 0).all() and (src + ln <= wav_len).all()):
+        raise ValueError("spec_bucket_batch: a clip's [src, src + len) leaves the waveform bank")
+    T = np.where(ln >= Nw, (ln - Nw) // Ns + 1, 0)
+    if N and not ((f0 >= 0).all() and (f0 + rsize <= T).all()):
+        raise ValueError("spec_bucket_batch: a clip's frames [f0, f0 + rsize) leave its spectrogram")
+    nfft = 1024
+    bank = xbatch._spec_filter_bank(a["fs"], a["Tw"], a["Ts"], a["alpha"], nfft, wav.device)
+    out = mat_empty(nfft // 2, rsize, 1, N, device=wav.device)
+    if N:
+        host = torch.empty(3 * N, dtype=torch.int64, pin_memory=True)
+        host.numpy()[:] = desc.reshape(-1)
+        up = host.to(wav.device, non_blocking=True)
+        _lib.check(_L().xm_spec_bucket_batch(_ptr(wav), wav_len, C.c_void_p(up.data_ptr()), N, rsize, _ptr(bank), Nw + 1, Ns,
+                                             nfft // 2, _ptr(out), _stream()))
+    return out
+
+
 _AGG = {"max": 0, "mean": 1, "peak": 2}   # XM_AGG_MAX / XM_AGG_MEAN / XM_AGG_PEAK
 
 

@@ -1,0 +1,133 @@
+#!/usr/bin/env python
+"""The whole-clip audio front-end of compute_audio_feats, clip by clip and batched.
+usage: python tools/spec_bucket_bench.py [--clips 256] [--reps 7]
+`clips` whole clips of as many DISTINCT lengths between 2 and 12 s (seeded 0.1 * randn, back to back in one bank) go
+from samples to the bucket batches the student's forward takes, by two paths that alternate in one process:
+  per-clip  what student_stats does today: batch.runSpec per clip (framing convolution + magnitude kernel),
+            external.test_getinput (row statistics over the whole clip, centre crop), a copy into the bucket's batch.
+            The first repetition meets every length for the first time (`cold`: the convolution's tile tuner measures
+            each new input width); the later ones are `warm`.
+  batched   external.audio_feats_plan on the host, then ONE vl.spec_bucket_batch call per bucket; `device` is the event
+            time around the same calls, `gemm` the time of spec_gemm_kernel alone from the library's profiler hooks.
+Wall times are host clocks around work that ends in a device synchronise."""
+import argparse
+import ctypes as C
+import os
+import statistics
+import sys
+import time
+
+import numpy as np
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+from mcncrossmodalemotions_amd import _lib, batch, external, vl  # noqa: E402
+
+FS, NW, NS = 16000, 400, 160
+
+
+def wall(fn):
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    out = fn()
+    torch.cuda.synchronize()
+    return (time.perf_counter() - t0) * 1e3, out
+
+
+def device_ms(fn):
+    s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    torch.cuda.synchronize()
+    s.record()
+    fn()
+    e.record()
+    torch.cuda.synchronize()
+    return s.elapsed_time(e)
+
+
+def per_clip(wav, offs):
+    """{rsize: 512 x rsize x 1 x n batch}, clip order kept inside a bucket -- compute_audio_feats' batch_by_bucket input"""
+    prepared = [external.test_getinput(batch.runSpec(wav[offs[i]:offs[i + 1]])[:, :, 0, 0]) for i in range(len(offs) - 1)]
+    groups = {}
+    for i, (_, rsize) in enumerate(prepared):
+        groups.setdefault(rsize, []).append(i)
+    out = {}
+    for rsize, idx in sorted(groups.items()):
+        x = vl.mat_empty(512, rsize, 1, len(idx), device=wav.device)
+        for k, i in enumerate(idx):
+            x[:, :, :, k].copy_(prepared[i][0][:, :, :, 0])
+        out[rsize] = x
+    return out
+
+
+def batched(wav, offs):
+    _, _, _, groups = external.audio_feats_plan(np.diff(offs), offs[:-1])
+    return {rsize: vl.spec_bucket_batch(wav, desc, rsize) for rsize, _, desc in groups}
+
+
+def gemm_ms(L, fn):
+    L.xm_prof_enable(1)
+    fn()
+    torch.cuda.synchronize()
+    L.xm_prof_enable(0)
+    cap = 32
+    keys, ms, fl, cnt = (C.c_int * cap)(), (C.c_double * cap)(), (C.c_double * cap)(), (C.c_longlong * cap)()
+    n = L.xm_prof_collect(cap, keys, ms, fl, cnt)
+    for i in range(min(n, cap)):
+        buf = C.create_string_buffer(128)
+        L.xm_prof_kernel_name(keys[i], buf, 128)
+        if buf.value.decode() == "spec_gemm_kernel":
+            return float(ms[i])
+    return float("nan")
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--clips", type=int, default=256)
+    ap.add_argument("--reps", type=int, default=7)
+    a = ap.parse_args()
+    dev = torch.device("cuda", 0)
+    torch.cuda.set_device(0)
+    L = _lib.load()
+    rng = np.random.default_rng(5)
+    lengths = rng.permutation(np.unique(np.linspace(2 * FS, 12 * FS - 37, a.clips).astype(np.int64) + 37))
+    assert lengths.size == a.clips
+    offs = np.concatenate([[0], np.cumsum(lengths)]).astype(np.int64)
+    g = torch.Generator(device=dev)
+    g.manual_seed(5)
+    wav = torch.randn(int(offs[-1]), generator=g, device=dev, dtype=torch.float32) * 0.1
+    frames = int(((lengths - NW) // NS + 1).sum())
+    flop = frames * 2.0 * (NW + 1) * 1024
+    print("%d clips of %d distinct lengths, %.1f .. %.1f s, %d frames in all (%.1f GFLOP of STFT), %d repetitions, ms"
+          % (a.clips, len(set(lengths.tolist())), lengths.min() / FS, lengths.max() / FS, frames, flop / 1e9, a.reps))
+    tot0, new0 = C.c_int(0), C.c_int(0)
+    L.xm_tune_entries(C.byref(tot0), C.byref(new0))
+    rows, cold, diff = [], None, 0.0
+    for rep in range(a.reps + 1):
+        t_clip, x1 = wall(lambda: per_clip(wav, offs))
+        t_bat, x2 = wall(lambda: batched(wav, offs))
+        t_dev = device_ms(lambda: batched(wav, offs))
+        t_gemm = gemm_ms(L, lambda: batched(wav, offs))
+        assert sorted(x1) == sorted(x2)
+        diff = max([diff] + [float((x1[k] - x2[k]).abs().max()) for k in x1])
+        if rep == 0:
+            cold = (t_clip, t_bat)
+            tot1, new1 = C.c_int(0), C.c_int(0)
+            L.xm_tune_entries(C.byref(tot1), C.byref(new1))
+        else:
+            rows.append((t_clip, t_bat, t_dev, t_gemm))
+    med = [statistics.median(r[i] for r in rows) for i in range(4)]
+    lo = [min(r[i] for r in rows) for i in range(4)]
+    hi = [max(r[i] for r in rows) for i in range(4)]
+    print("buckets: %s" % ", ".join("%d x %d" % (k, int(v.shape[3])) for k, v in sorted(x2.items())))
+    print("first repetition (cold): per-clip %.1f, batched %.3f; tuning entries %d -> %d" %
+          (cold[0], cold[1], tot0.value, tot1.value))
+    print("%-22s %10s %10s %10s" % ("warm repetitions", "median", "min", "max"))
+    for name, i in (("per-clip (wall)", 0), ("batched (wall)", 1), ("batched (device)", 2), ("spec_gemm_kernel", 3)):
+        print("%-22s %10.3f %10.3f %10.3f" % (name, med[i], lo[i], hi[i]))
+    print("per-clip / batched (warm medians): %.1fx; max |diff| between the two: %.3e" % (med[0] / med[1], diff))
+    print("spec_gemm_kernel: %.1f TFLOP/s of the 157.3 fp32-MFMA peak (%.0f %%)" %
+          (flop / med[3] / 1e9, 100 * flop / med[3] / 1e9 / 157.3))
+
+
+if __name__ == "__main__":
+    main()
