@@ -57,7 +57,7 @@ enum { XM_FUSE_RELU = 1, XM_BN_BATCH_MOMENTS = 2, XM_FUSE_SIGMOID = 4 };
 
 /* ABI revision: 100 = round 1; 101 = xm_nnbnorm_relu_pool_backward gained `y_pool`, exchange entry points return
  * XM_EINVAL without a communicator; 102 = + xm_nnconv_forward_moments, xm_nnbnorm_backward_dxsum, xm_nnconv_forward_gated;
- * 103 = + xm_nnpool_global_avg_backward_accum; 104 = + xm_nnconv_backward_filter_bnrelupool, xm_nndropout_forward / _apply, xm_resample, xm_se_tail_backward_reduce / _apply, xm_se_squeeze_bn, xm_scale_axpy_bn; 105 = + xm_set_exec_hint / xm_get_exec_hint; 106 = + xm_nnconv_bnorm_relu_pool_forward, xm_stem_gram, xm_stem_gram_moments, xm_nnconv_backward_filter_bnrelupool_gram; 107 = + xm_nnaffinegrid / _backward, xm_nnbilinearsampler / _backward, xm_ferplus_batch; 108 = + XM_AGG_PEAK, xm_mnrfit, xm_mnrval; 109 = + xm_roc, xm_roc_launches, xm_label_hist; 110 = + xm_group_rows, xm_gather_rows, xm_scatter_rows, xm_track_peaks; 111 = + xm_wav_batch; 112 = + xm_spec_bucket_batch (additions never change the revision's meaning for older bindings).  A binding checks xm_version() >= the revision it was written against. */
+ * 103 = + xm_nnpool_global_avg_backward_accum; 104 = + xm_nnconv_backward_filter_bnrelupool, xm_nndropout_forward / _apply, xm_resample, xm_se_tail_backward_reduce / _apply, xm_se_squeeze_bn, xm_scale_axpy_bn; 105 = + xm_set_exec_hint / xm_get_exec_hint; 106 = + xm_nnconv_bnorm_relu_pool_forward, xm_stem_gram, xm_stem_gram_moments, xm_nnconv_backward_filter_bnrelupool_gram; 107 = + xm_nnaffinegrid / _backward, xm_nnbilinearsampler / _backward, xm_ferplus_batch; 108 = + XM_AGG_PEAK, xm_mnrfit, xm_mnrval; 109 = + xm_roc, xm_roc_launches, xm_label_hist; 110 = + xm_group_rows, xm_gather_rows, xm_scatter_rows, xm_track_peaks; 111 = + xm_wav_batch; 112 = + xm_spec_bucket_batch; 113 = + xm_jpeg_plan, xm_jpeg_decode_batch (additions never change the revision's meaning for older bindings).  A binding checks xm_version() >= the revision it was written against. */
 int xm_version(void);
 const char *xm_last_error(void);
 /* Device memory for hosts that have no device-array type of their own (MATLAB's gpuArray is CUDA-only: on an
@@ -645,6 +645,51 @@ int xm_nnbilinearsampler_backward(const float *x, int H, int W, int C, int N, co
  * coordinates are the same bits). */
 int xm_ferplus_batch(const float *grey, int H, int W, int N, const int *flip, const float *A, int Ho, int Wo,
                      const float *avg3, float *out, void *stream);
+
+/* vl_imreadjpeg(paths, 'Pack', 'Interpolation', 'bilinear', 'CropSize', 1/1.6, 'CropLocation', 'center', 'Resize',
+ * imageSize) of fetch_emovoxceleb_imdb.m:160-172 and compute_visual_feats.m:130-143 for a batch of files, decoded on the
+ * device (ABI 113).  Supported: baseline sequential DCT (SOF0), 8-bit, Huffman, one interleaved scan; one component
+ * (grey; R = G = B = Y) or three (YCbCr) with luma sampling 1x1, 2x1 or 2x2 and chroma 1x1; any DQT / DHT tables with
+ * 8-bit quantiser entries; restart intervals; 1 x 1 up to 4096 x 4096 per image and fewer than 2^31 coefficients and
+ * pixel values per batch.  The arithmetic is libjpeg's default integer path (ISLOW IDCT with 13-bit constants and
+ * PASS1_BITS 2, "fancy" triangle upsampling for h2v1 / h2v2 -- replication where the chroma plane has one or two
+ * columns --, 16-bit fixed-point YCbCr -> RGB with range limiting): results are equal to libjpeg's, not close.  There
+ * is no host decode.
+ *
+ * xm_jpeg_plan: host only, no device call (usable without a GPU).  File i is bytes[offsets[i] .. offsets[i + 1]).
+ *   desc    N rows of XM_JPEG_DESC int64: 0, 1 byte range of the entropy data in `bytes`; 2 H; 3 W; 4 components (1 | 3);
+ *           5, 6 luma sampling h, v; 7 restart interval in MCUs (0 = none); 8, 9 MCUs across, down; 10-12 quantiser
+ *           table slot per component; 13-15 DC and 16-18 AC Huffman table slot per component (a grey image repeats
+ *           component 0); 19 first coefficient (int16 elements), 20 first plane byte, 21 first pixel value (floats) of
+ *           the image in the ragged device buffers; 22 first lane, 23 number of lanes
+ *   lanes   XM_JPEG_LANE int64 per restart interval (one per image without DRI): image, byte range, first MCU
+ *   tables  nq quantiser tables of XM_JPEG_QT_BYTES (64 uint16, row-major) then nh Huffman tables of XM_JPEG_HT_BYTES
+ *           (lookahead uint16[256] = code length << 8 | symbol for codes of up to 8 bits, symbols uint8[256],
+ *           maxcode int32[17], valoff int32[17] as jpeg_make_d_derived_tbl, zero padding); equal tables share a slot
+ *   sizes   XM_JPEG_SIZES int64: table bytes, nq, nh, coefficients, plane bytes, pixel values, lanes, N
+ * XM_ENOTSUP (valid file this build does not decode: progressive, arithmetic, 12-bit, multi-scan, 4 components, Adobe
+ * transform 0, other sampling factors, 16-bit quantiser tables, larger than the limit) and XM_EINVAL (malformed: no
+ * SOI, cut inside its headers, bad segment, missing table) name the index of the file.  A file whose entropy data is
+ * cut short is planned; decoding it reports XM_JPEG_TRUNCATED.  XM_ENOMEM: lanes_cap / tables_cap too small, `sizes`
+ * holds what is needed.  XM_EINVAL: NULL or negative arguments.
+ *
+ * xm_jpeg_decode_batch: device.  bytes (16-byte aligned, allocated up to the next multiple of 16 past nbytes), desc,
+ * lanes and tables (16-byte aligned) are the uploaded outputs of the plan.  pixels (optional): pixel_floats single,
+ * image i as H x W x 3 with values 0..255 in MATLAB layout at desc[i][21] -- vl_imreadjpeg without 'Resize'.  faces
+ * (optional): Ho x Wo x 3 x N, per image bit for bit xm_crop_resize_face of its pixels (centre crop of relative size
+ * `crop`, bilinear resize, uint8 rounding, rgb2gray, x3, minus avg3 -- HOST pointer; avg3 == NULL: the resized R, G, B
+ * instead).  status: N int32, a bit set of XM_JPEG_TRUNCATED (bits past the end of the image's entropy data were used;
+ * the reader yields zeros there) and XM_JPEG_BADCODE (an invalid Huffman code or a run past coefficient 63 ended a
+ * lane).  Four launches, five with faces, whatever N and the sizes are; no synchronisation.  Every read of file bytes
+ * is clamped to the image's byte range and every coefficient write to the image's blocks by the indexing itself. */
+enum { XM_JPEG_OK = 0, XM_JPEG_TRUNCATED = 1, XM_JPEG_BADCODE = 2 };
+enum { XM_JPEG_DESC = 24, XM_JPEG_LANE = 4, XM_JPEG_QT_BYTES = 128, XM_JPEG_HT_BYTES = 1024, XM_JPEG_SIZES = 8 };
+int xm_jpeg_plan(const unsigned char *bytes, const long long *offsets, int N, long long *desc, long long *lanes,
+                 long long lanes_cap, unsigned char *tables, long long tables_cap, long long *sizes);
+int xm_jpeg_decode_batch(const unsigned char *bytes, long long nbytes, const long long *desc, int N, const long long *lanes,
+                         int nlanes, const unsigned char *tables, int nq, int nh, long long coef_elems,
+                         long long plane_bytes, long long pixel_floats, float *pixels, float *faces, float crop, int Ho,
+                         int Wo, const float *avg3, int *status, void *stream);
 
 #ifdef __cplusplus
 }

@@ -254,6 +254,36 @@ class SyntheticDenseFrames:
         return raw.permute(3, 2, 1, 0)
 
 
+class JpegDenseFrames(SyntheticDenseFrames):
+    """The dense face frames as JPEG files held in memory: the `lister` / `find` interface of SyntheticDenseFrames over a
+    {path: bytes} table, and read(paths) -> list of bytes for buildImdb(read=...) / getImageBatch.  `files` is a list of
+    JPEG files (bytes); frame j of the track with id i is files[(7 i + j) mod len(files)], so the frames of one track and
+    of one batch differ in size when the files do.  index(path) names the file behind a listed path."""
+
+    def __init__(self, imdb, files, frameless=(), unclaimed=0):
+        super().__init__(imdb, frameless=frameless, unclaimed=unclaimed)
+        self.files = [bytes(f) for f in files]
+        if not self.files:
+            raise ValueError("JpegDenseFrames: no files")
+        self.table, self._index = {}, {}
+
+    def lister(self, track):
+        paths = super().lister(track)
+        for j, p in enumerate(paths):
+            self._index[p] = (7 * int(track["id"]) + j) % len(self.files)
+            self.table[p] = self.files[self._index[p]]
+        return paths
+
+    def index(self, path):
+        return self._index[path]
+
+    def read(self, paths):
+        return [self.table[p] for p in paths]
+
+    def __call__(self, paths, device=None):
+        raise RuntimeError("JpegDenseFrames holds files, not pixels: use buildImdb(read=frames.read)")
+
+
 def crop_window(total_samples, audSamp, fs, num_logit_rows, rng, fixedSegments=False, timeOffset=None):
     """(wr, startIdx, endIdx) of one clip, all 1-based as in cnn_get_batch_wav_emo (getBatchEmoVoxCeleb.m:81-152):
     wr is the first sample audioread takes, [startIdx, endIdx] the rows of the cached logits that are aggregated.

@@ -2447,6 +2447,12 @@ int xm_prof_kernel_name(int key, char *buf, int len) {
     snprintf(buf, len, "%s", names[key % 100 < 4 ? key % 100 : 0]);
     return XM_OK;
   }
+  if (kind == 21) {   // jpeg.hip
+    static const char *const names[5] = {"jpeg_clear_kernel", "jpeg_entropy_kernel", "jpeg_idct_kernel", "jpeg_colour_kernel",
+                                         "crop_resize_face_ragged_kernel"};
+    snprintf(buf, len, "%s", names[key % 100 < 5 ? key % 100 : 0]);
+    return XM_OK;
+  }
   if (kind == 3 || kind == 4) {
     const int v = key % 100;
     snprintf(buf, len, "%s<%s, %d>", kind == 3 ? "conv_halo_kernel" : "conv_halo_multi_kernel",

@@ -1,0 +1,706 @@
+// Baseline JPEG decode of a batch of face frames on gfx950: what vl_imreadjpeg does in front of the frozen teacher
+// (emoVoxCeleb/fetch_emovoxceleb_imdb.m:160-172, external/compute_visual_feats.m:130-143), with libjpeg's default
+// integer arithmetic (ISLOW IDCT, fancy chroma upsampling, 16-bit fixed-point YCbCr -> RGB), so results are compared
+// for equality.  include/xmodal.h documents the descriptor, lane and table layouts.
+//
+// xm_jpeg_plan (host, no device call) parses the headers, splits the entropy data at the RSTn markers into lanes, builds
+// the quantiser and Huffman lookup tables (shared between images with equal tables) and lays the ragged buffers out.
+// xm_jpeg_decode_batch enqueues a fixed number of launches, whatever N and the sizes are:
+//   jpeg_clear_kernel    zeroes the coefficients (the entropy kernel writes only the non-zero ones) and the status
+//   jpeg_entropy_kernel  one lane per restart interval (per image without DRI), kJpegLanes lanes per 64-thread block:
+//                        lanes diverge by design, so a wave carries few of them and the grid has many waves.  The
+//                        block's threads copy each lane's six Huffman tables into LDS; a lane reads its bytes in
+//                        16-byte pieces held in registers, unstuffs FF 00 and feeds a 64-bit accumulator.  A byte
+//                        position outside the lane's range -- itself clamped to the image's range and the buffer --
+//                        yields zero bits; using one sets TRUNCATED.  A block index comes from the MCU counter and is
+//                        below the image's block count, a coefficient index is at most 63; an invalid code or a run past
+//                        63 sets BADCODE and ends the lane.
+//   jpeg_idct_kernel     one thread per 8 x 8 block: dequantise, jpeg_idct_islow in int32 (13-bit constants,
+//                        PASS1_BITS 2), range limit, eight 8-byte stores into the component's uint8 plane
+//   jpeg_colour_kernel   one thread per pixel: triangle upsampling of the chroma (h2v1 / h2v2, edges replicated, planes
+//                        of one or two columns replicated as libjpeg does), YCbCr -> RGB, cropped to H x W, written as
+//                        H x W x 3 single in MATLAB layout
+//   crop_resize_face_ragged_kernel (misc.hip, next to the kernel it must equal bit for bit)   the teacher's input
+#include <algorithm>
+#include <vector>
+
+#include "xm_common.h"
+
+namespace xm {
+
+constexpr int kJpegDesc = XM_JPEG_DESC, kJpegLane = XM_JPEG_LANE;
+constexpr int kQtBytes = XM_JPEG_QT_BYTES, kHtBytes = XM_JPEG_HT_BYTES;
+constexpr int kJpegLanes = 4;        // lanes per 64-thread block of the entropy kernel
+constexpr int kJpegMaxSide = 4096;   // H, W <= 4096
+
+// descriptor columns
+enum { D_SCAN0 = 0, D_SCAN1, D_H, D_W, D_NCOMP, D_HS, D_VS, D_RI, D_MX, D_MY, D_QT, D_DC = 13, D_AC = 16, D_COEF = 19,
+       D_PLANE, D_PIX, D_LANE0, D_NLANES };
+
+static const unsigned char kNatural[64] = {0,  1,  8,  16, 9,  2,  3,  10, 17, 24, 32, 25, 18, 11, 4,  5,  12, 19, 26, 33, 40, 48,
+                                           41, 34, 27, 20, 13, 6,  7,  14, 21, 28, 35, 42, 49, 56, 57, 50, 43, 36, 29, 22, 15, 23,
+                                           30, 37, 44, 51, 58, 59, 52, 45, 38, 31, 39, 46, 53, 60, 61, 54, 47, 55, 62, 63};
+__constant__ unsigned char kNaturalDev[64] = {0,  1,  8,  16, 9,  2,  3,  10, 17, 24, 32, 25, 18, 11, 4,  5,  12, 19, 26, 33, 40, 48,
+                                              41, 34, 27, 20, 13, 6,  7,  14, 21, 28, 35, 42, 49, 56, 57, 50, 43, 36, 29, 22, 15, 23,
+                                              30, 37, 44, 51, 58, 59, 52, 45, 38, 31, 39, 46, 53, 60, 61, 54, 47, 55, 62, 63};
+
+// ---- jpeg_clear_kernel ---------------------------------------------------------------------------------------------
+__global__ void __launch_bounds__(256) jpeg_clear_kernel(uint4 *__restrict__ coef, size_t n16, int *__restrict__ status, int N) {
+  const size_t tid = blockIdx.x * (size_t)256 + threadIdx.x, step = (size_t)gridDim.x * 256;
+  for (size_t i = tid; i < n16; i += step) coef[i] = make_uint4(0, 0, 0, 0);
+  for (size_t i = tid; i < (size_t)N; i += step) status[i] = XM_JPEG_OK;
+}
+
+// ---- jpeg_entropy_kernel -------------------------------------------------------------------------------------------
+struct BitReader {
+  const uint4 *base;     // the batch's bytes, 16-byte pieces
+  long long pos, end;    // next byte and the end of the lane's range (absolute offsets, inside the buffer)
+  long long cidx;        // which piece `chunk` holds
+  uint4 chunk;
+  unsigned long long acc;   // next bit at the top
+  int nbits, fake;          // bits in acc; zero bits appended past the end of the range (they sit at the tail)
+
+  __device__ __forceinline__ unsigned byte_at(long long p) {
+    if ((p >> 4) != cidx) {
+      cidx = p >> 4;
+      chunk = base[cidx];
+    }
+    const int w = (int)(p >> 2) & 3;
+    const unsigned v = w == 0 ? chunk.x : (w == 1 ? chunk.y : (w == 2 ? chunk.z : chunk.w));
+    return (v >> (((int)p & 3) * 8)) & 255u;
+  }
+  __device__ __forceinline__ void refill() {
+    while (nbits <= 56) {
+      unsigned b = 0;
+      if (pos < end) {
+        b = byte_at(pos++);
+        if (b == 0xFFu && pos < end) {
+          if (byte_at(pos) == 0) {
+            ++pos;                 // FF 00: a stuffed zero
+          } else {                 // a marker inside the range: the entropy data ends here
+            end = pos - 1;
+            pos = end;
+            b = 0;
+            fake = min(fake + 8, 1 << 30);
+          }
+        }
+      } else {
+        fake = min(fake + 8, 1 << 30);
+      }
+      acc |= (unsigned long long)b << (56 - nbits);
+      nbits += 8;
+    }
+  }
+  __device__ __forceinline__ void drop(int n) {
+    acc <<= n;
+    nbits -= n;
+  }
+  __device__ __forceinline__ int take(int n) {   // n in 0 .. 16
+    refill();
+    const int v = n ? (int)(acc >> (64 - n)) : 0;
+    drop(n);
+    return v;
+  }
+  __device__ __forceinline__ bool starved() const { return nbits < fake; }
+};
+
+// one Huffman table in LDS: lut[256] of (nbits << 8 | symbol), huffval[256], maxcode[17], valoff[17]
+__device__ __forceinline__ int huff_decode(const unsigned char *t, BitReader &br) {
+  br.refill();
+  const unsigned w = (unsigned)(br.acc >> 48);
+  const unsigned e = ((const unsigned short *)t)[w >> 8];
+  if (e >> 8) {
+    br.drop((int)(e >> 8));
+    return (int)(e & 255u);
+  }
+  const int *maxcode = (const int *)(t + 768), *valoff = (const int *)(t + 836);
+  for (int l = 9; l <= 16; ++l) {
+    const int code = (int)(w >> (16 - l));
+    if (code <= maxcode[l]) {
+      br.drop(l);
+      return t[512 + ((code + valoff[l]) & 255)];
+    }
+  }
+  return -1;
+}
+
+__device__ __forceinline__ int huff_extend(int v, int s) { return (s && v < (1 << (s - 1))) ? v - (1 << s) + 1 : v; }
+
+// one block: 0 = fine, else XM_JPEG_BADCODE.  `out` holds 64 zeroed coefficients in row-major order.
+__device__ __forceinline__ int decode_block(BitReader &br, const unsigned char *dc, const unsigned char *ac,
+                                            const unsigned char *nat, int &pred, short *__restrict__ out) {
+  int s = huff_decode(dc, br);
+  if (s < 0 || s > 15) return XM_JPEG_BADCODE;
+  pred += huff_extend(br.take(s), s);
+  out[0] = (short)pred;
+  int k = 1;
+  while (k < 64) {
+    const int rs = huff_decode(ac, br);
+    if (rs < 0) return XM_JPEG_BADCODE;
+    const int r = rs >> 4;
+    s = rs & 15;
+    if (s == 0) {
+      if (r != 15) break;
+      k += 16;
+      continue;
+    }
+    k += r;
+    if (k > 63) return XM_JPEG_BADCODE;
+    out[nat[k & 63]] = (short)huff_extend(br.take(s), s);
+    ++k;
+  }
+  return 0;
+}
+
+__global__ void __launch_bounds__(64)
+jpeg_entropy_kernel(const uint4 *__restrict__ bytes, long long nbytes, const long long *__restrict__ desc, int N,
+                    const long long *__restrict__ lanes, int nlanes, const unsigned char *__restrict__ huff,
+                    int nh, short *__restrict__ coef, int *__restrict__ status) {
+  __shared__ __attribute__((aligned(16))) unsigned char s_tab[kJpegLanes][6][kHtBytes];
+  __shared__ unsigned char s_nat[64];
+  const int tid = threadIdx.x;
+  s_nat[tid] = kNaturalDev[tid];
+  // every lane's tables: DC and AC of its three components (a grey image repeats component 0)
+  for (int j = tid; j < kJpegLanes * 6 * (kHtBytes / 16); j += 64) {
+    const int l = j / (6 * (kHtBytes / 16)), rem = j - l * (6 * (kHtBytes / 16));
+    const int tb = rem / (kHtBytes / 16), q = rem - tb * (kHtBytes / 16);
+    const long long gl = min((long long)blockIdx.x * kJpegLanes + l, (long long)nlanes - 1);
+    const long long img = min(max(lanes[gl * kJpegLane], 0LL), (long long)N - 1);
+    const long long slot = desc[img * kJpegDesc + (tb < 3 ? D_DC + tb : D_AC + tb - 3)];
+    const long long sl = min(max(slot, 0LL), (long long)nh - 1);
+    ((uint4 *)&s_tab[l][tb][0])[q] = ((const uint4 *)(huff + sl * kHtBytes))[q];
+  }
+  __syncthreads();
+  const long long gl = (long long)blockIdx.x * kJpegLanes + tid;
+  if (tid >= kJpegLanes || gl >= nlanes) return;
+  const long long img = min(max(lanes[gl * kJpegLane], 0LL), (long long)N - 1);
+  const long long *d = desc + img * kJpegDesc;
+  // the lane's byte range, inside the image's, inside the buffer
+  const long long i0 = min(max(d[D_SCAN0], 0LL), nbytes), i1 = min(max(d[D_SCAN1], i0), nbytes);
+  BitReader br;
+  br.base = bytes;
+  br.pos = min(max(lanes[gl * kJpegLane + 1], i0), i1);
+  br.end = min(max(lanes[gl * kJpegLane + 2], br.pos), i1);
+  br.cidx = -1;
+  br.chunk = make_uint4(0, 0, 0, 0);
+  br.acc = 0;
+  br.nbits = 0;
+  br.fake = 0;
+  const int ncomp = (int)d[D_NCOMP], hs = (int)d[D_HS], vs = (int)d[D_VS], mx = (int)d[D_MX], my = (int)d[D_MY];
+  const long long ri = d[D_RI], total = (long long)mx * my;
+  const long long mcu0 = min(max(lanes[gl * kJpegLane + 3], 0LL), total);
+  const long long stop = ri > 0 ? min(mcu0 + ri, total) : total;
+  const long long nbY = total * hs * vs, nblocks = nbY + (ncomp == 3 ? 2 * total : 0);
+  short *cbase = coef + d[D_COEF];
+  int pred0 = 0, pred1 = 0, pred2 = 0, st = 0;
+  for (long long mcu = mcu0; mcu < stop && !st; ++mcu) {
+    const int ym = (int)(mcu / mx), xm = (int)(mcu - (long long)ym * mx);
+    for (int blk = 0; blk < hs * vs && !st; ++blk) {
+      const int by = ym * vs + blk / hs, bx = xm * hs + blk % hs;
+      const long long b = (long long)by * (mx * hs) + bx;
+      if (b < nblocks) st = decode_block(br, s_tab[tid][0], s_tab[tid][3], s_nat, pred0, cbase + b * 64);
+    }
+    if (ncomp == 3 && !st) {
+      const long long b = nbY + mcu;
+      if (b < nblocks) st = decode_block(br, s_tab[tid][1], s_tab[tid][4], s_nat, pred1, cbase + b * 64);
+      if (!st && b + total < nblocks)
+        st = decode_block(br, s_tab[tid][2], s_tab[tid][5], s_nat, pred2, cbase + (b + total) * 64);
+    }
+    if (br.starved()) st |= XM_JPEG_TRUNCATED;
+  }
+  if (st) atomicOr(status + img, st);
+}
+
+// ---- jpeg_idct_kernel ----------------------------------------------------------------------------------------------
+// the image whose range [desc[i][col] / unit, desc[i + 1][col] / unit) holds g
+__device__ __forceinline__ int find_image(const long long *__restrict__ desc, int N, int col, long long unit, long long g) {
+  int lo = 0, hi = N - 1;
+  while (lo < hi) {
+    const int mid = (lo + hi + 1) >> 1;
+    if (desc[(long long)mid * kJpegDesc + col] / unit <= g) lo = mid; else hi = mid - 1;
+  }
+  return lo;
+}
+
+#define XM_IDCT_1D(x0, x1, x2, x3, x4, x5, x6, x7, SHIFT)                                                   \
+  {                                                                                                         \
+    int z2 = x2, z3 = x6;                                                                                   \
+    int z1 = (z2 + z3) * 4433;                                                                              \
+    int tmp2 = z1 - z3 * 15137, tmp3 = z1 + z2 * 6270;                                                      \
+    int tmp0 = (x0 + x4) * 8192, tmp1 = (x0 - x4) * 8192;                                                   \
+    const int tmp10 = tmp0 + tmp3, tmp13 = tmp0 - tmp3, tmp11 = tmp1 + tmp2, tmp12 = tmp1 - tmp2;           \
+    tmp0 = x7;                                                                                              \
+    tmp1 = x5;                                                                                              \
+    tmp2 = x3;                                                                                              \
+    tmp3 = x1;                                                                                              \
+    z1 = tmp0 + tmp3;                                                                                       \
+    z2 = tmp1 + tmp2;                                                                                       \
+    z3 = tmp0 + tmp2;                                                                                       \
+    int z4 = tmp1 + tmp3;                                                                                   \
+    const int z5 = (z3 + z4) * 9633;                                                                        \
+    tmp0 *= 2446;                                                                                           \
+    tmp1 *= 16819;                                                                                          \
+    tmp2 *= 25172;                                                                                          \
+    tmp3 *= 12299;                                                                                          \
+    z1 *= -7373;                                                                                            \
+    z2 *= -20995;                                                                                           \
+    z3 = z3 * -16069 + z5;                                                                                  \
+    z4 = z4 * -3196 + z5;                                                                                   \
+    tmp0 += z1 + z3;                                                                                        \
+    tmp1 += z2 + z4;                                                                                        \
+    tmp2 += z2 + z3;                                                                                        \
+    tmp3 += z1 + z4;                                                                                        \
+    const int rnd = 1 << ((SHIFT)-1);                                                                       \
+    x0 = (tmp10 + tmp3 + rnd) >> (SHIFT);                                                                   \
+    x7 = (tmp10 - tmp3 + rnd) >> (SHIFT);                                                                   \
+    x1 = (tmp11 + tmp2 + rnd) >> (SHIFT);                                                                   \
+    x6 = (tmp11 - tmp2 + rnd) >> (SHIFT);                                                                   \
+    x2 = (tmp12 + tmp1 + rnd) >> (SHIFT);                                                                   \
+    x5 = (tmp12 - tmp1 + rnd) >> (SHIFT);                                                                   \
+    x3 = (tmp13 + tmp0 + rnd) >> (SHIFT);                                                                   \
+    x4 = (tmp13 - tmp0 + rnd) >> (SHIFT);                                                                   \
+  }
+
+// libjpeg's range_limit table after the IDCT: the 10-bit two's-complement value plus 128, clamped to 0 .. 255
+__device__ __forceinline__ unsigned idct_limit(int v) {
+  v &= 1023;
+  v = v >= 512 ? v - 1024 : v;
+  return (unsigned)min(max(v + 128, 0), 255);
+}
+
+__global__ void __launch_bounds__(256)
+jpeg_idct_kernel(const short *__restrict__ coef, long long nblocks_all, const long long *__restrict__ desc, int N,
+                 const unsigned char *__restrict__ qtabs, int nq, unsigned char *__restrict__ planes) {
+  const long long g = blockIdx.x * (long long)256 + threadIdx.x;
+  if (g >= nblocks_all) return;
+  const int img = find_image(desc, N, D_COEF, 64, g);
+  const long long *d = desc + (long long)img * kJpegDesc;
+  const int hs = (int)d[D_HS], vs = (int)d[D_VS], mx = (int)d[D_MX], my = (int)d[D_MY], ncomp = (int)d[D_NCOMP];
+  const long long total = (long long)mx * my, nbY = total * hs * vs;
+  const long long b = g - d[D_COEF] / 64;
+  if (b >= nbY + (ncomp == 3 ? 2 * total : 0)) return;
+  const int c = b < nbY ? 0 : (b < nbY + total ? 1 : 2);
+  const long long lb = c == 0 ? b : b - nbY - (c - 1) * total;
+  const int bw = c == 0 ? mx * hs : mx;
+  const int by = (int)(lb / bw), bx = (int)(lb - (long long)by * bw);
+  const long long slot = min(max(d[D_QT + c], 0LL), (long long)nq - 1);
+  const uint4 *q4 = (const uint4 *)(qtabs + slot * kQtBytes);
+  const uint4 *c4 = (const uint4 *)(coef + g * 64);
+  int x[64];
+#pragma unroll
+  for (int r = 0; r < 8; ++r) {
+    const uint4 cv = c4[r], qv = q4[r];
+    const unsigned cw[4] = {cv.x, cv.y, cv.z, cv.w}, qw[4] = {qv.x, qv.y, qv.z, qv.w};
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      x[r * 8 + 2 * j] = (int)(short)(cw[j] & 0xFFFFu) * (int)(qw[j] & 0xFFFFu);
+      x[r * 8 + 2 * j + 1] = (int)(short)(cw[j] >> 16) * (int)(qw[j] >> 16);
+    }
+  }
+#pragma unroll
+  for (int u = 0; u < 8; ++u)     // pass 1: columns
+    XM_IDCT_1D(x[u], x[8 + u], x[16 + u], x[24 + u], x[32 + u], x[40 + u], x[48 + u], x[56 + u], 11);
+  const long long ph = c == 0 ? (long long)my * vs * 8 : (long long)my * 8, pw = (long long)bw * 8;
+  const long long pY = (long long)my * vs * 8 * ((long long)mx * hs * 8), pC = (long long)my * 8 * ((long long)mx * 8);
+  unsigned char *plane = planes + d[D_PLANE] + (c == 0 ? 0 : pY + (c - 1) * pC);
+  (void)ph;
+#pragma unroll
+  for (int r = 0; r < 8; ++r) {   // pass 2: rows
+    XM_IDCT_1D(x[r * 8], x[r * 8 + 1], x[r * 8 + 2], x[r * 8 + 3], x[r * 8 + 4], x[r * 8 + 5], x[r * 8 + 6], x[r * 8 + 7], 18);
+    uint2 o;
+    o.x = idct_limit(x[r * 8]) | (idct_limit(x[r * 8 + 1]) << 8) | (idct_limit(x[r * 8 + 2]) << 16) | (idct_limit(x[r * 8 + 3]) << 24);
+    o.y = idct_limit(x[r * 8 + 4]) | (idct_limit(x[r * 8 + 5]) << 8) | (idct_limit(x[r * 8 + 6]) << 16) | (idct_limit(x[r * 8 + 7]) << 24);
+    *(uint2 *)(plane + ((long long)by * 8 + r) * pw + (long long)bx * 8) = o;
+  }
+}
+
+// ---- jpeg_colour_kernel --------------------------------------------------------------------------------------------
+// one upsampled chroma sample at (y, x) of the H x W image from a plane of dh x dw real samples (row pitch pw)
+__device__ __forceinline__ int chroma_at(const unsigned char *__restrict__ p, long long pw, int dh, int dw, int hs, int vs,
+                                         int y, int x) {
+  if (hs == 1) return p[y * pw + x];
+  if (dw <= 2) return p[(long long)(y / vs) * pw + (x >> 1)];     // jdsample.c: fancy only where downsampled_width > 2
+  const int i = x >> 1, odd = x & 1;
+  const int nb = odd ? min(i + 1, dw - 1) : max(i - 1, 0);
+  if (vs == 1) return (3 * p[y * pw + i] + p[y * pw + nb] + (odd ? 2 : 1)) >> 2;
+  const int near = y >> 1, far = (y & 1) ? min(near + 1, dh - 1) : max(near - 1, 0);
+  const int cs = 3 * p[near * pw + i] + p[far * pw + i], cn = 3 * p[near * pw + nb] + p[far * pw + nb];
+  return (3 * cs + cn + (odd ? 7 : 8)) >> 4;
+}
+
+__global__ void __launch_bounds__(256)
+jpeg_colour_kernel(const unsigned char *__restrict__ planes, const long long *__restrict__ desc, int N,
+                   long long npix_all, float *__restrict__ pixels) {
+  const long long g = blockIdx.x * (long long)256 + threadIdx.x;
+  if (g >= npix_all) return;
+  const int img = find_image(desc, N, D_PIX, 3, g);
+  const long long *d = desc + (long long)img * kJpegDesc;
+  const int H = (int)d[D_H], W = (int)d[D_W], hs = (int)d[D_HS], vs = (int)d[D_VS], mx = (int)d[D_MX], my = (int)d[D_MY];
+  const long long p = g - d[D_PIX] / 3;
+  if (p >= (long long)H * W) return;
+  const int x = (int)(p / H), y = (int)(p - (long long)x * H);
+  const long long pwY = (long long)mx * hs * 8, pY = (long long)my * vs * 8 * pwY, pwC = (long long)mx * 8, pC = (long long)my * 8 * pwC;
+  const unsigned char *base = planes + d[D_PLANE];
+  const int Y = base[y * pwY + x];
+  int r = Y, gg = Y, b = Y;
+  if ((int)d[D_NCOMP] == 3) {
+    const int dh = (H + vs - 1) / vs, dw = (W + hs - 1) / hs;
+    const int cb = chroma_at(base + pY, pwC, dh, dw, hs, vs, y, x) - 128;
+    const int cr = chroma_at(base + pY + pC, pwC, dh, dw, hs, vs, y, x) - 128;
+    r = Y + ((91881 * cr + 32768) >> 16);
+    gg = Y + ((-22554 * cb - 46802 * cr + 32768) >> 16);
+    b = Y + ((116130 * cb + 32768) >> 16);
+  }
+  float *o = pixels + d[D_PIX] + y + (long long)H * x;
+  const long long HW = (long long)H * W;
+  o[0] = (float)min(max(r, 0), 255);
+  o[HW] = (float)min(max(gg, 0), 255);
+  o[2 * HW] = (float)min(max(b, 0), 255);
+}
+
+// ---- host: parse ---------------------------------------------------------------------------------------------------
+struct JpegImage {
+  long long scan0 = 0, scan1 = 0;
+  int H = 0, W = 0, ncomp = 0, hs = 1, vs = 1, ri = 0, mx = 0, my = 0;
+  int tq[3] = {0, 0, 0}, td[3] = {0, 0, 0}, ta[3] = {0, 0, 0};
+};
+
+struct JpegTables {   // per file: what DQT / DHT defined
+  bool hasq[4] = {false, false, false, false}, hash[2][4] = {{false, false, false, false}, {false, false, false, false}};
+  unsigned short q[4][64];
+  unsigned char h[2][4][kHtBytes];
+};
+
+// jpeg_make_d_derived_tbl into the 1024-byte device form; false = invalid code lengths
+static bool derive_table(const unsigned char *counts, const unsigned char *vals, int nvals, unsigned char *out) {
+  memset(out, 0, kHtBytes);
+  unsigned short *lut = (unsigned short *)out;
+  unsigned char *hv = out + 512;
+  int *maxcode = (int *)(out + 768), *valoff = (int *)(out + 836);
+  int sizes[257], codes[257], n = 0;
+  for (int l = 1; l <= 16; ++l)
+    for (int i = 0; i < counts[l - 1]; ++i) sizes[n++] = l;
+  if (n != nvals || n > 256) return false;
+  int code = 0, si = n ? sizes[0] : 0, p = 0;
+  while (p < n) {
+    while (p < n && sizes[p] == si) codes[p++] = code++;
+    if (code > (1 << si)) return false;
+    code <<= 1;
+    ++si;
+  }
+  p = 0;
+  maxcode[0] = -1;
+  for (int l = 1; l <= 16; ++l) {
+    if (counts[l - 1]) {
+      valoff[l] = p - codes[p];
+      p += counts[l - 1];
+      maxcode[l] = codes[p - 1];
+    } else {
+      maxcode[l] = -1;
+    }
+  }
+  p = 0;
+  for (int l = 1; l <= 8; ++l)
+    for (int i = 0; i < counts[l - 1]; ++i, ++p) {
+      const int look = codes[p] << (8 - l);
+      for (int c = 0; c < (1 << (8 - l)); ++c) lut[look + c] = (unsigned short)((l << 8) | vals[p]);
+    }
+  memcpy(hv, vals, n);
+  return true;
+}
+
+static int parse_one(int idx, const unsigned char *d, long long n, JpegImage &im, JpegTables &tb,
+                     std::vector<long long> &cuts) {
+#define JBAD(...) return fail(XM_EINVAL, __VA_ARGS__)
+#define JNOT(...) return fail(XM_ENOTSUP, __VA_ARGS__)
+  if (n < 4 || d[0] != 0xFF || d[1] != 0xD8) JBAD("jpeg_plan: file %d: no SOI marker", idx);
+  long long pos = 2;
+  bool have_frame = false;
+  int adobe = -1, fid[3] = {0, 0, 0};
+  for (;;) {
+    if (pos + 2 > n) JBAD("jpeg_plan: file %d: cut inside its headers", idx);
+    if (d[pos] != 0xFF) JBAD("jpeg_plan: file %d: marker expected at byte %lld", idx, pos);
+    while (pos < n && d[pos] == 0xFF) ++pos;
+    if (pos + 1 > n) JBAD("jpeg_plan: file %d: cut inside its headers", idx);
+    const int m = d[pos++];
+    if (m == 0xD9) JBAD("jpeg_plan: file %d: EOI before SOS", idx);
+    if (pos + 2 > n) JBAD("jpeg_plan: file %d: cut inside its headers", idx);
+    const long long L = (d[pos] << 8) | d[pos + 1];
+    if (L < 2) JBAD("jpeg_plan: file %d: bad segment length", idx);
+    if (pos + L > n) JBAD("jpeg_plan: file %d: cut inside its headers", idx);
+    const unsigned char *s = d + pos + 2;
+    const long long sl = L - 2;
+    if (m == 0xDB) {
+      long long q = 0;
+      while (q < sl) {
+        const int pq = s[q] >> 4, tq = s[q] & 15;
+        if (pq) JNOT("jpeg_plan: file %d: 16-bit quantiser table", idx);
+        if (tq > 3 || q + 65 > sl) JBAD("jpeg_plan: file %d: bad DQT segment", idx);
+        for (int k = 0; k < 64; ++k) tb.q[tq][kNatural[k]] = s[q + 1 + k];
+        tb.hasq[tq] = true;
+        q += 65;
+      }
+    } else if (m == 0xC4) {
+      long long q = 0;
+      while (q < sl) {
+        if (q + 17 > sl) JBAD("jpeg_plan: file %d: bad DHT segment", idx);
+        const int tc = s[q] >> 4, th = s[q] & 15;
+        int tot = 0;
+        for (int k = 0; k < 16; ++k) tot += s[q + 1 + k];
+        if (tc > 1 || th > 3 || tot > 256 || q + 17 + tot > sl) JBAD("jpeg_plan: file %d: bad DHT segment", idx);
+        if (!derive_table(s + q + 1, s + q + 17, tot, tb.h[tc][th])) JBAD("jpeg_plan: file %d: invalid Huffman code lengths", idx);
+        tb.hash[tc][th] = true;
+        q += 17 + tot;
+      }
+    } else if (m == 0xC0) {
+      if (sl < 6) JBAD("jpeg_plan: file %d: bad SOF segment", idx);
+      if (s[0] != 8) JNOT("jpeg_plan: file %d: %d-bit samples", idx, (int)s[0]);
+      im.H = (s[1] << 8) | s[2];
+      im.W = (s[3] << 8) | s[4];
+      const int nf = s[5];
+      if (nf != 1 && nf != 3) JNOT("jpeg_plan: file %d: %d components (grey and YCbCr only)", idx, nf);
+      if (sl < 6 + 3 * nf || im.H == 0 || im.W == 0) JBAD("jpeg_plan: file %d: bad SOF segment", idx);
+      if (im.H > kJpegMaxSide || im.W > kJpegMaxSide)
+        JNOT("jpeg_plan: file %d: %d x %d, supported up to %d x %d", idx, im.H, im.W, kJpegMaxSide, kJpegMaxSide);
+      im.ncomp = nf;
+      for (int i = 0; i < nf; ++i) {
+        fid[i] = s[6 + 3 * i];
+        const int h = s[7 + 3 * i] >> 4, v = s[7 + 3 * i] & 15;
+        im.tq[i] = s[8 + 3 * i];
+        if (i == 0) {
+          im.hs = h;
+          im.vs = v;
+        } else if (h != 1 || v != 1) {
+          JNOT("jpeg_plan: file %d: chroma sampling %d x %d (1 x 1 only)", idx, h, v);
+        }
+      }
+      have_frame = true;
+    } else if (m >= 0xC1 && m <= 0xCF && m != 0xC4 && m != 0xC8) {
+      JNOT("jpeg_plan: file %d: SOF%d (progressive, arithmetic, lossless or 12-bit coding); baseline SOF0 only", idx, m - 0xC0);
+    } else if (m == 0xDD) {
+      if (sl < 2) JBAD("jpeg_plan: file %d: bad DRI segment", idx);
+      im.ri = (s[0] << 8) | s[1];
+    } else if (m == 0xEE && sl >= 12 && !memcmp(s, "Adobe", 5)) {
+      adobe = s[11];
+    } else if (m == 0xDA) {
+      if (!have_frame) JBAD("jpeg_plan: file %d: SOS before SOF", idx);
+      const int ns = sl ? s[0] : 0;
+      if (sl < 1 + 2 * ns + 3) JBAD("jpeg_plan: file %d: bad SOS segment", idx);
+      if (ns != im.ncomp) JNOT("jpeg_plan: file %d: multi-scan file (%d of %d components in the first scan)", idx, ns, im.ncomp);
+      for (int i = 0; i < ns; ++i) {
+        if (s[1 + 2 * i] != fid[i]) JNOT("jpeg_plan: file %d: scan components out of frame order", idx);
+        im.td[i] = s[2 + 2 * i] >> 4;
+        im.ta[i] = s[2 + 2 * i] & 15;
+      }
+      pos += L;
+      break;
+    }
+    pos += L;
+  }
+  if (im.ncomp == 3) {
+    if (adobe == 0) JNOT("jpeg_plan: file %d: Adobe transform 0 (RGB / CMYK data)", idx);
+    if (!((im.hs == 1 && im.vs == 1) || (im.hs == 2 && im.vs == 1) || (im.hs == 2 && im.vs == 2)))
+      JNOT("jpeg_plan: file %d: luma sampling %d x %d (1 x 1, 2 x 1, 2 x 2 only)", idx, im.hs, im.vs);
+  } else {
+    im.hs = im.vs = 1;   // a single component is never interleaved
+  }
+  for (int i = 0; i < im.ncomp; ++i)
+    if (im.tq[i] > 3 || im.td[i] > 3 || im.ta[i] > 3 || !tb.hasq[im.tq[i]] || !tb.hash[0][im.td[i]] || !tb.hash[1][im.ta[i]])
+      JBAD("jpeg_plan: file %d: component %d names a table the file does not define", idx, i);
+  // the entropy data ends at the first marker that is neither a stuffed zero nor RSTn
+  im.scan0 = pos;
+  im.scan1 = n;
+  long long i = pos;
+  while (i < n) {
+    const unsigned char *f = (const unsigned char *)memchr(d + i, 0xFF, (size_t)(n - i));
+    if (!f || f + 1 >= d + n) break;
+    const long long j = f - d;
+    const int b = d[j + 1];
+    if (b == 0) {
+      i = j + 2;
+    } else if (b == 0xFF) {
+      i = j + 1;
+    } else if (b >= 0xD0 && b <= 0xD7) {
+      cuts.push_back(j);
+      i = j + 2;
+    } else {
+      im.scan1 = j;
+      break;
+    }
+  }
+  im.mx = (im.W + 8 * im.hs - 1) / (8 * im.hs);
+  im.my = (im.H + 8 * im.vs - 1) / (8 * im.vs);
+  return XM_OK;
+#undef JBAD
+#undef JNOT
+}
+
+template <int B>
+static int intern(std::vector<unsigned char> &pool, const unsigned char *t) {
+  const int n = (int)(pool.size() / B);
+  for (int i = 0; i < n; ++i)
+    if (!memcmp(&pool[(size_t)i * B], t, B)) return i;
+  pool.insert(pool.end(), t, t + B);
+  return n;
+}
+
+}  // namespace xm
+
+using namespace xm;
+
+extern "C" {
+
+int xm_jpeg_plan(const unsigned char *bytes, const long long *offsets, int N, long long *desc, long long *lanes,
+                 long long lanes_cap, unsigned char *tables, long long tables_cap, long long *sizes) {
+  if (N < 0 || lanes_cap < 0 || tables_cap < 0)
+    return fail(XM_EINVAL, "jpeg_plan: need N >= 0, lanes_cap >= 0, tables_cap >= 0 (got N=%d lanes_cap=%lld tables_cap=%lld)", N,
+                lanes_cap, tables_cap);
+  if (!sizes) return fail(XM_EINVAL, "jpeg_plan: NULL sizes");
+  for (int k = 0; k < XM_JPEG_SIZES; ++k) sizes[k] = 0;
+  if (N == 0) return XM_OK;
+  if (!bytes || !offsets || !desc || !lanes || !tables) return fail(XM_EINVAL, "jpeg_plan: NULL argument");
+  std::vector<unsigned char> qpool, hpool;
+  std::vector<long long> lane_rows, cuts;
+  long long coef = 0, plane = 0, pix = 0;
+  JpegTables *tb = new JpegTables;
+  int rc = XM_OK;
+  for (int i = 0; i < N && rc == XM_OK; ++i) {
+    if (offsets[i] < 0 || offsets[i + 1] < offsets[i]) {
+      rc = fail(XM_EINVAL, "jpeg_plan: file %d: offsets must ascend from 0", i);
+      break;
+    }
+    JpegImage im;
+    *tb = JpegTables();
+    cuts.clear();
+    rc = parse_one(i, bytes + offsets[i], offsets[i + 1] - offsets[i], im, *tb, cuts);
+    if (rc) break;
+    long long *d = desc + (long long)i * kJpegDesc;
+    const long long base = offsets[i];
+    d[D_SCAN0] = base + im.scan0;
+    d[D_SCAN1] = base + im.scan1;
+    d[D_H] = im.H;
+    d[D_W] = im.W;
+    d[D_NCOMP] = im.ncomp;
+    d[D_HS] = im.hs;
+    d[D_VS] = im.vs;
+    d[D_RI] = im.ri;
+    d[D_MX] = im.mx;
+    d[D_MY] = im.my;
+    for (int c = 0; c < 3; ++c) {
+      const int s = c < im.ncomp ? c : 0;
+      d[D_QT + c] = intern<kQtBytes>(qpool, (const unsigned char *)tb->q[im.tq[s]]);
+      d[D_DC + c] = intern<kHtBytes>(hpool, tb->h[0][im.td[s]]);
+      d[D_AC + c] = intern<kHtBytes>(hpool, tb->h[1][im.ta[s]]);
+    }
+    const long long total = (long long)im.mx * im.my;
+    const long long nblocks = total * im.hs * im.vs + (im.ncomp == 3 ? 2 * total : 0);
+    d[D_COEF] = coef;
+    d[D_PLANE] = plane;
+    d[D_PIX] = pix;
+    coef += nblocks * 64;
+    plane += nblocks * 64;
+    pix += 3LL * im.H * im.W;
+    d[D_LANE0] = (long long)(lane_rows.size() / kJpegLane);
+    // one lane per restart interval; markers past the last interval of the image are ignored
+    long long begin = im.scan0, k = 0;
+    if (im.ri > 0) {
+      for (size_t c = 0; c < cuts.size() && (k + 1) * im.ri < total; ++c, ++k) {
+        const long long row[4] = {i, base + begin, base + cuts[c], k * im.ri};
+        lane_rows.insert(lane_rows.end(), row, row + 4);
+        begin = cuts[c] + 2;
+      }
+    }
+    const long long row[4] = {i, base + begin, base + im.scan1, im.ri > 0 ? k * im.ri : 0};
+    lane_rows.insert(lane_rows.end(), row, row + 4);
+    d[D_NLANES] = (long long)(lane_rows.size() / kJpegLane) - d[D_LANE0];
+    if (coef >= (1LL << 31) || pix >= (1LL << 31))
+      rc = fail(XM_ETOOBIG, "jpeg_plan: the batch holds 2^31 or more coefficients or pixel values at file %d", i);
+  }
+  delete tb;
+  if (rc) return rc;
+  const long long nq = (long long)(qpool.size() / kQtBytes), nh = (long long)(hpool.size() / kHtBytes);
+  const long long nl = (long long)(lane_rows.size() / kJpegLane);
+  sizes[0] = (long long)(qpool.size() + hpool.size());
+  sizes[1] = nq;
+  sizes[2] = nh;
+  sizes[3] = coef;
+  sizes[4] = plane;
+  sizes[5] = pix;
+  sizes[6] = nl;
+  sizes[7] = N;
+  if (nl > lanes_cap) return fail(XM_ENOMEM, "jpeg_plan: %lld lanes, room for %lld", nl, lanes_cap);
+  if (sizes[0] > tables_cap) return fail(XM_ENOMEM, "jpeg_plan: %lld table bytes, room for %lld", sizes[0], tables_cap);
+  memcpy(lanes, lane_rows.data(), lane_rows.size() * sizeof(long long));
+  memcpy(tables, qpool.data(), qpool.size());
+  memcpy(tables + qpool.size(), hpool.data(), hpool.size());
+  return XM_OK;
+}
+
+int xm_jpeg_decode_batch(const unsigned char *bytes, long long nbytes, const long long *desc, int N, const long long *lanes,
+                         int nlanes, const unsigned char *tables, int nq, int nh, long long coef_elems,
+                         long long plane_bytes, long long pixel_floats, float *pixels, float *faces, float crop, int Ho,
+                         int Wo, const float *avg3, int *status, void *stream) {
+  if (N < 0 || nbytes < 0 || nlanes < 0 || nq < 0 || nh < 0 || coef_elems < 0 || plane_bytes < 0 || pixel_floats < 0)
+    return fail(XM_EINVAL, "jpeg_decode_batch: negative size");
+  if (N == 0) return XM_OK;
+  if (!bytes || !desc || !lanes || !tables || !status) return fail(XM_EINVAL, "jpeg_decode_batch: NULL argument");
+  if (nlanes < N || nq < 1 || nh < 2 || coef_elems < 64 || (coef_elems & 63) || plane_bytes != coef_elems || pixel_floats < 3)
+    return fail(XM_EINVAL, "jpeg_decode_batch: sizes are not what xm_jpeg_plan reports");
+  if (coef_elems >= (1LL << 31) || pixel_floats >= (1LL << 31)) return fail(XM_ETOOBIG, "jpeg_decode_batch: batch too large");
+  if (((uintptr_t)bytes & 15) || ((uintptr_t)tables & 15) || ((uintptr_t)desc & 7) || ((uintptr_t)lanes & 7))
+    return fail(XM_EINVAL, "jpeg_decode_batch: bytes and tables must be 16-byte aligned, desc and lanes 8-byte aligned");
+  if (faces) {
+    if (Ho <= 0 || Wo <= 0) return fail(XM_EINVAL, "jpeg_decode_batch: faces need Ho > 0, Wo > 0");
+    if (!(crop > 0.f) || crop > 1.f) return fail(XM_EINVAL, "jpeg_decode_batch: crop must be in (0, 1]");
+    if (too_big(Ho, Wo, 3, N)) return fail(XM_ETOOBIG, "jpeg_decode_batch: faces too large");
+  }
+  hipStream_t st = (hipStream_t)stream;
+  WsCarver ws;
+  const size_t need = WsCarver::need((size_t)coef_elems, 2) + WsCarver::need((size_t)plane_bytes, 1) +
+                      (pixels ? 0 : WsCarver::need((size_t)pixel_floats, 4));
+  int rc = ws.init(need, st);
+  if (rc) return rc;
+  short *coef = ws.take<short>((size_t)coef_elems);
+  unsigned char *planes = ws.take<unsigned char>((size_t)plane_bytes);
+  float *pix = pixels ? pixels : ws.take<float>((size_t)pixel_floats);
+  const unsigned char *huff = tables + (size_t)nq * kQtBytes;
+  {
+    void *ps = prof_open(2100, 0, st);
+    const size_t n16 = (size_t)coef_elems / 8;
+    hipLaunchKernelGGL(jpeg_clear_kernel, dim3((unsigned)std::min<size_t>((n16 + 255) / 256, 4096)), dim3(256), 0, st,
+                       (uint4 *)coef, n16, status, N);
+    prof_close(ps);
+    XM_LAUNCH_CHECK();
+  }
+  {
+    void *ps = prof_open(2101, 0, st);
+    hipLaunchKernelGGL(jpeg_entropy_kernel, dim3((unsigned)((nlanes + kJpegLanes - 1) / kJpegLanes)), dim3(64), 0, st,
+                       (const uint4 *)bytes, nbytes, desc, N, lanes, nlanes, huff, nh, coef, status);
+    prof_close(ps);
+    XM_LAUNCH_CHECK();
+  }
+  {
+    void *ps = prof_open(2102, 0, st);
+    const long long nb = coef_elems / 64;
+    hipLaunchKernelGGL(jpeg_idct_kernel, dim3((unsigned)((nb + 255) / 256)), dim3(256), 0, st, coef, nb, desc, N, tables, nq,
+                       planes);
+    prof_close(ps);
+    XM_LAUNCH_CHECK();
+  }
+  {
+    void *ps = prof_open(2103, 0, st);
+    const long long np = pixel_floats / 3;
+    hipLaunchKernelGGL(jpeg_colour_kernel, dim3((unsigned)((np + 255) / 256)), dim3(256), 0, st, planes, desc, N, np, pix);
+    prof_close(ps);
+    XM_LAUNCH_CHECK();
+  }
+  if (faces) {
+    void *ps = prof_open(2104, 0, st);
+    rc = face_ragged_launch(pix, desc, kJpegDesc, D_H, D_W, D_PIX, N, crop, Ho, Wo, avg3, faces, st);
+    prof_close(ps);
+    if (rc) return rc;
+  }
+  return XM_OK;
+}
+
+}  // extern "C"

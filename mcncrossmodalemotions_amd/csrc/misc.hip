@@ -1179,6 +1179,101 @@ int xm_crop_resize_face(const float *src, int Hin, int Win, int N, float crop, i
   return XM_OK;
 }
 
+}  // extern "C"
+
+namespace xm {
+
+// bilin_u8 with the fused multiply-adds hipcc forms for it inside crop_resize_face_kernel written out, so that another
+// kernel gets the same roundings whatever its surroundings make the compiler prefer (a sample that lands on k + 0.5
+// rounds by the last bit of these products):  top = fma(fx, p01, (1 - fx) p00), bot likewise, v = fma(fy, bot, (1 - fy) top)
+__device__ __forceinline__ float bilin_u8_pinned(const float *__restrict__ p, int H, int W, double y, double x) {
+#pragma clang fp contract(off)
+  y = fmin(fmax(y, 0.0), (double)(H - 1));
+  x = fmin(fmax(x, 0.0), (double)(W - 1));
+  int y0 = (int)floor(y), x0 = (int)floor(x);
+  int y1 = y0 + 1 < H ? y0 + 1 : y0, x1 = x0 + 1 < W ? x0 + 1 : x0;
+  double fy = y - y0, fx = x - x0;
+  const double top = fma(fx, (double)p[y0 + (size_t)H * x1], (1 - fx) * (double)p[y0 + (size_t)H * x0]);
+  const double bot = fma(fx, (double)p[y1 + (size_t)H * x1], (1 - fx) * (double)p[y1 + (size_t)H * x0]);
+  double v = fma(fy, bot, (1 - fy) * top);
+  v = floor(v + 0.5);
+  return (float)fmin(fmax(v, 0.0), 255.0);
+}
+
+// crop_resize_face_kernel over images of different sizes (xm_jpeg_decode_batch, jpeg.hip): image n is Hin x Win x 3 at
+// pixels + desc[n][col_pix] with Hin, Win in its descriptor row.  The window is computed as xm_crop_resize_face's host
+// code does and every pixel with the operations crop_resize_face_kernel compiles to, spelled out with contraction off
+// (bilin_u8_pinned, the grey sum), so the output equals xm_crop_resize_face of that image alone bit for bit
+// (tests/test_gpu_jpeg.py holds it to that on sizes whose samples land on ties).  RGB: the resized R, G, B instead of
+// the normalised grey.
+template <bool RGB>
+__global__ void crop_resize_face_ragged_kernel(const float *__restrict__ pixels, float *__restrict__ out,
+                                               const long long *__restrict__ desc, int stride, int col_h, int col_w,
+                                               int col_pix, int N, float crop, int Ho, int Wo, float a0, float a1,
+                                               float a2) {
+  size_t idx = blockIdx.x * (size_t)blockDim.x + threadIdx.x;
+  const size_t HWo = (size_t)Ho * Wo;
+  if (idx >= HWo * N) return;
+  int n = (int)(idx / HWo);
+  size_t q = idx - (size_t)n * HWo;
+  int j = (int)(q / Ho), i = (int)(q - (size_t)j * Ho);
+  const long long *d = desc + (size_t)n * stride;
+  const int Hin = (int)d[col_h], Win = (int)d[col_w];
+  double ch, cw, h0, w0;
+  {
+#pragma clang fp contract(off)
+    ch = (double)crop * Hin;
+    cw = (double)crop * Win;
+    const double dh = Hin - ch, dw = Win - cw;
+    h0 = 0.5 * dh;
+    w0 = 0.5 * dw;
+  }
+  double y, x;
+  {
+#pragma clang fp contract(off)
+    y = (i + 0.5) * ch / Ho - 0.5 + h0;
+    x = (j + 0.5) * cw / Wo - 0.5 + w0;
+  }
+  const size_t HWi = (size_t)Hin * Win;
+  const float *p = pixels + d[col_pix];
+  float r = bilin_u8_pinned(p, Hin, Win, y, x), g = bilin_u8_pinned(p + HWi, Hin, Win, y, x),
+        b = bilin_u8_pinned(p + 2 * HWi, Hin, Win, y, x);
+  float *o = out + q + HWo * 3 * n;
+  if constexpr (RGB) {
+    o[0] = r;
+    o[HWo] = g;
+    o[2 * HWo] = b;
+  } else {
+    float gr;   // crop_resize_face_kernel: 0.2989f r + 0.5870f g + 0.1140f b as fma(b, .., fma(r, .., 0.5870f g))
+    {
+#pragma clang fp contract(off)
+      gr = fmaf(b, 0.1140f, fmaf(r, 0.2989f, 0.5870f * g)) + 0.5f;
+    }
+    gr = fminf(floorf(gr), 255.f);
+    o[0] = gr - a0;
+    o[HWo] = gr - a1;
+    o[2 * HWo] = gr - a2;
+  }
+}
+
+int face_ragged_launch(const float *pixels, const long long *desc, int stride, int col_h, int col_w, int col_pix, int N,
+                       float crop, int Ho, int Wo, const float *avg3, float *out, hipStream_t st) {
+  size_t n = (size_t)Ho * Wo * N;
+  const dim3 grid((unsigned)((n + 255) / 256)), block(256);
+  if (avg3)
+    hipLaunchKernelGGL(crop_resize_face_ragged_kernel<false>, grid, block, 0, st, pixels, out, desc, stride, col_h, col_w,
+                       col_pix, N, crop, Ho, Wo, avg3[0], avg3[1], avg3[2]);
+  else
+    hipLaunchKernelGGL(crop_resize_face_ragged_kernel<true>, grid, block, 0, st, pixels, out, desc, stride, col_h, col_w,
+                       col_pix, N, crop, Ho, Wo, 0.f, 0.f, 0.f);
+  XM_LAUNCH_CHECK();
+  return XM_OK;
+}
+
+}  // namespace xm
+
+extern "C" {
+
 int xm_normalize_face(const float *rgb, int H, int W, int N, const float *avg3, float *out,
                       void *stream) {
   if (H <= 0 || W <= 0 || N <= 0) return fail(XM_EINVAL, "normalize_face: empty input");

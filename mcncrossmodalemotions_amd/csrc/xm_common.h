@@ -112,6 +112,12 @@ int bnpool_backward_sums(WsCarver &ws, const float *x, int H, int W, int C, int 
                          const unsigned char *amax, const float *y_pool, const float *dzdy_pool, float *dg_out,
                          float *db_out, float *rowc_out, hipStream_t st);
 
+// misc.hip: crop_resize_face over images of different sizes, each described by a row of int64 (height, width and the
+// offset of its H x W x 3 pixels in `pixels` at the given columns); avg3 == nullptr: resized RGB instead of the
+// normalised grey.  Per image bit for bit what xm_crop_resize_face gives (jpeg.hip)
+int face_ragged_launch(const float *pixels, const long long *desc, int stride, int col_h, int col_w, int col_pix, int N,
+                       float crop, int Ho, int Wo, const float *avg3, float *out, hipStream_t st);
+
 static inline int out_size(int in, int pa, int pb, int f, int d, int s) {
   int feff = (f - 1) * d + 1;
   int t = in + pa + pb - feff;

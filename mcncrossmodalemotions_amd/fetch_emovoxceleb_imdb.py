@@ -131,14 +131,49 @@ def _as_teacher(teacher, lanes):
     return zoo.FrozenTeacher(teacher, lanes=lanes), tuple(norm["imageSize"][:2]), norm["averageImage"]
 
 
-def buildImdb(teacher, imdb, frames, *, limit=math.inf, batchSize=128, lanes=2, device=None):
+def read_files(faceDir):
+    """the default `read` of getImageBatch: paths -> the bytes of fullfile(faceDir, path) (:127)"""
+    def read(paths):
+        out = []
+        for p in paths:
+            with open(os.path.join(faceDir, p), "rb") as fh:
+                out.append(fh.read())
+        return out
+    return read
+
+
+def getImageBatch(imagePaths, dag, *, read=None, faceDir=os.path.join("data", "voxceleb", "faces"), device=None):
+    """data = getImageBatch(imagePaths, dag) -- :152-193: vl_imreadjpeg with CropSize 1/1.6, CropLocation center,
+    bilinear Resize to meta.normalization.imageSize (:160-172), rgb2gray, x3 and normalizeFace (:176-193), all on the
+    device from the files' bytes (vl.imreadjpeg).  `read(paths) -> list of bytes` (default: the files under faceDir);
+    `dag`: a network with meta.normalization, or an object with .imageSize / .averageImage.  Ho x Wo x 3 x n; nothing
+    is synchronised."""
+    if hasattr(dag, "meta"):
+        imageSize, avg = tuple(dag.meta["normalization"]["imageSize"][:2]), dag.meta["normalization"]["averageImage"]
+    else:
+        imageSize, avg = tuple(getattr(dag, "imageSize", (224, 224)))[:2], getattr(dag, "averageImage", AVERAGE_IMAGE)
+    read = read or read_files(faceDir)
+    return vl.imreadjpeg(read(list(imagePaths)), resize=imageSize, crop_size=1 / 1.6, crop_location="center",
+                         interpolation="bilinear", pack=True, num_threads=10, average_image=avg, device=device)
+
+
+class _Norm:
+    def __init__(self, imageSize, averageImage):
+        self.imageSize, self.averageImage = imageSize, averageImage
+
+
+def buildImdb(teacher, imdb, frames=None, *, read=None, limit=math.inf, batchSize=128, lanes=2, device=None):
     """imdb = buildImdb(teacher) -- :54-149, for an imdb that went through addFramesToImdb.  `teacher`: a ferPlusZoo
     network (losses are stripped, test mode, one input: :101-110) or any object with .logits(faces) -> 1 x 1 x E x n;
     `frames(paths, device)` -> the decoded frames Hin x Win x 3 x n (0..255), what vl_imreadjpeg returns for
     fullfile(faceDir, denseFrames(batch)) (:127,160-172).  Returns a new imdb with
       wavLogits        host list, one F_i x E float32 array per wav (empty past `limit`), downloaded once;
       device_logits()  the same rows concatenated on the device, already in place.
+    With `read(paths) -> list of bytes` instead of `frames` the batch comes from getImageBatch: the JPEG files are
+    decoded on the device (frames of any sizes in one batch).
     The loop enqueues work only; it neither synchronises nor downloads."""
+    if (frames is None) == (read is None):
+        raise ValueError("buildImdb: give either `frames` (decoded pixels) or `read` (JPEG bytes)")
     if not torch.cuda.is_available():
         raise RuntimeError("buildImdb needs a GPU; this build has no CPU path")
     device = device or torch.device("cuda", torch.cuda.current_device())
@@ -156,8 +191,12 @@ def buildImdb(teacher, imdb, frames, *, limit=math.inf, batchSize=128, lanes=2, 
     logits = vl.mat_zeros(max(numIms, 1), E, device=device)                              # zeros(numIms, numEmotions), :119
     for start in range(0, numIms, int(batchSize)):                                       # :122-136
         batch = range(start, min(start + int(batchSize), numIms))
-        data = frames([images["denseFrames"][i] for i in batch], device)                 # vl_imreadjpeg (:160-172)
-        faces = vl.crop_resize_face(data, avg, imageSize)                                # getImageBatch (:152-193)
+        paths = [images["denseFrames"][i] for i in batch]
+        if read is not None:
+            faces = getImageBatch(paths, _Norm(imageSize, avg), read=read, device=device)    # :152-193 from the bytes
+        else:
+            data = frames(paths, device)                                                 # vl_imreadjpeg (:160-172)
+            faces = vl.crop_resize_face(data, avg, imageSize)                            # getImageBatch (:152-193)
         out = model.logits(faces)                                                        # dag.eval, vars(end) (:129-130)
         vl.scatter_rows(out, logits, row0=start)                                         # logits(batch, :) = out' (:131)
     numWavs = len(images["name"])
@@ -216,7 +255,7 @@ def load_imdb(path):
 
 
 def fetch_emovoxceleb_imdb(teacher="senet50-ferplus", imdbDir=os.path.join("data", "xEmo18", "storedFeats"), *,
-                           net=None, imdb=None, frames=None, verbose=True, **buildOpts):
+                           net=None, imdb=None, frames=None, read=None, verbose=True, **buildOpts):
     """loadedImdb = fetch_emovoxceleb_imdb(teacher, 'imdbDir', ..) -- :1-51: the cached imdb of (teacher, imdbDir), else
     <imdbDir>/<teacher>-logits.mat when it exists, else buildImdb and save.  Building needs (keyword-only) `net` (default
     zoo.ferPlusZoo(teacher)), `imdb` (an imdb that went through addFramesToImdb; default a 64-track synthetic one) and
@@ -242,9 +281,10 @@ def fetch_emovoxceleb_imdb(teacher="senet50-ferplus", imdbDir=os.path.join("data
             src = src_imdb(syn)
             frames = frames or xbatch.SyntheticDenseFrames(src)
             imdb = addFramesToImdb(src, frames.lister, find=frames.find)
-        if frames is None:
+        if frames is None and read is None:
             raise ValueError("fetch_emovoxceleb_imdb: building needs `frames` for the given imdb")
-        loaded = buildImdb(net if net is not None else zoo.ferPlusZoo(teacher), imdb, frames, **buildOpts)
+        loaded = buildImdb(net if net is not None else zoo.ferPlusZoo(teacher), imdb, frames if read is None else None,
+                           read=read, **buildOpts)
         save_imdb(imdbPath, loaded)
     _CACHE[key] = loaded
     return loaded

@@ -1315,3 +1315,128 @@ def ferplus_batch(grey, transforms, flips, average_image, image_size=(224, 224))
     _lib.check(_L().xm_ferplus_batch(_ptr(grey), H, W, N, _ptr(flips), _ptr(transforms), Ho, Wo, avg, _ptr(out),
                                      _stream()))
     return out
+
+
+# --------------------------------------------------------------------------------------------
+# vl_imreadjpeg (fetch_emovoxceleb_imdb.m:160-172, compute_visual_feats.m:130-143): baseline JPEG decode on the device
+# --------------------------------------------------------------------------------------------
+JPEG_DESC, JPEG_LANE, JPEG_QT_BYTES, JPEG_HT_BYTES = 24, 4, 128, 1024          # include/xmodal.h XM_JPEG_*
+JPEG_OK, JPEG_TRUNCATED, JPEG_BADCODE = 0, 1, 2
+
+
+def jpeg_plan(files, stage=None):
+    """The host side of imreadjpeg (xm_jpeg_plan; touches no device): `files` is a list of bytes.  Lays one staging
+    buffer out as [file bytes | desc | lanes | tables] (16-byte aligned parts), parses every header into it and returns
+    (stage, plan): `stage` a uint8 numpy array (`stage(nbytes)`, when given, allocates it -- imreadjpeg hands out
+    pinned memory) and plan = dict(N, nbytes, desc, lanes, tables: (offset, used bytes) in the buffer, sizes: the
+    eight int64 of xm_jpeg_plan).  An unsupported or malformed file raises _lib.XmError naming its index."""
+    N = len(files)
+    lens = np.array([len(f) for f in files], np.int64)
+    offsets = np.concatenate([[0], np.cumsum(lens)]).astype(np.int64)
+    up = lambda v: (int(v) + 15) & ~15
+    nbytes = int(offsets[-1])
+    lanes_cap = N + 1024
+    while True:
+        o_desc = up(nbytes + 1)
+        o_lanes = up(o_desc + 8 * JPEG_DESC * N)
+        o_tab = up(o_lanes + 8 * JPEG_LANE * lanes_cap)
+        tab_cap = N * (3 * JPEG_QT_BYTES + 6 * JPEG_HT_BYTES)
+        total = up(o_tab + tab_cap)
+        buf = stage(total) if stage is not None else np.empty(total, np.uint8)
+        for f, o in zip(files, offsets):
+            buf[o:o + len(f)] = np.frombuffer(f, np.uint8)
+        buf[nbytes:o_desc] = 0
+        sizes = np.zeros(8, np.int64)
+        base = buf.ctypes.data
+        rc = _L().xm_jpeg_plan(C.c_void_p(base), C.c_void_p(offsets.ctypes.data), N, C.c_void_p(base + o_desc),
+                               C.c_void_p(base + o_lanes), lanes_cap, C.c_void_p(base + o_tab), tab_cap,
+                               C.c_void_p(sizes.ctypes.data))
+        if rc == 2 and int(sizes[6]) > lanes_cap:          # XM_ENOMEM: more restart intervals than assumed
+            lanes_cap = int(sizes[6])
+            continue
+        _lib.check(rc)
+        break
+    plan = dict(N=N, nbytes=nbytes, sizes=sizes, desc=(o_desc, 8 * JPEG_DESC * N),
+                lanes=(o_lanes, 8 * JPEG_LANE * int(sizes[6])), tables=(o_tab, int(sizes[0])), total=total)
+    return buf, plan
+
+
+def jpeg_decode(buf, plan, *, want_pixels=True, resize=None, crop=1.0, average_image=None, device=None):
+    """uploads a planned staging buffer (non-blocking, three slices of the one pinned buffer) and enqueues
+    xm_jpeg_decode_batch.  Returns (pixels ragged float32 | None, faces Ho x Wo x 3 x N | None, status int32[N], desc
+    numpy N x 24).  Nothing is synchronised."""
+    device = device or _dev()
+    N, sizes = plan["N"], plan["sizes"]
+    host = torch.from_numpy(buf) if isinstance(buf, np.ndarray) else buf
+    dev = torch.empty(plan["total"], dtype=torch.uint8, device=device)
+    head = plan["desc"][0] + plan["desc"][1]
+    with torch.cuda.device(device):
+        dev[:head].copy_(host[:head], non_blocking=True)
+        for o, n in (plan["lanes"], plan["tables"]):
+            dev[o:o + n].copy_(host[o:o + n], non_blocking=True)
+        pixels = torch.empty(int(sizes[5]), dtype=torch.float32, device=device) if want_pixels else None
+        faces, avg, Ho, Wo = None, None, 0, 0
+        if resize is not None:
+            Ho, Wo = _pair(resize, "RESIZE")
+            faces = mat_empty(Ho, Wo, 3, N, device=device)
+            if average_image is not None:
+                avg = (C.c_float * 3)(*[float(v) for v in np.ravel(average_image)[:3]])
+        status = torch.empty(N, dtype=torch.int32, device=device)
+        p = dev.data_ptr()
+        _lib.check(_L().xm_jpeg_decode_batch(
+            C.c_void_p(p), plan["nbytes"], C.c_void_p(p + plan["desc"][0]), N, C.c_void_p(p + plan["lanes"][0]),
+            int(sizes[6]), C.c_void_p(p + plan["tables"][0]), int(sizes[1]), int(sizes[2]), int(sizes[3]), int(sizes[4]),
+            int(sizes[5]), _ptr(pixels), _ptr(faces), float(crop), Ho, Wo, avg, _ptr(status), _stream()))
+    desc = np.array(buf[plan["desc"][0]:plan["desc"][0] + plan["desc"][1]]).view(np.int64).reshape(N, JPEG_DESC)
+    return pixels, faces, status, desc
+
+
+def _pinned(nbytes):
+    return torch.empty(int(nbytes), dtype=torch.uint8, pin_memory=True).numpy()
+
+
+def imreadjpeg(files, resize=None, crop_size=None, crop_location="center", interpolation="bilinear", pack=True,
+               num_threads=None, *, prefetch=False, average_image=None, device=None, return_status=False):
+    """vl_imreadjpeg (fetch_emovoxceleb_imdb.m:160-172, compute_visual_feats.m:130-143) for baseline JPEG files, decoded
+    on the device: `files` is a list of bytes or of paths.  Option names follow vl_imreadjpeg; `num_threads` is accepted
+    and ignored (there are no decoder threads), only 'center' and 'bilinear' exist, `prefetch` raises.
+      no resize                    a list of H x W x 3 device tensors (single, 0..255), one per file
+      resize, average_image        the teacher's input Ho x Wo x 3 x N: centre crop of relative size crop_size, bilinear
+                                   resize, uint8 rounding, rgb2gray, x3, minus average_image -- per image bit for bit
+                                   crop_resize_face of its decoded pixels
+      resize alone                 the resized R, G, B pack Ho x Wo x 3 x N (the same resampler)
+    The bytes, descriptors and tables go up through one pinned staging buffer with non-blocking copies and the call does
+    not synchronise; return_status=True also returns the int32 device vector of JPEG_OK / JPEG_TRUNCATED / JPEG_BADCODE
+    bits.  Progressive, arithmetic-coded, 12-bit, multi-scan, CMYK files and unusual sampling factors raise before
+    anything is launched, with the index of the file; there is no host decode to fall back to."""
+    if prefetch:
+        raise ValueError("imreadjpeg: 'Prefetch' is not supported: the call already returns without waiting")
+    if str(crop_location).lower() != "center":
+        raise ValueError("imreadjpeg: only CropLocation 'center' exists (got %r)" % (crop_location,))
+    if str(interpolation).lower() != "bilinear":
+        raise ValueError("imreadjpeg: only Interpolation 'bilinear' exists (got %r)" % (interpolation,))
+    if not torch.cuda.is_available():
+        raise RuntimeError("imreadjpeg needs a GPU; this build has no CPU path")
+    if resize is None and (crop_size is not None or average_image is not None):
+        raise ValueError("imreadjpeg: crop_size and average_image need resize")
+    datas = []
+    for f in files:
+        if isinstance(f, (bytes, bytearray, memoryview)):
+            datas.append(bytes(f))
+        else:
+            with open(f, "rb") as fh:
+                datas.append(fh.read())
+    if not datas:
+        return ([], None) if return_status else []
+    buf, plan = jpeg_plan(datas, stage=_pinned)
+    pixels, faces, status, desc = jpeg_decode(buf, plan, want_pixels=resize is None, resize=resize,
+                                              crop=1.0 if crop_size is None else float(crop_size),
+                                              average_image=average_image, device=device)
+    if resize is not None:
+        out = faces
+    else:
+        out = []
+        for d in desc:
+            H, W, o = int(d[2]), int(d[3]), int(d[21])
+            out.append(pixels[o:o + 3 * H * W].view(3, W, H).permute(2, 1, 0))
+    return (out, status) if return_status else out

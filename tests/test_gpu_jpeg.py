@@ -1,0 +1,237 @@
+"""GPU: vl.imreadjpeg / xm_jpeg_decode_batch against PIL's pixels stored in tests/golden/jpeg_small.npz -- exactly, the
+decode is integer arithmetic throughout -- in single-image and ragged batches with guard words around every output, a
+truncated file, the fused face tensor against vl.crop_resize_face bit for bit, the launch count, and buildImdb /
+compute_visual_feats fed JPEG bytes against the same functions fed PIL's pixels."""
+import ctypes as C
+
+import numpy as np
+import pytest
+import torch
+
+from test_jpeg_cpu import GOLDEN, complete_rows
+
+pytestmark = pytest.mark.gpu
+GUARD, SENTINEL = 64, -12345.0
+AVG = (131.0912, 103.8827, 91.4953)
+
+
+@pytest.fixture(scope="module")
+def golden():
+    return dict(np.load(GOLDEN))
+
+
+@pytest.fixture(scope="module")
+def names(golden):
+    return [str(n) for n in golden["names"]]
+
+
+def hwc(t):
+    """H x W x 3 device tensor -> uint8 numpy"""
+    a = t.cpu().numpy()
+    assert np.array_equal(a, np.rint(a)) and a.min() >= 0 and a.max() <= 255
+    return a.astype(np.uint8)
+
+
+@pytest.fixture(scope="module")
+def singles(gpu, golden, names):
+    """every supported fixture decoded alone: name -> (H x W x 3 uint8, status)"""
+    from mcncrossmodalemotions_amd import vl
+    out = {}
+    for n in names:
+        imgs, status = vl.imreadjpeg([golden["bytes_" + n].tobytes()], return_status=True)
+        out[n] = (hwc(imgs[0]), int(status.cpu()[0]))
+    return out
+
+
+def guarded(n, dtype, device):
+    t = torch.full((n + 2 * GUARD,), SENTINEL, dtype=dtype, device=device)
+    return t, t[GUARD:GUARD + n]
+
+
+def guards_intact(t):
+    return bool((t[:GUARD] == SENTINEL).all()) and bool((t[-GUARD:] == SENTINEL).all())
+
+
+def decode_guarded(gpu, files, resize=None, crop=1 / 1.6, avg=AVG):
+    """xm_jpeg_decode_batch into buffers with guard words on both sides -> (images, faces, status), guards checked"""
+    from mcncrossmodalemotions_amd import _lib, vl
+    L = _lib.load()
+    buf, plan = vl.jpeg_plan(files)
+    N, sizes = plan["N"], plan["sizes"]
+    dev = torch.from_numpy(buf).to(gpu)
+    gp, pixels = guarded(int(sizes[5]), torch.float32, gpu)
+    gs, status = guarded(N, torch.float32, gpu)                       # int32 words behind a float view of the same size
+    gf, faces = (None, None) if resize is None else guarded(resize[0] * resize[1] * 3 * N, torch.float32, gpu)
+    a3 = (C.c_float * 3)(*avg)
+    p = dev.data_ptr()
+    _lib.check(L.xm_jpeg_decode_batch(
+        C.c_void_p(p), plan["nbytes"], C.c_void_p(p + plan["desc"][0]), N, C.c_void_p(p + plan["lanes"][0]), int(sizes[6]),
+        C.c_void_p(p + plan["tables"][0]), int(sizes[1]), int(sizes[2]), int(sizes[3]), int(sizes[4]), int(sizes[5]),
+        C.c_void_p(pixels.data_ptr()), C.c_void_p(faces.data_ptr()) if faces is not None else None, float(crop),
+        resize[0] if resize else 0, resize[1] if resize else 0, a3, C.c_void_p(status.data_ptr()),
+        C.c_void_p(torch.cuda.current_stream().cuda_stream)))
+    torch.cuda.synchronize()
+    assert guards_intact(gp) and guards_intact(gs) and (gf is None or guards_intact(gf))
+    desc = buf[plan["desc"][0]:plan["desc"][0] + plan["desc"][1]].view(np.int64).reshape(N, 24)
+    imgs = [pixels[int(d[21]):int(d[21]) + 3 * int(d[2]) * int(d[3])].view(3, int(d[3]), int(d[2])).permute(2, 1, 0) for d in desc]
+    if faces is not None:
+        faces = faces.view(N, 3, resize[1], resize[0]).permute(3, 2, 1, 0)
+    return imgs, faces, status.view(torch.int32).cpu().numpy()
+
+
+@pytest.mark.parametrize("k", range(11))
+def test_every_fixture_equals_pil(singles, golden, names, k):
+    got, status = singles[names[k]]
+    want = golden["pix_" + names[k]]
+    assert status == 0 and got.shape == want.shape, names[k]
+    assert np.array_equal(got, want), (names[k], int(np.abs(got.astype(int) - want).max()))
+
+
+@pytest.mark.parametrize("seed", [0, 1])
+def test_one_ragged_batch_of_70(gpu, golden, names, singles, seed):
+    order = np.random.default_rng(seed).permutation(70) % len(names)           # more than one wave of lanes, any order
+    files = [golden["bytes_" + names[i]].tobytes() for i in order]
+    imgs, _, status = decode_guarded(gpu, files)
+    assert not status.any()
+    for j, i in enumerate(order):
+        assert np.array_equal(hwc(imgs[j]), singles[names[i]][0]), (j, names[i])
+
+
+def test_truncated_file_in_a_batch(gpu, golden, singles):
+    cut, whole = golden["bytes_truncated"].tobytes(), golden["bytes_s420_96x80_q50"].tobytes()
+    files = [golden["bytes_s420_16x16"].tobytes(), cut, golden["bytes_grey_17x23"].tobytes(), whole]
+    imgs, _, status = decode_guarded(gpu, files)
+    assert list(status) == [0, 1, 0, 0]                                          # XM_JPEG_TRUNCATED
+    rows = complete_rows(cut, whole)
+    assert 16 <= rows < 96
+    assert np.array_equal(hwc(imgs[1])[:rows], golden["pix_truncated"][:rows])
+    assert not np.array_equal(hwc(imgs[1]), golden["pix_truncated"])
+    for j, n in ((0, "s420_16x16"), (2, "grey_17x23"), (3, "s420_96x80_q50")):
+        assert np.array_equal(hwc(imgs[j]), golden["pix_" + n]), n
+
+
+def test_faces_equal_crop_resize_face_per_image(gpu, golden, names):
+    from mcncrossmodalemotions_amd import vl
+    files = [golden["bytes_" + n].tobytes() for n in names] * 2
+    for resize, crop in (((24, 20), 1 / 1.6), ((7, 9), 1.0)):
+        imgs, faces, status = decode_guarded(gpu, files, resize=resize, crop=crop)
+        assert not status.any() and tuple(faces.shape) == resize + (3, len(files))
+        for j, im in enumerate(imgs):
+            one = vl.crop_resize_face(vl.from_numpy(im.cpu().numpy()[..., None], gpu), AVG, resize, crop=crop)
+            assert torch.equal(faces[..., j].contiguous().view(torch.int32), one[..., 0].contiguous().view(torch.int32)), \
+                (names[j % len(names)], resize)
+
+
+def test_uniform_batch_through_imreadjpeg(gpu, golden):
+    from mcncrossmodalemotions_amd import vl
+    files = [golden["bytes_" + n].tobytes() for n in ("s444_16x16", "s420_16x16")] * 3
+    imgs = vl.imreadjpeg(files)
+    assert len(imgs) == 6 and all(tuple(i.shape) == (16, 16, 3) for i in imgs)
+    stacked = np.stack([i.cpu().numpy() for i in imgs], -1)                          # 16 x 16 x 3 x 6
+    faces = vl.imreadjpeg(files, resize=(12, 12), crop_size=1 / 1.6, average_image=AVG, num_threads=10)
+    want = vl.crop_resize_face(vl.from_numpy(stacked, gpu), AVG, (12, 12))
+    assert torch.equal(faces.contiguous().view(torch.int32), want.contiguous().view(torch.int32))
+    # resize alone: the R, G, B pack; at the image's own size and crop 1 the resampler is the identity
+    rgb = vl.imreadjpeg(files, resize=(16, 16))
+    assert tuple(rgb.shape) == (16, 16, 3, 6)
+    assert np.array_equal(vl.to_numpy(rgb), stacked)
+    with pytest.raises(ValueError, match="need resize"):
+        vl.imreadjpeg(files, crop_size=0.5)
+
+
+def _launches(L, fn):
+    L.xm_prof_enable(1)
+    fn()
+    torch.cuda.synchronize()
+    L.xm_prof_enable(0)
+    cap = 32
+    keys, ms, fl, cnt = (C.c_int * cap)(), (C.c_double * cap)(), (C.c_double * cap)(), (C.c_longlong * cap)()
+    n = L.xm_prof_collect(cap, keys, ms, fl, cnt)
+    out = {}
+    for i in range(min(n, cap)):
+        b = C.create_string_buffer(128)
+        L.xm_prof_kernel_name(keys[i], b, 128)
+        out[b.value.decode()] = int(cnt[i])
+    return out
+
+
+def test_launch_count_does_not_depend_on_n(gpu, golden, names):
+    from mcncrossmodalemotions_amd import _lib, vl
+    L = _lib.load()
+    files = [golden["bytes_" + names[i % len(names)]].tobytes() for i in range(70)]
+    vl.imreadjpeg(files, resize=(24, 24), average_image=AVG)                       # the workspace exists
+    one = _launches(L, lambda: vl.imreadjpeg(files[7:8], resize=(24, 24), average_image=AVG))
+    all70 = _launches(L, lambda: vl.imreadjpeg(files, resize=(24, 24), average_image=AVG))
+    print("launches:", all70)
+    assert one == all70 and sum(all70.values()) == 5
+    assert set(all70) == {"jpeg_clear_kernel", "jpeg_entropy_kernel", "jpeg_idct_kernel", "jpeg_colour_kernel",
+                          "crop_resize_face_ragged_kernel"}
+    plain = _launches(L, lambda: vl.imreadjpeg(files))
+    assert sum(plain.values()) == 4 and "crop_resize_face_ragged_kernel" not in plain
+
+
+# ------------------------------------------------------------------------------------------------ buildImdb, compute_visual_feats
+@pytest.fixture(scope="module")
+def teacher(gpu):
+    """the quarter-width ResNet-50 teacher of tests/test_gpu_imdb.py"""
+    from mcncrossmodalemotions_amd import zoo
+    return zoo.ferPlusZoo("resnet50-ferplus", seed=5, width_mult=0.25, blocks=(1, 1, 1, 1))
+
+
+def jpeg_imdb(golden, names):
+    from mcncrossmodalemotions_amd import batch, fetch_emovoxceleb_imdb as fe
+    syn = batch.SyntheticEmoVoxImdb(num_tracks=5, seed=4, min_seconds=0.8, max_seconds=1.6)
+    src = fe.src_imdb(syn)
+    use = [n for n in names if n != "s420_1x1"]
+    frames = batch.JpegDenseFrames(src, [golden["bytes_" + n].tobytes() for n in use], frameless=(2,), unclaimed=3)
+    imdb = fe.addFramesToImdb(src, frames.lister, find=frames.find)
+    pil = lambda path: golden["pix_" + use[frames.index(path)]]
+    return imdb, frames, pil
+
+
+def test_build_imdb_from_jpeg_bytes(gpu, golden, names, teacher):
+    from mcncrossmodalemotions_amd import fetch_emovoxceleb_imdb as fe, vl
+    imdb, frames, pil = jpeg_imdb(golden, names)
+    paths = imdb.images["denseFrames"]
+    assert len(imdb.images["id"]) == 4 and 8 <= len(paths) <= 60
+    assert len({pil(p).shape for p in paths[:7]}) > 2                              # one batch holds several sizes
+    decoded = lambda ps, device: vl.from_numpy(np.stack([pil(p) for p in ps], -1).astype(np.float32), device)
+    ref = fe.buildImdb(teacher, imdb, decoded, batchSize=1)                        # PIL's pixels, a frame at a time
+    got = fe.buildImdb(teacher, imdb, read=frames.read, batchSize=1)
+    assert len(got.wavLogits) == len(ref.wavLogits) == 4
+    for a, b in zip(got.wavLogits, ref.wavLogits):
+        assert a.shape == b.shape and a.shape[0] > 0 and np.array_equal(a.view(np.uint32), b.view(np.uint32))
+    # ragged batches of 7: the same faces in the same batches, made from PIL's pixels one frame at a time
+    model, imageSize, avg = fe._as_teacher(teacher, 2)
+    rows = []
+    for s in range(0, len(paths), 7):
+        faces = [vl.crop_resize_face(decoded([p], gpu), avg, imageSize) for p in paths[s:s + 7]]
+        stacked = vl.mat_empty(imageSize[0], imageSize[1], 3, len(faces), device=gpu)
+        for k, f in enumerate(faces):
+            stacked[..., k].copy_(f[..., 0])
+        rows.append(vl.to_numpy(model.logits(stacked)).reshape(8, -1, order="F").T)
+    rows = np.concatenate(rows, 0)
+    got7 = fe.buildImdb(teacher, imdb, read=frames.read, batchSize=7)
+    assert np.array_equal(np.concatenate(got7.wavLogits, 0).view(np.uint32), rows.view(np.uint32))
+    with pytest.raises(ValueError, match="either"):
+        fe.buildImdb(teacher, imdb)
+
+
+def test_compute_visual_feats_from_jpeg_bytes(gpu, golden, names, teacher):
+    from mcncrossmodalemotions_amd import external, fetch_emovoxceleb_imdb as fe, vl
+    imdb, frames, pil = jpeg_imdb(golden, names)
+    ids, wavIds, paths = imdb.images["id"], imdb.images["denseFramesWavIds"], imdb.images["denseFrames"]
+    tracks = [[p for p, w in zip(paths, wavIds) if w == i] for i in ids]
+    net = teacher
+    model, imageSize, avg = fe._as_teacher(net, 2)
+    mats = []
+    for t in tracks:
+        m = vl.mat_empty(imageSize[0], imageSize[1], 3, len(t), device=gpu)
+        for k, p in enumerate(t):
+            m[..., k].copy_(vl.crop_resize_face(vl.from_numpy(pil(p)[..., None].astype(np.float32), gpu), avg, imageSize)[..., 0])
+        mats.append(m)
+    ref = external.compute_visual_feats(net, mats, batchSize=6)
+    got = external.compute_visual_feats(net, tracks, batchSize=6, read=frames.read)
+    assert len(got) == len(ref) == len(tracks)
+    for a, b in zip(got, ref):
+        assert a.shape == b.shape and np.array_equal(a.view(np.uint32), b.view(np.uint32))

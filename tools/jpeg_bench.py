@@ -1,0 +1,175 @@
+#!/usr/bin/env python
+"""Timing of vl.imreadjpeg (xm_jpeg_plan / xm_jpeg_decode_batch) in front of the frozen teacher.
+usage: python tools/jpeg_bench.py [--teacher senet50-ferplus] [--batches 12] [--reps 10]
+128 files of 256 x 256, 4:2:0, quality 90, smooth-plus-noise content (made with PIL when it is importable; otherwise the
+golden files of tests/golden/jpeg_small.npz repeated, and the PIL lines are left out).  Prints
+ (a) ms per batch of each decode kernel (the library's profiler hook) and of the host parse and the enqueue;
+ (b) PIL decoding the same files on 10 and on 16 threads, img/s, twice;
+ (c) buildImdb's loop at batch 128 fed prepared decoded frames, PIL on 10 threads, and the device JPEG path, next to the
+     teacher alone measured in the same process."""
+import argparse
+import ctypes as C
+import io
+import os
+import sys
+import time
+from concurrent.futures import ThreadPoolExecutor
+
+import numpy as np
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+from mcncrossmodalemotions_amd import _lib, fetch_emovoxceleb_imdb as fe, vl, zoo  # noqa: E402
+
+
+def timeit(fn, reps):
+    fn()
+    torch.cuda.synchronize()
+    s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    s.record()
+    for _ in range(reps):
+        fn()
+    e.record()
+    torch.cuda.synchronize()
+    return s.elapsed_time(e) / reps * 1e-3
+
+
+def make_files(n):
+    try:
+        from PIL import Image
+    except ImportError:
+        g = np.load(os.path.join(ROOT, "tests", "golden", "jpeg_small.npz"))
+        names = [str(x) for x in g["names"]]
+        return [g["bytes_" + names[i % len(names)]].tobytes() for i in range(n)], False
+    sys.path.insert(0, os.path.join(ROOT, "tests", "golden"))
+    import make_golden_jpeg as mk
+    out = []
+    for i in range(n):
+        buf = io.BytesIO()
+        Image.fromarray(mk.smooth_noise(5000 + i, 256, 256, 3), "RGB").save(buf, "JPEG", quality=90, subsampling=2)
+        out.append(buf.getvalue())
+    return out, True
+
+
+def pil_rate(files, threads):
+    from PIL import Image
+    dec = lambda b: np.asarray(Image.open(io.BytesIO(b)).convert("RGB"))     # noqa: E731
+    with ThreadPoolExecutor(threads) as ex:
+        list(ex.map(dec, files))
+        t0 = time.perf_counter()
+        for _ in range(4):
+            list(ex.map(dec, files))
+        return 4 * len(files) / (time.perf_counter() - t0)
+
+
+def kernel_ms(L, fn, reps):
+    L.xm_prof_enable(1)
+    for _ in range(reps):
+        fn()
+    torch.cuda.synchronize()
+    L.xm_prof_enable(0)
+    cap = 32
+    keys, ms, fl, cnt = (C.c_int * cap)(), (C.c_double * cap)(), (C.c_double * cap)(), (C.c_longlong * cap)()
+    n = L.xm_prof_collect(cap, keys, ms, fl, cnt)
+    out = {}
+    for i in range(min(n, cap)):
+        b = C.create_string_buffer(128)
+        L.xm_prof_kernel_name(keys[i], b, 128)
+        out[b.value.decode()] = ms[i] / max(cnt[i], 1)
+    return out
+
+
+def loop_rate(teacher, imdb, numIms, **src):
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    fe.buildImdb(teacher, imdb, batchSize=128, **src)
+    torch.cuda.synchronize()
+    return numIms / (time.perf_counter() - t0)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--teacher", default="senet50-ferplus")
+    ap.add_argument("--batches", type=int, default=12)
+    ap.add_argument("--reps", type=int, default=10)
+    a = ap.parse_args()
+    dev = torch.device("cuda", 0)
+    torch.cuda.set_device(0)
+    L = _lib.load()
+    files, have_pil = make_files(128)
+    print("128 files, %s, %.1f kB on average" % ("256 x 256 4:2:0 quality 90 (PIL)" if have_pil else
+                                                  "the golden files repeated (PIL is not importable)",
+                                                  sum(map(len, files)) / 128e3))
+    full = lambda: vl.imreadjpeg(files, resize=(224, 224), crop_size=1 / 1.6, average_image=fe.AVERAGE_IMAGE)   # noqa: E731
+    full()
+    torch.cuda.synchronize()
+    print("(a) per batch of 128")
+    for k, v in kernel_ms(L, full, a.reps).items():
+        print("    %-34s %8.3f ms" % (k, v))
+    t0 = time.perf_counter()
+    for _ in range(a.reps):
+        vl.jpeg_plan(files, stage=vl._pinned)
+    t_plan = (time.perf_counter() - t0) / a.reps
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    for _ in range(a.reps):
+        full()
+    t_host = (time.perf_counter() - t0) / a.reps
+    torch.cuda.synchronize()
+    print("    %-34s %8.3f ms" % ("host: copy into pinned + xm_jpeg_plan", t_plan * 1e3))
+    print("    %-34s %8.3f ms" % ("host: whole imreadjpeg call", t_host * 1e3))
+    print("    %-34s %8.3f ms" % ("device: whole call, back to back", timeit(full, a.reps) * 1e3))
+    if have_pil:
+        print("(b) PIL on the same files")
+        for rep in range(2):
+            print("    10 threads %9.1f img/s    16 threads %9.1f img/s" % (pil_rate(files, 10), pil_rate(files, 16)))
+    # ---- (c) the loop ------------------------------------------------------------------------------------------------
+    n = 128 * a.batches
+    images = {"name": ["id%05d/v/1.wav" % i for i in range(1, n // 32 + 1)], "id": np.arange(1, n // 32 + 1),
+              "set": np.ones(n // 32, int), "numSamples": np.full(n // 32, 8 * 16000),
+              "denseFrames": ["%d" % (i % 128) for i in range(n)], "denseFramesWavIds": np.arange(n) // 32 + 1}
+    imdb = fe.EmoVoxImdb(images)
+    net = zoo.ferPlusZoo(a.teacher)
+    zoo.strip_losses(net)
+    net.mode = "test"
+    net.move("gpu")
+    teacher = zoo.FrozenTeacher(net, lanes=2)
+    teacher.imageSize, teacher.averageImage = (224, 224), fe.AVERAGE_IMAGE
+    faces = full()
+    for _ in range(a.batches):
+        teacher.logits(faces)
+    alone = max(128 / timeit(lambda: teacher.logits(faces), a.batches) for _ in range(3))
+    read = lambda paths: [files[int(p)] for p in paths]                                        # noqa: E731
+    imgs = vl.imreadjpeg(files)
+    uniform = len({tuple(i.shape) for i in imgs}) == 1
+    print("(c) %s, batch 128, %d frames" % (a.teacher, n))
+    print("    FrozenTeacher.logits alone (prepared faces)   %9.1f img/s  = %.3f ms per batch" % (alone, 128 / alone * 1e3))
+    if uniform:
+        one = torch.stack([i.permute(2, 1, 0) for i in imgs], 0).permute(3, 2, 1, 0)
+        prepared = lambda paths, device: one[..., :len(paths)]                                 # noqa: E731
+        fe.buildImdb(teacher, imdb, prepared, batchSize=128)
+        r = max(loop_rate(teacher, imdb, n, frames=prepared) for _ in range(3))
+        print("    buildImdb loop, prepared decoded frames       %9.1f img/s  (%+.1f %% vs alone)" % (r, 100 * (r / alone - 1)))
+    if have_pil and uniform:
+        from PIL import Image
+        pool = ThreadPoolExecutor(10)
+        dec = lambda b: np.asarray(Image.open(io.BytesIO(b)).convert("RGB"))                   # noqa: E731
+
+        def pil_frames(paths, device):
+            a8 = np.stack(list(pool.map(dec, read(paths))), 0)                                 # n x H x W x 3
+            t = torch.from_numpy(a8).pin_memory().to(device, non_blocking=True)
+            return t.to(torch.float32).permute(0, 3, 2, 1).contiguous().permute(3, 2, 1, 0)             # MATLAB layout
+        fe.buildImdb(teacher, imdb, pil_frames, batchSize=128)
+        for rep in range(2):
+            r = loop_rate(teacher, imdb, n, frames=pil_frames)
+            print("    buildImdb loop, PIL on 10 threads             %9.1f img/s  (%+.1f %% vs alone)" % (r, 100 * (r / alone - 1)))
+        pool.shutdown()
+    fe.buildImdb(teacher, imdb, read=read, batchSize=128)
+    for rep in range(2):
+        r = loop_rate(teacher, imdb, n, read=read)
+        print("    buildImdb loop, device JPEG decode            %9.1f img/s  (%+.1f %% vs alone)" % (r, 100 * (r / alone - 1)))
+
+
+if __name__ == "__main__":
+    main()
