@@ -473,6 +473,14 @@ static size_t gemm_slab_floats(const ConvGemmArgs &a, int ci, int *splits_out) {
   return need;
 }
 
+// combines the z partial slabs over `np` pixels in a fixed order (vec: pixel quads)
+static void launch_splitk_epilogue(const ConvGemmArgs &a, int z, int np, bool vec, hipStream_t st) {
+  const int cols = vec ? np / 4 : np;
+  const dim3 grid((unsigned)(((size_t)a.M * cols + 255) / 256));
+  if (vec) hipLaunchKernelGGL(conv_splitk_epilogue_kernel<true>, grid, dim3(256), 0, st, a, z, make_fastdiv((uint32_t)cols));
+  else hipLaunchKernelGGL(conv_splitk_epilogue_kernel<false>, grid, dim3(256), 0, st, a, z, make_fastdiv((uint32_t)cols));
+}
+
 static int launch_gemm(ConvGemmArgs &a, int mode, int ci, int splits, float *slab, hipStream_t st) {
   if (is_dma_cfg(ci) && !a.dmaOk) ci = base_cfg(ci);   // forced configuration on a geometry it cannot run
   if (ci == kCfgW8 && !path_on(kPathW8)) ci = 0;
@@ -523,19 +531,14 @@ static int launch_gemm(ConvGemmArgs &a, int mode, int ci, int splits, float *sla
     const int z = splits > 1 ? splits : hyS;
     const int np = a.NP - a.hyP0;                       // pixels the slabs cover
     const bool vec = a.vecStore && (np & 3) == 0 && (a.hyP0 & 3) == 0 && (a.NPs & 3) == 0 && ((uintptr_t)a.slab & 15) == 0;
-    const size_t n = (size_t)a.M * (vec ? np / 4 : np);
     if (hyS > 1 && a.statPart) {
       // the full rounds left their partial sums per pixel tile; the remainder's come from the combine kernel
       const int cols = np / 4, chunks = (cols + 255) / 256, statBase = a.hyFull / a.nbm;
       if (!vec) return fail(XM_EINVAL, "vl_nnconv: hybrid schedule with statistics needs vector stores");
       hipLaunchKernelGGL(conv_splitk_epilogue_stats_kernel, dim3(chunks, a.M), dim3(256), 0, st, a, z, cols, statBase);
       a.statNcg = statBase + chunks;
-    } else if (vec)
-      hipLaunchKernelGGL(conv_splitk_epilogue_kernel<true>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st,
-                         a, z, make_fastdiv((uint32_t)(np / 4)));
-    else
-      hipLaunchKernelGGL(conv_splitk_epilogue_kernel<false>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st,
-                         a, z, make_fastdiv((uint32_t)np));
+    } else
+      launch_splitk_epilogue(a, z, np, vec, st);
     XM_LAUNCH_CHECK();
   }
   return XM_OK;
@@ -673,13 +676,9 @@ static size_t halo_slab_floats(const ConvGemmArgs &a) {
 
 static void halo_prepare(ConvGemmArgs &a, int v) {
   const int bm = kHaloVars[v].bm;
-  a.nbm = (a.M + bm - 1) / bm;
-  a.nbn = (a.NP + 127) / 128;
+  a.nbm = (a.M + bm - 1) / bm, a.nbn = (a.NP + 127) / 128;
   a.nkt = a.Rtrue / (kHaloCB * a.nU * a.nV);   // stages (the split-K bookkeeping of the kernel counts in these)
-  a.tilesPerSplit = a.nkt;
-  a.NPs = (a.NP + 3) & ~3;
-  a.slab = nullptr;
-  a.dbgCycles = nullptr;
+  a.tilesPerSplit = a.nkt, a.NPs = (a.NP + 3) & ~3, a.slab = nullptr, a.dbgCycles = nullptr;
 }
 
 // test hook: xm_debug_force_conv_halo(1 + v) asks for variant v, any other runnable one if v cannot take the problem
@@ -687,6 +686,7 @@ static int forced_halo_variant(const bool *hok) {
   if (g_force_halo >= 1 && g_force_halo <= 3 && hok[g_force_halo]) return g_force_halo;
   return hok[2] ? 2 : (hok[1] ? 1 : 3);
 }
+static int halo_forced(const bool *hok) { return g_force_halo < 0 ? -1 : (g_force_halo == 0 ? 0 : forced_halo_variant(hok)); }
 
 static int launch_halo(ConvGemmArgs a, int v, float *slab, hipStream_t st) {
   halo_prepare(a, v);
@@ -705,14 +705,7 @@ static int launch_halo(ConvGemmArgs a, int v, float *slab, hipStream_t st) {
   }
   XM_LAUNCH_CHECK();
   if (splits > 1) {
-    const bool vec = a.vecStore && (a.NP & 3) == 0 && ((uintptr_t)a.slab & 15) == 0;
-    const size_t n = (size_t)a.M * (vec ? a.NP / 4 : a.NP);
-    if (vec)
-      hipLaunchKernelGGL(conv_splitk_epilogue_kernel<true>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st,
-                         a, splits, make_fastdiv((uint32_t)(a.NP / 4)));
-    else
-      hipLaunchKernelGGL(conv_splitk_epilogue_kernel<false>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st,
-                         a, splits, make_fastdiv((uint32_t)a.NP));
+    launch_splitk_epilogue(a, splits, a.NP, a.vecStore && (a.NP & 3) == 0 && ((uintptr_t)a.slab & 15) == 0, st);
     XM_LAUNCH_CHECK();
   }
   return XM_OK;
@@ -742,10 +735,6 @@ static int launch_halo_multi(const std::vector<ConvGemmArgs> &args, int v, hipSt
   return XM_OK;
 }
 
-static int choose_cfg(long long M, long long NP, int nkt) {
-  return g_force_cfg >= 0 ? g_force_cfg : pick_cfg(M, NP, nkt);
-}
-
 // ---- measured tile selection ("find mode") ---------------------------------------------------
 // The first time a (direction, geometry) is seen, every tile configuration is timed on the
 // caller's stream (HIP events, 2 launches each, best of) and the winner is cached for the life of
@@ -755,6 +744,19 @@ struct TuneKey {
   int kind, M, NP, Rp, mode, a, b, c, d;
   bool operator<(const TuneKey &o) const { return memcmp(this, &o, sizeof(TuneKey)) < 0; }
 };
+// one builder per key family (the kinds: DESIGN.md 2.0); the fields are what the shipped table was written with
+static TuneKey tune_key_forward(int kind, const Geo &g, int M, int NP, int Rp, int tmode) {
+  return TuneKey{kind, M, NP, Rp, tmode, g.sy * 16 + g.sx, g.FH * 64 + g.FW, g.H, g.W};
+}
+static TuneKey tune_key_class_dgrad(int kind, const Geo &g, const DgradClass &c, int M, int NP, int PI) {
+  return TuneKey{kind, M, NP, c.Rp, c.nU * 64 + c.nV, g.sy * 16 + g.sx, PI, c.PJ, g.Ho};
+}
+static TuneKey tune_key_merged_dgrad(int kind, const Geo &g, int M, long long npSum, int rpMax, int classes) {
+  return TuneKey{kind, M, (int)std::min<long long>(npSum, 1 << 30), rpMax, classes, g.sy * 16 + g.sx, g.FH * 64 + g.FW, g.H, g.W};
+}
+static TuneKey tune_key_wgrad(int kind, const Geo &g) {
+  return TuneKey{kind, g.Kg, g.Ho * g.Wo * g.N, g.R, g.G, g.sy * 16 + g.sx, g.FH * 64 + g.FW, g.H, g.W};
+}
 static std::map<TuneKey, int> g_tuned;
 
 // ---- persistent tuning table ------------------------------------------------------------------
@@ -901,6 +903,19 @@ static int tune_challengers(const TuneKey &key, hipStream_t st, F &&launch, int 
             key.M, key.NP, key.Rp, tmin[0], tmin[1], tmin[2], tmin[3], pick);
   return pick;
 }
+// The one selection routine behind every "incumbent against challengers" choice: arm 0 is the best implicit-GEMM
+// configuration, arms 1 .. n - 1 the special-purpose kernels with ok[i].  Returns the arm a force hook names (`forced` >= 0),
+// else the measured pick under `base` with its kind replaced (0 with find mode off).  The caller runs the pick.
+template <class F>
+static int select_arm(int kind, TuneKey base, hipStream_t st, int n, const bool *ok, float margin, int forced, F &&launch) {
+  bool any = false;
+  for (int i = 1; i < n; ++i) any = any || ok[i];
+  if (!any) return 0;          // no challenger can run: nothing to choose, nothing to record
+  if (forced >= 0) return forced;
+  base.kind = kind;
+  return tune_challengers(base, st, launch, n, ok, margin);
+}
+static const bool kOneChallenger[2] = {true, true};
 
 template <int AV>
 static void launch_wgrad_av(int ci, const WgradArgs &a, dim3 grid, hipStream_t st) {
@@ -933,11 +948,9 @@ static void launch_wgrad_cfg(int ci, const WgradArgs &a, dim3 grid, hipStream_t 
   }
 }
 
-// ---- geometry shared by the three directions ------------------------------------------------
-struct Geo {
-  int H, W, C, N, FH, FW, FC, K, G, Kg, Ho, Wo, R;
-  int sy, sx, pt, pb, pl, pr, dy, dx;
-};
+// ---- geometry shared by the three directions (struct Geo: conv_plan.h) ------------------------
+static_assert(sizeof(Tap2) == sizeof(int2) && alignof(Tap2) <= alignof(int2), "Tap2 has the layout of int2: {x, y}");
+static_assert(sizeof(Tap4) == sizeof(int4) && alignof(Tap4) <= alignof(int4), "Tap4 has the layout of int4: {x, y, z, w}");
 
 static int make_geo(Geo &g, int H, int W, int C, int N, int FH, int FW, int FC, int K, int sy,
                     int sx, int pt, int pb, int pl, int pr, int dy, int dx) {
@@ -961,34 +974,12 @@ static int make_geo(Geo &g, int H, int W, int C, int N, int FH, int FW, int FC, 
   return XM_OK;
 }
 
-// forward tap table for the implicit GEMM: r = u + FH*(v + FW*c) -> {byte offset in X, (u,v) index}
-static const int2 *fwd_taps2(const Geo &g, int Rp, bool all_valid = false) {
-  int count = Rp + 3 * kBK;  // kernels fetch the table three stages ahead
-  std::vector<int2> t(count);
-  for (int r = 0; r < count; ++r) {
-    if (r < g.R) {
-      int u = r % g.FH, v = (r / g.FH) % g.FW, c = r / (g.FH * g.FW);
-      // all_valid (no spatial padding, > 63 taps): every real tap shares mask bit 0 = tap (0,0)
-      t[r] = make_int2(4 * (u * g.dy + g.H * (v * g.dx) + g.H * g.W * c), all_valid ? 0 : u + g.FH * v);
-    } else {
-      t[r] = make_int2(0, 63);
-    }
-  }
-  return (const int2 *)cached_device_table(t.data(), t.size() * sizeof(int2));
+// the planning tables (conv_plan.h) on the device, cached by content
+static const int2 *device_taps(const std::vector<Tap2> &t) {
+  return (const int2 *)cached_device_table(t.data(), t.size() * sizeof(Tap2));
 }
-
-// wgrad tap table: {byte offset in X, u*dy, v*dx}
-static const int4 *fwd_taps(const Geo &g, int count) {
-  std::vector<int4> t(count);
-  for (int r = 0; r < count; ++r) {
-    if (r < g.R) {
-      int u = r % g.FH, v = (r / g.FH) % g.FW, c = r / (g.FH * g.FW);
-      t[r] = make_int4(4 * (u * g.dy + g.H * (v * g.dx) + g.H * g.W * c), u * g.dy, v * g.dx, 0);
-    } else {
-      t[r] = make_int4(0, -(1 << 28), 0, 0);
-    }
-  }
-  return (const int4 *)cached_device_table(t.data(), t.size() * sizeof(int4));
+static const int4 *device_taps(const std::vector<Tap4> &t) {
+  return (const int4 *)cached_device_table(t.data(), t.size() * sizeof(Tap4));
 }
 
 // ---- skinny fully-connected layers ------------------------------------------------------------
@@ -1194,37 +1185,26 @@ static int fc_skinny_forward(const float *x, const float *f, const float *b, flo
   return XM_OK;
 }
 
-// moments_out != NULL: also the batch moments [mean, sqrt(var + eps)] of Y (the statistics half of the train-mode
-// vl_nnbnorm that follows the convolution), from per-wave partial sums of the GEMM epilogue when the launch allows it
-// (16-byte-store epilogue, no split-K, no filter groups), else by a pass over Y.
 // ---- single-channel stem (conv_stem_kernel) ----------------------------------------------------------------------
 // Forward convolutions over ONE input channel with <= 8 x 7 taps, stride 1 / 2 along H, <= 96 filters, source columns of
 // <= 512 rows (the student's conv1 over 512-bin spectrograms).  `f` is the caller's filter bank, unpadded.
-static bool stem_ok(const ConvGemmArgs &a, const Geo &g, const float *x, const float *f) {
-  const bool off = !path_on(kPathStem);
-  if (off || g_force_cfg >= 0 || g_force_splits > 0) return false;
-  if (g.C != 1 || g.G != 1 || g.FC != 1 || g.dy != 1 || g.dx != 1) return false;
-  if (g.FH > 8 || g.FW > kStemNV || g.FH * g.FW < 16 || g.Kg > 96) return false;
-  if (g.sy != 1 && g.sy != 2) return false;
-  if (!a.vecStore || a.scale || a.resid || a.gate || a.relu) return false;
-  if (g.H % 4 != 0 || g.H > kStemHP - 8 || ((uintptr_t)x & 15) != 0) return false;
-  if (g.pt > 4 || 4 * ((g.sy * (g.Ho - 1) - g.pt + 4 + 7) >> 2) + 3 >= kStemHP) return false;   // last 16-byte row unit a tile loads
-  if (g.Ho < 128) return false;                                                  // a tile spans <= 2 output columns
-  if (g_force_stem != 1 && (long long)g.Ho * g.Wo * g.N < 128 * 512) return false;   // >= one round of the chip
-  (void)f;
-  return true;
+static bool forced_tiling() { return g_force_cfg >= 0 || g_force_splits > 0; }   // a test asked for one implicit-GEMM launch
+static bool fills_chip(const Geo &g) { return (long long)g.Ho * g.Wo * g.N >= 128 * 512; }   // >= one round of the chip
+static unsigned epilogue_flags(const ConvGemmArgs &a, bool stats) {
+  return (a.vecStore ? kEpiVecStore : 0u) | (a.scale ? kEpiScale : 0u) | (a.resid ? kEpiResid : 0u) |
+         (a.gate ? kEpiGate : 0u) | (a.relu ? kEpiRelu : 0u) | (stats ? kEpiStats : 0u);
+}
+static bool stem_ok(const ConvGemmArgs &a, const Geo &g, const float *x, bool stats) {
+  if (!path_on(kPathStem) || forced_tiling()) return false;
+  if (!stem_fwd_can(g, (uintptr_t)x, epilogue_flags(a, stats))) return false;
+  return g_force_stem == 1 || fills_chip(g);
 }
 
 static int stem_grid(int NP) { return std::min(256 * XM_STEM_OCC, ((NP + 127) / 128 + 7) / 8 * 8); }
 
 static int launch_stem(ConvGemmArgs a, const float *f, int R, hipStream_t st) {
-  a.A = f;
-  a.lda = R;
-  a.nbm = 1;
-  a.nbn = (a.NP + 127) / 128;
-  a.slab = nullptr;
-  a.hyS = 1, a.hyFull = 0, a.hyTps = 0, a.hyP0 = 0;
-  a.piReal = 0;
+  a.A = f, a.lda = R, a.nbm = 1, a.nbn = (a.NP + 127) / 128, a.slab = nullptr;
+  a.hyS = 1, a.hyFull = 0, a.hyTps = 0, a.hyP0 = 0, a.piReal = 0;
   a.dbgCycles = g_dbg_cycles;
   const double abytes = (double)a.xBytes + 4.0 * a.M * a.Rtrue + 4.0 * a.M * (double)a.NP;
   ProfScope ps(5 * 100, 2.0 * a.M * (double)a.NP * a.Rtrue, st, abytes);
@@ -1238,20 +1218,12 @@ static int launch_stem(ConvGemmArgs a, const float *f, int R, hipStream_t st) {
 // ---- three-channel stem (conv_stem3_kernel): 7 x 7 / stride 2 over RGB images, 64 filters -- the teachers' conv1 --------------
 static int g_force_stem3 = -1;   // test hook (xm_debug_force_conv_stem3)
 static bool stem3_ok(const ConvGemmArgs &a, const Geo &g, const float *x, bool stats) {
-  if (!path_on(kPathStem3) || g_force_cfg >= 0 || g_force_splits > 0 || stats) return false;
-  if (g.C != 3 || g.G != 1 || g.FC != 3 || g.FH != 7 || g.FW != 7 || g.sy != 2 || g.sx != 2 || g.dy != 1 || g.dx != 1) return false;
-  if (g.Kg != 64 || !a.vecStore || a.resid || a.gate) return false;
-  if ((g.Ho * g.Wo) % 128 != 0 || g.Ho < 64 || (g.H & 1) || g.pt > 4 || g.pl > 6) return false;
-  if (2 * (g.Ho - 1) + 8 + (4 - g.pt) + 1 > kStem3CS) return false;                 // patch rows of a column
-  if (((uintptr_t)x & 7) != 0 || (size_t)g.H * g.W * g.C * g.N * 4 >= (1ull << 31)) return false;
-  return g_force_stem3 == 1 || (long long)g.Ho * g.Wo * g.N >= 128 * 512;           // >= one round of the chip
+  if (!path_on(kPathStem3) || forced_tiling()) return false;
+  if (!stem3_can(g, (uintptr_t)x, epilogue_flags(a, stats))) return false;
+  return g_force_stem3 == 1 || fills_chip(g);
 }
 static int launch_stem3(ConvGemmArgs a, const float *f, int R, hipStream_t st) {
-  a.A = f;
-  a.lda = R;
-  a.nbm = 1;
-  a.nbn = a.NP / 128;
-  a.slab = nullptr;
+  a.A = f, a.lda = R, a.nbm = 1, a.nbn = a.NP / 128, a.slab = nullptr;
   const double abytes = (double)a.xBytes + 4.0 * a.M * a.Rtrue + 4.0 * a.M * (double)a.NP;
   // 256-pixel block tiles (four accumulator chains per wave) where they divide a sample and span <= 4 output columns
   static const bool wide_on = env_int("XM_STEM3_WIDE", 1) != 0;
@@ -1266,6 +1238,127 @@ static int launch_stem3(ConvGemmArgs a, const float *f, int R, hipStream_t st) {
   return XM_OK;
 }
 
+// scratch for the split-K slab of whichever of the first `ncfg` tile configurations (or halo variant: nU x nV taps over
+// Rtrue reduction steps) ends up running an M x NP problem
+static size_t slab_floats(int M, int NP, int Rp, int ncfg, int nU, int nV, int Rtrue) {
+  ConvGemmArgs proto{};
+  proto.M = M, proto.NP = NP, proto.Rp = Rp;
+  size_t need = 0;
+  for (int c = 0; c < ncfg; ++c) {
+    int sp;
+    need = std::max(need, gemm_slab_floats(proto, c, &sp));
+  }
+  if (nU <= 3 && nV <= 3 && nU * nV >= 4 && Rtrue % (kHaloCB * nU * nV) == 0) {   // halo-patch kernel splits
+    proto.Rtrue = Rtrue, proto.nU = nU, proto.nV = nV;
+    need = std::max(need, halo_slab_floats(proto));
+  }
+  return need;
+}
+
+// what every filter group of a forward call shares
+struct FwdOperands {
+  const float *x, *A, *b, *scale, *shift, *resid, *gate;
+  float *y;
+  const int2 *taps;
+  int lda, Rp, relu;
+  bool bigTaps, dma_ok;
+};
+
+// the implicit-GEMM problem of filter group `grp`
+static ConvGemmArgs forward_args(const Geo &g, int grp, const FwdOperands &o) {
+  ConvGemmArgs a{};
+  const size_t xoff = (size_t)grp * g.FC * g.H * g.W, yoff = (size_t)grp * g.Kg * g.Ho * g.Wo;
+  a.A = o.A + (size_t)grp * g.Kg * o.lda, a.lda = o.lda, a.aBytes = (unsigned)((size_t)g.Kg * o.lda * 4);
+  a.X = o.x + xoff, a.xBytes = (unsigned)((x_elements(g) - xoff) * 4), a.xSampleStride = g.H * g.W * g.C;
+  a.Y = o.y + yoff, a.taps = o.taps, a.tapStride = (unsigned)((size_t)g.H * g.W * 4);
+  a.bias = o.b ? o.b + grp * g.Kg : nullptr;
+  a.scale = o.scale ? o.scale + grp * g.Kg : nullptr, a.shift = o.shift ? o.shift + grp * g.Kg : nullptr;
+  a.resid = o.resid ? o.resid + yoff : nullptr, a.relu = o.relu;
+  a.gate = o.gate ? o.gate + (size_t)grp * g.Kg : nullptr, a.gateStride = g.K;
+  a.M = g.Kg, a.Rp = o.Rp, a.Rtrue = g.R;
+  a.PI = g.Ho, a.PJ = g.Wo, a.NP = g.Ho * g.Wo * g.N;
+  a.divPIJ = make_fastdiv((uint32_t)(g.Ho * g.Wo)), a.divPI = make_fastdiv((uint32_t)g.Ho);
+  a.gsy = g.sy, a.gsx = g.sx, a.gh0 = -g.pt, a.gw0 = -g.pl, a.LimH = g.H, a.LimW = g.W;
+  a.nU = o.bigTaps ? 1 : g.FH, a.nV = o.bigTaps ? 1 : g.FW;   // mask construction only looks at tap (0,0) then (always valid)
+  a.du0 = 0, a.dus = g.dy, a.dv0 = 0, a.dvs = g.dx;
+  a.osy = 1, a.osx = 1, a.oh0 = 0, a.ow0 = 0, a.OH = g.Ho;
+  a.oChanStride = g.Ho * g.Wo, a.oSampleStride = g.Ho * g.Wo * g.K, a.divMU = make_fastdiv(1), a.oUStride = 0;
+  // 4 consecutive output pixels are contiguous (same sample) and every tile starts on a multiple
+  // of 32 pixels; 16-byte alignment of (y, residual) rows needs Ho*Wo % 4 == 0
+  a.vecStore = ((g.Ho * g.Wo) % 4 == 0 && (((uintptr_t)a.Y | (uintptr_t)a.resid) & 15) == 0) ? 1 : 0;
+  a.dmaOk = (o.dma_ok && a.vecStore) ? 1 : 0;   // the LDS-DMA kernel only carries the 16-byte-store epilogue
+  return a;
+}
+
+// Batch statistics riding in the epilogue of the launch: `ok` = this group's launch may carry them (16-byte-store
+// epilogue, no relu / residual), `part` = room for the partial sums, `ncg` = partial rows per channel the launch that
+// ran LAST left behind (0: none -- split-K, or a kernel without the epilogue).
+struct FwdStats {
+  bool ok;
+  float *part;
+  int ncg;
+};
+static ConvGemmArgs stats_args(const ConvGemmArgs &a, FwdStats &s, int ncg) {
+  ConvGemmArgs aa = a;
+  s.ncg = ncg;
+  if (ncg > 0) aa.statPart = s.part, aa.statNcg = ncg;
+  return aa;
+}
+// [mean, sqrt(var + eps)] from the partial sums (fp64 across the partial rows, fixed order)
+static int forward_stats_reduce(const FwdStats &s, double *part2, float *moments_out, int K, int NP, float eps, hipStream_t st) {
+  const int S = std::max(1, std::min(64, s.ncg / 768));   // one launch up to ~1500 partial rows per channel
+  hipLaunchKernelGGL(conv_stats_reduce_kernel, dim3((K + 7) / 8, S), dim3(256), 0, st, s.part, moments_out, part2, K, s.ncg, S,
+                     (double)NP, eps);
+  XM_LAUNCH_CHECK();
+  if (S > 1) {
+    hipLaunchKernelGGL(conv_stats_finalize2_kernel, dim3((K + 255) / 256), dim3(256), 0, st, part2, moments_out, K, S,
+                       (double)NP, eps);
+    XM_LAUNCH_CHECK();
+  }
+  return XM_OK;
+}
+
+// Selection and launch of one group's forward problem: the best implicit-GEMM configuration, then ONE family of
+// special-purpose kernels against it (measured once per shape, alternating launches, the challenger must win by a margin).
+static int forward_run(const Geo &g, const ConvGemmArgs &a, const float *x, const float *f, int mode, float *slab,
+                       FwdStats &s, hipStream_t st) {
+  auto gemm = [&](int ci) {
+    int sp;
+    ci = a.dmaOk ? ci : base_cfg(ci);
+    gemm_slab_floats(a, ci, &sp);
+    const bool carry = s.ok && sp == 1 && g_force_splits <= 1;
+    ConvGemmArgs aa = stats_args(a, s, carry ? (a.NP + kCfgs[ci].bn() - 1) / kCfgs[ci].bn() : 0);
+    const int rc_ = launch_gemm(aa, mode, ci, sp, slab, st);
+    if (aa.statPart) s.ncg = aa.statNcg;     // (hybrid schedule: full pixel tiles + the combine kernel's chunks)
+    return rc_;
+  };
+  // the launch with fused batch statistics is its own entry: it excludes the LDS-DMA configurations and carries a
+  // longer epilogue, so whichever variant reached a shape first must not fix the choice for the other
+  const TuneKey key = tune_key_forward(0, g, a.M, a.NP, a.Rp, mode + (s.ok ? 4 : 0));
+  const int ci = tune_cfg(key, pick_cfg(a.M, a.NP, a.Rp / kBK), st, gemm, a.dmaOk ? kNumCfg : kNumBaseCfg, w8_skip(a.M, a.NP));
+  if (stem_ok(a, g, x, s.ok)) {     // the single-channel stem kernel: one partial row per (persistent) block
+    auto arm = [&](int h) { return h ? launch_stem(stats_args(a, s, s.ok ? stem_grid(a.NP) : 0), f, g.R, st) : gemm(ci); };
+    return arm(select_arm(7, key, st, 2, kOneChallenger, kHaloMargin, g_force_stem, arm));
+  }
+  if (stem3_ok(a, g, x, s.ok)) {    // the three-channel stem kernel
+    auto arm = [&](int h) { return h ? launch_stem3(a, f, g.R, st) : gemm(ci); };
+    return arm(select_arm(12, key, st, 2, kOneChallenger, kHaloMargin, g_force_stem3, arm));
+  }
+  // <= 3 x 3 taps / unit stride: the halo-patch kernel variants
+  ConvGemmArgs ah = a;
+  const int hneed = forced_tiling() ? 0 : halo_setup(ah, g.N);
+  const bool hok[4] = {true, halo_var_ok(ah, hneed, 0), halo_var_ok(ah, hneed, 1), halo_var_ok(ah, hneed, 2)};
+  auto arm = [&](int h) {
+    if (!h) return gemm(ci);
+    const bool carry = s.ok && halo_splits(ah, h - 1) == 1;
+    return launch_halo(stats_args(ah, s, carry ? (a.NP + 127) / 128 : 0), h - 1, slab, st);
+  };
+  return arm(select_arm(4, key, st, 4, hok, kHaloMargin, halo_forced(hok), arm));
+}
+
+// moments_out != NULL: also the batch moments [mean, sqrt(var + eps)] of Y (the statistics half of the train-mode
+// vl_nnbnorm that follows the convolution), from per-wave partial sums of the GEMM epilogue when the launch allows it
+// (16-byte-store epilogue, no split-K, no filter groups), else by a pass over Y.
 static int conv_forward(const float *x, const float *f, const float *b, float *y, const Geo &g,
                         const float *scale, const float *shift, const float *resid, int relu,
                         hipStream_t st, float *moments_out = nullptr, float eps = 0.f, const float *gate = nullptr) {
@@ -1278,198 +1371,47 @@ static int conv_forward(const float *x, const float *f, const float *b, float *y
                 g.FH, g.FW);
   const int Rp = (g.R + kBK - 1) / kBK * kBK;
   const bool need_pad = (g.R % kBK) != 0 || ((uintptr_t)f & 15);
-  const int mode = ((g.pt | g.pb | g.pl | g.pr) != 0 || Rp != g.R) ? 1 : 0;
-  ConvGemmArgs proto{};
-  proto.M = g.Kg;
-  proto.NP = g.Ho * g.Wo * g.N;
-  proto.Rp = Rp;
-  // scratch must fit the split-K slab of whichever tile configuration ends up being used
-  size_t slabf = 0;
-  for (int c = 0; c < kNumCfg; ++c) {
-    int sp;
-    slabf = std::max(slabf, gemm_slab_floats(proto, c, &sp));
-  }
-  if (g.FH <= 3 && g.FW <= 3 && g.FH * g.FW >= 4 && g.R % (kHaloCB * g.FH * g.FW) == 0) {   // halo-patch kernel splits
-    ConvGemmArgs ph = proto;
-    ph.Rtrue = g.R;
-    ph.nU = g.FH;
-    ph.nV = g.FW;
-    slabf = std::max(slabf, halo_slab_floats(ph));
-  }
+  const int mode = (padded || Rp != g.R) ? 1 : 0;
+  const int NP = g.Ho * g.Wo * g.N;
+  const size_t slabf = slab_floats(g.Kg, NP, Rp, kNumCfg, g.FH, g.FW, g.R);
   // LDS-DMA eligibility: a plain GEMM in memory (1x1, unit stride, no padding), pixel quads inside one sample,
   // 16-byte aligned operands
   const bool dma_ok = !need_pad && mode == 0 && g.FH == 1 && g.FW == 1 && g.sy == 1 && g.sx == 1 && g.dy == 1 &&
                       g.dx == 1 && (g.H * g.W) % 4 == 0 && ((uintptr_t)x & 15) == 0 && ((uintptr_t)f & 15) == 0 &&
                       g.R % kBK == 0 && path_on(kPathDma);
-  const bool no_fstats = !path_on(kPathFusedStats);
-  const bool want_stats = moments_out != nullptr && g.G == 1 && !no_fstats;
+  const bool want_stats = moments_out != nullptr && g.G == 1 && path_on(kPathFusedStats);
   // partial sums: one {sum, sum sq} pair per row and per pixel tile (>= 32 pixels), + 64 fp64 slabs for the reduction
   // (the persistent stem kernel leaves one row per block: stem_grid(NP) can exceed NP / 32 on small problems)
-  const size_t statf = want_stats ? (size_t)2 * g.K * std::max((proto.NP + 31) / 32, stem_grid(proto.NP)) : 0;
+  const size_t statf = want_stats ? (size_t)2 * g.K * std::max((NP + 31) / 32, stem_grid(NP)) : 0;
   const size_t stat2 = want_stats ? (size_t)2 * g.K * 64 : 0;
   WsCarver ws;
   int rc = ws.init(WsCarver::need(need_pad ? (size_t)g.K * Rp : 0, 4) + WsCarver::need(slabf, 4) +
                        WsCarver::need(statf, 4) + WsCarver::need(stat2, 8), st);
   if (rc) return rc;
-  const int2 *taps = fwd_taps2(g, Rp, bigTaps);
-  if (!taps) return fail(XM_ENOMEM, "vl_nnconv: tap table allocation failed");
-  const float *A = f;
-  int lda = g.R;
+  FwdOperands o{x, f, b, scale, shift, resid, gate, y, device_taps(fwd_tap_table(g, Rp, bigTaps)), g.R, Rp, relu, bigTaps, dma_ok};
+  if (!o.taps) return fail(XM_ENOMEM, "vl_nnconv: tap table allocation failed");
   if (need_pad) {
     float *Ap = ws.take<float>((size_t)g.K * Rp);
     size_t n = (size_t)g.K * Rp;
     hipLaunchKernelGGL(pad_filter_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, f, Ap,
                        g.K, g.R, Rp);
     XM_LAUNCH_CHECK();
-    A = Ap;
-    lda = Rp;
+    o.A = Ap;
+    o.lda = Rp;
   }
   float *slab = slabf ? ws.take<float>(slabf) : nullptr;
   float *statp = statf ? ws.take<float>(statf) : nullptr;
   double *statp2 = stat2 ? ws.take<double>(stat2) : nullptr;
   bool stats_done = false;
-  const size_t xTotal = (size_t)g.H * g.W * g.C * g.N;
   for (int grp = 0; grp < g.G; ++grp) {
-    ConvGemmArgs a{};
-    a.A = A + (size_t)grp * g.Kg * lda;
-    size_t xoff = (size_t)grp * g.FC * g.H * g.W;
-    a.X = x + xoff;
-    a.xBytes = (unsigned)((xTotal - xoff) * 4);
-    a.Y = y + (size_t)grp * g.Kg * g.Ho * g.Wo;
-    a.taps = taps;
-    a.bias = b ? b + grp * g.Kg : nullptr;
-    a.scale = scale ? scale + grp * g.Kg : nullptr;
-    a.shift = shift ? shift + grp * g.Kg : nullptr;
-    a.resid = resid ? resid + (size_t)grp * g.Kg * g.Ho * g.Wo : nullptr;
-    a.gate = gate ? gate + (size_t)grp * g.Kg : nullptr;
-    a.gateStride = g.K;
-    a.relu = relu;
-    a.lda = lda;
-    a.M = g.Kg;
-    a.Rp = Rp;
-    a.Rtrue = g.R;
-    a.PI = g.Ho;
-    a.PJ = g.Wo;
-    a.NP = g.Ho * g.Wo * g.N;
-    a.divPIJ = make_fastdiv((uint32_t)(g.Ho * g.Wo));
-    a.divPI = make_fastdiv((uint32_t)g.Ho);
-    a.gsy = g.sy;
-    a.gsx = g.sx;
-    a.gh0 = -g.pt;
-    a.gw0 = -g.pl;
-    a.LimH = g.H;
-    a.LimW = g.W;
-    a.xSampleStride = g.H * g.W * g.C;
-    a.nU = bigTaps ? 1 : g.FH;   // mask construction only looks at tap (0,0) then (always valid)
-    a.nV = bigTaps ? 1 : g.FW;
-    a.du0 = 0;
-    a.dus = g.dy;
-    a.dv0 = 0;
-    a.dvs = g.dx;
-    a.osy = 1;
-    a.osx = 1;
-    a.oh0 = 0;
-    a.ow0 = 0;
-    a.OH = g.Ho;
-    a.oChanStride = g.Ho * g.Wo;
-    a.oSampleStride = g.Ho * g.Wo * g.K;
-    a.divMU = make_fastdiv(1);
-    a.oUStride = 0;
-    // 4 consecutive output pixels are contiguous (same sample) and every tile starts on a multiple
-    // of 32 pixels; 16-byte alignment of (y, residual) rows needs Ho*Wo % 4 == 0
-    a.vecStore = ((g.Ho * g.Wo) % 4 == 0 && (((uintptr_t)a.Y | (uintptr_t)a.resid) & 15) == 0) ? 1 : 0;
-    a.dmaOk = (dma_ok && a.vecStore) ? 1 : 0;   // the LDS-DMA kernel only carries the 16-byte-store epilogue
-    const bool stats_ok = want_stats && a.vecStore && !relu && !resid;
-    if (stats_ok) a.dmaOk = 0;                  // the partial sums ride in the register-staged kernel's epilogue
-    a.aBytes = (unsigned)((size_t)g.Kg * lda * 4);
-    a.tapStride = (unsigned)((size_t)g.H * g.W * 4);
-    int stat_ncg = 0;
-    auto run = [&](int ci) {
-      int sp;
-      ci = a.dmaOk ? ci : base_cfg(ci);
-      gemm_slab_floats(a, ci, &sp);
-      ConvGemmArgs aa = a;
-      stat_ncg = 0;
-      if (stats_ok && sp == 1 && (g_force_splits <= 1)) {
-        const Cfg &c = kCfgs[ci];
-        stat_ncg = (a.NP + c.bn() - 1) / c.bn();
-        aa.statPart = statp;
-        aa.statNcg = stat_ncg;
-      }
-      const int rc_ = launch_gemm(aa, mode, ci, sp, slab, st);
-      if (aa.statPart) stat_ncg = aa.statNcg;     // (hybrid schedule: full pixel tiles + the combine kernel's chunks)
-      return rc_;
-    };
-    // the launch with fused batch statistics is its own entry: it excludes the LDS-DMA configurations and carries a
-    // longer epilogue, so whichever variant reached a shape first must not fix the choice for the other
-    const int tmode = mode + (stats_ok ? 4 : 0);
-    TuneKey key{0, a.M, a.NP, Rp, tmode, g.sy * 16 + g.sx, g.FH * 64 + g.FW, g.H, g.W};
-    int ci = tune_cfg(key, pick_cfg(a.M, a.NP, Rp / kBK), st, run, a.dmaOk ? kNumCfg : kNumBaseCfg, w8_skip(a.M, a.NP));
-    if (stem_ok(a, g, x, f)) {
-      // the single-channel stem kernel against the best implicit-GEMM configuration (measured once per shape)
-      auto run3 = [&](int h) {
-        if (!h) return run(ci);
-        ConvGemmArgs aa = a;
-        stat_ncg = 0;
-        if (stats_ok) {
-          stat_ncg = stem_grid(a.NP);             // one partial per (persistent) block
-          aa.statPart = statp;
-          aa.statNcg = stat_ncg;
-        }
-        return launch_stem(aa, f, g.R, st);
-      };
-      bool sok[2] = {true, true};
-      TuneKey skey{7, a.M, a.NP, Rp, tmode, g.sy * 16 + g.sx, g.FH * 64 + g.FW, g.H, g.W};
-      const int pick = g_force_stem >= 0 ? g_force_stem : tune_challengers(skey, st, run3, 2, sok, kHaloMargin);
-      rc = run3(pick);
-      if (rc) return rc;
-    } else if (stem3_ok(a, g, x, stats_ok)) {
-      // the three-channel stem kernel against the best implicit-GEMM configuration (measured once per shape)
-      auto run5 = [&](int h) { return h ? launch_stem3(a, f, g.R, st) : run(ci); };
-      bool sok[2] = {true, true};
-      TuneKey skey{12, a.M, a.NP, Rp, tmode, g.sy * 16 + g.sx, g.FH * 64 + g.FW, g.H, g.W};
-      const int pick = g_force_stem3 >= 0 ? g_force_stem3 : tune_challengers(skey, st, run5, 2, sok, kHaloMargin);
-      rc = run5(pick);
-      if (rc) return rc;
-    } else {
-    // <= 3 x 3 taps / unit stride: the halo-patch kernel variants against the best implicit-GEMM configuration
-    // (measured once per shape, alternating launches, the challenger must win by a margin)
-    ConvGemmArgs ah = a;
-    const int hneed = (g_force_cfg < 0 && g_force_splits == 0) ? halo_setup(ah, g.N) : 0;
-    bool hok[4] = {true, halo_var_ok(ah, hneed, 0), halo_var_ok(ah, hneed, 1), halo_var_ok(ah, hneed, 2)};
-    if (hok[1] || hok[2] || hok[3]) {
-      auto run2 = [&](int h) {
-        if (!h) return run(ci);
-        ConvGemmArgs aa = ah;
-        stat_ncg = 0;
-        if (stats_ok && halo_splits(aa, h - 1) == 1) {
-          stat_ncg = (a.NP + 127) / 128;
-          aa.statPart = statp;
-          aa.statNcg = stat_ncg;
-        }
-        return launch_halo(aa, h - 1, slab, st);
-      };
-      TuneKey hkey{4, a.M, a.NP, Rp, tmode, g.sy * 16 + g.sx, g.FH * 64 + g.FW, g.H, g.W};
-      int pick;
-      if (g_force_halo == 0) pick = 0;
-      else if (g_force_halo > 0) pick = forced_halo_variant(hok);
-      else pick = tune_challengers(hkey, st, run2, 4, hok, kHaloMargin);
-      rc = run2(pick);
-    } else {
-      rc = run(ci);
-    }
+    ConvGemmArgs a = forward_args(g, grp, o);
+    FwdStats s{want_stats && a.vecStore && !relu && !resid, statp, 0};
+    if (s.ok) a.dmaOk = 0;                  // the partial sums ride in the register-staged kernel's epilogue
+    rc = forward_run(g, a, x, f, mode, slab, s, st);
     if (rc) return rc;
-    }
-    if (stat_ncg > 0) {
-      const int S = std::max(1, std::min(64, stat_ncg / 768));   // one launch up to ~1500 partial rows per channel
-      hipLaunchKernelGGL(conv_stats_reduce_kernel, dim3((g.K + 7) / 8, S), dim3(256), 0, st, statp, moments_out,
-                         statp2, g.K, stat_ncg, S, (double)a.NP, eps);
-      XM_LAUNCH_CHECK();
-      if (S > 1) {
-        hipLaunchKernelGGL(conv_stats_finalize2_kernel, dim3((g.K + 255) / 256), dim3(256), 0, st, statp2, moments_out,
-                           g.K, S, (double)a.NP, eps);
-        XM_LAUNCH_CHECK();
-      }
+    if (s.ncg > 0) {
+      rc = forward_stats_reduce(s, statp2, moments_out, g.K, NP, eps, st);
+      if (rc) return rc;
       stats_done = true;
     }
   }
@@ -1506,18 +1448,11 @@ static PrepKey prep_key(const float *f, const Geo &g, bool fold) {
   return k;
 }
 
-// dX: one implicit GEMM per stride-parity class (a, b) of the input pixels.
-// accum != NULL: dX = dgrad + accum (the derivative another branch of a fork already produced), added in
-// the GEMM epilogue instead of by a separate pass
-// prepare_only: run just the filter transpositions into the persistent cache (xm_nnconv_prepare_backward)
 // ---- dgrad of 5 x 5 / stride 2 layers with both row parities per wave (conv_dgrad_s2_kernel, round 5) ---------------------
 static int g_force_dgrad_s2 = -1;   // test hook (xm_debug_force_dgrad_s2): 0 = never, 1 / -1 = wherever it can run
 static bool dgrad_s2_ok(const Geo &g, const float *dzdy, const float *dxo, const float *accum) {
-  if (!path_on(kPathDgradS2) || g_force_dgrad_s2 == 0 || g_force_cfg >= 0 || g_force_splits > 0 || accum) return false;
-  if (g.G != 1 || g.FH != 5 || g.FW != 5 || g.sy != 2 || g.sx != 2 || g.dy != 1 || g.dx != 1) return false;
-  if (g.pt != 1 || g.pl < 0 || g.pl > 4 || (g.H & 1) || (g.Ho & 1) || (g.K & 7)) return false;
-  if ((((uintptr_t)dzdy | (uintptr_t)dxo) & 7) != 0) return false;
-  if ((size_t)g.Ho * g.Wo * g.K * g.N * 4 >= (1ull << 31)) return false;   // dY byte offsets are formed in 32-bit arithmetic
+  if (!path_on(kPathDgradS2) || g_force_dgrad_s2 == 0 || forced_tiling()) return false;
+  if (!dgrad_s2_can(g, (uintptr_t)dzdy, (uintptr_t)dxo, accum != nullptr)) return false;
   if (g_force_dgrad_s2 == 1) return true;
   // Its blocks are large (two output columns x 64 row pairs x all filters: ~0.4 ms of a CU slot) and there are 37 of them per
   // 126 x 73 sample, so small batches pay the partly filled last round -- 32 spectrograms: 1.54 rounds of 768 slots cost 2
@@ -1564,95 +1499,57 @@ static int launch_dgrad_s2(const float *dzdy, const float *f, float *dxo, const 
   return XM_OK;
 }
 
-static int conv_dgrad(const float *f, const float *dzdy, float *dxo, const Geo &g, hipStream_t st,
-                      const float *accum = nullptr, bool prepare_only = false) {
-  struct Cls {
-    int a, b, u0, ustep, nU, v0, vstep, nV, Rc, Rp, i0, hi0, PI, j0, wi0, PJ;
-    size_t aoff;
-  };
-  if (dgrad_s2_ok(g, dzdy, dxo, accum)) {
-    // the student's conv2: both row parities per wave, whole-line stores (conv_dgrad_s2_kernel); its filter operand is laid
-    // out by a 3 MB pass inside the call, so there is nothing to prepare ahead
-    if (prepare_only) return XM_OK;
-    return launch_dgrad_s2(dzdy, f, dxo, g, st);
+// The dgrad GEMMs' A operands -- the filter bank transposed / split by stride parity, one [FC (* FH)][Rp] block per class
+// and group -- in one buffer, and the split-K scratch.
+struct DgradFilters {
+  char *base = nullptr;
+  std::vector<size_t> off;   // byte offset of class ic
+  float *slab = nullptr;
+  float *of(const Geo &g, const DgradClass &c, size_t ic, int grp, bool foldH) const {
+    return (float *)(base + off[ic]) + (size_t)grp * g.FC * (foldH ? g.FH : 1) * c.Rp;
   }
-  // H-collapsing convolution (FC layer sliding along W only, e.g. the student's fc6: 9x1 filter on a
-  // 9 x Wi map): every input row hi is touched by exactly one filter row u = hi, so folding u into
-  // the GEMM rows (M = FH*FC) avoids multiplying FH-1 masked-out taps per pixel.
-  const bool foldH = g.Ho == 1 && g.FH > 1 && g.FH == g.H && g.pt == 0 && g.pb == 0 && g.dy == 1 && g.sy == 1;
-  std::vector<Cls> cls;
+};
+// pure transpose (see transpose_filter_kernel): 1 x 1 filters, or an FH x 1 filter folded into the GEMM rows
+static bool dgrad_pure_transpose(const Geo &g, const DgradClass &c, bool foldH, const float *f, const float *Ag) {
+  const int Rrows = g.FC * (foldH ? g.FH : 1);
+  return g.FW == 1 && ((foldH && c.nU == g.FH && c.nV == 1) || (g.FH == 1 && !foldH)) && c.Rp == g.Kg &&
+         (Rrows & 3) == 0 && (g.Kg & 3) == 0 && g.G == 1 && (((uintptr_t)f | (uintptr_t)Ag) & 15) == 0 &&
+         path_on(kPathFastTranspose);
+}
+static int launch_dgrad_filter(const float *f, float *Ag, const Geo &g, const DgradClass &c, int grp, bool foldH, hipStream_t st) {
+  if (dgrad_pure_transpose(g, c, foldH, f, Ag)) {
+    const int Rrows = g.FC * (foldH ? g.FH : 1);
+    hipLaunchKernelGGL(transpose_filter_kernel, dim3((Rrows + 63) / 64, (g.Kg + 63) / 64), dim3(256), 0, st, f, Ag,
+                       g.Kg, Rrows, c.Rp);
+    XM_LAUNCH_CHECK();
+    return XM_OK;
+  }
+  const int T = g.FH * g.FW;
+  const int TS = T <= 14 ? 32 : (T <= 56 ? 16 : 8);
+  size_t lds = sizeof(float) * (size_t)TS * (TS * T + 1);
+  const int nT = c.nU * c.nV, used = (foldH ? c.nV : nT) * g.Kg;
+  PrepDiv pd;
+  pd.tsT = make_fastdiv((uint32_t)(TS * T)), pd.T = make_fastdiv((uint32_t)T);
+  pd.tsNT = make_fastdiv((uint32_t)std::max(1, TS * nT)), pd.nT = make_fastdiv((uint32_t)std::max(1, nT));
+  pd.nU = make_fastdiv((uint32_t)std::max(1, c.nU));
+  pd.padc = make_fastdiv((uint32_t)std::max(1, c.Rp - used));
+  pd.rows = make_fastdiv((uint32_t)(foldH ? std::max(1, c.nU) : 1));
+  hipLaunchKernelGGL(prep_dgrad_filter_kernel, dim3((g.FC + TS - 1) / TS, (g.Kg + TS - 1) / TS),
+                     dim3(256), lds, st, f + (size_t)g.R * g.Kg * grp, Ag, g.FH, g.FW, g.FC, g.Kg,
+                     c.u0, c.ustep, c.nU, c.v0, c.vstep, c.nV, c.Rp, TS, foldH ? 1 : 0, pd);
+  XM_LAUNCH_CHECK();
+  return XM_OK;
+}
+
+// Transposed filters: from the persistent cache when a current entry exists, else built now -- into the cache
+// (prepare_only: the entry is then stamped with the parameter version and its event recorded on `st`) or into scratch.
+static int dgrad_filter_operand(const float *f, const Geo &g, const std::vector<DgradClass> &cls, bool foldH,
+                                size_t slab_floats, bool prepare_only, hipStream_t st, WsCarver &ws, DgradFilters &F) {
   size_t abytes = 0;
-  bool covers_all = true;
-  for (int b = 0; b < g.sx; ++b)
-    for (int a = 0; a < g.sy; ++a) {
-      Cls c{};
-      c.a = a;
-      c.b = b;
-      // taps with (u*dy) % sy == a form an arithmetic progression u0, u0+ustep, ...
-      c.u0 = -1;
-      c.nU = 0;
-      for (int u = 0; u < g.FH; ++u)
-        if ((u * g.dy) % g.sy == a) {
-          if (c.u0 < 0) c.u0 = u;
-          else if (c.nU == 1) c.ustep = u - c.u0;
-          ++c.nU;
-        }
-      c.v0 = -1;
-      c.nV = 0;
-      for (int v = 0; v < g.FW; ++v)
-        if ((v * g.dx) % g.sx == b) {
-          if (c.v0 < 0) c.v0 = v;
-          else if (c.nV == 1) c.vstep = v - c.v0;
-          ++c.nV;
-        }
-      if (c.nU <= 1) c.ustep = 1;
-      if (c.nV <= 1) c.vstep = 1;
-      c.i0 = g.pt > a ? (g.pt - a + g.sy - 1) / g.sy : 0;
-      c.hi0 = g.sy * c.i0 + a - g.pt;
-      c.PI = c.hi0 < g.H ? (g.H - c.hi0 + g.sy - 1) / g.sy : 0;
-      c.j0 = g.pl > b ? (g.pl - b + g.sx - 1) / g.sx : 0;
-      c.wi0 = g.sx * c.j0 + b - g.pl;
-      c.PJ = c.wi0 < g.W ? (g.W - c.wi0 + g.sx - 1) / g.sx : 0;
-      if (c.PI <= 0 || c.PJ <= 0) continue;
-      if (c.nU == 0 || c.nV == 0) {
-        covers_all = false;
-        continue;
-      }
-      c.Rc = (foldH ? c.nV : c.nU * c.nV) * g.Kg;
-      c.Rp = (c.Rc + kBK - 1) / kBK * kBK;
-      c.aoff = abytes;
-      abytes += WsCarver::need((size_t)g.FC * (foldH ? g.FH : 1) * c.Rp * g.G, 4);
-      cls.push_back(c);
-    }
-  // pixels whose class has no tap (e.g. 1x1 stride 2) receive no gradient
-  if (!prepare_only && (!covers_all || cls.empty())) {
-    const size_t bytes = sizeof(float) * (size_t)g.H * g.W * g.C * g.N;
-    if (accum)
-      XM_HIP(hipMemcpyAsync(dxo, accum, bytes, hipMemcpyDeviceToDevice, st));
-    else
-      XM_HIP(hipMemsetAsync(dxo, 0, bytes, st));
+  for (const DgradClass &c : cls) {
+    F.off.push_back(abytes);
+    abytes += WsCarver::need((size_t)g.FC * (foldH ? g.FH : 1) * c.Rp * g.G, 4);
   }
-  if (cls.empty()) return XM_OK;
-  // scratch for the split-K slab of the largest class under any tile configuration
-  size_t slab_max = 0;
-  for (size_t i = 0; i < cls.size(); ++i) {
-    const Cls &c = cls[i];
-    ConvGemmArgs proto{};
-    proto.M = foldH ? g.FC * g.FH : g.FC;
-    proto.NP = (foldH ? 1 : c.PI) * c.PJ * g.N;
-    proto.Rp = c.Rp;
-    for (int ci = 0; ci < kNumBaseCfg; ++ci) {
-      int sp;
-      slab_max = std::max(slab_max, gemm_slab_floats(proto, ci, &sp));
-    }
-    if (!foldH && c.nU <= 3 && c.nV <= 3 && c.nU * c.nV >= 4 && c.Rc % (kHaloCB * c.nU * c.nV) == 0) {
-      proto.Rtrue = c.Rc;
-      proto.nU = c.nU;
-      proto.nV = c.nV;
-      slab_max = std::max(slab_max, halo_slab_floats(proto));
-    }
-  }
-  // transposed filters: from the persistent cache when a current entry exists (or is being built now), else scratch
   const PrepKey pkey = prep_key(f, g, foldH);
   PrepEntry *pe = nullptr;
   bool have_prepared = false;
@@ -1676,218 +1573,197 @@ static int conv_dgrad(const float *f, const float *dzdy, float *dxo, const Geo &
       if (pe->st != st) XM_HIP(hipStreamWaitEvent(st, pe->ev, 0));
     }
   }
-  WsCarver ws;
-  int rc = ws.init((pe ? 0 : abytes) + WsCarver::need(slab_max, 4), st);
+  int rc = ws.init((pe ? 0 : abytes) + WsCarver::need(slab_floats, 4), st);
   if (rc) return rc;
-  char *abase = pe ? (char *)pe->buf : ws.base;
-  float *slab = slab_max ? (float *)(ws.base + (pe ? 0 : abytes)) : nullptr;
-  const size_t dyTotal = (size_t)g.Ho * g.Wo * g.K * g.N;
-  double pair_total = 0;
-  for (const Cls &c : cls) pair_total += (double)(foldH ? 1 : c.PI) * c.PJ * g.N * c.Rc;
-  // merged launch: 2-4 classes, no filter groups, and enough tiles per class that none would be split
-  bool merge = g.G == 1 && !foldH && cls.size() >= 2 && cls.size() <= 4 && g_force_splits == 0 &&
-               path_on(kPathDgradMerge);
-  {
-    // the merged launch never splits K: it needs enough tiles in total to fill the chip by itself
-    long long tiles = 0;
-    for (const Cls &c : cls) tiles += (long long)((g.FC + 127) / 128) * (((long long)c.PI * c.PJ * g.N + 255) / 256);
-    if (tiles < 512) merge = false;
-  }
-  std::vector<ConvGemmArgs> merged;
-  for (size_t ic = 0; ic < cls.size(); ++ic) {
-    const Cls &c = cls[ic];
-    if (c.nU * c.nV > 63)
-      return fail(XM_ENOTSUP, "vl_nnconv: more than 63 spatial taps per stride class is not built");
-    // tap table in dY space: r' = iu + nU*(iv + nV*k); u' = (u*dy - a)/sy; ho = i' - u'
-    const int up0 = ((c.u0 * g.dy) - c.a) / g.sy, ups = c.ustep * g.dy / g.sy;
-    const int vp0 = ((c.v0 * g.dx) - c.b) / g.sx, vps = c.vstep * g.dx / g.sx;
-    std::vector<int2> t(c.Rp + 3 * kBK);
-    for (int r = 0; r < c.Rp + 3 * kBK; ++r) {
-      if (r < c.Rc && foldH) {
-        int iv = r % c.nV, k = r / c.nV;
-        t[r] = make_int2(4 * (-g.Ho * (vp0 + iv * vps) + g.Ho * g.Wo * k), iv);
-      } else if (r < c.Rc) {
-        int iu = r % c.nU, iv = (r / c.nU) % c.nV, k = r / (c.nU * c.nV);
-        int up = up0 + iu * ups, vp = vp0 + iv * vps;
-        t[r] = make_int2(4 * (-up - g.Ho * vp + g.Ho * g.Wo * k), iu + c.nU * iv);
-      } else {
-        t[r] = make_int2(0, 63);
-      }
-    }
-    const int2 *taps = (const int2 *)cached_device_table(t.data(), t.size() * sizeof(int2));
-    if (!taps) return fail(XM_ENOMEM, "vl_nnconv: tap table allocation failed");
-    float *At = (float *)(abase + c.aoff);
+  F.base = pe ? (char *)pe->buf : ws.base;
+  F.slab = slab_floats ? (float *)(ws.base + (pe ? 0 : abytes)) : nullptr;
+  for (size_t ic = 0; ic < cls.size() && !have_prepared; ++ic)
     for (int grp = 0; grp < g.G; ++grp) {
-      float *Ag = At + (size_t)grp * g.FC * (foldH ? g.FH : 1) * c.Rp;
-      // pure transpose (see transpose_filter_kernel): 1 x 1 filters, or an FH x 1 filter folded into the GEMM rows
-      const int Rrows = g.FC * (foldH ? g.FH : 1);
-      const bool pure_t = g.FW == 1 && ((foldH && c.nU == g.FH && c.nV == 1) || (g.FH == 1 && !foldH)) &&
-                          c.Rp == g.Kg && (Rrows & 3) == 0 && (g.Kg & 3) == 0 && g.G == 1 &&
-                          (((uintptr_t)f | (uintptr_t)Ag) & 15) == 0 && path_on(kPathFastTranspose);
-      if (!have_prepared && pure_t) {
-        hipLaunchKernelGGL(transpose_filter_kernel, dim3((Rrows + 63) / 64, (g.Kg + 63) / 64), dim3(256), 0, st, f, Ag,
-                           g.Kg, Rrows, c.Rp);
-        XM_LAUNCH_CHECK();
-      } else if (!have_prepared) {
-        const int T = g.FH * g.FW;
-        const int TS = T <= 14 ? 32 : (T <= 56 ? 16 : 8);
-        size_t lds = sizeof(float) * (size_t)TS * (TS * T + 1);
-        const int nT = c.nU * c.nV, used = (foldH ? c.nV : nT) * g.Kg;
-        PrepDiv pd;
-        pd.tsT = make_fastdiv((uint32_t)(TS * T)), pd.T = make_fastdiv((uint32_t)T);
-        pd.tsNT = make_fastdiv((uint32_t)std::max(1, TS * nT)), pd.nT = make_fastdiv((uint32_t)std::max(1, nT));
-        pd.nU = make_fastdiv((uint32_t)std::max(1, c.nU));
-        pd.padc = make_fastdiv((uint32_t)std::max(1, c.Rp - used));
-        pd.rows = make_fastdiv((uint32_t)(foldH ? std::max(1, c.nU) : 1));
-        hipLaunchKernelGGL(prep_dgrad_filter_kernel, dim3((g.FC + TS - 1) / TS, (g.Kg + TS - 1) / TS),
-                           dim3(256), lds, st, f + (size_t)g.R * g.Kg * grp, Ag, g.FH, g.FW, g.FC, g.Kg,
-                           c.u0, c.ustep, c.nU, c.v0, c.vstep, c.nV, c.Rp, TS, foldH ? 1 : 0, pd);
-        XM_LAUNCH_CHECK();
-      }
-      if (prepare_only) continue;
-      // FC-shaped layer over few pixels (the student's fc7, the SE gates of a trainable teacher): dX = W^T dY is the
-      // skinny forward product with the transposed filter bank as its filter
-      if (pure_t && !foldH && !accum && g.FH == 1 && g.sy == 1 && g.sx == 1 && (g.pt | g.pb | g.pl | g.pr) == 0 &&
-          g.H * g.W == 1 && (g.FC & 3) == 0 && g.N <= 512 && g_force_cfg < 0 && g_force_splits == 0) {
-        Geo gs = g;
-        gs.C = gs.FC = g.Kg;
-        gs.K = gs.Kg = g.FC;
-        gs.R = g.Kg;
-        if (fc_skinny_ok(gs, true)) {
-          int rc = fc_skinny_forward(dzdy, Ag, nullptr, dxo, gs, 0, st);
-          if (rc) return rc;
-          continue;
-        }
-      }
-      ConvGemmArgs a{};
-      a.A = Ag;
-      a.lda = c.Rp;
-      size_t xoff = (size_t)grp * g.Kg * g.Ho * g.Wo;
-      a.X = dzdy + xoff;
-      a.xBytes = (unsigned)((dyTotal - xoff) * 4);
-      a.Y = dxo + (size_t)grp * g.FC * g.H * g.W;
-      a.resid = accum ? accum + (size_t)grp * g.FC * g.H * g.W : nullptr;
-      a.taps = taps;
-      a.M = foldH ? g.FC * g.FH : g.FC;
-      a.Rp = c.Rp;
-      a.Rtrue = c.Rc;
-      a.PI = foldH ? 1 : c.PI;
-      a.PJ = c.PJ;
-      a.NP = a.PI * c.PJ * g.N;
-      a.divPIJ = make_fastdiv((uint32_t)(a.PI * c.PJ));
-      a.divPI = make_fastdiv((uint32_t)a.PI);
-      a.gsy = 1;
-      a.gsx = 1;
-      a.gh0 = c.i0;
-      a.gw0 = c.j0;
-      a.LimH = g.Ho;
-      a.LimW = g.Wo;
-      a.xSampleStride = g.Ho * g.Wo * g.K;
-      a.nU = foldH ? 1 : c.nU;
-      a.nV = c.nV;
-      a.du0 = foldH ? 0 : -up0;
-      a.dus = -ups;
-      a.dv0 = -vp0;
-      a.dvs = -vps;
-      a.osy = g.sy;
-      a.osx = g.sx;
-      a.oh0 = c.hi0;
-      a.ow0 = c.wi0;
-      a.OH = g.H;
-      a.oChanStride = g.H * g.W;
-      a.oSampleStride = g.H * g.W * g.C;
-      a.divMU = make_fastdiv(foldH ? (uint32_t)g.FH : 1u);
-      a.oUStride = foldH ? 1 : 0;
-      a.vecStore = (!foldH && g.sy == 1 && g.sx == 1 && (c.PI * c.PJ) % 4 == 0 && c.PI == g.H &&
-                    c.PJ == g.W && (((uintptr_t)a.Y | (uintptr_t)a.resid) & 15) == 0) ? 1 : 0;
-      if (foldH) {
-        a.gh0 = 0;  // the single dY row; destination row comes from the GEMM row (m % FH)
-        a.oh0 = 0;
-        a.osy = 0;
-      }
-      // algorithmic work of dgrad == forward MACs (2*Ho*Wo*N*K*R), apportioned over the classes by
-      // their share of (pixel, tap) pairs; masked-out pairs are not work
-      a.algoFlops = 2.0 * g.Ho * g.Wo * (double)g.N * g.Kg * g.R * ((double)a.NP * c.Rc) / pair_total;
-      if (merge) {
-        merged.push_back(a);
-        continue;
-      }
-      auto run = [&](int ci) {
-        int sp;
-        gemm_slab_floats(a, ci, &sp);
-        ConvGemmArgs aa = a;
-        return launch_gemm(aa, 1, ci, sp, slab, st);
-      };
-      TuneKey key{1, a.M, a.NP, c.Rp, c.nU * 64 + c.nV, g.sy * 16 + g.sx, a.PI, c.PJ, g.Ho};
-      int ci = tune_cfg(key, pick_cfg(a.M, a.NP, c.Rp / kBK), st, run, kNumBaseCfg, w8_skip(a.M, a.NP));
-      ConvGemmArgs ah = a;
-      const int hneed = (g_force_cfg < 0 && g_force_splits == 0 && !foldH) ? halo_setup_padded(ah, g.N) : 0;
-      bool hok[4] = {true, halo_var_ok(ah, hneed, 0), halo_var_ok(ah, hneed, 1), halo_var_ok(ah, hneed, 2)};
-      if (hok[1] || hok[2] || hok[3]) {
-        auto run2 = [&](int h) { return h ? launch_halo(ah, h - 1, slab, st) : run(ci); };
-        TuneKey hkey{5, a.M, a.NP, c.Rp, c.nU * 64 + c.nV, g.sy * 16 + g.sx, a.PI, c.PJ, g.Ho};
-        int pick;
-        if (g_force_halo == 0) pick = 0;
-        else if (g_force_halo > 0) pick = forced_halo_variant(hok);
-        else pick = tune_challengers(hkey, st, run2, 4, hok, kHaloMargin);
-        rc = run2(pick);
-      } else {
-        rc = run(ci);
-      }
+      rc = launch_dgrad_filter(f, F.of(g, cls[ic], ic, grp, foldH), g, cls[ic], grp, foldH, st);
       if (rc) return rc;
     }
-  }
   if (prepare_only) {
     pe->version = g_param_version;
     pe->st = st;
     XM_HIP(hipEventRecord(pe->ev, st));
-    return XM_OK;
-  }
-  if (merge) {
-    // all stride-parity classes in one launch (each alone is a fraction more than one round of the chip)
-    auto run = [&](int ci) { return launch_gemm_multi(merged, ci, st); };
-    long long npSum = 0;
-    int rpMax = 0;
-    for (const ConvGemmArgs &a : merged) {
-      npSum += a.NP;
-      rpMax = std::max(rpMax, a.Rp);
-    }
-    TuneKey key{3, merged[0].M, (int)std::min<long long>(npSum, 1 << 30), rpMax, (int)merged.size(),
-                g.sy * 16 + g.sx, g.FH * 64 + g.FW, g.H, g.W};
-    int ci = tune_cfg(key, pick_cfg(merged[0].M, npSum, rpMax / kBK), st, run, kNumBaseCfg, w8_skip(merged[0].M, npSum));
-    // every class a halo-patch problem (unit-stride gathers of <= 3 x 3 taps in dY space)?  Then the same variant for all
-    std::vector<ConvGemmArgs> mh = merged;
-    bool hok[4] = {true, g_force_cfg < 0, g_force_cfg < 0, g_force_cfg < 0};
-    for (ConvGemmArgs &a : mh) {
-      const int need = hok[1] || hok[2] || hok[3] ? halo_setup_padded(a, g.N) : 0;
-      for (int v = 0; v < 3; ++v) hok[v + 1] = hok[v + 1] && halo_var_ok(a, need, v);
-    }
-    if (hok[3] && !hok[2])      // the tall-patch variant may serve classes that would also fit the short one
-      ;
-    else if (!hok[3]) {         // classes of mixed patch height: let the tall variant take them all if each fits 1024
-      bool all = g_force_cfg < 0;
-      for (ConvGemmArgs &a : mh) {
-        ConvGemmArgs t = a;
-        const int need = all ? halo_setup_padded(t, g.N) : 0;
-        all = all && need > 0 && need <= 1024 && t.M % 96 == 0;
-      }
-      hok[3] = all && !hok[2];
-    }
-    if (hok[1] || hok[2] || hok[3]) {
-      auto run2 = [&](int h) { return h ? launch_halo_multi(mh, h - 1, st) : run(ci); };
-      TuneKey hkey{6, merged[0].M, (int)std::min<long long>(npSum, 1 << 30), rpMax, (int)merged.size(),
-                   g.sy * 16 + g.sx, g.FH * 64 + g.FW, g.H, g.W};
-      int pick;
-      if (g_force_halo == 0) pick = 0;
-      else if (g_force_halo > 0) pick = forced_halo_variant(hok);
-      else pick = tune_challengers(hkey, st, run2, 4, hok, kHaloMargin);
-      rc = run2(pick);
-    } else {
-      rc = run(ci);
-    }
-    if (rc) return rc;
   }
   return XM_OK;
+}
+
+// what every class and group of a dgrad call shares
+struct DgradOperands {
+  const float *dzdy, *accum;
+  float *dxo;
+  bool foldH;
+  double pair_total;   // (pixel, tap) pairs over all classes: apportions the algorithmic work
+};
+
+// the implicit-GEMM problem of class `c`, filter group `grp`: dY is the gather source, dX the (strided) destination
+static ConvGemmArgs dgrad_args(const Geo &g, const DgradClass &c, int grp, const DgradOperands &o, const float *Ag,
+                               const int2 *taps) {
+  const bool foldH = o.foldH;
+  const DgradGather q = dgrad_gather(g, c, foldH);
+  ConvGemmArgs a{};
+  const size_t xoff = (size_t)grp * g.Kg * g.Ho * g.Wo, yoff = (size_t)grp * g.FC * g.H * g.W;
+  a.A = Ag, a.lda = c.Rp, a.taps = taps;
+  a.X = o.dzdy + xoff, a.xBytes = (unsigned)((y_elements(g) - xoff) * 4), a.xSampleStride = g.Ho * g.Wo * g.K;
+  a.Y = o.dxo + yoff, a.resid = o.accum ? o.accum + yoff : nullptr;
+  a.M = foldH ? g.FC * g.FH : g.FC, a.Rp = c.Rp, a.Rtrue = c.Rc;
+  a.PI = foldH ? 1 : c.PI, a.PJ = c.PJ, a.NP = a.PI * c.PJ * g.N;
+  a.divPIJ = make_fastdiv((uint32_t)(a.PI * c.PJ)), a.divPI = make_fastdiv((uint32_t)a.PI);
+  a.gsy = 1, a.gsx = 1, a.gh0 = q.gh0, a.gw0 = q.gw0, a.LimH = g.Ho, a.LimW = g.Wo;
+  a.nU = q.nU, a.nV = c.nV, a.du0 = q.du0, a.dus = q.dus, a.dv0 = q.dv0, a.dvs = q.dvs;
+  a.osy = foldH ? 0 : g.sy, a.oh0 = foldH ? 0 : c.hi0;    // foldH: the destination row comes from the GEMM row (m % FH)
+  a.osx = g.sx, a.ow0 = c.wi0, a.OH = g.H;
+  a.oChanStride = g.H * g.W, a.oSampleStride = g.H * g.W * g.C;
+  a.divMU = make_fastdiv(foldH ? (uint32_t)g.FH : 1u), a.oUStride = foldH ? 1 : 0;
+  a.vecStore = (!foldH && g.sy == 1 && g.sx == 1 && (c.PI * c.PJ) % 4 == 0 && c.PI == g.H &&
+                c.PJ == g.W && (((uintptr_t)a.Y | (uintptr_t)a.resid) & 15) == 0) ? 1 : 0;
+  // algorithmic work of dgrad == forward MACs (2*Ho*Wo*N*K*R), apportioned over the classes by
+  // their share of (pixel, tap) pairs; masked-out pairs are not work
+  a.algoFlops = 2.0 * g.Ho * g.Wo * (double)g.N * g.Kg * g.R * ((double)a.NP * c.Rc) / o.pair_total;
+  return a;
+}
+
+// FC-shaped layer over few pixels (the student's fc7, the SE gates of a trainable teacher): dX = W^T dY is the
+// skinny forward product with the transposed filter bank as its filter -- `gs` is that product's geometry
+static bool dgrad_as_skinny_fc(const Geo &g, bool pure_t, bool foldH, const float *accum, Geo &gs) {
+  if (!pure_t || foldH || accum || g.FH != 1 || g.sy != 1 || g.sx != 1 || (g.pt | g.pb | g.pl | g.pr) != 0 ||
+      g.H * g.W != 1 || (g.FC & 3) != 0 || g.N > 512 || forced_tiling())
+    return false;
+  gs = g;
+  gs.C = gs.FC = g.Kg;
+  gs.K = gs.Kg = g.FC;
+  gs.R = g.Kg;
+  return fc_skinny_ok(gs, true);
+}
+
+// one class by itself: the best implicit-GEMM configuration, the halo-patch variants against it
+static int dgrad_run_class(const Geo &g, const DgradClass &c, const ConvGemmArgs &a, bool foldH, float *slab, hipStream_t st) {
+  auto gemm = [&](int ci) {
+    int sp;
+    gemm_slab_floats(a, ci, &sp);
+    ConvGemmArgs aa = a;
+    return launch_gemm(aa, 1, ci, sp, slab, st);
+  };
+  const TuneKey key = tune_key_class_dgrad(1, g, c, a.M, a.NP, a.PI);
+  const int ci = tune_cfg(key, pick_cfg(a.M, a.NP, c.Rp / kBK), st, gemm, kNumBaseCfg, w8_skip(a.M, a.NP));
+  ConvGemmArgs ah = a;
+  const int hneed = (!forced_tiling() && !foldH) ? halo_setup_padded(ah, g.N) : 0;
+  const bool hok[4] = {true, halo_var_ok(ah, hneed, 0), halo_var_ok(ah, hneed, 1), halo_var_ok(ah, hneed, 2)};
+  auto arm = [&](int h) { return h ? launch_halo(ah, h - 1, slab, st) : gemm(ci); };
+  return arm(select_arm(5, key, st, 4, hok, kHaloMargin, halo_forced(hok), arm));
+}
+
+// merged launch: 2-4 classes, no filter groups, and enough tiles per class that none would be split
+static bool dgrad_merge_ok(const Geo &g, const std::vector<DgradClass> &cls, bool foldH) {
+  if (g.G != 1 || foldH || cls.size() < 2 || cls.size() > 4 || g_force_splits != 0 || !path_on(kPathDgradMerge)) return false;
+  // the merged launch never splits K: it needs enough tiles in total to fill the chip by itself
+  long long tiles = 0;
+  for (const DgradClass &c : cls) tiles += (long long)((g.FC + 127) / 128) * (((long long)c.PI * c.PJ * g.N + 255) / 256);
+  return tiles >= 512;
+}
+
+// all stride-parity classes in one launch (each alone is a fraction more than one round of the chip)
+static int dgrad_run_merged(const Geo &g, const std::vector<ConvGemmArgs> &merged, hipStream_t st) {
+  auto gemm = [&](int ci) { return launch_gemm_multi(merged, ci, st); };
+  long long npSum = 0;
+  int rpMax = 0;
+  for (const ConvGemmArgs &a : merged) {
+    npSum += a.NP;
+    rpMax = std::max(rpMax, a.Rp);
+  }
+  const TuneKey key = tune_key_merged_dgrad(3, g, merged[0].M, npSum, rpMax, (int)merged.size());
+  const int ci = tune_cfg(key, pick_cfg(merged[0].M, npSum, rpMax / kBK), st, gemm, kNumBaseCfg, w8_skip(merged[0].M, npSum));
+  // every class a halo-patch problem (unit-stride gathers of <= 3 x 3 taps in dY space)?  Then the same variant for all
+  std::vector<ConvGemmArgs> mh = merged;
+  bool hok[4] = {true, g_force_cfg < 0, g_force_cfg < 0, g_force_cfg < 0};
+  for (ConvGemmArgs &a : mh) {
+    const int need = hok[1] || hok[2] || hok[3] ? halo_setup_padded(a, g.N) : 0;
+    for (int v = 0; v < 3; ++v) hok[v + 1] = hok[v + 1] && halo_var_ok(a, need, v);
+  }
+  // the tall-patch variant may serve classes that would also fit the short one (hok[3] && !hok[2]: as it stands);
+  // classes of mixed patch height: let the tall variant take them all if each fits 1024
+  if (!hok[3]) {
+    bool all = g_force_cfg < 0;
+    for (ConvGemmArgs &a : mh) {
+      ConvGemmArgs t = a;
+      const int need = all ? halo_setup_padded(t, g.N) : 0;
+      all = all && need > 0 && need <= 1024 && t.M % 96 == 0;
+    }
+    hok[3] = all && !hok[2];
+  }
+  auto arm = [&](int h) { return h ? launch_halo_multi(mh, h - 1, st) : gemm(ci); };
+  return arm(select_arm(6, key, st, 4, hok, kHaloMargin, halo_forced(hok), arm));
+}
+
+// dX: one implicit GEMM per stride-parity class (a, b) of the input pixels (conv_plan.h).
+// accum != NULL: dX = dgrad + accum (the derivative another branch of a fork already produced), added in
+// the GEMM epilogue instead of by a separate pass
+// prepare_only: run just the filter transpositions into the persistent cache (xm_nnconv_prepare_backward)
+static int conv_dgrad(const float *f, const float *dzdy, float *dxo, const Geo &g, hipStream_t st,
+                      const float *accum = nullptr, bool prepare_only = false) {
+  if (dgrad_s2_ok(g, dzdy, dxo, accum)) {
+    // the student's conv2: both row parities per wave, whole-line stores (conv_dgrad_s2_kernel); its filter operand is laid
+    // out by a 3 MB pass inside the call, so there is nothing to prepare ahead
+    if (prepare_only) return XM_OK;
+    return launch_dgrad_s2(dzdy, f, dxo, g, st);
+  }
+  // plan
+  const bool foldH = dgrad_fold_h(g);
+  bool covers_all = true;
+  const std::vector<DgradClass> cls = dgrad_classes(g, foldH, &covers_all);
+  // pixels whose class has no tap (e.g. 1x1 stride 2) receive no gradient
+  if (!prepare_only && (!covers_all || cls.empty())) {
+    const size_t bytes = sizeof(float) * x_elements(g);
+    if (accum)
+      XM_HIP(hipMemcpyAsync(dxo, accum, bytes, hipMemcpyDeviceToDevice, st));
+    else
+      XM_HIP(hipMemsetAsync(dxo, 0, bytes, st));
+  }
+  if (cls.empty()) return XM_OK;
+  for (const DgradClass &c : cls)
+    if (c.nU * c.nV > 63)
+      return fail(XM_ENOTSUP, "vl_nnconv: more than 63 spatial taps per stride class is not built");
+  size_t slab_max = 0;   // split-K scratch of the largest class (foldH: no halo-patch problem)
+  for (const DgradClass &c : cls)
+    slab_max = std::max(slab_max, slab_floats(foldH ? g.FC * g.FH : g.FC, (foldH ? 1 : c.PI) * c.PJ * g.N, c.Rp, kNumBaseCfg,
+                                              foldH ? 0 : c.nU, foldH ? 0 : c.nV, c.Rc));
+  // operands: the transposed filters and the tap tables (both also when only preparing: the backward call finds them)
+  WsCarver ws;
+  DgradFilters F;
+  int rc = dgrad_filter_operand(f, g, cls, foldH, slab_max, prepare_only, st, ws, F);
+  if (rc) return rc;
+  std::vector<const int2 *> taps;
+  for (const DgradClass &c : cls) {
+    taps.push_back(device_taps(dgrad_tap_table(g, c, foldH)));
+    if (!taps.back()) return fail(XM_ENOMEM, "vl_nnconv: tap table allocation failed");
+  }
+  if (prepare_only) return XM_OK;
+  // launch
+  DgradOperands o{dzdy, accum, dxo, foldH, 0.0};
+  for (const DgradClass &c : cls) o.pair_total += (double)(foldH ? 1 : c.PI) * c.PJ * g.N * c.Rc;
+  const bool merge = dgrad_merge_ok(g, cls, foldH);
+  std::vector<ConvGemmArgs> merged;
+  for (size_t ic = 0; ic < cls.size(); ++ic)
+    for (int grp = 0; grp < g.G; ++grp) {
+      const DgradClass &c = cls[ic];
+      const float *Ag = F.of(g, c, ic, grp, foldH);
+      Geo gs;
+      if (dgrad_as_skinny_fc(g, dgrad_pure_transpose(g, c, foldH, f, Ag), foldH, accum, gs)) {
+        rc = fc_skinny_forward(dzdy, Ag, nullptr, dxo, gs, 0, st);
+        if (rc) return rc;
+        continue;
+      }
+      const ConvGemmArgs a = dgrad_args(g, c, grp, o, Ag, taps[ic]);
+      if (merge) {
+        merged.push_back(a);
+        continue;
+      }
+      rc = dgrad_run_class(g, c, a, foldH, F.slab, st);
+      if (rc) return rc;
+    }
+  return merge ? dgrad_run_merged(g, merged, st) : XM_OK;
 }
 
 // one wgrad launch (+ split reduction) with tile configuration ci; `part` has room for 1024 slabs
@@ -1907,44 +1783,22 @@ static int wgrad_run(const float *x, const float *dzdy, float *dfo, const Geo &g
   splits = std::min(splits, 1024);
   int tps = (nkt + splits - 1) / splits;
   splits = (nkt + tps - 1) / tps;
-  const int4 *taps = fwd_taps(g, Rn);
+  const int4 *taps = device_taps(wgrad_tap_table(g, Rn));
   if (!taps) return fail(XM_ENOMEM, "vl_nnconv: tap table allocation failed");
   const size_t slab = (size_t)g.Kg * g.R;
   for (int grp = 0; grp < g.G; ++grp) {
     WgradArgs a{};
-    a.dY = dzdy + (size_t)grp * g.Kg * g.Ho * g.Wo;
-    a.X = x + (size_t)grp * g.FC * g.H * g.W;
+    const size_t xoff = (size_t)grp * g.FC * g.H * g.W, doff = (size_t)grp * g.Kg * g.Ho * g.Wo;
     float *dst = dfo + (size_t)grp * g.Kg * g.R;
-    a.out = splits > 1 ? part : dst;
-    a.taps = taps;
-    {
-      size_t xoff = (size_t)grp * g.FC * g.H * g.W, doff = (size_t)grp * g.Kg * g.Ho * g.Wo;
-      a.xBytes = (unsigned)(((size_t)g.H * g.W * g.C * g.N - xoff) * 4);
-      a.dyBytes = (unsigned)(((size_t)g.Ho * g.Wo * g.K * g.N - doff) * 4);
-    }
-    a.M = g.Kg;
-    a.R = g.R;
-    a.Rn = Rn;
-    a.ldo = g.R;
-    a.Ho = g.Ho;
-    a.Wo = g.Wo;
-    a.NP = NP;
-    a.divHW = make_fastdiv((uint32_t)(g.Ho * g.Wo));
-    a.divHo = make_fastdiv((uint32_t)g.Ho);
-    a.sy = g.sy;
-    a.sx = g.sx;
-    a.pt = g.pt;
-    a.pl_ = g.pl;
-    a.H = g.H;
-    a.W = g.W;
-    a.xSampleStride = g.H * g.W * g.C;
-    a.dyChanStride = g.Ho * g.Wo;
-    a.dySampleStride = g.Ho * g.Wo * g.K;
-    a.nbm = nbm;
-    a.nbn = nbn;
-    a.tilesPerSplit = tps;
-    a.nkt = nkt;
-    a.splitStride = slab;
+    a.dY = dzdy + doff, a.dyBytes = (unsigned)((y_elements(g) - doff) * 4);
+    a.X = x + xoff, a.xBytes = (unsigned)((x_elements(g) - xoff) * 4);
+    a.out = splits > 1 ? part : dst, a.taps = taps;
+    a.M = g.Kg, a.R = g.R, a.Rn = Rn, a.ldo = g.R;
+    a.Ho = g.Ho, a.Wo = g.Wo, a.NP = NP;
+    a.divHW = make_fastdiv((uint32_t)(g.Ho * g.Wo)), a.divHo = make_fastdiv((uint32_t)g.Ho);
+    a.sy = g.sy, a.sx = g.sx, a.pt = g.pt, a.pl_ = g.pl, a.H = g.H, a.W = g.W;
+    a.xSampleStride = g.H * g.W * g.C, a.dyChanStride = g.Ho * g.Wo, a.dySampleStride = g.Ho * g.Wo * g.K;
+    a.nbm = nbm, a.nbn = nbn, a.tilesPerSplit = tps, a.nkt = nkt, a.splitStride = slab;
     {
       const int av = wgrad_av(a);
       ProfScope ps(1 * 100 + ci * 4 + (av == 4 ? 2 : av == 2 ? 1 : 0), 2.0 * g.Kg * (double)NP * g.R, st,
@@ -1961,18 +1815,10 @@ static int wgrad_run(const float *x, const float *dzdy, float *dfo, const Geo &g
 }
 
 // ---- filter derivative of the single-channel stem (conv_stem_wgrad_kernel) ------------------------------------------
-static bool stem_wgrad_ok(const Geo &g, const float *x, const float *dzdy, bool structural_only = false) {
-  const bool off = !path_on(kPathStem) || !path_on(kPathStemWgrad);
-  if (!structural_only && (off || g_force_cfg >= 0 || g_force_splits > 0)) return false;
-  if (g.C != 1 || g.G != 1 || g.FC != 1 || g.dy != 1 || g.dx != 1) return false;
-  if (g.FH > 8 || g.FW > kStemNV || g.FH * g.FW < 16 || g.FH * g.FW > 64 || g.Kg > 96) return false;
-  if (g.sy != 1 && g.sy != 2) return false;
-  if (g.H % 4 != 0 || g.H > kStemHP - 8 || (((uintptr_t)x | (uintptr_t)dzdy) & 15) != 0) return false;
-  if ((g.Ho * g.Wo) % 4 != 0) return false;                                      // dY pixel quads stay inside a sample
-  if (g.pt > 4 || 4 * ((g.sy * (g.Ho - 1) - g.pt + 4 + 7) >> 2) + 3 >= kStemHP) return false;
-  if (g.Ho < 128) return false;
-  if (!structural_only && g_force_stem != 1 && (long long)g.Ho * g.Wo * g.N < 128 * 512) return false;
-  return true;
+static bool stem_wgrad_ok(const Geo &g, const float *x, const float *dzdy) {
+  if (!path_on(kPathStem) || !path_on(kPathStemWgrad) || forced_tiling()) return false;
+  if (!stem_wgrad_can(g, (uintptr_t)x, (uintptr_t)dzdy)) return false;
+  return g_force_stem == 1 || fills_chip(g);
 }
 
 // BNP (bnp != NULL): `dzdy` is the convolution's own OUTPUT, the derivative is rebuilt on the fly (StemWgradArgs)
@@ -1986,33 +1832,15 @@ struct StemBnp {
 static int launch_stem_wgrad(const float *x, const float *dzdy, float *dfo, const Geo &g, float *part, int grid, hipStream_t st,
                              const StemBnp *bnp = nullptr) {
   StemWgradArgs a{};
-  a.dY = dzdy;
-  a.X = x;
-  a.part = part;
-  a.M = g.Kg;
-  a.R = g.R;
-  a.nU = g.FH;
-  a.nV = g.FW;
-  a.PI = g.Ho;
-  a.PJ = g.Wo;
-  a.NP = g.Ho * g.Wo * g.N;
-  a.divPIJ = make_fastdiv((uint32_t)(g.Ho * g.Wo));
-  a.divPI = make_fastdiv((uint32_t)g.Ho);
-  a.gsx = g.sx;
-  a.gh0 = -g.pt;
-  a.gw0 = -g.pl;
-  a.LimH = g.H;
-  a.LimW = g.W;
-  a.xSampleStride = g.H * g.W;
-  a.dySampleStride = g.Ho * g.Wo * g.K;
-  a.dyChanStride = g.Ho * g.Wo;
+  a.dY = dzdy, a.X = x, a.part = part;
+  a.M = g.Kg, a.R = g.R, a.nU = g.FH, a.nV = g.FW;
+  a.PI = g.Ho, a.PJ = g.Wo, a.NP = g.Ho * g.Wo * g.N;
+  a.divPIJ = make_fastdiv((uint32_t)(g.Ho * g.Wo)), a.divPI = make_fastdiv((uint32_t)g.Ho);
+  a.gsx = g.sx, a.gh0 = -g.pt, a.gw0 = -g.pl, a.LimH = g.H, a.LimW = g.W;
+  a.xSampleStride = g.H * g.W, a.dySampleStride = g.Ho * g.Wo * g.K, a.dyChanStride = g.Ho * g.Wo;
   a.onesCol = -1;
   if (bnp) {
-    a.dP = bnp->dP;
-    a.amax = bnp->amax;
-    a.rowc = bnp->rowc;
-    a.pHo = bnp->pHo;
-    a.pWo = bnp->pWo;
+    a.dP = bnp->dP, a.amax = bnp->amax, a.rowc = bnp->rowc, a.pHo = bnp->pHo, a.pWo = bnp->pWo;
     const size_t pooled = (size_t)bnp->pHo * bnp->pWo * g.K * g.N;
     a.dpBytes = (unsigned)(pooled * 4);
     a.amBytes = (unsigned)pooled;
@@ -2064,41 +1892,31 @@ static int launch_stem_wgrad(const float *x, const float *dzdy, float *dfo, cons
 // stream 1.7 %; launched on a side stream next to the dgrad of the same layer it fills the chip with three 48 KB blocks per CU
 // for its whole life and the pair takes LONGER than with the generic kernel (student step at 64: - 1.5 %).
 // The choice depends on the shape, the tuning table and that explicit hint -- never on what the process called before.
-static bool wgrad_patch_ok(const Geo &g, const float *x, const float *dzdy, hipStream_t st) {
-  if (!path_on(kPathWgradPatch) || g_force_cfg >= 0 || g_force_splits > 0) return false;
+static bool wgrad_patch_ok(const Geo &g, const float *x, const float *dzdy) {
+  if (!path_on(kPathWgradPatch) || forced_tiling()) return false;
   // a candidate for hosts that declared one stream, and -- whatever the host does -- for launches of at least
   // XM_WGRAD_PATCH_MIN_STAGES output columns (default 4096: the batch-256 layers, which fill the chip for ~2 ms by
   // themselves; like the eight-wave rule "from 1024 tiles" a function of the shape only)
   static const long long min_stages = env_int("XM_WGRAD_PATCH_MIN_STAGES", 4096);
   if (g_force_wgrad_patch < 0 && !(g_exec_hint & XM_EXEC_SINGLE_STREAM) && (long long)g.N * g.W < min_stages) return false;
-  if (g.G != 1 || g.FH != 3 || g.FW != 3 || g.sy != 1 || g.sx != 1 || g.dy != 1 || g.dx != 1) return false;
-  if (g.pt != 1 || g.pb != 1 || g.pl != 1 || g.pr != 1) return false;
-  if (g.H != 30 || g.Ho != g.H || g.Wo != g.W) return false;          // instantiated row counts (HH)
-  if ((((uintptr_t)x | (uintptr_t)dzdy) & 7) != 0) return false;
-  if ((size_t)g.H * g.W * g.C * g.N * 4 >= (1ull << 31) || (size_t)g.Ho * g.Wo * g.K * g.N * 4 >= (1ull << 31)) return false;
+  if (!wgrad_patch_can(g, (uintptr_t)x, (uintptr_t)dzdy)) return false;
   return (long long)g.N * g.W >= 64;                                    // enough stages to split
+}
+// stages per split and the split count of a patch wgrad launch: tiles x splits fill one round of 3 blocks per CU
+static int patch_splits(int nStages, int tiles, int max_splits, int *stagesPerSplit) {
+  static const int slots = std::max(64, (int)env_int("XM_WGRAD_PATCH_SLOTS", 768));
+  const int splits = std::max(1, std::min(std::min(nStages / 8, slots / std::max(1, tiles)), max_splits));
+  *stagesPerSplit = (nStages + splits - 1) / splits;
+  return (nStages + *stagesPerSplit - 1) / *stagesPerSplit;
 }
 static int launch_wgrad_patch(const float *x, const float *dzdy, float *dfo, const Geo &g, float *part, int max_splits,
                               hipStream_t st) {
   WgradPatchArgs a{};
-  a.dY = dzdy;
-  a.X = x;
-  a.xBytes = (unsigned)((size_t)g.H * g.W * g.C * g.N * 4);
-  a.dyBytes = (unsigned)((size_t)g.Ho * g.Wo * g.K * g.N * 4);
-  a.M = g.Kg;
-  a.R = g.R;
-  a.ldo = g.R;
-  a.C = g.C;
-  a.W = g.W;
-  a.K = g.K;
+  a.dY = dzdy, a.dyBytes = (unsigned)(y_elements(g) * 4), a.X = x, a.xBytes = (unsigned)(x_elements(g) * 4);
+  a.M = g.Kg, a.R = g.R, a.ldo = g.R, a.C = g.C, a.W = g.W, a.K = g.K;
   a.nStages = g.N * g.W;
-  a.nbm = (g.Kg + 127) / 128;
-  a.nbn = (g.R + 127) / 128;
-  const int tiles = a.nbm * a.nbn;
-  static const int slots = std::max(64, (int)env_int("XM_WGRAD_PATCH_SLOTS", 768));   // one round of 3 blocks per CU
-  int splits = std::max(1, std::min(std::min(a.nStages / 8, slots / std::max(1, tiles)), max_splits));
-  a.stagesPerSplit = (a.nStages + splits - 1) / splits;
-  splits = (a.nStages + a.stagesPerSplit - 1) / a.stagesPerSplit;
+  a.nbm = (g.Kg + 127) / 128, a.nbn = (g.R + 127) / 128;
+  const int tiles = a.nbm * a.nbn, splits = patch_splits(a.nStages, tiles, max_splits, &a.stagesPerSplit);
   const size_t slab = (size_t)g.Kg * g.R;
   a.splitStride = slab;
   a.out = splits > 1 ? part : dfo;
@@ -2119,37 +1937,21 @@ static int launch_wgrad_patch(const float *x, const float *dzdy, float *dfo, con
 // (measured once per shape against the best generic configuration): 53 KB of LDS per block, three blocks per CU.
 static int g_force_wgrad_patch_s2 = -1; // test hook (xm_debug_force_wgrad_patch_s2)
 static bool wgrad_patch_s2_ok(const Geo &g, const float *x, const float *dzdy) {
-  if (!path_on(kPathWgradPatchS2) || g_force_cfg >= 0 || g_force_splits > 0) return false;
-  if (g.G != 1 || g.FH != 5 || g.FW != 5 || g.sy != 2 || g.sx != 2 || g.dy != 1 || g.dx != 1) return false;
-  if (g.pt < 1 || g.pt > 2 || g.pl < 0 || g.pl > 4) return false;
-  if ((g.H & 1) || (g.Ho & 1)) return false;                            // 8-byte loads of row pairs
-  if ((((uintptr_t)x | (uintptr_t)dzdy) & 7) != 0) return false;
-  // byte offsets are formed in 32-bit arithmetic: both tensors below 2 GiB (904 MB / 585 MB at 256 spectrograms)
-  if ((size_t)g.H * g.W * g.C * g.N * 4 >= (1ull << 31) || (size_t)g.Ho * g.Wo * g.K * g.N * 4 >= (1ull << 31)) return false;
+  if (!path_on(kPathWgradPatchS2) || forced_tiling()) return false;
+  if (!wgrad_patch_s2_can(g, (uintptr_t)x, (uintptr_t)dzdy)) return false;
   return (long long)g.N * g.Wo * ((g.Ho + 31) / 32) >= 64;              // enough stages to split
 }
 static int launch_wgrad_patch_s2(const float *x, const float *dzdy, float *dfo, const Geo &g, float *part, int max_splits,
                                  hipStream_t st) {
   WgradPatchS2Args a{};
-  a.dY = dzdy;
-  a.X = x;
-  a.xBytes = (unsigned)((size_t)g.H * g.W * g.C * g.N * 4);
-  a.dyBytes = (unsigned)((size_t)g.Ho * g.Wo * g.K * g.N * 4);
-  a.M = g.Kg;
-  a.R = g.R;
-  a.ldo = g.R;
-  a.C = g.C;
+  a.dY = dzdy, a.dyBytes = (unsigned)(y_elements(g) * 4), a.X = x, a.xBytes = (unsigned)(x_elements(g) * 4);
+  a.M = g.Kg, a.R = g.R, a.ldo = g.R, a.C = g.C;
   a.H = g.H, a.W = g.W, a.Ho = g.Ho, a.Wo = g.Wo, a.K = g.K;
   a.pt = g.pt, a.pl = g.pl;
   a.nSeg = (g.Ho + 31) / 32;
   a.nStages = g.N * g.Wo * a.nSeg;
-  a.nbm = (g.Kg + 127) / 128;
-  a.nbn = (g.R + 127) / 128;
-  const int tiles = a.nbm * a.nbn;
-  static const int slots = std::max(64, (int)env_int("XM_WGRAD_PATCH_SLOTS", 768));   // one round of 3 blocks per CU
-  int splits = std::max(1, std::min(std::min(a.nStages / 8, slots / std::max(1, tiles)), max_splits));
-  a.stagesPerSplit = (a.nStages + splits - 1) / splits;
-  splits = (a.nStages + a.stagesPerSplit - 1) / a.stagesPerSplit;
+  a.nbm = (g.Kg + 127) / 128, a.nbn = (g.R + 127) / 128;
+  const int tiles = a.nbm * a.nbn, splits = patch_splits(a.nStages, tiles, max_splits, &a.stagesPerSplit);
   a.splits = splits;
   const size_t slab = (size_t)g.Kg * g.R;
   a.splitStride = slab;
@@ -2169,18 +1971,11 @@ static int launch_wgrad_patch_s2(const float *x, const float *dzdy, float *dfo, 
 static int conv_wgrad(const float *x, const float *dzdy, float *dfo, const Geo &g, hipStream_t st) {
   // analytic fallback: minimal padded work (split-K supplies the parallelism)
   int fb = 0;
-  {
-    double best = 1e300;
-    for (int i = 0; i < kNumWgradCfg; ++i) {
-      const Cfg &cc = kCfgs[i];
-      double eff = cfg_eff(cc);
-      double cost = (double)((g.Kg + cc.bm() - 1) / cc.bm() * cc.bm()) *
-                    ((g.R + cc.bn() - 1) / cc.bn() * cc.bn()) * eff;
-      if (cost < best) {
-        best = cost;
-        fb = i;
-      }
-    }
+  double best = 1e300;
+  for (int i = 0; i < kNumWgradCfg; ++i) {
+    const Cfg &cc = kCfgs[i];
+    const double cost = (double)((g.Kg + cc.bm() - 1) / cc.bm() * cc.bm()) * ((g.R + cc.bn() - 1) / cc.bn() * cc.bn()) * cfg_eff(cc);
+    if (cost < best) best = cost, fb = i;
   }
   const int NP = g.Ho * g.Wo * g.N;
   const int nkt = (NP + kBK - 1) / kBK;
@@ -2194,64 +1989,35 @@ static int conv_wgrad(const float *x, const float *dzdy, float *dfo, const Geo &
   float *part = ws.take<float>(slab * max_splits);
   float *spart = stem ? ws.take<float>((size_t)stem_grid_ * 96 * 64) : nullptr;
   auto run = [&](int ci) { return wgrad_run(x, dzdy, dfo, g, ci, part, st); };
-  TuneKey key{2, g.Kg, NP, g.R, g.G, g.sy * 16 + g.sx, g.FH * 64 + g.FW, g.H, g.W};
-  int ci = tune_cfg(key, fb, st, run, kNumWgradCfg);
+  const TuneKey key = tune_key_wgrad(2, g);
+  const int ci = tune_cfg(key, fb, st, run, kNumWgradCfg);
+  // one special-purpose kernel at the most against the best generic configuration (measured once per shape).  The patch
+  // kernels remove work -- gathers and address arithmetic -- so they do not have to clear the margin the equal-work
+  // challengers need: DESIGN.md 2.1f
   if (stem) {
-    // the single-channel stem's own wgrad kernel against the best generic configuration (measured once per shape)
-    auto run2 = [&](int h) { return h ? launch_stem_wgrad(x, dzdy, dfo, g, spart, stem_grid_, st) : run(ci); };
-    bool sok[2] = {true, true};
-    TuneKey skey{8, g.Kg, NP, g.R, g.G, g.sy * 16 + g.sx, g.FH * 64 + g.FW, g.H, g.W};
-    const int pick = g_force_stem >= 0 ? g_force_stem : tune_challengers(skey, st, run2, 2, sok, kHaloMargin);
-    return run2(pick);
+    auto arm = [&](int h) { return h ? launch_stem_wgrad(x, dzdy, dfo, g, spart, stem_grid_, st) : run(ci); };
+    return arm(select_arm(8, key, st, 2, kOneChallenger, kHaloMargin, g_force_stem, arm));
   }
-  if (wgrad_patch_ok(g, x, dzdy, st)) {
-    // the patch kernel against the best generic configuration (measured once per shape; it removes work -- gathers and
-    // address arithmetic -- so it does not have to clear the margin the equal-work challengers need: DESIGN.md 2.1f)
-    auto run3 = [&](int h) { return h ? launch_wgrad_patch(x, dzdy, dfo, g, part, max_splits, st) : run(ci); };
-    bool pok[2] = {true, true};
-    TuneKey pkey{9, g.Kg, NP, g.R, g.G, g.sy * 16 + g.sx, g.FH * 64 + g.FW, g.H, g.W};
-    const int pick = g_force_wgrad_patch >= 0 ? g_force_wgrad_patch : tune_challengers(pkey, st, run3, 2, pok, 0.01f);
-    return run3(pick);
+  if (wgrad_patch_ok(g, x, dzdy)) {
+    auto arm = [&](int h) { return h ? launch_wgrad_patch(x, dzdy, dfo, g, part, max_splits, st) : run(ci); };
+    return arm(select_arm(9, key, st, 2, kOneChallenger, 0.01f, g_force_wgrad_patch, arm));
   }
   if (wgrad_patch_s2_ok(g, x, dzdy)) {
-    auto run4 = [&](int h) { return h ? launch_wgrad_patch_s2(x, dzdy, dfo, g, part, max_splits, st) : run(ci); };
-    bool pok[2] = {true, true};
-    TuneKey pkey{10, g.Kg, NP, g.R, g.G, g.sy * 16 + g.sx, g.FH * 64 + g.FW, g.H, g.W};
-    const int pick = g_force_wgrad_patch_s2 >= 0 ? g_force_wgrad_patch_s2 : tune_challengers(pkey, st, run4, 2, pok, 0.01f);
-    return run4(pick);
+    auto arm = [&](int h) { return h ? launch_wgrad_patch_s2(x, dzdy, dfo, g, part, max_splits, st) : run(ci); };
+    return arm(select_arm(10, key, st, 2, kOneChallenger, 0.01f, g_force_wgrad_patch_s2, arm));
   }
   return run(ci);
 }
 
 // ---- conv1 -> bnorm -> relu -> pool through the Gram matrix of the input patches (stem_pool_kernels.h) -------------------
-static bool stem_pool_ok(const Geo &g, const float *x) {
-  if (!path_on(kPathStem)) return false;
-  if (g.C != 1 || g.G != 1 || g.FC != 1 || g.dy != 1 || g.dx != 1) return false;
-  if (g.FH > 8 || g.FW > kStemNV || g.FH * g.FW < 16 || g.FH * g.FW > 63 || g.Kg > 96) return false;
-  if ((g.sy != 1 && g.sy != 2) || g.sx + g.FW > kSpNC) return false;      // two output columns sit on <= 9 source columns
-  if (g.H % 4 != 0 || g.H > kStemHP - 8 || ((uintptr_t)x & 15) != 0) return false;
-  if (g.pt > 4 || 4 * ((g.sy * (g.Ho - 1) - g.pt + 4 + 7) >> 2) + 3 >= kStemHP) return false;
-  return g.Ho >= 32;
-}
+static bool stem_pool_ok(const Geo &g, const float *x) { return path_on(kPathStem) && stem_pool_can(g, (uintptr_t)x); }
 
 static int stem_pool_units(const Geo &g) { return g.N * ((g.Wo + 1) / 2) * ((g.Ho + 255) / 256); }
 static void stem_pool_args(StemPoolArgs &a, const float *x, const Geo &g) {
-  a.X = x;
-  a.M = g.Kg;
-  a.R = g.R;
-  a.nU = g.FH;
-  a.nV = g.FW;
-  a.PI = g.Ho;
-  a.PJ = g.Wo;
+  a.X = x, a.M = g.Kg, a.R = g.R, a.nU = g.FH, a.nV = g.FW, a.PI = g.Ho, a.PJ = g.Wo;
   const int G = (g.Ho + 255) / 256;
-  a.divJG = make_fastdiv((uint32_t)(((g.Wo + 1) / 2) * G));
-  a.divG = make_fastdiv((uint32_t)G);
-  a.gsx = g.sx;
-  a.gh0 = -g.pt;
-  a.gw0 = -g.pl;
-  a.LimH = g.H;
-  a.LimW = g.W;
-  a.xSampleStride = g.H * g.W;
+  a.divJG = make_fastdiv((uint32_t)(((g.Wo + 1) / 2) * G)), a.divG = make_fastdiv((uint32_t)G);
+  a.gsx = g.sx, a.gh0 = -g.pt, a.gw0 = -g.pl, a.LimH = g.H, a.LimW = g.W, a.xSampleStride = g.H * g.W;
 }
 
 static int stem_pool_grid(int nunits, int occ) { return std::min(256 * occ, (nunits + 7) / 8 * 8); }
@@ -2287,36 +2053,43 @@ static int launch_stem_gram(WsCarver &ws, const float *x, const Geo &g, double *
 
 using namespace xm;
 
+// the test / tools switches behind xm_debug_set / xm_debug_get: name, the global it drives, how a request is normalised
+static int norm_tri(int v) { return v < 0 ? -1 : (v ? 1 : 0); }
+static const struct DebugSwitch {
+  const char *name;
+  int *value;
+  int (*normalise)(int);
+} kDebugSwitches[] = {
+    {"conv_cfg", &g_force_cfg, [](int v) { return (v >= 0 && v < kNumCfg) ? v : -1; }},
+    {"conv_splits", &g_force_splits, [](int v) { return v > 0 ? v : 0; }},
+    {"conv_halo", &g_force_halo, [](int v) { return v < 0 ? -1 : std::min(v, 3); }},
+    {"conv_stem", &g_force_stem, norm_tri},         {"conv_stem3", &g_force_stem3, norm_tri},
+    {"wgrad_patch", &g_force_wgrad_patch, norm_tri}, {"wgrad_patch_s2", &g_force_wgrad_patch_s2, norm_tri},
+    {"dgrad_s2", &g_force_dgrad_s2, norm_tri},
+};
+static const DebugSwitch *debug_switch(const char *key) {
+  for (const DebugSwitch &s : kDebugSwitches)
+    if (key && strcmp(key, s.name) == 0) return &s;
+  return nullptr;
+}
+
 extern "C" {
 
 // ONE entry for the test / tools switches (round-5 review: the library exported eleven xm_debug_* functions that set
 // process-global state).  Returns the previous value, INT_MIN for an unknown key.  Keys and values: include/xmodal_prof.h.
 int xm_debug_set(const char *key, int value) {
-  auto tri = [](int &g, int v) { int old = g; g = v < 0 ? -1 : (v ? 1 : 0); return old; };
-  const std::string k = key ? key : "";
-  if (k == "conv_cfg") { int old = g_force_cfg; g_force_cfg = (value >= 0 && value < kNumCfg) ? value : -1; return old; }
-  if (k == "conv_splits") { int old = g_force_splits; g_force_splits = value > 0 ? value : 0; return old; }
-  if (k == "conv_halo") { int old = g_force_halo; g_force_halo = value < 0 ? -1 : std::min(value, 3); return old; }
-  if (k == "conv_stem") return tri(g_force_stem, value);
-  if (k == "conv_stem3") return tri(g_force_stem3, value);
-  if (k == "wgrad_patch") return tri(g_force_wgrad_patch, value);
-  if (k == "wgrad_patch_s2") return tri(g_force_wgrad_patch_s2, value);
-  if (k == "dgrad_s2") return tri(g_force_dgrad_s2, value);
-  if (k == "comm_single") return comm_force_single(value);
+  if (const DebugSwitch *s = debug_switch(key)) {
+    const int old = *s->value;
+    *s->value = s->normalise(value);
+    return old;
+  }
+  if (key && strcmp(key, "comm_single") == 0) return comm_force_single(value);
   return INT_MIN;
 }
 int xm_debug_get(const char *key) {
-  const std::string k = key ? key : "";
-  if (k == "num_conv_cfgs") return kNumCfg;
-  if (k == "conv_cfg") return g_force_cfg;
-  if (k == "conv_splits") return g_force_splits;
-  if (k == "conv_halo") return g_force_halo;
-  if (k == "conv_stem") return g_force_stem;
-  if (k == "conv_stem3") return g_force_stem3;
-  if (k == "wgrad_patch") return g_force_wgrad_patch;
-  if (k == "wgrad_patch_s2") return g_force_wgrad_patch_s2;
-  if (k == "dgrad_s2") return g_force_dgrad_s2;
-  return INT_MIN;
+  if (key && strcmp(key, "num_conv_cfgs") == 0) return kNumCfg;
+  const DebugSwitch *s = debug_switch(key);
+  return s ? *s->value : INT_MIN;
 }
 
 int xm_set_exec_hint(unsigned flags) {
@@ -2387,6 +2160,13 @@ int xm_prof_enable(int on) {
   return XM_OK;
 }
 
+// index of `key` in the keys seen so far (appended when new): first-launch order
+static size_t prof_slot(std::vector<int> &ks, int key) {
+  const size_t i = std::find(ks.begin(), ks.end(), key) - ks.begin();
+  if (i == ks.size()) ks.push_back(key);
+  return i;
+}
+
 // Aggregates the recorded launches by kernel instantiation.  Caller must have synchronised the
 // stream(s).  Returns the number of distinct kernels; fills up to `cap` entries.
 int xm_prof_collect(int cap, int *keys, double *total_ms, double *total_flops, long long *launches) {
@@ -2396,15 +2176,8 @@ int xm_prof_collect(int cap, int *keys, double *total_ms, double *total_flops, l
   for (auto &r : g_prof) {
     float t = 0.f;
     if (hipEventElapsedTime(&t, r.start, r.stop) != hipSuccess) continue;
-    size_t i = 0;
-    for (; i < ks.size(); ++i)
-      if (ks[i] == r.key) break;
-    if (i == ks.size()) {
-      ks.push_back(r.key);
-      ms.push_back(0);
-      fl.push_back(0);
-      cnt.push_back(0);
-    }
+    const size_t i = prof_slot(ks, r.key);
+    if (i == ms.size()) ms.push_back(0), fl.push_back(0), cnt.push_back(0);
     ms[i] += t;
     fl[i] += r.flops;
     cnt[i] += 1;
@@ -2423,13 +2196,8 @@ int xm_prof_collect_bytes(int cap, int *keys, double *total_bytes) {
   std::vector<int> ks;
   std::vector<double> by;
   for (auto &r : g_prof) {
-    size_t i = 0;
-    for (; i < ks.size(); ++i)
-      if (ks[i] == r.key) break;
-    if (i == ks.size()) {
-      ks.push_back(r.key);
-      by.push_back(0);
-    }
+    const size_t i = prof_slot(ks, r.key);
+    if (i == by.size()) by.push_back(0);
     by[i] += r.bytes;
   }
   for (size_t i = 0; i < ks.size() && (int)i < cap; ++i) {
@@ -2589,10 +2357,9 @@ int xm_nnconv_backward_filter_bnrelupool(const float *x, int H, int W, int C, in
     return fail(XM_EINVAL, "vl_nnconv(filter derivative through bnorm+relu+pool): NULL tensor");
   hipStream_t st = (hipStream_t)stream;
   const int pHo = out_size(g.Ho, ppt, ppb, ph, 1, psy), pWo = out_size(g.Wo, ppl, ppr, pw, 1, psx);
-  const bool ok = stem_wgrad_ok(g, x, y, true) && g.G == 1 && g.K == g.Kg && y_pool != nullptr && ph == 3 && pw == 3 &&
-                  psy == 2 && psx == 2 && ppt == 0 && ppb == 0 && ppl == 0 && ppr == 0 && (g.Ho & 1) == 0 && pHo >= 1 &&
-                  pWo >= 1 && (!dbias_out || g.R < 64) && !too_big((long long)pHo * pWo, g.K, g.N, 4) &&
-                  g_force_stem != 0;
+  const bool ok = g_force_stem != 0 && stem_wgrad_can(g, (uintptr_t)x, (uintptr_t)y) && g.K == g.Kg && y_pool != nullptr &&
+                  pool3x3s2_unpadded(ph, pw, psy, psx, ppt, ppb, ppl, ppr) && (g.Ho & 1) == 0 && pHo >= 1 && pWo >= 1 &&
+                  (!dbias_out || g.R < 64) && fits_i32_bytes((size_t)pHo * pWo * g.K * g.N);
   if (!ok)
     return fail(XM_ENOTSUP, "vl_nnconv(filter derivative through bnorm+relu+pool): geometry not covered by the fused kernel");
   const int grid = stem_grid(g.Ho * g.Wo * g.N);
@@ -2652,9 +2419,8 @@ int xm_nnconv_bnorm_relu_pool_forward(const float *x, int H, int W, int C, int N
   hipStream_t st = (hipStream_t)stream;
   const int pHo = out_size(g.Ho, ppt, ppb, ph, 1, psy), pWo = out_size(g.Wo, ppl, ppr, pw, 1, psx);
   const long long pooled = (long long)pHo * pWo * g.K * g.N;
-  const bool ok = stem_pool_ok(g, x) && g.K == g.Kg && g.sy == 2 && g.sx == 2 && g.FH <= 7 && g.FW == kStemNV && g.K % 8 == 0 &&
-                  ph == 3 && pw == 3 && psy == 2 && psx == 2 && ppt == 0 && ppb == 0 && ppl == 0 && ppr == 0 && pHo >= 1 &&
-                  pWo >= 1 && pooled < (1LL << 30) && g_force_stem != 0 && (((uintptr_t)y_pool) & 3) == 0;
+  const bool ok = path_on(kPathStem) && g_force_stem != 0 &&
+                  fused_stem_can(kFusedStemForward, g, (uintptr_t)x, ph, pw, psy, psx, ppt, ppb, ppl, ppr, pHo, pWo, (uintptr_t)y_pool);
   if (!ok)
     return fail(XM_ENOTSUP, "vl_nnconv + bnorm + relu + pool (fused forward): geometry not covered by the fused kernel");
   const float *moments = moments_in;
@@ -2725,9 +2491,9 @@ int xm_nnconv_backward_filter_bnrelupool_gram(const float *x, int H, int W, int 
   hipStream_t st = (hipStream_t)stream;
   const int pHo = out_size(g.Ho, ppt, ppb, ph, 1, psy), pWo = out_size(g.Wo, ppl, ppr, pw, 1, psx);
   const long long pooled = (long long)pHo * pWo * g.K * g.N;
-  const bool ok = stem_pool_ok(g, x) && g.K == g.Kg && ph == 3 && pw == 3 && psy == 2 && psx == 2 && ppt == 0 && ppb == 0 &&
-                  ppl == 0 && ppr == 0 && pHo >= 4 && pWo >= 1 && pooled < (1LL << 30) && g_force_stem != 0 &&
-                  ((((uintptr_t)dzdy_pool | (uintptr_t)y_pool) & 3) == 0);   // (y_pool NULL: the table marks closed windows itself)
+  const bool ok = path_on(kPathStem) && g_force_stem != 0 &&      // (y_pool NULL: the table marks closed windows itself)
+                  fused_stem_can(kFusedStemBackward, g, (uintptr_t)x, ph, pw, psy, psx, ppt, ppb, ppl, ppr, pHo, pWo,
+                                 (uintptr_t)dzdy_pool | (uintptr_t)y_pool);
   if (!ok)
     return fail(XM_ENOTSUP, "vl_nnconv(filter derivative through bnorm+relu+pool, gram): geometry not covered by the fused kernel");
   StemPoolArgs a{};

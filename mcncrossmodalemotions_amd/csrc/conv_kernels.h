@@ -29,6 +29,7 @@
 #pragma once
 #include <type_traits>
 
+#include "conv_plan.h"
 #include "xm_common.h"
 
 namespace xm {
@@ -101,7 +102,7 @@ __device__ __forceinline__ int xcd_remap(int bid, int nblk) {
   return start + idx;
 }
 
-constexpr int kBK = 16;  // reduction depth per LDS stage
+// (kBK, the reduction depth per LDS stage, and the other limits the host predicates read: conv_plan.h)
 constexpr int kNG = 4;   // float4 groups per stage (kBK / 4)
 
 __device__ __forceinline__ float buf_load(__amdgpu_buffer_rsrc_t r, unsigned byte_off) {
@@ -972,8 +973,6 @@ conv_gemm_dma_kernel(const ConvGemmArgs a) {
 // issue slot); loads spread over the taps of the stage 129-135.  The filter quads of a wave-wide load sit in 64
 // different cache lines (two threads per row, compile-time reorder): 5 % -- a pre-ordered filter copy would remove it.
 // Epilogue, accumulator map, split-K slabs: conv_gemm_kernel's.
-constexpr int kHaloCB = 8;
-
 template <int T, int TM, int TN, int WGM, int WGN, int PS>
 __device__ __forceinline__ void conv_halo_body(const ConvGemmArgs &a, float *smem) {
   constexpr int BM = 32 * TM * WGM, BN = 32 * TN * WGN;
@@ -1187,7 +1186,7 @@ conv_halo_multi_kernel(const ConvGemmMulti m) {
 // asm loads, issued before the MFMAs) and is parked between two barriers; the epilogue (bias / folded bnorm / relu; row
 // constants loaded once, they are the same for every tile) leaves through asm stores the waits do not count:
 // `s_waitcnt vmcnt(8)` in front of the patch store = the loads are in, this tile's 8 stores may still be in flight.
-constexpr int kStem3CS = 232, kStem3G = 42;
+constexpr int kStem3G = 42;
 
 // TN = 32-pixel tiles per wave: 1 (128-pixel block tiles, 11 source columns) or 2 (256 pixels, 13 columns: FOUR independent
 // accumulator chains per wave instead of two)
@@ -1382,8 +1381,6 @@ conv_stem3_kernel(const ConvGemmArgs a, const int ntiles) {
 #ifndef XM_STEM_OCC
 #define XM_STEM_OCC 2
 #endif
-constexpr int kStemHP = 520;   // source columns of <= 512 rows (+ 4 rows of padding either side)
-constexpr int kStemNV = 7;     // filter columns; 8 filter rows (the 8th has zero weights) per column
 constexpr int kStemHW = 104;   // row pitch of a wave's patch per (column group, source column): 24 units of 16 bytes + 8 (104 = 40
                                // mod 64: the 49 taps u + 104 v of a pixel fall into 49 different LDS banks -- conv_stem_wgrad_kernel reads one tap per lane)
 constexpr int kStemTP = 36;    // row pitch (floats) of the epilogue's transpose tile: 32 pixels + 4
@@ -2906,7 +2903,7 @@ struct DgradS2Args {
   int ncg[2], xfirst[2], nv[2];     // per column-parity class: column pairs, first column, filter columns (3 / 2)
 };
 
-constexpr int kDgS2Rows = 96, kDgS2Planes = 10, kDgS2PLA = kDgS2Rows * 4 + 4;   // plane pitch: one float4 of padding (the two
+constexpr int kDgS2Planes = 10, kDgS2PLA = kDgS2Rows * 4 + 4;   // plane pitch: one float4 of padding (the two
 constexpr int kDgS2Tile = kDgS2Planes * kDgS2PLA;                               // half-waves read neighbouring planes)
 
 // Fd from the filter bank F (FH x FW x C x K, u fastest): plane p = 2 u + (kk >> 2) of stage (class, v slot, k-group)

@@ -53,7 +53,6 @@ struct StemPoolArgs {
 // (= one line) of window columns jp - 1 and jp ONCE per row tile of filters and keeps them in registers for its four tiles.
 constexpr int kSpHW = 168;                    // row pitch of a source column in the patch: 35 units of 16 bytes + 28 (168 = 40 mod 64:
                                               // the taps u + 168 v of a pixel fall into different LDS banks, as kStemHW)
-constexpr int kSpNC = 9;                      // source columns under two output columns (stride 2: 7 + 2)
 constexpr int kSpPatch = kSpNC * kSpHW + 4;   // floats of a wave's source patch + a dummy unit
 constexpr int kSpTP = 36;                     // row pitch (floats) of a dz region: 32 pixels + 4
 constexpr int kSpCst = 64;                    // 32 ones + 32 zeros: what the B lanes of the ones column / the padding columns read
