@@ -57,7 +57,7 @@ enum { XM_FUSE_RELU = 1, XM_BN_BATCH_MOMENTS = 2, XM_FUSE_SIGMOID = 4 };
 
 /* ABI revision: 100 = round 1; 101 = xm_nnbnorm_relu_pool_backward gained `y_pool`, exchange entry points return
  * XM_EINVAL without a communicator; 102 = + xm_nnconv_forward_moments, xm_nnbnorm_backward_dxsum, xm_nnconv_forward_gated;
- * 103 = + xm_nnpool_global_avg_backward_accum; 104 = + xm_nnconv_backward_filter_bnrelupool, xm_nndropout_forward / _apply, xm_resample, xm_se_tail_backward_reduce / _apply, xm_se_squeeze_bn, xm_scale_axpy_bn; 105 = + xm_set_exec_hint / xm_get_exec_hint; 106 = + xm_nnconv_bnorm_relu_pool_forward, xm_stem_gram, xm_stem_gram_moments, xm_nnconv_backward_filter_bnrelupool_gram; 107 = + xm_nnaffinegrid / _backward, xm_nnbilinearsampler / _backward, xm_ferplus_batch; 108 = + XM_AGG_PEAK, xm_mnrfit, xm_mnrval; 109 = + xm_roc, xm_roc_launches, xm_label_hist; 110 = + xm_group_rows, xm_gather_rows, xm_scatter_rows, xm_track_peaks; 111 = + xm_wav_batch; 112 = + xm_spec_bucket_batch; 113 = + xm_jpeg_plan, xm_jpeg_decode_batch (additions never change the revision's meaning for older bindings).  A binding checks xm_version() >= the revision it was written against. */
+ * 103 = + xm_nnpool_global_avg_backward_accum; 104 = + xm_nnconv_backward_filter_bnrelupool, xm_nndropout_forward / _apply, xm_resample, xm_se_tail_backward_reduce / _apply, xm_se_squeeze_bn, xm_scale_axpy_bn; 105 = + xm_set_exec_hint / xm_get_exec_hint; 106 = + xm_nnconv_bnorm_relu_pool_forward, xm_stem_gram, xm_stem_gram_moments, xm_nnconv_backward_filter_bnrelupool_gram; 107 = + xm_nnaffinegrid / _backward, xm_nnbilinearsampler / _backward, xm_ferplus_batch; 108 = + XM_AGG_PEAK, xm_mnrfit, xm_mnrval; 109 = + xm_roc, xm_roc_launches, xm_label_hist; 110 = + xm_group_rows, xm_gather_rows, xm_scatter_rows, xm_track_peaks; 111 = + xm_wav_batch; 112 = + xm_spec_bucket_batch; 113 = + xm_jpeg_plan, xm_jpeg_decode_batch; 114 = + xm_wav_plan, xm_wav_decode_batch (additions never change the revision's meaning for older bindings).  A binding checks xm_version() >= the revision it was written against. */
 int xm_version(void);
 const char *xm_last_error(void);
 /* Device memory for hosts that have no device-array type of their own (MATLAB's gpuArray is CUDA-only: on an
@@ -690,6 +690,48 @@ int xm_jpeg_decode_batch(const unsigned char *bytes, long long nbytes, const lon
                          int nlanes, const unsigned char *tables, int nq, int nh, long long coef_elems,
                          long long plane_bytes, long long pixel_floats, float *pixels, float *faces, float crop, int Ho,
                          int Wo, const float *avg3, int *status, void *stream);
+
+/* audioinfo / audioread of a batch of WAV files, decoded on the device into the waveform bank that xm_wav_batch and
+ * xm_spec_bucket_batch read (ABI 114): info = audioinfo(audfile) -> TotalSamples, SampleRate (getBatchEmoVoxCeleb.m:79),
+ * audioread(audfile, [wr wend]) and whole files (:97-117), the noise files %02d.wav (:126), and [z, fs] = audioread of
+ * compute_audio_feats.m:173-175 with its assert(size(z,2) <= 2) and z(:,1).  There is no host decode.
+ *
+ * xm_wav_plan: host only, no device call (usable without a GPU).  File i is bytes[offsets[i] .. offsets[i + 1]).
+ *   ranges   optional N x 2 int64, 1-based inclusive [first last] as audioread(file, [a b]); last == -1: to the end
+ *   channel  -1: every channel; c >= 0: channel c only (z(:, c + 1))
+ *   out_base first float of the batch in the bank (chunked calls fill one bank)
+ *   desc     N rows of XM_WAV_DESC int64: 0, 1 byte range of the sample data in `bytes`, clamped to the file; 2 SampleRate;
+ *            3 NumChannels; 4 BitsPerSample; 5 format (XM_WAV_U8 .. XM_WAV_F64); 6 TotalSamples = floor(data bytes / block
+ *            align) frames; 7 first frame decoded (0-based); 8 frames decoded; 9 channels written; 10 the channel
+ *            selector; 11 first output float (out_base + the floats of the files before); 12 status (XM_WAV_TRUNCATED:
+ *            the data chunk claimed more bytes than the file holds); 13 block align; 14, 15 zero
+ *   sizes    XM_WAV_SIZES int64: output floats of the batch, N
+ * Accepted: RIFF ... WAVE, chunks walked with the pad byte after odd sizes, unknown chunks (LIST, fact, bext ...) skipped
+ * before and after `data`, `fmt ` before `data`, the first `data` chunk; format tag 1 (PCM 8 / 16 / 24 / 32 bits), 3
+ * (IEEE float 32 / 64) and 0xFFFE (extensible) whose SubFormat is one of the two and whose valid bits equal the container
+ * bits; block align == channels x bits / 8; 1 .. 64 channels.  A data size past the end of the file (0xFFFFFFFF of a
+ * streamed writer) is clamped and flagged, a trailing partial frame is dropped, a file of 0 frames yields 0 floats.
+ * XM_ENOTSUP (valid file this build does not decode: RF64 / BW64, RIFX, A-law, mu-law, ADPCM, MPEG and every other tag,
+ * valid bits unlike the container bits, any other bit depth, more than 64 channels) and XM_EINVAL (malformed: no RIFF /
+ * WAVE, cut inside its headers, an fmt chunk shorter than 16 bytes -- 40 when extensible --, data before fmt, no data
+ * chunk, a wrong block align, zero channels or rate; a range outside 1 .. TotalSamples or with first > last; a channel
+ * the file does not have) name the index of the file.  XM_EINVAL: NULL or negative arguments.
+ *
+ * xm_wav_decode_batch: device, ONE launch whatever N, the formats and the lengths are; no atomics, no workspace, no
+ * tuning entries, no synchronisation.  bytes (16-byte aligned, allocated up to the next multiple of 16 past nbytes) and
+ * desc (8-byte aligned) are the uploaded file bytes and plan.  File i is written at out + desc[i][11] as a frames x
+ * channels-written matrix in MATLAB layout (channel c at + c * frames); every float of the batch is written exactly
+ * once and nothing outside [0, out_floats).  Values are single(audioread's double): U8 (v - 128) / 128; S16 v / 2^15;
+ * S24 v / 2^23; S32 float(v) * 2^-31 with the conversion rounding to nearest even; F32 the bits unchanged (NaN payloads
+ * included); F64 rounded to nearest even.  Every byte read is clamped to the file's data range by the indexing itself.
+ * N == 0: XM_OK.  XM_EINVAL: a negative argument, a NULL or misaligned pointer with N > 0. */
+enum { XM_WAV_U8 = 0, XM_WAV_S16 = 1, XM_WAV_S24 = 2, XM_WAV_S32 = 3, XM_WAV_F32 = 4, XM_WAV_F64 = 5 };
+enum { XM_WAV_OK = 0, XM_WAV_TRUNCATED = 1 };
+enum { XM_WAV_DESC = 16, XM_WAV_SIZES = 2 };
+int xm_wav_plan(const unsigned char *bytes, const long long *offsets, int N, const long long *ranges, int channel,
+                long long out_base, long long *desc, long long *sizes);
+int xm_wav_decode_batch(const unsigned char *bytes, long long nbytes, const long long *desc, int N, float *out,
+                        long long out_floats, void *stream);
 
 #ifdef __cplusplus
 }

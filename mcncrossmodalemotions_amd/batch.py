@@ -13,6 +13,8 @@ shapes the tensors the hot path consumes, fed from seeded synthetic sources:
     additive noise ('N')         getBatchEmoVoxCeleb.m:123-135      -> HIP xm_scale_axpy (z + Nratio * y)
     the three above, batched     getBatchEmoVoxCeleb.m:102-135      -> HIP xm_wav_batch (wavBatch: one descriptor table per
                                                                        batch, the resampling taps evaluated in the kernel)
+    audioinfo / audioread        getBatchEmoVoxCeleb.m:79,97-117,126   -> WavFileEmoVoxImdb: the bank decoded from WAV files
+                                                                       on the device (vl.audioread, xm_wav_decode_batch)
     target selection + maxLabel  getBatchEmoVoxCeleb.m:30-32
     face normalisation           fetch_emovoxceleb_imdb.m:176-193   -> HIP xm_normalize_face
     dense face frames            fetch_emovoxceleb_imdb.m:127,196-285 -> SyntheticDenseFrames (lister, find, decoded frames)
@@ -198,6 +200,125 @@ class SyntheticEmoVoxImdb:
             cat = np.asfortranarray(np.concatenate(self.wavLogits, 0))
             self._dev = (vl.from_numpy(cat, device), offs)
         return self._dev
+
+
+class WavFileEmoVoxImdb(SyntheticEmoVoxImdb):
+    """The interface of SyntheticEmoVoxImdb over WAV files: what cnn_get_batch_wav_emo reads through audioinfo /
+    audioread (getBatchEmoVoxCeleb.m:79,97-117) and the noise files of meta.noise.noisedir (:126), decoded on the device
+    by vl.audioread.  `files` is a {name: bytes} table or a callable read(names) -> list of bytes, `names` the tracks in
+    imdb order (default: the table's keys); `noise` likewise with `noiseNames`.  wavLogits (one F_i x E single array per
+    track) and `set` come from the caller.
+      fs, num_samples      from vl.audioinfo alone (no device); a file at another rate or with more than one channel
+                           raises ValueError naming it -- cnn_get_batch_wav_emo pads with zeros(n, 1) and fails there too
+      device_wav_bank      the bank is allocated once from the planned total and filled in chunks of at most
+                           `chunkBytes` of file bytes (out_base), so the staging buffer stays small next to the dataset
+      device_wav(ii)       a view of the bank
+      noisenum, noiselen   the number of noise files and the shortest of them (the reference has one `noiselen`);
+                           noise_offsets() are the real cumulative offsets"""
+
+    def __init__(self, files, wavLogits, set=None, names=None, fs=16000, noise=None, noiseNames=None, noisevol=0.3,
+                 chunkBytes=64 << 20, seed=0):
+        self.fs, self.seed, self.noisevol, self.chunkBytes = int(fs), seed, noisevol, int(chunkBytes)
+        self._read, self.names = self._source(files, names)
+        self.num_samples = self._lengths(self._read, self.names, "track")
+        self.wavLogits = [np.asfortranarray(l, dtype=np.float32) for l in wavLogits]
+        if len(self.wavLogits) != len(self.names):
+            raise ValueError("WavFileEmoVoxImdb: %d tracks, %d wavLogits" % (len(self.names), len(self.wavLogits)))
+        self.set = np.ones(len(self.names), int) if set is None else np.asarray(set, int)
+        self._read_noise, self.noise_names = self._source(noise, noiseNames) if noise is not None else (None, [])
+        self.noise_samples = self._lengths(self._read_noise, self.noise_names, "noise file")
+        self.noisenum = len(self.noise_names)
+        self.noiselen = int(self.noise_samples.min()) if self.noisenum else 0
+        self._dev = None
+        self._banks = {}
+
+    @classmethod
+    def from_dir(cls, wavDir, names, wavLogits, set=None, noiseDir=None, **kw):
+        """tracks wavDir/<name> read from disk chunk by chunk; noise files noiseDir/01.wav, 02.wav, ... (:126)"""
+        import os
+
+        def reader(root):
+            def read(ns):
+                out = []
+                for n in ns:
+                    with open(os.path.join(root, n), "rb") as fh:
+                        out.append(fh.read())
+                return out
+            return read
+
+        noise = noiseNames = None
+        if noiseDir is not None:
+            noiseNames = []
+            while os.path.exists(os.path.join(noiseDir, "%02d.wav" % (len(noiseNames) + 1))):
+                noiseNames.append("%02d.wav" % (len(noiseNames) + 1))
+            noise = reader(noiseDir)
+        return cls(reader(wavDir), wavLogits, set=set, names=list(names), noise=noise, noiseNames=noiseNames, **kw)
+
+    @staticmethod
+    def _source(files, names):
+        if callable(files):
+            if names is None:
+                raise ValueError("WavFileEmoVoxImdb: a read(names) callable needs the list of names")
+            return files, list(names)
+        if isinstance(files, dict):
+            names = list(files) if names is None else list(names)
+            return (lambda ns: [files[n] for n in ns]), names
+        files = list(files)
+        return (lambda ns: [files[n] for n in ns]), list(range(len(files)))
+
+    def _lengths(self, read, names, what):
+        total = np.zeros(len(names), np.int64)
+        for s in range(0, len(names), 256):
+            info = vl.audioinfo(read(names[s:s + 256]))
+            for n, i in zip(names[s:s + 256], info):
+                if i["SampleRate"] != self.fs:
+                    raise ValueError("WavFileEmoVoxImdb: %s %r is sampled at %d Hz, the imdb at %d" % (what, n, i["SampleRate"], self.fs))
+                if i["NumChannels"] != 1:
+                    raise ValueError("WavFileEmoVoxImdb: %s %r has %d channels, one is required" % (what, n, i["NumChannels"]))
+            total[s:s + 256] = [i["TotalSamples"] for i in info]
+        return total
+
+    def _bank(self, key, read, names, lengths, device):
+        if key not in self._banks:
+            offs = np.concatenate([[0], np.cumsum(lengths)]).astype(np.int64)
+            bank = torch.empty(int(offs[-1]), dtype=torch.float32, device=device)
+            s = 0
+            while s < len(names):                       # chunks of at most chunkBytes of file bytes, one file at least
+                datas, used = [], 0
+                while s + len(datas) < len(names):
+                    d = read(names[s + len(datas):s + len(datas) + 1])[0]
+                    if datas and used + len(d) > self.chunkBytes:
+                        break
+                    datas.append(d)
+                    used += len(d)
+                _, got = vl.audioread(datas, out=bank, out_base=int(offs[s]))
+                if int(got[-1]) != int(offs[s + len(datas)]):
+                    raise RuntimeError("WavFileEmoVoxImdb: the files changed since their lengths were read")
+                s += len(datas)
+            self._banks[key] = (bank, offs)
+        return self._banks[key]
+
+    def wav_offsets(self):
+        return np.concatenate([[0], np.cumsum(self.num_samples)]).astype(np.int64)
+
+    def noise_offsets(self):
+        return np.concatenate([[0], np.cumsum(self.noise_samples)]).astype(np.int64)
+
+    def device_wav_bank(self, device):
+        return self._bank("wav", self._read, self.names, self.num_samples, device)
+
+    def device_noise_bank(self, device):
+        if not self.noisenum:
+            raise ValueError("WavFileEmoVoxImdb: no noise files were given")
+        return self._bank("noise", self._read_noise, self.noise_names, self.noise_samples, device)
+
+    def device_wav(self, ii, device):
+        bank, offs = self.device_wav_bank(device)
+        return bank[int(offs[ii]):int(offs[ii + 1])]
+
+    def device_noise(self, ir, device):
+        bank, offs = self.device_noise_bank(device)
+        return bank[int(offs[ir - 1]):int(offs[ir])]
 
 
 class SyntheticDenseFrames:

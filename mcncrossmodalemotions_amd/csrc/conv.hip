@@ -2221,6 +2221,10 @@ int xm_prof_kernel_name(int key, char *buf, int len) {
     snprintf(buf, len, "%s", names[key % 100 < 5 ? key % 100 : 0]);
     return XM_OK;
   }
+  if (kind == 22) {   // wav.hip
+    snprintf(buf, len, "wav_decode_kernel");
+    return XM_OK;
+  }
   if (kind == 3 || kind == 4) {
     const int v = key % 100;
     snprintf(buf, len, "%s<%s, %d>", kind == 3 ? "conv_halo_kernel" : "conv_halo_multi_kernel",

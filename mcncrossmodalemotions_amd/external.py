@@ -5,11 +5,13 @@
         the largest bucket width <= T, resize `pool6` to that bucket, one test-mode forward.
     compute_audio_feats_wav  the same from the waveform bank: audio_feats_plan on the host, then per bucket one
         xm_spec_bucket_batch call (whole-clip STFT, row statistics, crop) and one forward.
+    compute_audio_feats_files  the same from the WAV files: vl.audioread (channel 0) into the bank, then the above.
     compute_visual_feats  external/compute_visual_feats.m:60-116
         frozen teacher over the flattened frames of all tracks in minibatches, logits split per track.
 
-File I/O (wav / jpeg decoding, the .mat imdb) and the FFT front-end stay outside: the
-functions take device tensors (spectrogram magnitudes 512 x T, normalised faces 224 x 224 x 3 x F).
+The .mat imdb stays outside: the functions take device tensors (spectrogram magnitudes 512 x T, the
+waveform bank, normalised faces 224 x 224 x 3 x F) or, through compute_audio_feats_files / compute_visual_feats(read=...),
+the bytes of the WAV / JPEG files, which are decoded on the device.
 """
 import math
 
@@ -218,6 +220,22 @@ def compute_audio_feats_wav(dag, wav, offsets, numEmotions=8, limit=float("inf")
         out = vl.to_numpy(val).reshape(-1, len(idx), order="F")   # squeeze: E x N
         logits[idx, :] = out.T[:, :numEmotions]
     return logits
+
+
+def compute_audio_feats_files(dag, files, numEmotions=8, limit=float("inf"), maxBatch=64):
+    """logits = compute_audio_feats from the WAV files themselves (compute_audio_feats.m:116-136,172-176): `files` is a
+    list of bytes or of paths.  [z, fs] = audioread(path); assert(size(z,2) <= 2, 'unexpected number of streams');
+    z = z(:,1): vl.audioread with channel=0 (the left stream) decodes every file on the device into one bank, then
+    compute_audio_feats_wav runs on it.  As upstream there is no check of the sample rate.  `limit` as there: only the
+    first limit + 1 files are read."""
+    files = list(files)
+    if limit != float("inf"):
+        files = files[:max(0, min(len(files), int(limit) + 1))]
+    for k, i in enumerate(vl.audioinfo(files)):
+        if i["NumChannels"] > 2:
+            raise ValueError("unexpected number of streams: file %d has %d channels" % (k, i["NumChannels"]))   # :174
+    bank, offsets = vl.audioread(files, channel=0)
+    return compute_audio_feats_wav(dag, bank, offsets, numEmotions=numEmotions, maxBatch=maxBatch)
 
 
 def compute_visual_feats(dag, track_frames, batchSize=128, numEmotions=8, limit=float("inf"), lanes=2, *, read=None):

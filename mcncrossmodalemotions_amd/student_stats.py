@@ -21,7 +21,8 @@ What differs, because there is neither MATLAB, vlfeat nor the dataset here:
     scipy.io.savemat through emo_benchmarks.save_feats (tracks, faceLogits) plus the cell `wavLogits` that :97 reads
     from it and `set`; `refresh` recomputes it (upstream the option is parsed and never read);
   * student features come from imdb.device_wav -> batch.runSpec -> external.compute_audio_feats (batch_by_bucket):
-    whole clips, as compute_audio_feats.m does, file reading left out;
+    whole clips, as compute_audio_feats.m does; the files themselves are read by a batch.WavFileEmoVoxImdb passed as
+    `imdb` (vl.audioread, DESIGN.md section 14);
   * vl_roc is vlfeat's [EXT]: restated from its documentation, AUC = S / (p n) with S an exact
     integer; the reference's -1 labels for every other class are kept, no label is 0 here;
   * figures are data, not .jpg: figDir/<emotion>-<partition>.json holds auc, p, n, retrieved and the curve thinned to

@@ -1440,3 +1440,125 @@ def imreadjpeg(files, resize=None, crop_size=None, crop_location="center", inter
             H, W, o = int(d[2]), int(d[3]), int(d[21])
             out.append(pixels[o:o + 3 * H * W].view(3, W, H).permute(2, 1, 0))
     return (out, status) if return_status else out
+
+
+# --------------------------------------------------------------------------------------------
+# audioinfo / audioread (getBatchEmoVoxCeleb.m:79,97-117,126, compute_audio_feats.m:173-175): WAV decode on the device
+# --------------------------------------------------------------------------------------------
+WAV_DESC = 16                                                                   # include/xmodal.h XM_WAV_*
+WAV_U8, WAV_S16, WAV_S24, WAV_S32, WAV_F32, WAV_F64 = range(6)
+WAV_OK, WAV_TRUNCATED = 0, 1
+
+
+def _file_bytes(files):
+    datas = []
+    for f in files:
+        if isinstance(f, (bytes, bytearray, memoryview)):
+            datas.append(bytes(f))
+        else:
+            with open(f, "rb") as fh:
+                datas.append(fh.read())
+    return datas
+
+
+def wav_plan(files, ranges=None, channel=None, out_base=0, stage=None):
+    """The host side of audioread (xm_wav_plan; touches no device): `files` is a list of bytes.  Lays one staging buffer
+    out as [file bytes | desc] (16-byte aligned parts), parses every header into it and returns (stage, plan): `stage` a
+    uint8 numpy array (`stage(nbytes)`, when given, allocates it -- audioread hands out pinned memory) and plan =
+    dict(N, nbytes, desc: (offset, bytes) in the buffer, rows: the N x 16 int64 view of it, floats, total).
+    ranges: None, one [first last] pair for every file, or N pairs (1-based inclusive, last = -1 or inf: to the end);
+    channel: None for all channels or the 0-based channel to keep; out_base: first float of the batch in the bank.
+    An unsupported or malformed file raises _lib.XmError naming its index."""
+    N = len(files)
+    lens = np.array([len(f) for f in files], np.int64)
+    offsets = np.concatenate([[0], np.cumsum(lens)]).astype(np.int64)
+    nbytes = int(offsets[-1])
+    up = lambda v: (int(v) + 15) & ~15
+    o_desc = up(nbytes + 1)
+    total = up(o_desc + 8 * WAV_DESC * N + 1)
+    buf = stage(total) if stage is not None else np.empty(total, np.uint8)
+    for f, o in zip(files, offsets):
+        buf[o:o + len(f)] = np.frombuffer(f, np.uint8)
+    buf[nbytes:o_desc] = 0
+    rng = None
+    if ranges is not None:
+        r = np.asarray(ranges, np.float64)
+        r = np.where(np.isinf(r), -1, r)
+        if r.ndim == 1 and r.size == 2:
+            r = np.tile(r, (N, 1))
+        if r.shape != (N, 2):
+            raise ValueError("wav_plan: RANGES must be [first last] or N x 2")
+        rng = np.ascontiguousarray(r, np.int64)
+    sizes = np.zeros(2, np.int64)
+    base = buf.ctypes.data
+    _lib.check(_L().xm_wav_plan(C.c_void_p(base), C.c_void_p(offsets.ctypes.data), N,
+                                C.c_void_p(rng.ctypes.data) if rng is not None else None,
+                                -1 if channel is None else int(channel), int(out_base), C.c_void_p(base + o_desc),
+                                C.c_void_p(sizes.ctypes.data)))
+    rows = buf[o_desc:o_desc + 8 * WAV_DESC * N].view(np.int64).reshape(N, WAV_DESC)
+    return buf, dict(N=N, nbytes=nbytes, desc=(o_desc, 8 * WAV_DESC * N), rows=rows, floats=int(sizes[0]), total=total,
+                     out_base=int(out_base))
+
+
+def _wav_info(rows):
+    return [dict(SampleRate=int(d[2]), TotalSamples=int(d[6]), NumChannels=int(d[3]), BitsPerSample=int(d[4]),
+                 Duration=float(d[6]) / float(d[2]), Truncated=bool(int(d[12]) & WAV_TRUNCATED)) for d in rows]
+
+
+def audioinfo(files):
+    """info = audioinfo(file) for a list of WAV files (bytes or paths): a list of dicts with SampleRate, TotalSamples
+    (frames), NumChannels, BitsPerSample, Duration (and Truncated: the data chunk claimed more than the file holds).
+    Host only -- the parse of xm_wav_plan; no device call."""
+    datas = _file_bytes(files)
+    if not datas:
+        return []
+    return _wav_info(wav_plan(datas)[1]["rows"])
+
+
+def audioread(files, ranges=None, *, channel=None, out=None, out_base=0, device=None, return_info=False):
+    """[y, Fs] = audioread(file) / audioread(file, [first last]) for a batch of WAV files (bytes or paths), decoded on
+    the device into one waveform bank: returns (bank, offsets), `bank` a 1-D float32 device tensor and `offsets` int64
+    numpy with N + 1 entries -- file i is bank[offsets[i]:offsets[i + 1]], a frames x channels matrix in MATLAB layout
+    (channel c at + c * frames; mono files and channel=c are plain vectors).  PCM 8 / 16 / 24 / 32 and float 32 / 64, also
+    as WAVE_FORMAT_EXTENSIBLE; values are single(audioread's double), bit for bit.  `out` / `out_base` decode into a
+    slice of an existing bank starting at float out_base.  One pinned staging buffer, one non-blocking upload, one
+    launch, no wait.  return_info=True appends the audioinfo dicts.  Anything else (companded, compressed, RF64 ...)
+    raises before anything is launched, with the index of the file; there is no host decode to fall back to."""
+    if not torch.cuda.is_available():
+        raise RuntimeError("audioread needs a GPU; this build has no CPU path")
+    datas = _file_bytes(files)
+    out_base = int(out_base)
+    if out is None and out_base:
+        raise ValueError("audioread: out_base needs out")
+    if out is not None:
+        _chk(out, "OUT")
+        if out.dtype != torch.float32 or out.dim() != 1 or not out.is_contiguous():
+            raise ValueError("audioread: OUT must be a contiguous 1-D float32 device tensor")
+        device = out.device
+    device = device or _dev()
+    if not datas:
+        bank = out if out is not None else torch.empty(0, dtype=torch.float32, device=device)
+        res = (bank, np.array([out_base], np.int64))
+        return res + ([],) if return_info else res
+    held = []
+
+    def stage(n):
+        held.append(torch.empty(int(n), dtype=torch.uint8, pin_memory=True))
+        return held[-1].numpy()
+
+    buf, plan = wav_plan(datas, ranges, channel, out_base, stage=stage)
+    rows, floats = plan["rows"], plan["floats"]
+    if out is None:
+        out = torch.empty(floats, dtype=torch.float32, device=device)
+    elif out_base + floats > out.numel():
+        raise ValueError("audioread: %d floats from %d on do not fit OUT of %d" % (floats, out_base, out.numel()))
+    offsets = np.concatenate([rows[:, 11], [out_base + floats]]).astype(np.int64)
+    if floats:
+        with torch.cuda.device(device):
+            dev = torch.empty(plan["total"], dtype=torch.uint8, device=device)
+            dev.copy_(held[-1], non_blocking=True)
+            p = dev.data_ptr()
+            _lib.check(_L().xm_wav_decode_batch(C.c_void_p(p), plan["nbytes"], C.c_void_p(p + plan["desc"][0]), plan["N"],
+                                                _ptr(out), out.numel(), _stream()))
+    res = (out, offsets)
+    return res + (_wav_info(rows),) if return_info else res

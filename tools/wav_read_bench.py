@@ -1,0 +1,186 @@
+#!/usr/bin/env python
+"""Timing of vl.audioread (xm_wav_plan / xm_wav_decode_batch): 256 PCM16 mono files of 4 - 12 s in one call.
+usage: python tools/wav_read_bench.py [--files 256] [--reps 20] [--out profiles/wav/wav_read_bench.txt]
+Prints, and writes verbatim to --out,
+ (a) the decode kernel: ms per call (the library's profiler hook), bytes read + written per second, next to a device-to-
+     device copy of the same number of bytes timed in the same call (a copy is the ceiling for a converter);
+ (b) the host side: copy into the pinned staging buffer + xm_wav_plan, and the whole enqueue;
+ (c) the whole vl.audioread call (host clock around a device synchronise) against decoding on the host and uploading per
+     file -- numpy, and scipy.io.wavfile where it imports --, the only path there was before;
+ (d) the other formats through the same kernel, for the record."""
+import argparse
+import ctypes as C
+import io
+import os
+import struct
+import sys
+import time
+
+import numpy as np
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+from mcncrossmodalemotions_amd import _lib, vl  # noqa: E402
+
+FS = 16000
+DT = {vl.WAV_U8: "u1", vl.WAV_S16: "<i2", vl.WAV_S24: None, vl.WAV_S32: "<i4", vl.WAV_F32: "<f4", vl.WAV_F64: "<f8"}
+BITS = {vl.WAV_U8: 8, vl.WAV_S16: 16, vl.WAV_S24: 24, vl.WAV_S32: 32, vl.WAV_F32: 32, vl.WAV_F64: 64}
+
+
+def wav_file(fmt, frames, rng):
+    if fmt == vl.WAV_S24:
+        body = rng.integers(0, 256, 3 * frames).astype(np.uint8).tobytes()
+    elif fmt in (vl.WAV_F32, vl.WAV_F64):
+        body = (rng.standard_normal(frames) * 0.1).astype(DT[fmt]).tobytes()
+    else:
+        body = rng.integers(0, 2 ** BITS[fmt], frames, dtype=np.uint64).astype("u%d" % (BITS[fmt] // 8)).tobytes()
+    align = BITS[fmt] // 8
+    head = struct.pack("<HHIIHH", 3 if fmt in (vl.WAV_F32, vl.WAV_F64) else 1, 1, FS, FS * align, align, BITS[fmt])
+    riff = b"WAVE" + b"fmt " + struct.pack("<I", 16) + head + b"data" + struct.pack("<I", len(body)) + body + (b"\0" if len(body) & 1 else b"")
+    return b"RIFF" + struct.pack("<I", len(riff)) + riff
+
+
+def device_ms(fn, reps):
+    fn()
+    torch.cuda.synchronize()
+    s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    s.record()
+    for _ in range(reps):
+        fn()
+    e.record()
+    torch.cuda.synchronize()
+    return s.elapsed_time(e) / reps
+
+
+def kernel_ms(L, fn, reps):
+    L.xm_prof_enable(1)
+    for _ in range(reps):
+        fn()
+    torch.cuda.synchronize()
+    L.xm_prof_enable(0)
+    cap = 32
+    keys, ms, fl, cnt = (C.c_int * cap)(), (C.c_double * cap)(), (C.c_double * cap)(), (C.c_longlong * cap)()
+    n = L.xm_prof_collect(cap, keys, ms, fl, cnt)
+    out = {}
+    for i in range(min(n, cap)):
+        b = C.create_string_buffer(128)
+        L.xm_prof_kernel_name(keys[i], b, 128)
+        out[b.value.decode()] = ms[i] / max(cnt[i], 1)
+    return out
+
+
+def host_clock(fn, reps):
+    fn()
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    for _ in range(reps):
+        fn()
+    torch.cuda.synchronize()
+    return (time.perf_counter() - t0) / reps * 1e3
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--files", type=int, default=256)
+    ap.add_argument("--reps", type=int, default=20)
+    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "wav", "wav_read_bench.txt"))
+    a = ap.parse_args()
+    if not torch.cuda.is_available():
+        raise SystemExit("wav_read_bench: no GPU")
+    dev = torch.device("cuda", 0)
+    torch.cuda.set_device(0)
+    L = _lib.load()
+    lines = []
+
+    def say(s):
+        print(s, flush=True)
+        lines.append(s)
+
+    rng = np.random.default_rng(1)
+    frames = rng.integers(4 * FS, 12 * FS, a.files)
+    files = [wav_file(vl.WAV_S16, int(n), rng) for n in frames]
+    nfile, nout = sum(map(len, files)), 4 * int(frames.sum())
+    say("%d PCM16 mono files of 4 - 12 s: %.1f MB of files, %.1f MB of float32 samples" % (a.files, nfile / 1e6, nout / 1e6))
+
+    # ---- (a) the kernel alone: staged bytes already on the device --------------------------------------------------
+    def staged(fs):
+        buf, plan = vl.wav_plan(fs)
+        d = torch.from_numpy(buf).to(dev)
+        out = torch.empty(plan["floats"], dtype=torch.float32, device=dev)
+        p = d.data_ptr()
+        call = lambda: _lib.check(L.xm_wav_decode_batch(C.c_void_p(p), plan["nbytes"], C.c_void_p(p + plan["desc"][0]), plan["N"],   # noqa: E731
+                                                         C.c_void_p(out.data_ptr()), out.numel(),
+                                                         C.c_void_p(torch.cuda.current_stream().cuda_stream)))
+        return call, plan, (d, out)
+
+    call, plan, keep = staged(files)
+    moved = 2 * int(frames.sum()) + nout                                   # sample bytes read + floats written
+    src = torch.empty(moved // 2, dtype=torch.uint8, device=dev)
+    dst = torch.empty_like(src)
+    say("(a) decode kernel, %d calls each, alternating with a device-to-device copy of %.1f MB read + %.1f MB written" %
+        (a.reps, moved / 2e6, moved / 2e6))
+    for rep in range(3):
+        k = kernel_ms(L, call, a.reps)["wav_decode_kernel"]
+        t = device_ms(call, a.reps)
+        c = device_ms(lambda: dst.copy_(src), a.reps)
+        say("    wav_decode_kernel %8.4f ms (profiler hook) %8.4f ms (back to back) = %7.1f GB/s read + written | copy %8.4f ms = %7.1f GB/s"
+            " | kernel / copy rate %.2f" % (k, t, moved / t / 1e6, c, moved / c / 1e6, c / t))
+
+    # ---- (b) host side ---------------------------------------------------------------------------------------------
+    t0 = time.perf_counter()
+    for _ in range(a.reps):
+        vl.wav_plan(files, stage=vl._pinned)
+    t_plan = (time.perf_counter() - t0) / a.reps * 1e3
+    full = lambda: vl.audioread(files)                                      # noqa: E731
+    full()
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    for _ in range(a.reps):
+        full()
+    t_enq = (time.perf_counter() - t0) / a.reps * 1e3
+    torch.cuda.synchronize()
+    say("(b) host: pinned allocation + copy into it + xm_wav_plan %8.3f ms; the whole audioread call returns after %8.3f ms" % (t_plan, t_enq))
+
+    # ---- (c) whole call against the host path -----------------------------------------------------------------------
+    def numpy_path():
+        out = []
+        for f in files:
+            pos = f.index(b"data") + 8
+            out.append(torch.from_numpy(np.frombuffer(f, "<i2", offset=pos).astype(np.float32) / np.float32(32768)).to(dev))
+        return out
+
+    t_dev = min(host_clock(full, a.reps) for _ in range(3))
+    t_np = min(host_clock(numpy_path, 3) for _ in range(2))
+    say("(c) whole call, host clock to a device synchronise: vl.audioread %8.3f ms | numpy decode + upload per file %8.3f ms (%.1f x)" %
+        (t_dev, t_np, t_np / t_dev))
+    try:
+        from scipy.io import wavfile
+
+        def scipy_path():
+            return [torch.from_numpy(wavfile.read(io.BytesIO(f))[1].astype(np.float32) / np.float32(32768)).to(dev) for f in files]
+        t_sp = min(host_clock(scipy_path, 3) for _ in range(2))
+        say("    scipy.io.wavfile.read + upload per file %8.3f ms (%.1f x)" % (t_sp, t_sp / t_dev))
+    except ImportError:
+        say("    scipy is not importable: no scipy line")
+    got, offs = full()
+    ref = torch.cat(numpy_path())
+    say("    equal to the host decode bit for bit: %s" % bool(torch.equal(got.view(torch.int32), ref.view(torch.int32))))
+
+    # ---- (d) the other formats ---------------------------------------------------------------------------------------
+    say("(d) 64 mono files of 4 - 12 s per format, kernel back to back")
+    for fmt, name in ((vl.WAV_U8, "U8"), (vl.WAV_S16, "S16"), (vl.WAV_S24, "S24"), (vl.WAV_S32, "S32"), (vl.WAV_F32, "F32"),
+                      (vl.WAV_F64, "F64")):
+        fr = rng.integers(4 * FS, 12 * FS, 64)
+        fs_ = [wav_file(fmt, int(n), rng) for n in fr]
+        call, plan, keep = staged(fs_)
+        mv = int(fr.sum()) * (BITS[fmt] // 8 + 4)
+        t = min(device_ms(call, a.reps) for _ in range(2))
+        say("    %-4s %8.4f ms = %7.1f GB/s read + written" % (name, t, mv / t / 1e6))
+    os.makedirs(os.path.dirname(a.out), exist_ok=True)
+    with open(a.out, "w") as fh:
+        fh.write("\n".join(lines) + "\n")
+
+
+if __name__ == "__main__":
+    main()
