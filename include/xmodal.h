@@ -373,7 +373,9 @@ int xm_nnsoftmaxceloss(const float *x, const float *p, int C, int N, float tempe
 #define XM_REGLOSS_HUBER 1
 int xm_nnregloss(const float *x, const float *t, int E, int N, int kind, float sigma,
                  const float *instance_weights, const float *dzdy, float *y, void *stream);
-/* vl_nnloss(X, c [, DZDY], 'loss', 'softmaxlog'|'classerror'); labels are 1-based floats */
+/* vl_nnloss(X, c [, DZDY], 'loss', 'softmaxlog'|'classerror'); labels are 1-based floats.  A sample whose label is
+ * outside 1..C (MatConvNet's "label 0 is skipped", extended to every invalid label) adds 0 to Y and gets a zero column of
+ * DZDX, for both losses. */
 int xm_nnloss(const float *x, const float *labels, int C, int N, int loss, const float *dzdy,
               float *y, void *stream);
 

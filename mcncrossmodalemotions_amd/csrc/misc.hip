@@ -166,7 +166,8 @@ se_tail_reduce_kernel(const float *__restrict__ y, const float *__restrict__ dzd
   const size_t off = (size_t)plane * HW;
   const double mu = (double)mom[c];
   double s0 = 0.0, s1 = 0.0, s2 = 0.0;
-  if ((HW & 3) == 0) {
+  // HW % 4 == 0 keeps every plane as aligned as its tensor's base
+  if ((HW & 3) == 0 && ((((uintptr_t)y | (uintptr_t)dzdy | (uintptr_t)u) & 15) == 0)) {
     for (int i = lane * 4; i < HW; i += 256) {
       const float4 yv = *reinterpret_cast<const float4 *>(y + off + i), dv = *reinterpret_cast<const float4 *>(dzdy + off + i),
                    uv = *reinterpret_cast<const float4 *>(u + off + i);
@@ -399,7 +400,13 @@ nnloss_kernel(const float *__restrict__ x, const float *__restrict__ labels, int
   double total = 0;
   for (int n = threadIdx.x; n < N; n += 256) {
     const float *xn = x + (size_t)C * n;
-    int c0 = (int)labels[n] - 1;
+    const int lab = (int)labels[n];
+    if (lab < 1 || lab > C) {   // vl_nnloss skips label 0; every label outside 1..C is skipped alike (class_stats_kernel)
+      if (dzdy)
+        for (int c = 0; c < C; ++c) y[(size_t)C * n + c] = 0.f;
+      continue;
+    }
+    const int c0 = lab - 1;
     double mx = -INFINITY, s = 0;
     int arg = 0;
     for (int c = 0; c < C; ++c)

@@ -978,7 +978,13 @@ void orc_nnloss(const float *x, const float *labels, int C, int N, int loss, con
   double total = 0;
   for (int n = 0; n < N; ++n) {
     const float *xn = x + (size_t)C * n;
-    int c0 = (int)labels[n] - 1;
+    const int lab = (int)labels[n];
+    if (lab < 1 || lab > C) { /* vl_nnloss skips label 0; every label outside 1..C is skipped alike */
+      if (dzdy)
+        for (int c = 0; c < C; ++c) y[(size_t)C * n + c] = 0.f;
+      continue;
+    }
+    int c0 = lab - 1;
     double mx = -INFINITY, s = 0;
     int arg = 0;
     for (int c = 0; c < C; ++c)

@@ -149,6 +149,37 @@ def test_distillation_loss_semantics_and_gradient():
     assert O.vl_nnloss(x, lab, loss="classerror") == err
 
 
+def test_nnloss_skips_labels_outside_the_classes():
+    """a label outside 1..C (vl_nnloss's "label 0 is skipped", and every other invalid label) adds nothing to either loss
+    and leaves a zero column in DZDX; the valid samples are untouched -- against a float64 numpy restatement"""
+    rng = np.random.default_rng(41)
+    for C_, N in ((1, 5), (8, 9), (100, 257)):
+        x = O.F(rng.standard_normal((1, 1, C_, N)) * 4)
+        lab = O.F(rng.integers(1, C_ + 1, (1, 1, 1, N)))
+        lab[0, 0, 0, 0], lab[0, 0, 0, N - 1], lab[0, 0, 0, N // 2] = 0, C_ + 1, -3
+        l = lab.ravel().astype(np.int64)
+        ok = (l >= 1) & (l <= C_)
+        assert ok.sum() == N - 3
+        z = x.reshape(C_, N, order="F").astype(np.float64)
+        e = np.exp(z - z.max(0))
+        q = e / e.sum(0)
+        c0 = np.where(ok, l - 1, 0)
+        nll = np.log(e.sum(0)) + z.max(0) - z[c0, np.arange(N)]
+        ref = float(nll[ok].sum())
+        assert abs(O.vl_nnloss(x, lab, loss="softmaxlog") - ref) <= 1e-6 * max(1.0, abs(ref))
+        assert O.vl_nnloss(x, lab, loss="classerror") == ((z.argmax(0) != c0) & ok).sum()
+        dref = q.copy()
+        dref[c0, np.arange(N)] -= 1
+        dref = 0.37 * dref * ok
+        dx = O.vl_nnloss(x, lab, np.full(1, 0.37, np.float32), loss="softmaxlog").reshape(C_, N, order="F")
+        assert np.abs(dx - dref).max() <= 1e-6
+        assert not dx[:, ~ok].any() and (C_ == 1 or dx[:, ok].any(0).all())
+        assert not O.vl_nnloss(x, lab, np.ones(1, np.float32), loss="classerror").any()
+        # a batch of invalid labels only
+        assert O.vl_nnloss(x, np.zeros((1, 1, 1, N), np.float32), loss="softmaxlog") == 0
+        assert O.vl_nnloss(x, np.full((1, 1, 1, N), C_ + 1, np.float32), loss="classerror") == 0
+
+
 def test_elementwise_and_sgd():
     rng = np.random.default_rng(5)
     x, d = O.F(rng.standard_normal((4, 3, 2, 2))), O.F(rng.standard_normal((4, 3, 2, 2)))
