@@ -51,6 +51,9 @@ int xm_prof_kernel_name(int key, char *buf, int len);
  *   "wgrad_patch"    1: conv_wgrad_patch_kernel (filter derivative of 3 x 3 / stride 1 / pad 1 layers) wherever it can run; 0: never; -1: default
  *   "wgrad_patch_s2" the same for conv_wgrad_patch_s2_kernel (5 x 5 / stride 2: the student's conv2)
  *   "dgrad_s2"       0: never conv_dgrad_s2_kernel (dgrad of 5 x 5 / stride 2 layers); 1 / -1: wherever it can run (default)
+ *   "spec_blocks"    v >= 1: xm_spec_bucket_batch launches spec_gemm_kernel with min(v, 65535) blocks (and sizes the partial
+ *                    slots from it), so that a small input gives every block many tiles; 0 or negative: CUs x 2 (default).
+ *                    Only the grouping of the fp64 merges of a clip's statistics follows it (tests/test_gpu_spec_edges.py)
  *   "comm_single"    1: xm_comm_init with one worker creates a real one-rank RCCL communicator (tests of the exchange path)
  * (xm_debug_conv_cycles -- per-block shader-clock records for tools/conv_bench.py --cycles -- exists only in a library
  * built with XM_DEBUG_CYCLES=1.) */

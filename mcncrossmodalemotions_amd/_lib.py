@@ -146,7 +146,8 @@ _DEBUG = {"xm_debug_set": [C.c_char_p, _i], "xm_debug_get": [C.c_char_p],
 _SWITCHES = {"xm_debug_force_conv_cfg": "conv_cfg", "xm_debug_force_conv_splits": "conv_splits",
              "xm_debug_force_conv_halo": "conv_halo", "xm_debug_force_conv_stem": "conv_stem",
              "xm_debug_force_conv_stem3": "conv_stem3", "xm_debug_force_wgrad_patch": "wgrad_patch",
-             "xm_debug_force_wgrad_patch_s2": "wgrad_patch_s2", "xm_debug_force_dgrad_s2": "dgrad_s2"}
+             "xm_debug_force_wgrad_patch_s2": "wgrad_patch_s2", "xm_debug_force_dgrad_s2": "dgrad_s2",
+             "xm_debug_force_spec_blocks": "spec_blocks"}
 
 _lib = None
 

@@ -2066,6 +2066,7 @@ static const struct DebugSwitch {
     {"conv_stem", &g_force_stem, norm_tri},         {"conv_stem3", &g_force_stem3, norm_tri},
     {"wgrad_patch", &g_force_wgrad_patch, norm_tri}, {"wgrad_patch_s2", &g_force_wgrad_patch_s2, norm_tri},
     {"dgrad_s2", &g_force_dgrad_s2, norm_tri},
+    {"spec_blocks", &g_spec_blocks, [](int v) { return v > 0 ? v : 0; }},
 };
 static const DebugSwitch *debug_switch(const char *key) {
   for (const DebugSwitch &s : kDebugSwitches)

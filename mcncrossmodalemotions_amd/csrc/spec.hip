@@ -36,6 +36,10 @@ constexpr int kSpecPasses = kSpecBins / 128;
 constexpr int kSpecChunk = 7;      // rounds of eight taps whose products form one fmaf chain
 constexpr int kSpecOcc = 2;        // blocks per CU the grid is sized for (241 registers: two waves per SIMD)
 
+// test switch behind xm_debug_set("spec_blocks", v): v >= 1 launches spec_gemm_kernel with min(v, 65535) blocks whatever
+// the device is, so that a small input gives a block many tiles (tests/test_gpu_spec_edges.py); 0 = CUs x kSpecOcc
+int g_spec_blocks = 0;
+
 // T = floor((len - Nw) / Ns) + 1 frames, 0 for a clip shorter than one frame; len is cut at 2^31 samples
 __device__ __forceinline__ long long spec_frames(long long len, int taps, int hop) {
   if (len > (1LL << 31)) len = 1LL << 31;
@@ -295,7 +299,7 @@ int xm_spec_bucket_batch(const float *wav, long long wav_len, const long long *d
   int dev = 0, cus = 0;
   XM_HIP(hipGetDevice(&dev));
   XM_HIP(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
-  const int G = cus * kSpecOcc;
+  const int G = g_spec_blocks >= 1 ? std::min(g_spec_blocks, 65535) : cus * kSpecOcc;
   const size_t slots = (size_t)N + G;
   WsCarver ws;
   int rc = ws.init(WsCarver::need((size_t)Kp * 2 * B, 4) + WsCarver::need((size_t)N + 1, 8) +

@@ -91,6 +91,8 @@ double env_double(const char *name, double dflt);
 
 // comm.cpp: test switch behind xm_debug_set("comm_single", v)
 int comm_force_single(int on);
+// spec.hip: test switch behind xm_debug_set("spec_blocks", v)
+extern int g_spec_blocks;
 
 // conv.hip: one record of the xm_prof_* hooks (include/xmodal_prof.h) around a launch of another translation unit;
 // prof_open returns nullptr while the profiler is off, prof_close(nullptr) does nothing
