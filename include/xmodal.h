@@ -57,7 +57,7 @@ enum { XM_FUSE_RELU = 1, XM_BN_BATCH_MOMENTS = 2, XM_FUSE_SIGMOID = 4 };
 
 /* ABI revision: 100 = round 1; 101 = xm_nnbnorm_relu_pool_backward gained `y_pool`, exchange entry points return
  * XM_EINVAL without a communicator; 102 = + xm_nnconv_forward_moments, xm_nnbnorm_backward_dxsum, xm_nnconv_forward_gated;
- * 103 = + xm_nnpool_global_avg_backward_accum; 104 = + xm_nnconv_backward_filter_bnrelupool, xm_nndropout_forward / _apply, xm_resample, xm_se_tail_backward_reduce / _apply, xm_se_squeeze_bn, xm_scale_axpy_bn; 105 = + xm_set_exec_hint / xm_get_exec_hint; 106 = + xm_nnconv_bnorm_relu_pool_forward, xm_stem_gram, xm_stem_gram_moments, xm_nnconv_backward_filter_bnrelupool_gram; 107 = + xm_nnaffinegrid / _backward, xm_nnbilinearsampler / _backward, xm_ferplus_batch; 108 = + XM_AGG_PEAK, xm_mnrfit, xm_mnrval; 109 = + xm_roc, xm_roc_launches, xm_label_hist; 110 = + xm_group_rows, xm_gather_rows, xm_scatter_rows, xm_track_peaks; 111 = + xm_wav_batch; 112 = + xm_spec_bucket_batch; 113 = + xm_jpeg_plan, xm_jpeg_decode_batch; 114 = + xm_wav_plan, xm_wav_decode_batch (additions never change the revision's meaning for older bindings).  A binding checks xm_version() >= the revision it was written against. */
+ * 103 = + xm_nnpool_global_avg_backward_accum; 104 = + xm_nnconv_backward_filter_bnrelupool, xm_nndropout_forward / _apply, xm_resample, xm_se_tail_backward_reduce / _apply, xm_se_squeeze_bn, xm_scale_axpy_bn; 105 = + xm_set_exec_hint / xm_get_exec_hint; 106 = + xm_nnconv_bnorm_relu_pool_forward, xm_stem_gram, xm_stem_gram_moments, xm_nnconv_backward_filter_bnrelupool_gram; 107 = + xm_nnaffinegrid / _backward, xm_nnbilinearsampler / _backward, xm_ferplus_batch; 108 = + XM_AGG_PEAK, xm_mnrfit, xm_mnrval; 109 = + xm_roc, xm_roc_launches, xm_label_hist; 110 = + xm_group_rows, xm_gather_rows, xm_scatter_rows, xm_track_peaks; 111 = + xm_wav_batch; 112 = + xm_spec_bucket_batch; 113 = + xm_jpeg_plan, xm_jpeg_decode_batch; 114 = + xm_wav_plan, xm_wav_decode_batch; 115 = + xm_jpeg_decode_batch_split, xm_jpeg_split_geometry (additions never change the revision's meaning for older bindings).  A binding checks xm_version() >= the revision it was written against. */
 int xm_version(void);
 const char *xm_last_error(void);
 /* Device memory for hosts that have no device-array type of their own (MATLAB's gpuArray is CUDA-only: on an
@@ -692,6 +692,26 @@ int xm_jpeg_decode_batch(const unsigned char *bytes, long long nbytes, const lon
                          int nlanes, const unsigned char *tables, int nq, int nh, long long coef_elems,
                          long long plane_bytes, long long pixel_floats, float *pixels, float *faces, float crop, int Ho,
                          int Wo, const float *avg3, int *status, void *stream);
+
+/* xm_jpeg_decode_batch with a segment-parallel entropy stage (ABI 115): what a file without restart markers needs, whose
+ * one lane is otherwise one serial decoder.  The arguments up to `status` are those of xm_jpeg_decode_batch and mean
+ * the same; the plan, its descriptors and its lanes are the same.  Segment i of a lane is the raw bytes
+ * [begin + i * seg_bytes, min(begin + (i + 1) * seg_bytes, end)) of the lane's range.  One workgroup owns a lane, one
+ * thread a segment: every thread decodes its segment from a guessed state, takes its predecessor's exit state (bit
+ * position, block inside the MCU, coefficient index) as its entry until no exit changes -- that fixed point is the
+ * sequential decode --, and decodes once more to write.  A lane of more segments than xm_jpeg_split_geometry's
+ * segments_per_pass runs in consecutive passes inside its workgroup.  seg_bytes: a multiple of 16 in 16 .. 65536, else
+ * XM_EINVAL before any device call.  rounds (optional, device): nlanes int32, the decode rounds a lane took, the first
+ * one included, summed over its passes (1 <= rounds <= segments).  Pixels, faces and status are bit for bit those of
+ * xm_jpeg_decode_batch for every input, truncated and corrupted files included.  The number of launches is that of
+ * xm_jpeg_decode_batch and xm_jpeg_split_geometry reports it (with faces); no synchronisation.
+ * xm_jpeg_split_geometry: host only, no device call. */
+int xm_jpeg_decode_batch_split(const unsigned char *bytes, long long nbytes, const long long *desc, int N,
+                               const long long *lanes, int nlanes, const unsigned char *tables, int nq, int nh,
+                               long long coef_elems, long long plane_bytes, long long pixel_floats, float *pixels,
+                               float *faces, float crop, int Ho, int Wo, const float *avg3, int *status, int seg_bytes,
+                               int *rounds, void *stream);
+int xm_jpeg_split_geometry(int *segments_per_pass, int *launches);
 
 /* audioinfo / audioread of a batch of WAV files, decoded on the device into the waveform bank that xm_wav_batch and
  * xm_spec_bucket_batch read (ABI 114): info = audioinfo(audfile) -> TotalSamples, SampleRate (getBatchEmoVoxCeleb.m:79),

@@ -2217,9 +2217,9 @@ int xm_prof_kernel_name(int key, char *buf, int len) {
     return XM_OK;
   }
   if (kind == 21) {   // jpeg.hip
-    static const char *const names[5] = {"jpeg_clear_kernel", "jpeg_entropy_kernel", "jpeg_idct_kernel", "jpeg_colour_kernel",
-                                         "crop_resize_face_ragged_kernel"};
-    snprintf(buf, len, "%s", names[key % 100 < 5 ? key % 100 : 0]);
+    static const char *const names[6] = {"jpeg_clear_kernel", "jpeg_entropy_kernel", "jpeg_idct_kernel", "jpeg_colour_kernel",
+                                         "crop_resize_face_ragged_kernel", "jpeg_entropy_split_kernel"};
+    snprintf(buf, len, "%s", names[key % 100 < 6 ? key % 100 : 0]);
     return XM_OK;
   }
   if (kind == 22) {   // wav.hip

@@ -21,6 +21,8 @@
 //                        of one or two columns replicated as libjpeg does), YCbCr -> RGB, cropped to H x W, written as
 //                        H x W x 3 single in MATLAB layout
 //   crop_resize_face_ragged_kernel (misc.hip, next to the kernel it must equal bit for bit)   the teacher's input
+// xm_jpeg_decode_batch_split enqueues the same launches with jpeg_entropy_split_kernel as the entropy stage: one block
+// per lane, one thread per segment of seg_bytes raw bytes, for files without restart markers (described at the kernel).
 #include <algorithm>
 #include <vector>
 
@@ -209,6 +211,366 @@ jpeg_entropy_kernel(const uint4 *__restrict__ bytes, long long nbytes, const lon
     if (br.starved()) st |= XM_JPEG_TRUNCATED;
   }
   if (st) atomicOr(status + img, st);
+}
+
+// ---- jpeg_entropy_split_kernel -------------------------------------------------------------------------------------
+// The entropy stage of xm_jpeg_decode_batch_split: one block per lane, one thread per segment of seg_bytes raw bytes, a
+// lane of more than kJpegSplitThreads segments in consecutive passes.  A decoder state is (bit position, block inside
+// the MCU, coefficient index k; k == 0: a DC symbol comes next) or "ended".  A bit position is canonical: 8 x the raw
+// offset of a byte the reader delivers (never the 00 of an FF 00 pair) + 0 .. 7, so two threads at the same bit compare
+// equal whatever they hold in their accumulators; past the end of the entropy data it goes on counting the zero bits
+// consumed.  A thread decodes symbols until one starts at or past its segment's end and publishes the state there.
+// Once the front of its reader stands at or past the end of the data (the lane's last byte or a marker inside it) a
+// thread is in the tail: it publishes "ended", and in the writing pass it is the thread that goes on, over zero bits,
+// to the end of the MCU, as jpeg_entropy_kernel does before it sets TRUNCATED.
+//   rounds   round 0: thread 0 decodes from the pass's confirmed entry, every other thread from the first byte of its
+//            segment with (block 0, k 0) -- there an invalid code or a run past 63 drops one bit and resets k, the
+//            thread is guessing.  Then every thread whose predecessor's exit differs from its own entry takes it and
+//            decodes again (an invalid code now ends the chain), and so does a thread whose guessed entry turned out
+//            right but whose decode had skipped an invalid symbol, until no thread did: thread i is final after round i,
+//            so the loop is bounded by the pass's segments and its condition is block-uniform (__syncthreads_or).
+//            Each decode also counts the blocks completed and sums the DC differences per component.
+//   scan     exclusive over (blocks, dc0, dc1, dc2, ended): a thread's first block ordinal and DC predictors
+//   write    decode once more from the final entry; block ordinal n of the lane is block n % blocks_per_mcu of MCU
+//            mcu0 + n / blocks_per_mcu, at jpeg_entropy_kernel's address.  Ordinals at or past the lane's block count
+//            write nothing and flag nothing; the status bits are set by the one thread that meets the condition.
+// Every loop consumes at least one bit per iteration or leaves: the symbol loop ends at the segment's end, at the
+// lane's block count or, in the tail, at the next MCU boundary.
+constexpr int kJpegSplitThreads = 64;   // segments per pass
+constexpr int kJpegEnded = 1 << 9;      // state word: blk | k << 3 | ended
+
+struct SegReader {
+  const uint4 *base;
+  long long pos, end;    // next byte to fetch (counts on past `end`, where bytes are zero) and the end of the data
+  long long cidx;
+  unsigned c0, c1, c2, c3;      // the 16-byte piece cidx
+  unsigned long long acc, sk;   // next bit at the top; sk: a one under the last bit of a byte that a stuffed 00 followed
+  int nbits;
+
+  __device__ __forceinline__ unsigned byte_at(long long p) {
+    if ((p >> 4) != cidx) {
+      cidx = p >> 4;
+      const uint4 c = base[cidx];
+      c0 = c.x;
+      c1 = c.y;
+      c2 = c.z;
+      c3 = c.w;
+    }
+    const int w = (int)(p >> 2) & 3;
+    const unsigned v = w == 0 ? c0 : (w == 1 ? c1 : (w == 2 ? c2 : c3));
+    return (v >> (((int)p & 3) * 8)) & 255u;
+  }
+  __device__ __forceinline__ void refill() {
+    while (nbits <= 56) {
+      unsigned b = 0;
+      if (pos < end) {
+        b = byte_at(pos++);
+        if (b == 0xFFu && pos < end) {
+          if (byte_at(pos) == 0) {
+            ++pos;                 // FF 00: a stuffed zero
+            sk |= 1ull << (56 - nbits);
+          } else {                 // a marker inside the range: the entropy data ends here, this byte is the first zero
+            end = pos - 1;
+            b = 0;
+          }
+        }
+      } else {
+        ++pos;
+      }
+      acc |= (unsigned long long)b << (56 - nbits);
+      nbits += 8;
+    }
+  }
+  __device__ __forceinline__ void drop(int n) {
+    acc <<= n;
+    sk <<= n;
+    nbits -= n;
+  }
+  __device__ __forceinline__ int take(int n) {   // n in 0 .. 16
+    refill();
+    const int v = n ? (int)(acc >> (64 - n)) : 0;
+    drop(n);
+    return v;
+  }
+  // canonical position of the next bit
+  __device__ __forceinline__ long long front() const {
+    return (pos - ((nbits + 7) >> 3) - __popcll(sk)) * 8 + ((8 - (nbits & 7)) & 7);
+  }
+  __device__ __forceinline__ void start(const uint4 *b, long long bit, long long e) {
+    base = b;
+    pos = bit >> 3;
+    end = e;
+    cidx = -1;
+    c0 = c1 = c2 = c3 = 0;
+    acc = sk = 0;
+    nbits = 0;
+    refill();
+    drop((int)(bit & 7));
+  }
+};
+
+__device__ __forceinline__ int huff_decode_seg(const unsigned char *t, SegReader &br) {   // huff_decode on a SegReader
+  br.refill();
+  const unsigned w = (unsigned)(br.acc >> 48);
+  const unsigned e = ((const unsigned short *)t)[w >> 8];
+  if (e >> 8) {
+    br.drop((int)(e >> 8));
+    return (int)(e & 255u);
+  }
+  const int *maxcode = (const int *)(t + 768), *valoff = (const int *)(t + 836);
+  for (int l = 9; l <= 16; ++l) {
+    const int code = (int)(w >> (16 - l));
+    if (code <= maxcode[l]) {
+      br.drop(l);
+      return t[512 + ((code + valoff[l]) & 255)];
+    }
+  }
+  return -1;
+}
+
+struct SplitLane {   // block-uniform: the lane and its image
+  long long begin, end, mcu0, total, nbY, nblocks, nlb;
+  int hv, hs, vs, mx, bpm;
+  short *cbase;
+};
+
+// the 64 coefficients of block ordinal n of the lane; NULL where jpeg_entropy_kernel would not write
+__device__ __forceinline__ short *split_block(const SplitLane &g, long long n) {
+  const long long mcu = g.mcu0 + n / g.bpm;
+  const int j = (int)(n % g.bpm);
+  long long b;
+  if (j < g.hv) {
+    const int ym = (int)(mcu / g.mx), xm = (int)(mcu - (long long)ym * g.mx);
+    b = (long long)(ym * g.vs + j / g.hs) * (g.mx * g.hs) + xm * g.hs + j % g.hs;
+  } else {
+    b = g.nbY + mcu + (j - g.hv) * g.total;
+  }
+  return (n < g.nlb && b >= 0 && b < g.nblocks) ? g.cbase + b * 64 : nullptr;
+}
+
+// Decodes from state (bit, m) to the end of the segment.  WRITE false: counts blocks into n and DC differences into
+// p0 .. p2 (all zero on entry) and returns the exit state in (bit, m); guess: recover from invalid symbols, and return
+// 1 if that happened -- such a result serves as a guess for the threads after it but must never become final.  WRITE
+// true: n is the first block ordinal, p0 .. p2 the DC predictors; stores coefficients and returns the status bits.
+template <bool WRITE>
+__device__ __forceinline__ int split_run(const SplitLane &g, const uint4 *bytes, const unsigned char *tab,
+                                         const unsigned char *nat, long long seg_end, bool guess, long long &bit, int &m,
+                                         long long &n, int &p0, int &p1, int &p2) {
+  SegReader br;
+  br.start(bytes, bit, g.end);
+  int blk = m & 7, k = (m >> 3) & 63, recovered = 0;
+  short *out = nullptr;
+  if (WRITE && k > 0) out = split_block(g, n);
+  for (;;) {
+    br.refill();
+    if (WRITE && n >= g.nlb) return 0;
+    if (br.pos >= seg_end || br.pos >= br.end) {   // near an end: look at the exact position
+      const long long f = br.front();
+      const bool tail = f >= br.end * 8;
+      if (!tail && f >= seg_end * 8) {
+        bit = f;
+        m = blk | (k << 3);
+        return WRITE ? 0 : recovered;
+      }
+      if (tail && !WRITE) {
+        bit = 0;
+        m = kJpegEnded;
+        return recovered;
+      }
+    }
+    const int c = blk < g.hv ? 0 : blk - g.hv + 1;
+    bool bad = false;
+    if (k == 0) {
+      const int s = huff_decode_seg(tab + c * kHtBytes, br);
+      if (s < 0 || s > 15) {
+        bad = true;
+      } else {
+        const int diff = huff_extend(br.take(s), s);
+        const int pred = (c == 0 ? p0 : (c == 1 ? p1 : p2)) + diff;
+        p0 = c == 0 ? pred : p0;
+        p1 = c == 1 ? pred : p1;
+        p2 = c == 2 ? pred : p2;
+        if (WRITE) {
+          out = split_block(g, n);
+          if (out) out[0] = (short)pred;
+        }
+        k = 1;
+      }
+    } else {
+      const int rs = huff_decode_seg(tab + (3 + c) * kHtBytes, br);
+      if (rs < 0) {
+        bad = true;
+      } else {
+        const int r = rs >> 4, s = rs & 15;
+        if (s == 0) {
+          k = r != 15 ? 64 : k + 16;
+        } else {
+          k += r;
+          if (k > 63) {
+            bad = true;
+          } else {
+            const int v = huff_extend(br.take(s), s);
+            if (WRITE && out) out[nat[k & 63]] = (short)v;
+            ++k;
+          }
+        }
+      }
+    }
+    if (bad) {
+      if (WRITE) return XM_JPEG_BADCODE | (br.front() > br.end * 8 ? XM_JPEG_TRUNCATED : 0);
+      if (!guess) {
+        bit = 0;
+        m = kJpegEnded;
+        return 0;
+      }
+      br.refill();
+      br.drop(1);   // a guess went wrong: one bit on, a DC symbol next
+      k = 0;
+      recovered = 1;
+      continue;
+    }
+    if (k >= 64) {
+      k = 0;
+      ++n;
+      blk = blk + 1 == g.bpm ? 0 : blk + 1;
+      if (WRITE && (n >= g.nlb || blk == 0) && br.front() > br.end * 8) return XM_JPEG_TRUNCATED;
+    }
+  }
+}
+
+__global__ void __launch_bounds__(kJpegSplitThreads)
+jpeg_entropy_split_kernel(const uint4 *__restrict__ bytes, long long nbytes, const long long *__restrict__ desc, int N,
+                          const long long *__restrict__ lanes, int nlanes, const unsigned char *__restrict__ huff, int nh,
+                          short *__restrict__ coef, int *__restrict__ status, int seg_bytes, int *__restrict__ rounds) {
+  constexpr int T = kJpegSplitThreads;
+  __shared__ __attribute__((aligned(16))) unsigned char s_tab[6 * kHtBytes];
+  __shared__ unsigned char s_nat[64];
+  __shared__ long long s_bit[T + 1];           // exit states; [T]: the confirmed entry of the pass
+  __shared__ int s_m[T + 1];
+  __shared__ int s_cnt[T][4];                  // blocks, dc0, dc1, dc2
+  __shared__ long long s_n0;                   // blocks before the pass
+  __shared__ int s_pred[3];
+  const int tid = threadIdx.x;
+  const long long gl = blockIdx.x;
+  if (gl >= nlanes) return;
+  const long long img = min(max(lanes[gl * kJpegLane], 0LL), (long long)N - 1);
+  const long long *d = desc + img * kJpegDesc;
+  s_nat[tid] = kNaturalDev[tid];
+  for (int j = tid; j < 6 * (kHtBytes / 16); j += T) {
+    const int tb = j / (kHtBytes / 16), q = j - tb * (kHtBytes / 16);
+    const long long slot = d[tb < 3 ? D_DC + tb : D_AC + tb - 3];
+    const long long sl = min(max(slot, 0LL), (long long)nh - 1);
+    ((uint4 *)(s_tab + tb * kHtBytes))[q] = ((const uint4 *)(huff + sl * kHtBytes))[q];
+  }
+  // the lane's byte range, inside the image's, inside the buffer
+  const long long i0 = min(max(d[D_SCAN0], 0LL), nbytes), i1 = min(max(d[D_SCAN1], i0), nbytes);
+  SplitLane g;
+  g.begin = min(max(lanes[gl * kJpegLane + 1], i0), i1);
+  g.end = min(max(lanes[gl * kJpegLane + 2], g.begin), i1);
+  const int ncomp = (int)d[D_NCOMP];
+  g.hs = min(max((int)d[D_HS], 1), 2);
+  g.vs = min(max((int)d[D_VS], 1), 2);
+  g.mx = max((int)d[D_MX], 1);
+  g.hv = g.hs * g.vs;
+  g.bpm = g.hv + (ncomp == 3 ? 2 : 0);
+  g.total = (long long)g.mx * max((int)d[D_MY], 0);
+  const long long ri = d[D_RI];
+  g.mcu0 = min(max(lanes[gl * kJpegLane + 3], 0LL), g.total);
+  const long long stop = ri > 0 ? min(g.mcu0 + ri, g.total) : g.total;
+  g.nbY = g.total * g.hv;
+  g.nblocks = g.nbY + (ncomp == 3 ? 2 * g.total : 0);
+  g.nlb = (stop - g.mcu0) * g.bpm;
+  g.cbase = coef + d[D_COEF];
+  const long long nseg = max((g.end - g.begin + seg_bytes - 1) / seg_bytes, 1LL);
+  if (tid == 0) {
+    s_bit[T] = g.begin * 8;
+    s_m[T] = 0;
+    s_n0 = 0;
+    s_pred[0] = s_pred[1] = s_pred[2] = 0;
+  }
+  __syncthreads();
+  int total_rounds = 0;
+  for (long long seg0 = 0; seg0 < nseg; seg0 += T) {
+    if (s_m[T] & kJpegEnded) break;            // the chain ended in an earlier pass (block-uniform)
+    const int nact = (int)min((long long)T, nseg - seg0);
+    const bool active = tid < nact;
+    const long long sb = min(g.begin + (seg0 + tid) * seg_bytes, g.end), se = min(sb + seg_bytes, g.end);
+    long long ebit = s_bit[T], xbit = 0, cnt = 0;
+    int em = s_m[T], xm = 0, c0 = 0, c1 = 0, c2 = 0;
+    if (tid > 0 && active) {                   // a guess: the first byte of the segment, or the one after a stuffed 00
+      const unsigned char *raw = (const unsigned char *)bytes;
+      const bool stuffed = sb > g.begin && sb < g.end && raw[sb] == 0 && raw[sb - 1] == 0xFFu;
+      ebit = (sb + (stuffed ? 1 : 0)) * 8;
+      em = 0;
+    }
+    bool redo = active, guess = tid > 0, unconfirmed = false;
+    for (int r = 0;; ++r) {
+      if (redo) {
+        xbit = ebit;
+        xm = em;
+        cnt = 0;
+        c0 = c1 = c2 = 0;
+        unconfirmed = split_run<false>(g, bytes, s_tab, s_nat, se, guess, xbit, xm, cnt, c0, c1, c2) != 0;
+        s_bit[tid] = xbit;
+        s_m[tid] = xm;
+      }
+      __syncthreads();
+      redo = false;
+      guess = false;
+      if (tid > 0 && active) {
+        const long long pb = s_bit[tid - 1];
+        const int pm = s_m[tid - 1];
+        if (pb != ebit || pm != em) {
+          ebit = pb;
+          em = pm;
+          redo = !(pm & kJpegEnded);           // an ended entry: keep the result, the scan marks this thread dead
+        } else if (unconfirmed && !(em & kJpegEnded)) {   // the guess was right, but its decode skipped an invalid symbol
+          redo = true;
+        }
+      }
+      const int any = __syncthreads_or(redo);
+      if (!any || r + 2 > nact) {
+        total_rounds += r + 1;
+        break;
+      }
+    }
+    // scan: every thread sums what the threads before it published, at most T - 1 steps of five LDS reads -- small
+    // next to a segment decode at T = 64; a wave scan would be the thing to use if T grew
+    s_cnt[tid][0] = (int)cnt;
+    s_cnt[tid][1] = c0;
+    s_cnt[tid][2] = c1;
+    s_cnt[tid][3] = c2;
+    __syncthreads();
+    long long n0 = s_n0;
+    int p0 = s_pred[0], p1 = s_pred[1], p2 = s_pred[2];
+    bool dead = !active || (em & kJpegEnded);
+    for (int j = 0; j < tid && j < nact; ++j) {
+      n0 += s_cnt[j][0];
+      p0 += s_cnt[j][1];
+      p1 += s_cnt[j][2];
+      p2 += s_cnt[j][3];
+      dead = dead || (s_m[j] & kJpegEnded);
+    }
+    // write
+    if (!dead) {
+      long long wbit = ebit, wn = n0;
+      int wm = em, q0 = p0, q1 = p1, q2 = p2;
+      const int st = split_run<true>(g, bytes, s_tab, s_nat, se, false, wbit, wm, wn, q0, q1, q2);
+      if (st) atomicOr(status + img, st);
+    }
+    __syncthreads();
+    if (tid == nact - 1) {                     // the carry into the next pass
+      const bool ended = dead || (xm & kJpegEnded);
+      s_bit[T] = ended ? 0 : xbit;
+      s_m[T] = ended ? kJpegEnded : xm;
+      s_n0 = n0 + cnt;
+      s_pred[0] = p0 + c0;
+      s_pred[1] = p1 + c1;
+      s_pred[2] = p2 + c2;
+    }
+    __syncthreads();
+  }
+  if (rounds && tid == 0) rounds[gl] = total_rounds;
 }
 
 // ---- jpeg_idct_kernel ----------------------------------------------------------------------------------------------
@@ -636,10 +998,13 @@ int xm_jpeg_plan(const unsigned char *bytes, const long long *offsets, int N, lo
   return XM_OK;
 }
 
-int xm_jpeg_decode_batch(const unsigned char *bytes, long long nbytes, const long long *desc, int N, const long long *lanes,
-                         int nlanes, const unsigned char *tables, int nq, int nh, long long coef_elems,
-                         long long plane_bytes, long long pixel_floats, float *pixels, float *faces, float crop, int Ho,
-                         int Wo, const float *avg3, int *status, void *stream) {
+}  // extern "C"
+
+// xm_jpeg_decode_batch (seg_bytes == 0) and xm_jpeg_decode_batch_split: the same launches but for the entropy stage
+static int jpeg_decode_launch(const unsigned char *bytes, long long nbytes, const long long *desc, int N, const long long *lanes,
+                              int nlanes, const unsigned char *tables, int nq, int nh, long long coef_elems,
+                              long long plane_bytes, long long pixel_floats, float *pixels, float *faces, float crop, int Ho,
+                              int Wo, const float *avg3, int *status, int seg_bytes, int *rounds, void *stream) {
   if (N < 0 || nbytes < 0 || nlanes < 0 || nq < 0 || nh < 0 || coef_elems < 0 || plane_bytes < 0 || pixel_floats < 0)
     return fail(XM_EINVAL, "jpeg_decode_batch: negative size");
   if (N == 0) return XM_OK;
@@ -673,9 +1038,13 @@ int xm_jpeg_decode_batch(const unsigned char *bytes, long long nbytes, const lon
     XM_LAUNCH_CHECK();
   }
   {
-    void *ps = prof_open(2101, 0, st);
-    hipLaunchKernelGGL(jpeg_entropy_kernel, dim3((unsigned)((nlanes + kJpegLanes - 1) / kJpegLanes)), dim3(64), 0, st,
-                       (const uint4 *)bytes, nbytes, desc, N, lanes, nlanes, huff, nh, coef, status);
+    void *ps = prof_open(seg_bytes ? 2105 : 2101, 0, st);
+    if (seg_bytes)
+      hipLaunchKernelGGL(jpeg_entropy_split_kernel, dim3((unsigned)nlanes), dim3(kJpegSplitThreads), 0, st,
+                         (const uint4 *)bytes, nbytes, desc, N, lanes, nlanes, huff, nh, coef, status, seg_bytes, rounds);
+    else
+      hipLaunchKernelGGL(jpeg_entropy_kernel, dim3((unsigned)((nlanes + kJpegLanes - 1) / kJpegLanes)), dim3(64), 0, st,
+                         (const uint4 *)bytes, nbytes, desc, N, lanes, nlanes, huff, nh, coef, status);
     prof_close(ps);
     XM_LAUNCH_CHECK();
   }
@@ -700,6 +1069,33 @@ int xm_jpeg_decode_batch(const unsigned char *bytes, long long nbytes, const lon
     prof_close(ps);
     if (rc) return rc;
   }
+  return XM_OK;
+}
+
+extern "C" {
+
+int xm_jpeg_decode_batch(const unsigned char *bytes, long long nbytes, const long long *desc, int N, const long long *lanes,
+                         int nlanes, const unsigned char *tables, int nq, int nh, long long coef_elems,
+                         long long plane_bytes, long long pixel_floats, float *pixels, float *faces, float crop, int Ho,
+                         int Wo, const float *avg3, int *status, void *stream) {
+  return jpeg_decode_launch(bytes, nbytes, desc, N, lanes, nlanes, tables, nq, nh, coef_elems, plane_bytes, pixel_floats,
+                            pixels, faces, crop, Ho, Wo, avg3, status, 0, nullptr, stream);
+}
+
+int xm_jpeg_decode_batch_split(const unsigned char *bytes, long long nbytes, const long long *desc, int N,
+                               const long long *lanes, int nlanes, const unsigned char *tables, int nq, int nh,
+                               long long coef_elems, long long plane_bytes, long long pixel_floats, float *pixels,
+                               float *faces, float crop, int Ho, int Wo, const float *avg3, int *status, int seg_bytes,
+                               int *rounds, void *stream) {
+  if (seg_bytes < 16 || seg_bytes > 65536 || (seg_bytes & 15))
+    return fail(XM_EINVAL, "jpeg_decode_batch_split: seg_bytes must be a multiple of 16 in 16 .. 65536 (got %d)", seg_bytes);
+  return jpeg_decode_launch(bytes, nbytes, desc, N, lanes, nlanes, tables, nq, nh, coef_elems, plane_bytes, pixel_floats,
+                            pixels, faces, crop, Ho, Wo, avg3, status, seg_bytes, rounds, stream);
+}
+
+int xm_jpeg_split_geometry(int *segments_per_pass, int *launches) {
+  if (segments_per_pass) *segments_per_pass = kJpegSplitThreads;
+  if (launches) *launches = 5;   // clear, entropy, IDCT, colour, faces
   return XM_OK;
 }
 

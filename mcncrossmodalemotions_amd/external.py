@@ -238,12 +238,13 @@ def compute_audio_feats_files(dag, files, numEmotions=8, limit=float("inf"), max
     return compute_audio_feats_wav(dag, bank, offsets, numEmotions=numEmotions, maxBatch=maxBatch)
 
 
-def compute_visual_feats(dag, track_frames, batchSize=128, numEmotions=8, limit=float("inf"), lanes=2, *, read=None):
+def compute_visual_feats(dag, track_frames, batchSize=128, numEmotions=8, limit=float("inf"), lanes=2, *, read=None,
+                         split=None):
     """faceLogits = compute_visual_feats(dag, track_frames): the frames of all tracks are flattened
     (:63-69), pushed through the frozen teacher `batchSize` at a time (:81-94) and the logits are split
     back per track (:104-109).  track_frames: list of 224 x 224 x 3 x F_i normalised face mats; with
     `read(paths) -> list of bytes` a list of frame-path lists instead, and every batch comes from
-    fetch_emovoxceleb_imdb.getImageBatch (:123-164: the JPEG files decoded on the device)."""
+    fetch_emovoxceleb_imdb.getImageBatch (:123-164: the JPEG files decoded on the device; `split` goes there)."""
     _prepare(dag)
     first_ok = [i for i in range(len(track_frames)) if i <= limit]   # frameIdx <= firstId + limit, :72
     if read is not None:
@@ -251,7 +252,7 @@ def compute_visual_feats(dag, track_frames, batchSize=128, numEmotions=8, limit=
         counts = [len(track_frames[i]) for i in first_ok]
         paths = [p for i in first_ok for p in track_frames[i]]
         teacher = zoo.FrozenTeacher(dag, lanes=lanes)
-        outs = [teacher.logits(fe.getImageBatch(paths[s:s + batchSize], dag, read=read))
+        outs = [teacher.logits(fe.getImageBatch(paths[s:s + batchSize], dag, read=read, split=split))
                 for s in range(0, len(paths), batchSize)]
         logits = (np.concatenate([vl.to_numpy(o).reshape(-1, int(o.shape[3]), order="F").T for o in outs], 0)
                   if outs else np.zeros((0, numEmotions), np.float32))

@@ -142,19 +142,21 @@ def read_files(faceDir):
     return read
 
 
-def getImageBatch(imagePaths, dag, *, read=None, faceDir=os.path.join("data", "voxceleb", "faces"), device=None):
+def getImageBatch(imagePaths, dag, *, read=None, faceDir=os.path.join("data", "voxceleb", "faces"), device=None,
+                  split=None):
     """data = getImageBatch(imagePaths, dag) -- :152-193: vl_imreadjpeg with CropSize 1/1.6, CropLocation center,
     bilinear Resize to meta.normalization.imageSize (:160-172), rgb2gray, x3 and normalizeFace (:176-193), all on the
     device from the files' bytes (vl.imreadjpeg).  `read(paths) -> list of bytes` (default: the files under faceDir);
     `dag`: a network with meta.normalization, or an object with .imageSize / .averageImage.  Ho x Wo x 3 x n; nothing
-    is synchronised."""
+    is synchronised.  `split`: vl.imreadjpeg's seg_bytes (the segment-parallel entropy decode; the same faces)."""
     if hasattr(dag, "meta"):
         imageSize, avg = tuple(dag.meta["normalization"]["imageSize"][:2]), dag.meta["normalization"]["averageImage"]
     else:
         imageSize, avg = tuple(getattr(dag, "imageSize", (224, 224)))[:2], getattr(dag, "averageImage", AVERAGE_IMAGE)
     read = read or read_files(faceDir)
     return vl.imreadjpeg(read(list(imagePaths)), resize=imageSize, crop_size=1 / 1.6, crop_location="center",
-                         interpolation="bilinear", pack=True, num_threads=10, average_image=avg, device=device)
+                         interpolation="bilinear", pack=True, num_threads=10, average_image=avg, device=device,
+                         split=split)
 
 
 class _Norm:
@@ -162,7 +164,8 @@ class _Norm:
         self.imageSize, self.averageImage = imageSize, averageImage
 
 
-def buildImdb(teacher, imdb, frames=None, *, read=None, limit=math.inf, batchSize=128, lanes=2, device=None):
+def buildImdb(teacher, imdb, frames=None, *, read=None, limit=math.inf, batchSize=128, lanes=2, device=None,
+              split=None):
     """imdb = buildImdb(teacher) -- :54-149, for an imdb that went through addFramesToImdb.  `teacher`: a ferPlusZoo
     network (losses are stripped, test mode, one input: :101-110) or any object with .logits(faces) -> 1 x 1 x E x n;
     `frames(paths, device)` -> the decoded frames Hin x Win x 3 x n (0..255), what vl_imreadjpeg returns for
@@ -170,10 +173,12 @@ def buildImdb(teacher, imdb, frames=None, *, read=None, limit=math.inf, batchSiz
       wavLogits        host list, one F_i x E float32 array per wav (empty past `limit`), downloaded once;
       device_logits()  the same rows concatenated on the device, already in place.
     With `read(paths) -> list of bytes` instead of `frames` the batch comes from getImageBatch: the JPEG files are
-    decoded on the device (frames of any sizes in one batch).
+    decoded on the device (frames of any sizes in one batch); `split` goes to getImageBatch.
     The loop enqueues work only; it neither synchronises nor downloads."""
     if (frames is None) == (read is None):
         raise ValueError("buildImdb: give either `frames` (decoded pixels) or `read` (JPEG bytes)")
+    if split is not None and read is None:
+        raise ValueError("buildImdb: `split` belongs to the device JPEG decode, which needs `read`")
     if not torch.cuda.is_available():
         raise RuntimeError("buildImdb needs a GPU; this build has no CPU path")
     device = device or torch.device("cuda", torch.cuda.current_device())
@@ -193,7 +198,7 @@ def buildImdb(teacher, imdb, frames=None, *, read=None, limit=math.inf, batchSiz
         batch = range(start, min(start + int(batchSize), numIms))
         paths = [images["denseFrames"][i] for i in batch]
         if read is not None:
-            faces = getImageBatch(paths, _Norm(imageSize, avg), read=read, device=device)    # :152-193 from the bytes
+            faces = getImageBatch(paths, _Norm(imageSize, avg), read=read, device=device, split=split)    # :152-193
         else:
             data = frames(paths, device)                                                 # vl_imreadjpeg (:160-172)
             faces = vl.crop_resize_face(data, avg, imageSize)                            # getImageBatch (:152-193)
@@ -255,11 +260,12 @@ def load_imdb(path):
 
 
 def fetch_emovoxceleb_imdb(teacher="senet50-ferplus", imdbDir=os.path.join("data", "xEmo18", "storedFeats"), *,
-                           net=None, imdb=None, frames=None, read=None, verbose=True, **buildOpts):
+                           net=None, imdb=None, frames=None, read=None, split=None, verbose=True, **buildOpts):
     """loadedImdb = fetch_emovoxceleb_imdb(teacher, 'imdbDir', ..) -- :1-51: the cached imdb of (teacher, imdbDir), else
     <imdbDir>/<teacher>-logits.mat when it exists, else buildImdb and save.  Building needs (keyword-only) `net` (default
     zoo.ferPlusZoo(teacher)), `imdb` (an imdb that went through addFramesToImdb; default a 64-track synthetic one) and
-    `frames`; buildOpts go to buildImdb (limit, batchSize, lanes).  A loaded imdb uploads its logits on first use.
+    `frames` or `read` (with `split`, as buildImdb); buildOpts go to buildImdb (limit, batchSize, lanes).  A loaded
+    imdb uploads its logits on first use.
     The cache key and the file name hold the teacher's NAME and imdbDir, nothing else: a later call with another
     `net`, `imdb`, `frames` or `limit` under the same name and directory gets the first build back, from the module
     cache or from the file.  Use another imdbDir (or call buildImdb) for a different build."""
@@ -284,7 +290,7 @@ def fetch_emovoxceleb_imdb(teacher="senet50-ferplus", imdbDir=os.path.join("data
         if frames is None and read is None:
             raise ValueError("fetch_emovoxceleb_imdb: building needs `frames` for the given imdb")
         loaded = buildImdb(net if net is not None else zoo.ferPlusZoo(teacher), imdb, frames if read is None else None,
-                           read=read, **buildOpts)
+                           read=read, split=split, **buildOpts)
         save_imdb(imdbPath, loaded)
     _CACHE[key] = loaded
     return loaded

@@ -1361,10 +1361,24 @@ def jpeg_plan(files, stage=None):
     return buf, plan
 
 
-def jpeg_decode(buf, plan, *, want_pixels=True, resize=None, crop=1.0, average_image=None, device=None):
+def jpeg_split_geometry():
+    """(segments per pass, launches) of the segment-parallel entropy decode (xm_jpeg_split_geometry; no device call)"""
+    spp, launches = C.c_int(0), C.c_int(0)
+    _lib.check(_L().xm_jpeg_split_geometry(C.byref(spp), C.byref(launches)))
+    return spp.value, launches.value
+
+
+def jpeg_decode(buf, plan, *, want_pixels=True, resize=None, crop=1.0, average_image=None, device=None, split=None,
+                return_rounds=False):
     """uploads a planned staging buffer (non-blocking, three slices of the one pinned buffer) and enqueues
     xm_jpeg_decode_batch.  Returns (pixels ragged float32 | None, faces Ho x Wo x 3 x N | None, status int32[N], desc
-    numpy N x 24).  Nothing is synchronised."""
+    numpy N x 24).  Nothing is synchronised.  split=seg_bytes (a multiple of 16 in 16 .. 65536) decodes the entropy data
+    segment-parallel (xm_jpeg_decode_batch_split): the same pixels, faces and status bit for bit; return_rounds=True then
+    appends the int32 device vector of decode rounds per lane."""
+    if split is None and return_rounds:
+        raise ValueError("jpeg_decode: return_rounds needs split")
+    if split is not None and (int(split) != split or not 16 <= split <= 65536 or split % 16):
+        raise ValueError("jpeg_decode: split must be a multiple of 16 in 16 .. 65536 (got %r)" % (split,))
     device = device or _dev()
     N, sizes = plan["N"], plan["sizes"]
     host = torch.from_numpy(buf) if isinstance(buf, np.ndarray) else buf
@@ -1383,12 +1397,18 @@ def jpeg_decode(buf, plan, *, want_pixels=True, resize=None, crop=1.0, average_i
                 avg = (C.c_float * 3)(*[float(v) for v in np.ravel(average_image)[:3]])
         status = torch.empty(N, dtype=torch.int32, device=device)
         p = dev.data_ptr()
-        _lib.check(_L().xm_jpeg_decode_batch(
-            C.c_void_p(p), plan["nbytes"], C.c_void_p(p + plan["desc"][0]), N, C.c_void_p(p + plan["lanes"][0]),
-            int(sizes[6]), C.c_void_p(p + plan["tables"][0]), int(sizes[1]), int(sizes[2]), int(sizes[3]), int(sizes[4]),
-            int(sizes[5]), _ptr(pixels), _ptr(faces), float(crop), Ho, Wo, avg, _ptr(status), _stream()))
+        args = [C.c_void_p(p), plan["nbytes"], C.c_void_p(p + plan["desc"][0]), N, C.c_void_p(p + plan["lanes"][0]),
+                int(sizes[6]), C.c_void_p(p + plan["tables"][0]), int(sizes[1]), int(sizes[2]), int(sizes[3]), int(sizes[4]),
+                int(sizes[5]), _ptr(pixels), _ptr(faces), float(crop), Ho, Wo, avg, _ptr(status)]
+        rounds = None
+        if split is None:
+            _lib.check(_L().xm_jpeg_decode_batch(*args, _stream()))
+        else:
+            if return_rounds:
+                rounds = torch.empty(int(sizes[6]), dtype=torch.int32, device=device)
+            _lib.check(_L().xm_jpeg_decode_batch_split(*args, int(split), _ptr(rounds), _stream()))
     desc = np.array(buf[plan["desc"][0]:plan["desc"][0] + plan["desc"][1]]).view(np.int64).reshape(N, JPEG_DESC)
-    return pixels, faces, status, desc
+    return (pixels, faces, status, desc, rounds) if return_rounds else (pixels, faces, status, desc)
 
 
 def _pinned(nbytes):
@@ -1396,7 +1416,7 @@ def _pinned(nbytes):
 
 
 def imreadjpeg(files, resize=None, crop_size=None, crop_location="center", interpolation="bilinear", pack=True,
-               num_threads=None, *, prefetch=False, average_image=None, device=None, return_status=False):
+               num_threads=None, *, prefetch=False, average_image=None, device=None, return_status=False, split=None):
     """vl_imreadjpeg (fetch_emovoxceleb_imdb.m:160-172, compute_visual_feats.m:130-143) for baseline JPEG files, decoded
     on the device: `files` is a list of bytes or of paths.  Option names follow vl_imreadjpeg; `num_threads` is accepted
     and ignored (there are no decoder threads), only 'center' and 'bilinear' exist, `prefetch` raises.
@@ -1408,7 +1428,8 @@ def imreadjpeg(files, resize=None, crop_size=None, crop_location="center", inter
     The bytes, descriptors and tables go up through one pinned staging buffer with non-blocking copies and the call does
     not synchronise; return_status=True also returns the int32 device vector of JPEG_OK / JPEG_TRUNCATED / JPEG_BADCODE
     bits.  Progressive, arithmetic-coded, 12-bit, multi-scan, CMYK files and unusual sampling factors raise before
-    anything is launched, with the index of the file; there is no host decode to fall back to."""
+    anything is launched, with the index of the file; there is no host decode to fall back to.  split=seg_bytes: the
+    segment-parallel entropy decode of jpeg_decode, for files without restart markers; the same result bit for bit."""
     if prefetch:
         raise ValueError("imreadjpeg: 'Prefetch' is not supported: the call already returns without waiting")
     if str(crop_location).lower() != "center":
@@ -1431,7 +1452,7 @@ def imreadjpeg(files, resize=None, crop_size=None, crop_location="center", inter
     buf, plan = jpeg_plan(datas, stage=_pinned)
     pixels, faces, status, desc = jpeg_decode(buf, plan, want_pixels=resize is None, resize=resize,
                                               crop=1.0 if crop_size is None else float(crop_size),
-                                              average_image=average_image, device=device)
+                                              average_image=average_image, device=device, split=split)
     if resize is not None:
         out = faces
     else:

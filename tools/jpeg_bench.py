@@ -1,12 +1,15 @@
 #!/usr/bin/env python
 """Timing of vl.imreadjpeg (xm_jpeg_plan / xm_jpeg_decode_batch) in front of the frozen teacher.
-usage: python tools/jpeg_bench.py [--teacher senet50-ferplus] [--batches 12] [--reps 10]
+usage: python tools/jpeg_bench.py [--teacher senet50-ferplus] [--batches 12] [--reps 10] [--split]
 128 files of 256 x 256, 4:2:0, quality 90, smooth-plus-noise content (made with PIL when it is importable; otherwise the
 golden files of tests/golden/jpeg_small.npz repeated, and the PIL lines are left out).  Prints
  (a) ms per batch of each decode kernel (the library's profiler hook) and of the host parse and the enqueue;
  (b) PIL decoding the same files on 10 and on 16 threads, img/s, twice;
  (c) buildImdb's loop at batch 128 fed prepared decoded frames, PIL on 10 threads, and the device JPEG path, next to the
-     teacher alone measured in the same process."""
+     teacher alone measured in the same process.
+--split prints instead, in one call on the same files, the table of the segment-parallel entropy decode (imreadjpeg's
+split=): the entropy kernel's time unsplit and at seg_bytes 64 / 128 / 256 / 512 with the mean and the maximum of the
+rounds per lane, the whole decode back to back, and buildImdb's loop unsplit, split and fed by PIL on 10 threads."""
 import argparse
 import ctypes as C
 import io
@@ -88,11 +91,93 @@ def loop_rate(teacher, imdb, numIms, **src):
     return numIms / (time.perf_counter() - t0)
 
 
+SPLITS = (64, 128, 256, 512)
+
+
+def loop_setup(a, faces):
+    """the imdb of 128 * batches frames that name the 128 files, the frozen teacher and its rate alone"""
+    n = 128 * a.batches
+    images = {"name": ["id%05d/v/1.wav" % i for i in range(1, n // 32 + 1)], "id": np.arange(1, n // 32 + 1),
+              "set": np.ones(n // 32, int), "numSamples": np.full(n // 32, 8 * 16000),
+              "denseFrames": ["%d" % (i % 128) for i in range(n)], "denseFramesWavIds": np.arange(n) // 32 + 1}
+    imdb = fe.EmoVoxImdb(images)
+    net = zoo.ferPlusZoo(a.teacher)
+    zoo.strip_losses(net)
+    net.mode = "test"
+    net.move("gpu")
+    teacher = zoo.FrozenTeacher(net, lanes=2)
+    teacher.imageSize, teacher.averageImage = (224, 224), fe.AVERAGE_IMAGE
+    for _ in range(a.batches):
+        teacher.logits(faces)
+    alone = max(128 / timeit(lambda: teacher.logits(faces), a.batches) for _ in range(3))
+    return teacher, imdb, n, alone
+
+
+def split_table(a, L, files, have_pil):
+    face = dict(resize=(224, 224), crop_size=1 / 1.6, average_image=fe.AVERAGE_IMAGE)
+    faces = vl.imreadjpeg(files, **face)
+    print("entropy stage per batch of 128 (the library's profiler hook), rounds per lane, the whole decode back to back")
+    print("    %-10s %-26s %10s %12s %8s %8s %12s" % ("seg_bytes", "kernel", "ms", "segs / lane", "rounds", "max", "decode ms"))
+    best, best_ms, base_ms = None, None, None
+    for seg in (None,) + SPLITS:
+        fn = lambda: vl.imreadjpeg(files, split=seg, **face)                                   # noqa: E731
+        got = fn()
+        assert torch.equal(got.contiguous().view(torch.int32), faces.contiguous().view(torch.int32)), seg
+        name = "jpeg_entropy_kernel" if seg is None else "jpeg_entropy_split_kernel"
+        ms = kernel_ms(L, fn, a.reps)[name]
+        whole = timeit(fn, a.reps) * 1e3
+        if seg is None:
+            base_ms = ms
+            print("    %-10s %-26s %10.3f %12s %8s %8s %12.3f" % ("unsplit", name, ms, "1", "-", "-", whole))
+            continue
+        buf, plan = vl.jpeg_plan(files, stage=vl._pinned)
+        rounds = vl.jpeg_decode(buf, plan, want_pixels=False, resize=(224, 224), crop=1 / 1.6,
+                                average_image=fe.AVERAGE_IMAGE, split=seg, return_rounds=True)[4].cpu().numpy()
+        lanes = buf[plan["lanes"][0]:plan["lanes"][0] + plan["lanes"][1]].view(np.int64).reshape(-1, 4)
+        segs = np.maximum(-(-(lanes[:, 2] - lanes[:, 1]) // seg), 1)
+        print("    %-10d %-26s %10.3f %12.1f %8.1f %8d %12.3f   (%.1f x the unsplit kernel)" % (
+            seg, name, ms, segs.mean(), rounds.mean(), rounds.max(), whole, base_ms / ms))
+        if best_ms is None or ms < best_ms:
+            best, best_ms = seg, ms
+    teacher, imdb, n, alone = loop_setup(a, faces)
+    read = lambda paths: [files[int(p)] for p in paths]                                        # noqa: E731
+    print("buildImdb loop, %s, batch 128, %d frames" % (a.teacher, n))
+    print("    FrozenTeacher.logits alone (prepared faces)   %9.1f img/s  = %.3f ms per batch" % (alone, 128 / alone * 1e3))
+    rates = {}
+    srcs = [("device JPEG decode, unsplit", dict(read=read)), ("device JPEG decode, split=%d" % best, dict(read=read, split=best))]
+    if have_pil:
+        srcs.append(("PIL on 10 threads", dict(frames=pil_frames_fn(files))))
+    for label, src in srcs:
+        fe.buildImdb(teacher, imdb, batchSize=128, **src)
+        for rep in range(2):
+            r = loop_rate(teacher, imdb, n, **src)
+            rates[label] = max(r, rates.get(label, 0.0))
+            print("    %-45s %9.1f img/s  (%+.1f %% vs alone)" % (label, r, 100 * (r / alone - 1)))
+    keys = list(rates)
+    print("    split=%d against the unsplit device decode: %.2f x" % (best, rates[keys[1]] / rates[keys[0]]))
+    if have_pil:
+        print("    split=%d against the PIL-fed loop:           %.2f x" % (best, rates[keys[1]] / rates[keys[2]]))
+
+
+def pil_frames_fn(files):
+    """frames(paths, device) for buildImdb: PIL on 10 host threads, uploaded from pinned memory"""
+    from PIL import Image
+    pool = ThreadPoolExecutor(10)
+    dec = lambda b: np.asarray(Image.open(io.BytesIO(b)).convert("RGB"))                       # noqa: E731
+
+    def pil_frames(paths, device):
+        a8 = np.stack(list(pool.map(dec, [files[int(p)] for p in paths])), 0)                  # n x H x W x 3
+        t = torch.from_numpy(a8).pin_memory().to(device, non_blocking=True)
+        return t.to(torch.float32).permute(0, 3, 2, 1).contiguous().permute(3, 2, 1, 0)         # MATLAB layout
+    return pil_frames
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--teacher", default="senet50-ferplus")
     ap.add_argument("--batches", type=int, default=12)
     ap.add_argument("--reps", type=int, default=10)
+    ap.add_argument("--split", action="store_true", help="the table of the segment-parallel entropy decode")
     a = ap.parse_args()
     dev = torch.device("cuda", 0)
     torch.cuda.set_device(0)
@@ -101,6 +186,8 @@ def main():
     print("128 files, %s, %.1f kB on average" % ("256 x 256 4:2:0 quality 90 (PIL)" if have_pil else
                                                   "the golden files repeated (PIL is not importable)",
                                                   sum(map(len, files)) / 128e3))
+    if a.split:
+        return split_table(a, L, files, have_pil)
     full = lambda: vl.imreadjpeg(files, resize=(224, 224), crop_size=1 / 1.6, average_image=fe.AVERAGE_IMAGE)   # noqa: E731
     full()
     torch.cuda.synchronize()
@@ -125,21 +212,7 @@ def main():
         for rep in range(2):
             print("    10 threads %9.1f img/s    16 threads %9.1f img/s" % (pil_rate(files, 10), pil_rate(files, 16)))
     # ---- (c) the loop ------------------------------------------------------------------------------------------------
-    n = 128 * a.batches
-    images = {"name": ["id%05d/v/1.wav" % i for i in range(1, n // 32 + 1)], "id": np.arange(1, n // 32 + 1),
-              "set": np.ones(n // 32, int), "numSamples": np.full(n // 32, 8 * 16000),
-              "denseFrames": ["%d" % (i % 128) for i in range(n)], "denseFramesWavIds": np.arange(n) // 32 + 1}
-    imdb = fe.EmoVoxImdb(images)
-    net = zoo.ferPlusZoo(a.teacher)
-    zoo.strip_losses(net)
-    net.mode = "test"
-    net.move("gpu")
-    teacher = zoo.FrozenTeacher(net, lanes=2)
-    teacher.imageSize, teacher.averageImage = (224, 224), fe.AVERAGE_IMAGE
-    faces = full()
-    for _ in range(a.batches):
-        teacher.logits(faces)
-    alone = max(128 / timeit(lambda: teacher.logits(faces), a.batches) for _ in range(3))
+    teacher, imdb, n, alone = loop_setup(a, full())
     read = lambda paths: [files[int(p)] for p in paths]                                        # noqa: E731
     imgs = vl.imreadjpeg(files)
     uniform = len({tuple(i.shape) for i in imgs}) == 1
@@ -152,19 +225,11 @@ def main():
         r = max(loop_rate(teacher, imdb, n, frames=prepared) for _ in range(3))
         print("    buildImdb loop, prepared decoded frames       %9.1f img/s  (%+.1f %% vs alone)" % (r, 100 * (r / alone - 1)))
     if have_pil and uniform:
-        from PIL import Image
-        pool = ThreadPoolExecutor(10)
-        dec = lambda b: np.asarray(Image.open(io.BytesIO(b)).convert("RGB"))                   # noqa: E731
-
-        def pil_frames(paths, device):
-            a8 = np.stack(list(pool.map(dec, read(paths))), 0)                                 # n x H x W x 3
-            t = torch.from_numpy(a8).pin_memory().to(device, non_blocking=True)
-            return t.to(torch.float32).permute(0, 3, 2, 1).contiguous().permute(3, 2, 1, 0)             # MATLAB layout
+        pil_frames = pil_frames_fn(files)
         fe.buildImdb(teacher, imdb, pil_frames, batchSize=128)
         for rep in range(2):
             r = loop_rate(teacher, imdb, n, frames=pil_frames)
             print("    buildImdb loop, PIL on 10 threads             %9.1f img/s  (%+.1f %% vs alone)" % (r, 100 * (r / alone - 1)))
-        pool.shutdown()
     fe.buildImdb(teacher, imdb, read=read, batchSize=128)
     for rep in range(2):
         r = loop_rate(teacher, imdb, n, read=read)
