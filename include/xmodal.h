@@ -57,7 +57,7 @@ enum { XM_FUSE_RELU = 1, XM_BN_BATCH_MOMENTS = 2, XM_FUSE_SIGMOID = 4 };
 
 /* ABI revision: 100 = round 1; 101 = xm_nnbnorm_relu_pool_backward gained `y_pool`, exchange entry points return
  * XM_EINVAL without a communicator; 102 = + xm_nnconv_forward_moments, xm_nnbnorm_backward_dxsum, xm_nnconv_forward_gated;
- * 103 = + xm_nnpool_global_avg_backward_accum; 104 = + xm_nnconv_backward_filter_bnrelupool, xm_nndropout_forward / _apply, xm_resample, xm_se_tail_backward_reduce / _apply, xm_se_squeeze_bn, xm_scale_axpy_bn; 105 = + xm_set_exec_hint / xm_get_exec_hint; 106 = + xm_nnconv_bnorm_relu_pool_forward, xm_stem_gram, xm_stem_gram_moments, xm_nnconv_backward_filter_bnrelupool_gram; 107 = + xm_nnaffinegrid / _backward, xm_nnbilinearsampler / _backward, xm_ferplus_batch; 108 = + XM_AGG_PEAK, xm_mnrfit, xm_mnrval; 109 = + xm_roc, xm_roc_launches, xm_label_hist; 110 = + xm_group_rows, xm_gather_rows, xm_scatter_rows, xm_track_peaks; 111 = + xm_wav_batch; 112 = + xm_spec_bucket_batch; 113 = + xm_jpeg_plan, xm_jpeg_decode_batch; 114 = + xm_wav_plan, xm_wav_decode_batch; 115 = + xm_jpeg_decode_batch_split, xm_jpeg_split_geometry (additions never change the revision's meaning for older bindings).  A binding checks xm_version() >= the revision it was written against. */
+ * 103 = + xm_nnpool_global_avg_backward_accum; 104 = + xm_nnconv_backward_filter_bnrelupool, xm_nndropout_forward / _apply, xm_resample, xm_se_tail_backward_reduce / _apply, xm_se_squeeze_bn, xm_scale_axpy_bn; 105 = + xm_set_exec_hint / xm_get_exec_hint; 106 = + xm_nnconv_bnorm_relu_pool_forward, xm_stem_gram, xm_stem_gram_moments, xm_nnconv_backward_filter_bnrelupool_gram; 107 = + xm_nnaffinegrid / _backward, xm_nnbilinearsampler / _backward, xm_ferplus_batch; 108 = + XM_AGG_PEAK, xm_mnrfit, xm_mnrval; 109 = + xm_roc, xm_roc_launches, xm_label_hist; 110 = + xm_group_rows, xm_gather_rows, xm_scatter_rows, xm_track_peaks; 111 = + xm_wav_batch; 112 = + xm_spec_bucket_batch; 113 = + xm_jpeg_plan, xm_jpeg_decode_batch; 114 = + xm_wav_plan, xm_wav_decode_batch; 115 = + xm_jpeg_decode_batch_split, xm_jpeg_split_geometry; 116 = + xm_pixcsv_plan, xm_pixcsv_decode_batch, xm_pixcsv_geometry (additions never change the revision's meaning for older bindings).  A binding checks xm_version() >= the revision it was written against. */
 int xm_version(void);
 const char *xm_last_error(void);
 /* Device memory for hosts that have no device-array type of their own (MATLAB's gpuArray is CUDA-only: on an
@@ -754,6 +754,54 @@ int xm_wav_plan(const unsigned char *bytes, const long long *offsets, int N, con
                 long long out_base, long long *desc, long long *sizes);
 int xm_wav_decode_batch(const unsigned char *bytes, long long nbytes, const long long *desc, int N, float *out,
                         long long out_floats, void *stream);
+
+/* The pixel column of the FER2013 CSV, decoded on the device into the image array of the FER+ imdb (ABI 116): what
+ * imdb = getFerPlusImdb(opts.dataDir) (ferplus_baselines.m:103-110) reads before getBatchFerPlus gathers
+ * imdb.images.data(:,:,:,batch) (:181), and the `dataDir` of benchmark_ferplus_models.m:15-17,46-54 ("the FER2013 and
+ * FER2013+ datasets files (in csv format)").  A row of fer2013.csv is `emotion,pixels,Usage`; `pixels` holds the 48 x 48
+ * image row-major as 2304 decimal numbers separated by blanks.  There is no host parse of the numbers.
+ *
+ * xm_pixcsv_plan: host only, no device call (usable without a GPU).  Finds the rows and their pixel fields.
+ *   An optional UTF-8 byte order mark is skipped.  A line ends at LF or CRLF; a last line without a newline is a row;
+ *   empty lines are skipped (they count in the line numbers).  Fields split at commas outside double quotes; a quote
+ *   still open at the end of its line is an error.  If the first byte of the first non-empty line is not a digit the
+ *   line is a header and the columns are found by name (one pair of enclosing quotes and blanks around the name are
+ *   dropped): `pixels` is required, `emotion` and `Usage` are optional, other columns are ignored.  Without a header the
+ *   columns are emotion,pixels,Usage.  A row needs at least as many fields as the header (3 without one).
+ *   desc     N rows of XM_PIX_DESC int64: 0, 1 byte range of the pixel field in `bytes`, one pair of enclosing quotes
+ *            stripped; 2 `emotion` as an integer (up to nine digits), -1 if the column or the value is absent or is not
+ *            one; 3 usage code: 0 Training, 1 PublicTest, 2 PrivateTest, -1 anything else or no column; 4 1-based line
+ *            number; 5 output image index, preset to the row's ordinal -- the caller may overwrite it, a negative value
+ *            means "skip this row"; 6, 7 zero.  desc == NULL only counts (max_rows is then not looked at).
+ *   sizes    XM_PIX_SIZES int64: the row count, the longest pixel field in bytes
+ *   XM_EINVAL names the line: an unterminated quote, a row with fewer fields than the header, a header without a `pixels`
+ *   column, more rows than max_rows.  XM_EINVAL: NULL sizes, NULL bytes with nbytes > 0, negative arguments.
+ *
+ * xm_pixcsv_decode_batch: device, ONE launch whatever N, the field lengths and their alignments are; no atomics, no
+ * workspace, no tuning entries, no synchronisation.  bytes (16-byte aligned, allocated up to the next multiple of 16
+ * past nbytes) holds the file or a part of it, desc (device, 8-byte aligned) the plan's rows with byte ranges relative
+ * to `bytes`.  The k-th number of row i's field is written as a float at out + desc[i][5] * H * W + p, where
+ * p = (k mod W) * H + k div W when transpose is 1 (the MATLAB H x W array of a row-major image) and p = k when it is 0.
+ * Every float of every image that is not skipped is written exactly once; positions the field has no number for get 0;
+ * numbers past H * W are counted and not written; nothing is written outside [0, out_floats).  Every byte read is
+ * clamped to the field's range, itself clamped to [0, nbytes), by the indexing itself.
+ *   A number is a maximal run of digits; every other byte separates.  status (device) is N x 2 int32: the count of
+ *   numbers found and a flag word: XM_PIX_BADCHAR a byte that is not a digit, a space or a tab (it separates like a
+ *   blank); XM_PIX_RANGE a run of more than three digits or a value above 255 -- that pixel is written as 255;
+ *   XM_PIX_COUNT count != H * W; XM_PIX_NOFIT the image of the row's output index does not lie inside out_floats: no
+ *   pixel of it is written and its count is 0 (the descriptor is device memory, so the kernel and not this entry point
+ *   sees the index; vl.pixcsv_decode checks its host copy before the launch and raises).  Skipped rows get (0, 0).
+ * N == 0: XM_OK.  XM_EINVAL: negative arguments; a transpose other than 0 / 1; with N > 0: NULL or misaligned pointers,
+ * H * W <= 0, out_floats < H * W.
+ *
+ * xm_pixcsv_geometry: host only.  bytes_per_pass: a block walks a field in passes of that many bytes, starting at the
+ * 16-byte boundary at or below the field's first byte, 16 bytes per thread; launches: what one decode call enqueues. */
+enum { XM_PIX_DESC = 8, XM_PIX_SIZES = 2 };
+enum { XM_PIX_BADCHAR = 1, XM_PIX_RANGE = 2, XM_PIX_COUNT = 4, XM_PIX_NOFIT = 8 };
+int xm_pixcsv_plan(const unsigned char *bytes, long long nbytes, long long *desc, long long max_rows, long long *sizes);
+int xm_pixcsv_decode_batch(const unsigned char *bytes, long long nbytes, const long long *desc, int N, int H, int W,
+                           int transpose, float *out, long long out_floats, int *status, void *stream);
+int xm_pixcsv_geometry(int *bytes_per_pass, int *launches);
 
 #ifdef __cplusplus
 }

@@ -134,6 +134,9 @@ SIGNATURES = {
     "xm_jpeg_split_geometry": [C.POINTER(C.c_int), C.POINTER(C.c_int)],
     "xm_wav_plan": [_vp, _vp, _i, _vp, _i, C.c_longlong, _vp, _vp],
     "xm_wav_decode_batch": [c_fp, C.c_longlong, c_fp, _i, c_fp, C.c_longlong, _vp],
+    "xm_pixcsv_plan": [_vp, C.c_longlong, _vp, C.c_longlong, _vp],
+    "xm_pixcsv_decode_batch": [c_fp, C.c_longlong, c_fp, _i, _i, _i, _i, c_fp, C.c_longlong, c_fp, _vp],
+    "xm_pixcsv_geometry": [C.POINTER(C.c_int), C.POINTER(C.c_int)],
 }
 _RESTYPES = {"xm_get_exec_hint": C.c_uint, "xm_last_error": C.c_char_p, "xm_workspace_bytes": C.c_size_t,
              "xm_workspace_generation": C.c_ulonglong}

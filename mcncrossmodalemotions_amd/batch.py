@@ -20,8 +20,11 @@ shapes the tensors the hot path consumes, fed from seeded synthetic sources:
     dense face frames            fetch_emovoxceleb_imdb.m:127,196-285 -> SyntheticDenseFrames (lister, find, decoded frames)
     FER+ batch (getBatchFerPlus) ferplus_baselines.m:153-268        -> HIP xm_ferplus_batch (grey -> flip -> x3 minus
                                                                        averageImage -> affine grid -> bilinear sampler)
+    FER+ imdb (getFerPlusImdb)   ferplus_baselines.m:103-110        -> FerPlusImdb: fer2013.csv's pixel column parsed on the
+                                                                       device (vl.pixcsv_decode, xm_pixcsv_decode_batch)
 """
 import math
+import os
 
 import numpy as np
 import torch
@@ -690,6 +693,130 @@ class SyntheticFerPlusImdb:
             hard = torch.from_numpy(self.images["hardLabels"].reshape(-1).astype(np.float32)).to(device)
             self._dev[key] = (data, probs, hard)
         return self._dev[key]
+
+
+class FerPlusImdb:
+    """The FER+ imdb built by getFerPlusImdb from fer2013.csv and fer2013new.csv.  The fields the reference reads
+    (ferplus_baselines.m:139,167-181): images.data (H x W x 1 x N, a DEVICE tensor in MATLAB layout -- the images are
+    never on the host), images.votes (N x 10), images.hardLabels (1 x N, 1-based first argmax over the eight
+    emotions, as SyntheticFerPlusImdb), images.set (N: 1 / 2 / 3 from Training / PublicTest / PrivateTest),
+    meta.classes; and two more: images.ferLabels (the `emotion` column of fer2013.csv) and images.row (the CSV line of
+    every kept image)."""
+
+    def __init__(self, data, votes, sets, ferLabels, rows):
+        N = len(votes)
+        self.images = {"data": data, "votes": votes, "set": sets,
+                       "hardLabels": (votes[:, :8].argmax(1) + 1).reshape(1, N).astype(np.float64),
+                       "ferLabels": ferLabels, "row": rows}
+        self.meta = {"classes": list(FERPLUS_CLASSES)}
+        self._dev = {}
+
+    @property
+    def set(self):
+        return self.images["set"]
+
+    def device_arrays(self, numClasses, device):
+        """the contract of SyntheticFerPlusImdb.device_arrays: (images N x 1 x W x H, vote distributions N x numClasses,
+        hard labels N), made once per (numClasses, device).  The images are the storage of images.data itself."""
+        key = (int(numClasses), str(device))
+        if key not in self._dev:
+            data = self.images["data"].permute(3, 2, 1, 0)
+            assert data.is_contiguous()
+            data = data.to(device)
+            v = self.images["votes"][:, :numClasses]
+            with np.errstate(invalid="ignore", divide="ignore"):
+                probs = torch.from_numpy((v / v.sum(1, keepdims=True)).astype(np.float32)).to(device)   # :167-168
+            hard = torch.from_numpy(self.images["hardLabels"].reshape(-1).astype(np.float32)).to(device)
+            self._dev[key] = (data, probs, hard)
+        return self._dev[key]
+
+
+FERPLUS_SETS = ("Training", "PublicTest", "PrivateTest")
+
+
+def readFerPlusVotes(path):
+    """fer2013new.csv on the host (36 k short rows, the csv module): header `Usage,Image name,neutral,...,NF` with the ten
+    vote columns in the FERPLUS_CLASSES order.  Returns (usage: list of str, names: list of str, votes: n x 10 float64,
+    lines: the CSV line of every row)."""
+    import csv
+    usage, names, votes, lines = [], [], [], []
+    with open(path, newline="", encoding="utf-8-sig") as fh:
+        reader = csv.reader(fh)
+        header = None
+        for rec in reader:
+            if not rec or not any(f.strip() for f in rec):
+                continue
+            if header is None:
+                header = [f.strip() for f in rec]
+                want = ["Usage", "Image name"] + FERPLUS_CLASSES
+                if header[:12] != want:
+                    raise ValueError("%s: line %d: the header must be %s" % (path, reader.line_num, ",".join(want)))
+                continue
+            if len(rec) < 12:
+                raise ValueError("%s: line %d: %d fields, the header has 12" % (path, reader.line_num, len(rec)))
+            try:
+                votes.append([float(f) for f in rec[2:12]])
+            except ValueError:
+                raise ValueError("%s: line %d: a vote is not a number" % (path, reader.line_num)) from None
+            usage.append(rec[0].strip())
+            names.append(rec[1].strip())
+            lines.append(reader.line_num)
+    if header is None:
+        raise ValueError("%s: no header" % path)
+    return usage, names, np.array(votes, np.float64).reshape(len(votes), 10), np.array(lines, np.int64)
+
+
+def ferPlusKeep(names, votes, dataType="CNTK"):
+    """Which rows of the FER2013 / FER+ pair become images.  A PROJECT RULE, not the reference's: getFerPlusImdb is not
+    part of the reference.  Rows with an empty `Image name` (those FER+ removed from FER2013) are dropped; for 'CNTK' and
+    'clean' -- the eight-class problems -- rows without a vote among the eight emotions are dropped too, because
+    votes ./ sum(votes, 2) of ferplus_baselines.m:168-169 would be NaN for them.  'full' keeps those."""
+    ferplus_num_classes(dataType)
+    keep = np.array([bool(n) for n in names], bool)
+    if dataType in ("CNTK", "clean"):
+        keep &= np.asarray(votes)[:, :8].sum(1) > 0
+    return keep
+
+
+def ferPlusPlan(dataDir, dataType="CNTK"):
+    """The host side of getFerPlusImdb (no device call): reads the vote file, plans the pixel file, checks that the two
+    correspond and applies ferPlusKeep.  Returns dict(data: the pixel file's bytes, plan: vl.pixcsv_plan's with the
+    output index of every kept row set and -1 for the others, keep, votes, sets, ferLabels, row -- the last four for the
+    kept rows only)."""
+    pix_path, vote_path = os.path.join(dataDir, "fer2013.csv"), os.path.join(dataDir, "fer2013new.csv")
+    usage, names, votes, vlines = readFerPlusVotes(vote_path)
+    data = np.fromfile(pix_path, np.uint8)
+    plan = vl.pixcsv_plan(data)
+    rows = plan["rows"]
+    if plan["N"] != len(usage):
+        raise ValueError("%s has %d rows and %s has %d: they must correspond 1 : 1" % (pix_path, plan["N"], vote_path, len(usage)))
+    sets = np.array([FERPLUS_SETS.index(u) + 1 if u in FERPLUS_SETS else 0 for u in usage], int)
+    for i in np.nonzero((sets == 0) | ((rows[:, 3] >= 0) & (rows[:, 3] != sets - 1)))[0][:1]:
+        theirs = FERPLUS_SETS[rows[i, 3]] if rows[i, 3] >= 0 else "no known Usage"
+        raise ValueError("%s: line %d: Usage %r, but %s has %s on its line %d"
+                         % (vote_path, vlines[i], usage[i], pix_path, theirs, rows[i, 4]))
+    keep = ferPlusKeep(names, votes, dataType)
+    rows = rows.copy()
+    rows[:, 5] = np.where(keep, np.cumsum(keep) - 1, -1)
+    return dict(data=data, plan=dict(plan, rows=rows), keep=keep, votes=votes[keep], sets=sets[keep],
+                ferLabels=rows[keep, 2].astype(np.float64), row=rows[keep, 4].copy())
+
+
+def getFerPlusImdb(dataDir, dataType="CNTK", *, chunk_bytes=64 << 20, device=None, size=(48, 48)):
+    """imdb = getFerPlusImdb(opts.dataDir) (ferplus_baselines.m:106; the function itself is not in the reference): reads
+    fer2013.csv (emotion,pixels,Usage -- 35,887 rows of 2,304 numbers, about 290 MB of text) and fer2013new.csv (the
+    FER+ votes, row for row) from dataDir and returns a FerPlusImdb.  The vote file is read on the host; the pixel file
+    is planned on the host (where the fields lie, the two small columns) and its numbers are parsed on the device in
+    chunks of about chunk_bytes cut at row boundaries, straight into the layout getBatchFerPlus gathers from -- the
+    images are never on the host.  Rows kept: ferPlusKeep.  ValueError: a different row count in the two files, or a
+    Usage that is unknown or disagrees with the pixel file's, with the line; a pixel field that is not size[0] * size[1]
+    numbers in 0 .. 255 raises _lib.XmError with the line."""
+    h = ferPlusPlan(dataDir, dataType)
+    N, (H, W) = len(h["votes"]), size
+    device = device or torch.device("cuda", torch.cuda.current_device())
+    out = torch.empty(N * H * W, dtype=torch.float32, device=device)
+    images, _ = vl.pixcsv_decode(h["data"], h["plan"], size=(H, W), transpose=True, out=out, chunk_bytes=chunk_bytes)
+    return FerPlusImdb(images, h["votes"], h["sets"], h["ferLabels"], h["row"])
 
 
 def zoomOut(zoomScale, minYX):

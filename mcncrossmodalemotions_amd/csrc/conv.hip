@@ -2226,6 +2226,10 @@ int xm_prof_kernel_name(int key, char *buf, int len) {
     snprintf(buf, len, "wav_decode_kernel");
     return XM_OK;
   }
+  if (kind == 23) {   // pixcsv.hip
+    snprintf(buf, len, "pixcsv_decode_kernel");
+    return XM_OK;
+  }
   if (kind == 3 || kind == 4) {
     const int v = key % 100;
     snprintf(buf, len, "%s<%s, %d>", kind == 3 ? "conv_halo_kernel" : "conv_halo_multi_kernel",

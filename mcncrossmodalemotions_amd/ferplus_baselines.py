@@ -5,9 +5,10 @@
 Same option names, defaults and flow as the reference (:59-80): name the experiment directory (buildExpDirName,
 :297-309), pick 8 or 10 classes from `dataType`, build the network with ferPlusZoo's training branch, optionally
 evaluate only (the set remapping of :120-136), bind getBatchFerPlus and call cnn_train_dag with batch 128 and the
-3 x 60-epoch learning-rate schedule.  What differs, because there is no FER+ data / MatConvNet here: the imdb is the
-seeded batch.SyntheticFerPlusImdb (getFerPlusImdb is not in the reference), the weights are synthetic, and `gpus` is the
-torchrun world as in run_distillation.  `evaluateOnly.fromCkpt` picks the checkpoint whose saved info has the lowest
+3 x 60-epoch learning-rate schedule.  What differs, because there is no MatConvNet here: the imdb comes from
+batch.getFerPlusImdb when `dataDir` holds fer2013.csv and fer2013new.csv (the function is not in the reference; its
+rules are written down there) and is the seeded batch.SyntheticFerPlusImdb otherwise, the weights are synthetic, and
+`gpus` is the torchrun world as in run_distillation.  `evaluateOnly.fromCkpt` picks the checkpoint whose saved info has the lowest
 validation classerror; unlike the external findBestEpoch it prunes no file.  Extensions are keyword-only.
 """
 import copy
@@ -19,6 +20,28 @@ from . import batch as xbatch
 from . import train, zoo
 
 LEARNING_RATE = np.concatenate([np.full(60, 0.01), np.full(60, 0.001), np.full(60, 0.0001)])   # :77-79
+
+
+PRETRAINED = ("resnet50-ferplus", "senet50-ferplus")      # ferPlusZoo.m:60-63
+
+
+def pretrained_heads(dag, lossType):
+    """The published FER+ teachers are checkpoints of this very training and are loaded with its heads: 'loss' ->
+    objective and 'classerror' -> classerror (benchmark_ferplus_models.m:55-56 reads val.classerror).  The synthetic
+    stand-ins of zoo.ferPlusZoo carry the heads of the architecture they are built from (softmaxlog / top1error on
+    'label'); they are replaced by what configureForClassification (ferPlusZoo.m:239-263) attaches for `lossType`."""
+    from . import dagnn
+    zoo.strip_losses(dag)
+    if lossType == "softmaxlog":
+        layer, hard = dagnn.Loss("softmaxlog"), "label"
+    elif lossType == "distributions":
+        layer, hard = dagnn.SoftmaxCELoss(temperature=1, logitTargets=False), "hardlabel"
+    else:
+        raise ValueError("unrecognised loss: %s" % lossType)
+    dag.addLayer("loss", layer, ["prediction", "label"], "objective")
+    dag.addLayer("classerror", dagnn.Loss("classerror"), ["prediction", hard], "classerror")
+    dag._flat = None
+    return dag
 
 
 def buildExpDirName(modelName="senet50_ft-dag", lossType="distributions", dataType="CNTK", dropoutRate=0.5,
@@ -63,8 +86,9 @@ def ferplus_baselines(dev=False, useBnorm=1, dataAug=True, dataType="CNTK", loss
                       numImages=512, verbose=False):
     """Options as in ferplus_baselines.m:59-80 (`cont` is opts.train.continue, `gpus` / `batchSize` /
     `learningRate` are opts.train.*; `numEpochs` is cnn_train_dag's default, 300, with the last rate held after
-    epoch 180).  `evaluateOnly` = {'subset': '' | 'val' | 'test', 'fromCkpt': bool}.  `dataDir` would hold the FER2013
-    CSVs; it is not read.  Extensions (keyword-only): `imdb` (a prepared imdb, default a SyntheticFerPlusImdb of
+    epoch 180).  `evaluateOnly` = {'subset': '' | 'val' | 'test', 'fromCkpt': bool}.  `dataDir` holds the FER2013 and
+    FER+ CSVs (fer2013.csv, fer2013new.csv): when both are there and no `imdb` is given, getFerPlusImdb reads them.
+    Extensions (keyword-only): `imdb` (a prepared imdb; without it and without the CSVs a SyntheticFerPlusImdb of
     `numImages` images), `expRoot` (root of the experiment directories), `widthMult` / `blocks` (narrow networks for
     tests), `seed` (synthetic weights, imdb and batch draws)."""
     ev = {"subset": "", "fromCkpt": False}
@@ -76,8 +100,13 @@ def ferplus_baselines(dev=False, useBnorm=1, dataAug=True, dataType="CNTK", loss
     dag = zoo.ferPlusZoo(modelName, seed=100 + seed, width_mult=widthMult, blocks=blocks, useBnorm=useBnorm,
                          finetuneLR=finetuneLR, dropoutRate=dropoutRate, lossType=lossType,
                          numOutputs=numOutputs)                                          # :95-100
-    if imdb is None:
-        imdb = xbatch.SyntheticFerPlusImdb(num_images=numImages, seed=seed)             # :103-110
+    if modelName in PRETRAINED:
+        pretrained_heads(dag, lossType)
+    if imdb is None:                                                                    # :103-110
+        if all(os.path.isfile(os.path.join(dataDir, f)) for f in ("fer2013.csv", "fer2013new.csv")):
+            imdb = xbatch.getFerPlusImdb(dataDir, dataType)
+        else:
+            imdb = xbatch.SyntheticFerPlusImdb(num_images=numImages, seed=seed)
     sets = np.array(imdb.images["set"], copy=True)
     if dev:                                                                             # :112-118
         sample = 1000

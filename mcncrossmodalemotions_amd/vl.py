@@ -1583,3 +1583,135 @@ def audioread(files, ranges=None, *, channel=None, out=None, out_base=0, device=
                                                 _ptr(out), out.numel(), _stream()))
     res = (out, offsets)
     return res + (_wav_info(rows),) if return_info else res
+
+
+# --------------------------------------------------------------------------------------------
+# The pixel column of the FER2013 CSV (getFerPlusImdb(opts.dataDir), ferplus_baselines.m:103-110): parsed on the device
+# --------------------------------------------------------------------------------------------
+PIX_DESC = 8                                                                    # include/xmodal.h XM_PIX_*
+PIX_BADCHAR, PIX_RANGE, PIX_COUNT, PIX_NOFIT = 1, 2, 4, 8
+PIX_USAGE = ("Training", "PublicTest", "PrivateTest")
+
+
+def _pix_bytes(data):
+    """bytes-like, a uint8 numpy array or a path -> a contiguous uint8 numpy array (no copy where there is none to make)"""
+    if isinstance(data, np.ndarray):
+        if data.dtype != np.uint8 or data.ndim != 1:
+            raise TypeError("pixcsv: expected a 1-D uint8 array")
+        return np.ascontiguousarray(data)
+    if isinstance(data, (bytes, bytearray, memoryview)):
+        return np.frombuffer(data, np.uint8)
+    return np.fromfile(data, np.uint8)
+
+
+def pixcsv_geometry():
+    """(bytes per pass, launches) of the pixel-field decode (xm_pixcsv_geometry; no device call)"""
+    bpp, launches = C.c_int(0), C.c_int(0)
+    _lib.check(_L().xm_pixcsv_geometry(C.byref(bpp), C.byref(launches)))
+    return bpp.value, launches.value
+
+
+def pixcsv_plan(data):
+    """The host side of pixcsv_decode (xm_pixcsv_plan; touches no device): `data` is the CSV as bytes, a uint8 array or a
+    path.  Returns plan = dict(N, nbytes, rows: N x 8 int64 -- byte range of the pixel field, emotion, usage code (index
+    into PIX_USAGE or -1), 1-based line, output image index (preset to the row's ordinal; overwrite it to place or, with
+    -1, skip a row), two zeros --, longest: the longest pixel field in bytes, data: the uint8 array).  A malformed file
+    raises _lib.XmError naming the line."""
+    buf = _pix_bytes(data)
+    sizes = np.zeros(2, np.int64)
+    p = C.c_void_p(buf.ctypes.data) if buf.size else None
+    _lib.check(_L().xm_pixcsv_plan(p, buf.size, None, 0, C.c_void_p(sizes.ctypes.data)))
+    N = int(sizes[0])
+    rows = np.zeros((N, PIX_DESC), np.int64)
+    _lib.check(_L().xm_pixcsv_plan(p, buf.size, C.c_void_p(rows.ctypes.data), N, C.c_void_p(sizes.ctypes.data)))
+    return dict(N=N, nbytes=int(buf.size), rows=rows, longest=int(sizes[1]), data=buf)
+
+
+def _pix_chunks(rows, chunk_bytes):
+    """consecutive row ranges [a, b) whose bytes -- from the 16-byte boundary at or below the first field to the end of
+    the last -- stay within chunk_bytes where a single row allows it.  Rows must ascend in the file."""
+    N = len(rows)
+    if chunk_bytes is None:
+        return [(0, N)] if N else []
+    cuts, a = [], 0
+    while a < N:
+        start = int(rows[a, 0]) & ~15
+        b = a + 1
+        while b < N and int(rows[b, 1]) - start <= chunk_bytes:
+            b += 1
+        cuts.append((a, b))
+        a = b
+    return cuts
+
+
+def pixcsv_decode(data, plan, size=(48, 48), transpose=True, out=None, image_base=0, *, strict=True, chunk_bytes=None,
+                  device=None):
+    """Decodes the pixel fields of a planned CSV on the device (xm_pixcsv_decode_batch): the row whose output index is j
+    becomes image image_base + j.  Returns (images, status): `images` the H x W x 1 x M device view (MATLAB layout) of
+    `out` -- a contiguous 1-D float32 device tensor of M * H * W floats, allocated (and zeroed, so that an image no row
+    names is defined) when not given, M then being image_base + 1 + the largest index --, `status` the N x 2 int32 host
+    array [count of numbers, XM_PIX_* flags].  transpose=True reads a field as a row-major image (FER2013) and stores
+    the MATLAB H x W array; False stores the numbers in file order.  Rows with a negative index are skipped.
+    chunk_bytes cuts the upload at row boundaries: one pinned staging buffer, one upload and one launch per chunk,
+    whatever the number of rows in it; the images never exist on the host.  A row with a status flag raises
+    _lib.XmError naming the CSV line unless strict=False.  An index whose image does not fit `out` raises before
+    anything is launched."""
+    if not torch.cuda.is_available():
+        raise RuntimeError("pixcsv_decode needs a GPU; this build has no CPU path")
+    buf = _pix_bytes(data)
+    H, W = _pair(size, "SIZE")
+    if H * W <= 0:
+        raise ValueError("pixcsv_decode: SIZE must be positive (got %r)" % (size,))
+    rows = np.array(plan["rows"], np.int64, copy=True).reshape(-1, PIX_DESC)
+    N, image_base = len(rows), int(image_base)
+    if image_base < 0:
+        raise ValueError("pixcsv_decode: image_base must not be negative")
+    if N and (rows[:, 0].min() < 0 or rows[:, 1].max() > buf.size or (rows[:, 1] < rows[:, 0]).any()):
+        raise ValueError("pixcsv_decode: the plan's byte ranges do not lie inside DATA")
+    live = rows[:, 5] >= 0
+    rows[live, 5] += image_base
+    need = int(rows[live, 5].max()) + 1 if live.any() else image_base
+    if out is None:
+        device = device or _dev()
+        out = torch.zeros(need * H * W, dtype=torch.float32, device=device)
+    else:
+        if not isinstance(out, torch.Tensor) or out.dtype != torch.float32 or out.dim() != 1 or not out.is_contiguous() or not out.is_cuda:
+            raise ValueError("pixcsv_decode: OUT must be a contiguous 1-D float32 device tensor")
+        device = out.device
+        if need * H * W > out.numel():
+            bad = int(np.nonzero(live & ((rows[:, 5] + 1) * H * W > out.numel()))[0][0])
+            raise _lib.XmError(1, "pixcsv_decode: line %d: image %d of %d x %d does not fit OUT of %d floats"
+                               % (rows[bad, 4], rows[bad, 5], H, W, out.numel()))
+    M = out.numel() // (H * W)
+    status = torch.zeros((N, 2), dtype=torch.int32, device=device)
+    up = lambda v: (int(v) + 15) & ~15
+    with torch.cuda.device(device):
+        for a, b in _pix_chunks(rows, chunk_bytes):
+            if not live[a:b].any():              # nothing but skipped rows: their status is (0, 0) already
+                continue
+            start, end = int(rows[a:b, 0].min()) & ~15, int(rows[a:b, 1].max())
+            nb = end - start
+            o_desc = up(nb + 1)
+            total = o_desc + 8 * PIX_DESC * (b - a)
+            host = torch.empty(total, dtype=torch.uint8, pin_memory=True)
+            stage = host.numpy()
+            stage[:nb] = buf[start:end]
+            stage[nb:o_desc] = 0
+            d = stage[o_desc:].view(np.int64).reshape(b - a, PIX_DESC)
+            d[:] = rows[a:b]
+            d[:, 0:2] -= start
+            dev = torch.empty(total, dtype=torch.uint8, device=device)
+            dev.copy_(host, non_blocking=True)
+            p = dev.data_ptr()
+            _lib.check(_L().xm_pixcsv_decode_batch(C.c_void_p(p), nb, C.c_void_p(p + o_desc), b - a, H, W, int(bool(transpose)),
+                                                   _ptr(out), out.numel(), C.c_void_p(status.data_ptr() + 8 * a), _stream()))
+    st = status.cpu().numpy()
+    if strict and N and st[:, 1].any():
+        i = int(np.nonzero(st[:, 1])[0][0])
+        f = int(st[i, 1])
+        what = [w for bit, w in ((PIX_BADCHAR, "a byte that is not a digit, a space or a tab"),
+                                 (PIX_RANGE, "a number above 255 or of more than three digits"),
+                                 (PIX_COUNT, "%d numbers where %d x %d = %d are expected" % (st[i, 0], H, W, H * W)),
+                                 (PIX_NOFIT, "an image index outside the output")) if f & bit]
+        raise _lib.XmError(1, "pixcsv_decode: line %d: %s (%d rows flagged)" % (rows[i, 4], "; ".join(what), int((st[:, 1] != 0).sum())))
+    return out[:M * H * W].view(M, 1, W, H).permute(3, 2, 1, 0), st
