@@ -9,8 +9,9 @@ ferplus_baselines evaluates the model twice with train.batchSize 32 -- evaluateO
 (PrivateTest) -- and valAcc / testAcc = 1 - val.classerror are cached and printed with the reference's text.  `dataDir`
 holds fer2013.csv and fer2013new.csv (:15-17); ferplus_baselines reads them through batch.getFerPlusImdb.
 
-THE ACCURACIES ARE MEANINGLESS: the weights are the seeded synthetic stand-ins of zoo.ferPlusZoo, as everywhere in this
-project -- the published teachers cannot be loaded.  What is mirrored is the flow, the data path and the cache.
+WITHOUT `modelDir` THE ACCURACIES ARE MEANINGLESS: the weights are then the seeded synthetic stand-ins of zoo.ferPlusZoo
+and what is mirrored is the flow, the data path and the cache.  With `modelDir` the published teachers are read from
+<modelDir>/<modelName>.mat (dagnn.load_mat); nobody has run that against the published figures yet.
 Extensions are keyword-only.
 """
 import json
@@ -23,9 +24,10 @@ PRETRAINED = (("resnet50-ferplus", "softmaxlog"), ("senet50-ferplus", "distribut
 
 
 def benchmark_ferplus_models(refresh=False, dataDir="data/datasets/fer2013+", benchmarkCacheDir="data/ferPlus/benchCache",
-                             *, imdb=None, widthMult=1.0, blocks=(3, 4, 6, 3), seed=0, verbose=True):
+                             *, imdb=None, widthMult=1.0, blocks=(3, 4, 6, 3), seed=0, verbose=True, modelDir=None):
     """Options as in benchmark_ferplus_models.m:22-25.  Extensions (keyword-only): `imdb` (a prepared imdb instead of
-    the CSVs of dataDir), `widthMult` / `blocks` (narrow networks for tests), `seed`, `verbose` (the printout).
+    the CSVs of dataDir), `widthMult` / `blocks` (narrow networks for tests), `seed`, `verbose` (the printout),
+    `modelDir` (the directory of resnet50-ferplus.mat / senet50-ferplus.mat: the published teachers are evaluated).
     Returns {modelName: {'valAcc': .., 'testAcc': ..}} -- the reference only prints."""
     say = (lambda *a: print(*a, end="", flush=True)) if verbose else (lambda *a: None)
     os.makedirs(benchmarkCacheDir, exist_ok=True)                                        # :27-29
@@ -39,7 +41,7 @@ def benchmark_ferplus_models(refresh=False, dataDir="data/datasets/fer2013+", be
                 stats = json.load(fh)
         else:
             commonArgs = dict(modelName=modelName, batchSize=32, lossType=lossType, dataDir=dataDir, imdb=imdb,
-                              widthMult=widthMult, blocks=blocks, seed=seed)             # :46-49
+                              widthMult=widthMult, blocks=blocks, seed=seed, modelDir=modelDir)   # :46-49
             say("evaluating %s on FER+...\n" % modelName)
             _, valInfo = ferplus_baselines(evaluateOnly={"subset": "val"}, **commonArgs)     # :51-52
             _, testInfo = ferplus_baselines(evaluateOnly={"subset": "test"}, **commonArgs)   # :53-54

@@ -459,7 +459,7 @@ class _LayerRec:
 
 class DagNN:
     """dagnn.DagNN subset: addLayer, removeLayer, renameVar, getVarIndex, getParamIndex,
-    getLayerIndex, getInputs, initParams, rebuild, move, eval, mode, vars, params, layers, meta."""
+    getLayerIndex, getInputs, initParams, rebuild, move, eval, mode, vars, params, layers, meta, loadobj, saveobj."""
 
     def __init__(self):
         self.layers = []
@@ -594,6 +594,18 @@ class DagNN:
         for name, v in self.vars.items():
             r.vars[name].precious = v.precious
         return r
+
+    # ---- model files (matfile.py) ------------------------------------------------------------
+    @staticmethod
+    def loadobj(s):
+        """net = dagnn.DagNN.loadobj(s): the struct of a MatConvNet model file (emoVoxZoo.m:44, ferPlusZoo.m:100) -> DagNN"""
+        from . import matfile
+        return matfile.loadobj(s)
+
+    def saveobj(self):
+        """s = net.saveobj(): the struct MatConvNet writes for this net, as scipy.io.savemat takes it"""
+        from . import matfile
+        return matfile.saveobj(self)
 
     def getLayerIndex(self, name):
         for i, l in enumerate(self.layers):
@@ -797,6 +809,18 @@ class DagNN:
         self._plan_key, self._plan_cache = key, steps
         self._plan_layers = [id(l) for l in self.layers]
         return steps
+
+
+def load_mat(path):
+    """net = load_mat(path): load(path); if isfield(net, 'net'), net = net.net; end; dagnn.DagNN.loadobj(net)"""
+    from . import matfile
+    return matfile.load_mat(path)
+
+
+def save_mat(net, path, wrap=None):
+    """save_mat(net, path): save(path, '-struct', 'net'); wrap='net' writes the checkpoint form (the struct in `net`)"""
+    from . import matfile
+    return matfile.save_mat(net, path, wrap)
 
 
 class FlatParams:

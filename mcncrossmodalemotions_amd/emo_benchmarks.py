@@ -116,7 +116,7 @@ def load_feats(path):
     return tracks, faceLogits
 
 
-def _compute_feats(modality, modelName, imdb, net, numSrcEmotions, rng, device):
+def _compute_feats(modality, modelName, imdb, net, numSrcEmotions, rng, device, modelDir=None):
     """compute_audio_feats / compute_visual_feats with the file I/O left out: one logit row per track (audio) or
     per face frame (visual)."""
     N = len(imdb.tracks["set"])
@@ -125,26 +125,27 @@ def _compute_feats(modality, modelName, imdb, net, numSrcEmotions, rng, device):
             logits = rng.standard_normal(N * numSrcEmotions).reshape((N, numSrcEmotions), order="F")
             logits = logits.astype(np.float32)
         else:
-            dag = net if net is not None else zoo.emoVoxZoo(modelName)
+            dag = net if net is not None else zoo.inference_student(modelName, modelDir)
             specs = [imdb.device_spec(i, device) for i in range(N)]
             logits = external.compute_audio_feats(dag, specs, numEmotions=numSrcEmotions, batch_by_bucket=True)
         return [logits[i:i + 1] for i in range(N)]
     if modelName == "random":
         raise ValueError("compute_visual_feats has no 'random' model")
-    dag = net if net is not None else zoo.ferPlusZoo(modelName)
+    dag = net if net is not None else zoo.ferPlusZoo(modelName, modelDir=modelDir)
     frames = [imdb.device_faces(i, device) for i in range(N)]
     return external.compute_visual_feats(dag, frames, numEmotions=numSrcEmotions)
 
 
 def run_cross_val(numFolds=10, aggregator="max", targetDataset="rml", numTargetEmotions=6, numSrcEmotions=8,
                   labelType="labels", useExstingVal=False, modality="visual", modelName="emovoxceleb-student", *,
-                  imdb=None, net=None, root="data", maxIter=100, tolX=1e-6, verbose=False):
+                  imdb=None, net=None, root="data", maxIter=100, tolX=1e-6, verbose=False, modelDir=None):
     """Options as in run_cross_val.m:44-52.  Returns (miniImdb, expDirs, valIdxSets): miniImdb = {'labels',
     'fusedLogits' (N x numSrcEmotions single), 'images': {'set'}}, one experiment directory per fold holding
     mnr-params.mat (`coefficients`, (numSrcEmotions + 1) x (numTargetEmotions - 1) double), 1-based validation indices.
     Extensions (keyword-only): `imdb` (default a SyntheticBenchmarkImdb of numTargetEmotions classes), `net` (the
     network to extract features with, default zoo.emoVoxZoo / zoo.ferPlusZoo(modelName); 'random' builds none),
-    `root` (vl_rootnn), `maxIter` / `tolX` (statset('mnrfit')), `verbose`."""
+    `root` (vl_rootnn), `maxIter` / `tolX` (statset('mnrfit')), `verbose`, `modelDir` (the zoo reads the model file from
+    there when no `net` is passed)."""
     rng = np.random.default_rng(0)                                                       # rng(0), :55
     if targetDataset not in TARGET_DATASETS:
         raise ValueError("unknown dataset %s" % targetDataset)
@@ -162,7 +163,7 @@ def run_cross_val(numFolds=10, aggregator="max", targetDataset="rml", numTargetE
                                                  val_fraction=0.5 if useExstingVal else 0.0)
         if device is None and modelName != "random":
             raise RuntimeError("computing features needs a GPU; this build has no CPU path")
-        feats = _compute_feats(modality, modelName, imdb, net, numSrcEmotions, rng, device)
+        feats = _compute_feats(modality, modelName, imdb, net, numSrcEmotions, rng, device, modelDir)
         save_feats(imdbPath, imdb.tracks, feats)
     elif verbose:
         print("found features at %s... skipping" % imdbPath, flush=True)
@@ -229,11 +230,13 @@ def _write_confmat(normed, confSum, labels, dataset, figDir, modelName):
 
 
 def emo_benchmarks(modality="audio", datasets=("rml", "enterface"), modelName="emovoxceleb-student",
-                   figDir="data/affine-figs-audio-splits", *, net=None, imdbs=None, root="data", verbose=True):
+                   figDir="data/affine-figs-audio-splits", *, net=None, imdbs=None, root="data", verbose=True,
+                   modelDir=None):
     """Options as in emo_benchmarks.m:36-40.  Returns {dataset: {'foldAccs', 'mean', 'std', 'confSum', 'normed',
     'labels' (canonical), 'adjustmentFactor', 'expDirs', 'valIdxSets', 'preds', 'confPath'}}.
     Extensions (keyword-only): `net` (a trained or reduced network instead of the zoo's), `imdbs` ({dataset: imdb},
-    default SyntheticBenchmarkImdb), `root` (vl_rootnn), `verbose` (the reference's printout)."""
+    default SyntheticBenchmarkImdb), `root` (vl_rootnn), `verbose` (the reference's printout), `modelDir` (as in
+    run_cross_val)."""
     if isinstance(datasets, str):
         datasets = [datasets]
     out = {}
@@ -247,7 +250,7 @@ def emo_benchmarks(modality="audio", datasets=("rml", "enterface"), modelName="e
         miniImdb, expDirs, valIdxSets = run_cross_val(
             modelName=modelName, targetDataset=dataset, numSrcEmotions=len(MODEL_EMO_LABELS),
             useExstingVal=useExstingVal, numFolds=numFolds, numTargetEmotions=numTargetEmotions, modality=modality,
-            imdb=(imdbs or {}).get(dataset), net=net, root=root, verbose=verbose)
+            imdb=(imdbs or {}).get(dataset), net=net, root=root, verbose=verbose, modelDir=modelDir)
         from scipy.io import loadmat
         coefs = [loadmat(os.path.join(e, "mnr-params.mat"))["coefficients"] for e in expDirs]   # :92-93
         device = torch.device("cuda", torch.cuda.current_device())

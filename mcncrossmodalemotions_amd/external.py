@@ -47,6 +47,12 @@ def test_getinput(spec):
     return n[:, s0:s0 + rsize], rsize
 
 
+def _student(dag, modelDir):
+    """compute_audio_feats.m:52 `dag = emoVoxZoo(opts.modelName)`: a model name instead of a network builds the zoo's (from
+    <modelDir>/<name>.mat when `modelDir` is given)"""
+    return zoo.inference_student(dag, modelDir) if isinstance(dag, str) else dag
+
+
 def _prepare(dag):
     names = [l.name for l in dag.layers if isinstance(l.block, dagnn.LossBase)]   # :98-103
     if names:
@@ -113,7 +119,7 @@ class _GraphedEval:
         return static_out.clone()
 
 
-def compute_audio_feats(dag, specs, numEmotions=8, batch_by_bucket=False, use_graphs=False):
+def compute_audio_feats(dag, specs, numEmotions=8, batch_by_bucket=False, use_graphs=False, *, modelDir=None):
     """logits = compute_audio_feats(dag, specs): one row of `numEmotions` logits per clip.
 
     specs: list of 512 x T spectrogram-magnitude device tensors (any T >= 100).
@@ -121,7 +127,9 @@ def compute_audio_feats(dag, specs, numEmotions=8, batch_by_bucket=False, use_gr
     minibatch instead of one launch chain per clip -- same logits (test-mode BN, samples independent),
     far fewer launches.
     use_graphs (extension): the forward of every (bucket, batch) shape is captured into a HIP graph once
-    and replayed -- same kernels, same results, no per-layer launch cost."""
+    and replayed -- same kernels, same results, no per-layer launch cost.
+    `dag` may be a model name, as upstream (:52): zoo.emoVoxZoo builds it, from `modelDir` when that is given."""
+    dag = _student(dag, modelDir)
     inp, ind1 = _prepare(dag)
     if ind1 is None:
         raise ValueError("the audio model has no pool6 layer")
@@ -189,13 +197,14 @@ def audio_feats_plan(lengths, offsets, fs=16000, Tw=25, Ts=10):
     return T, rsize, f0, groups
 
 
-def compute_audio_feats_wav(dag, wav, offsets, numEmotions=8, limit=float("inf"), maxBatch=64):
+def compute_audio_feats_wav(dag, wav, offsets, numEmotions=8, limit=float("inf"), maxBatch=64, *, modelDir=None):
     """logits = compute_audio_feats from the waveforms (compute_audio_feats.m:91-136,160-185): `wav` is the device bank
     of all clips back to back, `offsets` their first samples plus the bank's length (imdb.device_wav_bank).  The clips
     are planned on the host (audio_feats_plan); per bucket and chunk of `maxBatch` clips ONE vl.spec_bucket_batch call
     makes the normalised, cropped 512 x rsize x 1 x n input and ONE test-mode forward with pool6 resized follows.  The
     logits are read back once at the end.  `limit`: only the clips with id <= firstId + limit are processed (:91-93;
-    ids 1, 2, ...: the first limit + 1 clips)."""
+    ids 1, 2, ...: the first limit + 1 clips).  `dag` / `modelDir` as in compute_audio_feats."""
+    dag = _student(dag, modelDir)
     inp, ind1 = _prepare(dag)
     if ind1 is None:
         raise ValueError("the audio model has no pool6 layer")
@@ -222,7 +231,7 @@ def compute_audio_feats_wav(dag, wav, offsets, numEmotions=8, limit=float("inf")
     return logits
 
 
-def compute_audio_feats_files(dag, files, numEmotions=8, limit=float("inf"), maxBatch=64):
+def compute_audio_feats_files(dag, files, numEmotions=8, limit=float("inf"), maxBatch=64, *, modelDir=None):
     """logits = compute_audio_feats from the WAV files themselves (compute_audio_feats.m:116-136,172-176): `files` is a
     list of bytes or of paths.  [z, fs] = audioread(path); assert(size(z,2) <= 2, 'unexpected number of streams');
     z = z(:,1): vl.audioread with channel=0 (the left stream) decodes every file on the device into one bank, then
@@ -235,16 +244,19 @@ def compute_audio_feats_files(dag, files, numEmotions=8, limit=float("inf"), max
         if i["NumChannels"] > 2:
             raise ValueError("unexpected number of streams: file %d has %d channels" % (k, i["NumChannels"]))   # :174
     bank, offsets = vl.audioread(files, channel=0)
-    return compute_audio_feats_wav(dag, bank, offsets, numEmotions=numEmotions, maxBatch=maxBatch)
+    return compute_audio_feats_wav(dag, bank, offsets, numEmotions=numEmotions, maxBatch=maxBatch, modelDir=modelDir)
 
 
 def compute_visual_feats(dag, track_frames, batchSize=128, numEmotions=8, limit=float("inf"), lanes=2, *, read=None,
-                         split=None):
+                         split=None, modelDir=None):
     """faceLogits = compute_visual_feats(dag, track_frames): the frames of all tracks are flattened
     (:63-69), pushed through the frozen teacher `batchSize` at a time (:81-94) and the logits are split
     back per track (:104-109).  track_frames: list of 224 x 224 x 3 x F_i normalised face mats; with
     `read(paths) -> list of bytes` a list of frame-path lists instead, and every batch comes from
-    fetch_emovoxceleb_imdb.getImageBatch (:123-164: the JPEG files decoded on the device; `split` goes there)."""
+    fetch_emovoxceleb_imdb.getImageBatch (:123-164: the JPEG files decoded on the device; `split` goes there).
+    `dag` may be a model name, as upstream (:49 ferPlusZoo(opts.modelName)); `modelDir` then names the model files' directory."""
+    if isinstance(dag, str):
+        dag = zoo.ferPlusZoo(dag, modelDir=modelDir)
     _prepare(dag)
     first_ok = [i for i in range(len(track_frames)) if i <= limit]   # frameIdx <= firstId + limit, :72
     if read is not None:

@@ -83,14 +83,15 @@ def ferplus_baselines(dev=False, useBnorm=1, dataAug=True, dataType="CNTK", loss
                       modelName="senet50_ft-dag", dataDir="data/datasets/fer2013+", evaluateOnly=None, gpus=1,
                       finetuneLR=0.1, dropoutRate=0.5, cont=True, batchSize=128, learningRate=None, numEpochs=300,
                       *, imdb=None, expRoot="data/grimaces/fer2013+", widthMult=1.0, blocks=(3, 4, 6, 3), seed=0,
-                      numImages=512, verbose=False):
+                      numImages=512, verbose=False, modelDir=None):
     """Options as in ferplus_baselines.m:59-80 (`cont` is opts.train.continue, `gpus` / `batchSize` /
     `learningRate` are opts.train.*; `numEpochs` is cnn_train_dag's default, 300, with the last rate held after
     epoch 180).  `evaluateOnly` = {'subset': '' | 'val' | 'test', 'fromCkpt': bool}.  `dataDir` holds the FER2013 and
     FER+ CSVs (fer2013.csv, fer2013new.csv): when both are there and no `imdb` is given, getFerPlusImdb reads them.
     Extensions (keyword-only): `imdb` (a prepared imdb; without it and without the CSVs a SyntheticFerPlusImdb of
     `numImages` images), `expRoot` (root of the experiment directories), `widthMult` / `blocks` (narrow networks for
-    tests), `seed` (synthetic weights, imdb and batch draws)."""
+    tests), `seed` (synthetic weights, imdb and batch draws), `modelDir` (zoo.ferPlusZoo reads the model file from there
+    instead of building the seeded stand-in)."""
     ev = {"subset": "", "fromCkpt": False}
     ev.update(evaluateOnly or {})
     if learningRate is None:
@@ -99,7 +100,7 @@ def ferplus_baselines(dev=False, useBnorm=1, dataAug=True, dataType="CNTK", loss
     numOutputs = xbatch.ferplus_num_classes(dataType)                                   # :88-93
     dag = zoo.ferPlusZoo(modelName, seed=100 + seed, width_mult=widthMult, blocks=blocks, useBnorm=useBnorm,
                          finetuneLR=finetuneLR, dropoutRate=dropoutRate, lossType=lossType,
-                         numOutputs=numOutputs)                                          # :95-100
+                         numOutputs=numOutputs, modelDir=modelDir)                       # :95-100
     if modelName in PRETRAINED:
         pretrained_heads(dag, lossType)
     if imdb is None:                                                                    # :103-110

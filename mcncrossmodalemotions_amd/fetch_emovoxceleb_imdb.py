@@ -260,10 +260,11 @@ def load_imdb(path):
 
 
 def fetch_emovoxceleb_imdb(teacher="senet50-ferplus", imdbDir=os.path.join("data", "xEmo18", "storedFeats"), *,
-                           net=None, imdb=None, frames=None, read=None, split=None, verbose=True, **buildOpts):
+                           net=None, imdb=None, frames=None, read=None, split=None, verbose=True, modelDir=None,
+                           **buildOpts):
     """loadedImdb = fetch_emovoxceleb_imdb(teacher, 'imdbDir', ..) -- :1-51: the cached imdb of (teacher, imdbDir), else
     <imdbDir>/<teacher>-logits.mat when it exists, else buildImdb and save.  Building needs (keyword-only) `net` (default
-    zoo.ferPlusZoo(teacher)), `imdb` (an imdb that went through addFramesToImdb; default a 64-track synthetic one) and
+    zoo.ferPlusZoo(teacher, modelDir=modelDir): with `modelDir` the teacher's model file), `imdb` (an imdb that went through addFramesToImdb; default a 64-track synthetic one) and
     `frames` or `read` (with `split`, as buildImdb); buildOpts go to buildImdb (limit, batchSize, lanes).  A loaded
     imdb uploads its logits on first use.
     The cache key and the file name hold the teacher's NAME and imdbDir, nothing else: a later call with another
@@ -289,7 +290,8 @@ def fetch_emovoxceleb_imdb(teacher="senet50-ferplus", imdbDir=os.path.join("data
             imdb = addFramesToImdb(src, frames.lister, find=frames.find)
         if frames is None and read is None:
             raise ValueError("fetch_emovoxceleb_imdb: building needs `frames` for the given imdb")
-        loaded = buildImdb(net if net is not None else zoo.ferPlusZoo(teacher), imdb, frames if read is None else None,
+        loaded = buildImdb(net if net is not None else zoo.ferPlusZoo(teacher, modelDir=modelDir), imdb,
+                           frames if read is None else None,
                            read=read, split=split, **buildOpts)
         save_imdb(imdbPath, loaded)
     _CACHE[key] = loaded

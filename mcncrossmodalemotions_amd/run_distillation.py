@@ -24,12 +24,14 @@ def run_distillation(gpus=(2,), cont=True, miniVal=0.2, numSeconds=4, batchSize=
                      lossType="hot-cross-ent", temperature=2, fixedSegments=False, learningRate=None,
                      parameterServer="tmove", wavDir=None,
                      *, imdb=None, dataDir="data/xEmo18", numTracks=256, widthMult=1.0, seed=0, verbose=False,
-                     useWav=False, transformation="I"):
+                     useWav=False, transformation="I", modelDir=None):
     """Options as in run_distillation.m:72-90.  Extensions (keyword-only): `imdb` (a prepared imdb),
     `dataDir` (root of the experiment directories), `numTracks` / `seed` (synthetic imdb), `widthMult`
     (narrow student for tests), `useWav` (the batches come from the imdb's waveforms through the batched device
     front-end, batch.getBatchEmoVoxCeleb(use_wav, wavBatch), instead of the seeded spectrogram generator) and
-    `transformation` (net.meta.augmentation.transformation, :130: 'I', 'IS', 'ISN' ...; 'S' / 'N' need useWav)."""
+    `transformation` (net.meta.augmentation.transformation, :130: 'I', 'IS', 'ISN' ...; 'S' / 'N' need useWav) and
+    `modelDir` (emoVoxZoo's option: the student comes from <modelDir>/<student>.mat -- with fromScratch its architecture,
+    without it the network as saved, loss heads included -- instead of the seeded stand-in)."""
     gpus = list(np.atleast_1d(gpus))
     if miniEpochRatio is None:
         miniEpochRatio = 0.05 * len(gpus)                      # :77
@@ -63,7 +65,7 @@ def run_distillation(gpus=(2,), cont=True, miniVal=0.2, numSeconds=4, batchSize=
     else:   # all workers agree on the backend (a failed communicator start falls back to torch.distributed everywhere)
         parserv = train.ParameterServer.start_agreed(parameterServer)
     net = zoo.emoVoxZoo(student, scratch=1 if fromScratch else 0, lossType=lossType, numSeconds=numSeconds,
-                        numOutputs=numPredEmotions, width_mult=widthMult)             # :125-129
+                        numOutputs=numPredEmotions, width_mult=widthMult, modelDir=modelDir)   # :125-129
     net.meta.setdefault("augmentation", {})["transformation"] = transformation       # :130
     trainSamples = [i for i in range(len(imdb.set)) if imdb.set[i] == 1]              # :137-138
     valSamples = [i for i in range(len(imdb.set)) if imdb.set[i] == 2]

@@ -146,7 +146,8 @@ def _hist_json(path, title, counts, emotions):
 
 def student_stats(refresh=False, visHist=False, partition="all", student="emovoxceleb-student",
                   teacher="senet50-ferplus", ignore=("fear", "contempt", "disgust"), figDir="data/emovoxceleb-figs",
-                  cachePath=None, expRoot=None, *, imdb=None, net=None, root="data", verbose=True, wavBatch=False):
+                  cachePath=None, expRoot=None, *, imdb=None, net=None, root="data", verbose=True, wavBatch=False,
+                  modelDir=None):
     """Options as in student_stats.m:39-50 (cachePath defaults to <root>/mcnCrossModalEmotions/cache/
     emovoxceleb-student-stats.mat, expRoot to <root>/xEmo18; expRoot is parsed and unused, as upstream).
     Returns {partition: {'auc' (E doubles), 'meanAuc', 'represented' (1-based), 'counts' {'p', 'n', 'retrieved'},
@@ -154,7 +155,7 @@ def student_stats(refresh=False, visHist=False, partition="all", student="emovox
     Extensions (keyword-only): `imdb` (default a three-set SyntheticEmoVoxImdb), `net` (default
     zoo.emoVoxZoo(student)), `root` (vl_rootnn), `verbose` (the reference's printout), `wavBatch` (the features come from
     external.compute_audio_feats_wav on imdb.device_wav_bank -- one xm_spec_bucket_batch call per bucket -- instead of
-    the per-clip runSpec loop; off by default)."""
+    the per-clip runSpec loop; off by default), `modelDir` (without `net`: the student of <modelDir>/<student>.mat)."""
     partitions = partition_list(partition)
     cachePath = cachePath or os.path.join(root, "mcnCrossModalEmotions", "cache", CACHE_NAME)
     expRoot = expRoot or os.path.join(root, "xEmo18")
@@ -163,7 +164,7 @@ def student_stats(refresh=False, visHist=False, partition="all", student="emovox
     if refresh or not os.path.exists(featPath):                                          # :56-58
         if imdb is None:
             imdb = xbatch.SyntheticEmoVoxImdb(num_tracks=96, val_fraction=0.25, heard_fraction=0.125)
-        dag = net if net is not None else zoo.emoVoxZoo(student)
+        dag = net if net is not None else zoo.inference_student(student, modelDir)
         if wavBatch:
             wav, offsets = imdb.device_wav_bank(device)
             logits = external.compute_audio_feats_wav(dag, wav, offsets, numEmotions=len(EMOTIONS))

@@ -1,16 +1,20 @@
 """emoVoxZoo / ferPlusZoo mirrors: the student and teacher graphs of the reference.
 
 The reference downloads the networks as .mat files (emoVoxCeleb/emoVoxZoo.m:36-40,95-97;
-teacher/ferPlusZoo.m:93-101); those files are not available offline, so the architectures are
-restated from the published models and the weights are seeded synthetic
-ones.  The one structural pin the reference holds -- the pool6 width table at
-emoVoxZoo.m:258-259 -- is reproduced exactly by `vggvox()` (tests/test_pins.py).
+teacher/ferPlusZoo.m:93-101); those files are not available offline, so by default the architectures
+are restated from the published models and the weights are seeded synthetic
+ones.  With `modelDir` both zoos read the model files from that directory instead
+(dagnn.load_mat); nothing is ever downloaded.  The one structural pin the reference holds
+-- the pool6 width table at emoVoxZoo.m:258-259 -- is reproduced exactly by `vggvox()`
+(tests/test_pins.py).
 
 Net surgery follows the reference line by line where it exists:
     prepareFromDagNN        emoVoxZoo.m:187-253   strip Loss/SoftMax, last FC -> numOutputs
     configureForRegression  emoVoxZoo.m:105-183   loss + classerror + ErrorStats layers
     updatePooling           emoVoxZoo.m:256-269   pool6 <- [1 p1] from the bucket table
 """
+import os
+
 import numpy as np
 import torch
 
@@ -181,9 +185,51 @@ def calibrate_moments(net, inputs):
 # ---------------------------------------------------------------------------------------------
 FERPLUS_TRAINABLE = {"resnet50_ft-dag": False, "senet50_ft-dag": True}     # VGGFace2 imports -> SE or not
 
+# the model lists of ferPlusZoo.m:37-69; only looked at when the models come from files (modelDir)
+VGGFACE2_MODELS = ["resnet50_ft-dag", "resnet50_scratch-dag", "senet50_ft-dag", "senet50_scratch-dag"]
+STANDARD_MODELS = ["vgg-m-face-bn-fer", "vgg-m-face-bn", "vgg-vd-face-fer", "vgg-vd-face", "vgg_face", "resnet50_ft-dag"]
+FER_MODELS = ["vgg-vd-face-fer", "vgg-vd-face-sfew-dag", "vgg-m-face-bn-fer"]
+SFEW_MODELS = ["vgg-vd-face-sfew", "resnet50-face-sfew"]
+FERPLUS_MODELS = ["resnet50-ferplus", "senet50-ferplus"]
+FERPLUS_MODELS_DEV = {"resnet50_ft-dag-dropout-0.1": "net-epoch-17",                   # :81-91
+                      "resnet50_ft-dag-dropout-0.5": "net-epoch-122",
+                      "senet50_ft-dag-distributions-dropout-0.5-aug": "net-epoch-98",
+                      "senet50_ft-dag-distributions-CNTK-dropout-0.5-aug": "net-epoch-90"}
+PUBLIC_MODELS = ["resnet50-ferplus", "senet50-ferplus", "emovoxceleb-student"]         # ensure_compatibility.m:13-15
+
+
+def fixInputVarnames(net):
+    """ferPlusZoo.m:127-133 / emoVoxZoo.m:65-71: an input variable called 'input' or 'x0' becomes 'data'"""
+    for v in net.getInputs():
+        if v in ("input", "x0"):
+            net.renameVar(v, "data")
+    return net
+
+
+def load_model(path):
+    """net = load(path) ; if isfield(net, 'net'), net = net.net ; end ; dag = dagnn.DagNN.loadobj(net).  A missing file
+    raises: the reference's offer to download it (emoVoxZoo.m:74-102) is not mirrored."""
+    if not os.path.isfile(path):
+        raise FileNotFoundError("no model file at %s (model files are never downloaded: put it there)" % path)
+    return dagnn.load_mat(path)
+
+
+def ferPlusModelPath(modelName, modelDir):
+    """ferPlusZoo.m:72-94: (path of the model file, name of the file without '.mat').  The VGGFace2 imports live in
+    vggface2_models/, the development models in grimaces/<modelName>/net-epoch-N.mat."""
+    names = VGGFACE2_MODELS + STANDARD_MODELS + FER_MODELS + SFEW_MODELS + FERPLUS_MODELS + list(FERPLUS_MODELS_DEV)
+    if modelName not in names:
+        raise ValueError("%s is not a recognised FER+ teacher" % modelName)                 # :72-73
+    subfolder, fileName = "", modelName
+    if modelName in VGGFACE2_MODELS:
+        subfolder = "vggface2_models"
+    elif modelName in FERPLUS_MODELS_DEV:
+        subfolder, fileName = os.path.join("grimaces", modelName), FERPLUS_MODELS_DEV[modelName]
+    return os.path.join(os.fspath(modelDir), subfolder, fileName + ".mat"), fileName
+
 
 def ferPlusZoo(modelName, seed=100, width_mult=1.0, blocks=(3, 4, 6, 3), *, useBnorm=False, finetuneLR=1,
-               dropoutRate=0, lossType="distributions", numOutputs=7):
+               dropoutRate=0, lossType="distributions", numOutputs=7, modelDir=None):
     """dag = ferPlusZoo(modelName, 'useBnorm', .., 'finetuneLR', .., 'dropoutRate', .., 'lossType', ..,
     'numOutputs', ..) -- teacher/ferPlusZoo.m (option defaults :30-36).
 
@@ -203,7 +249,20 @@ def ferPlusZoo(modelName, seed=100, width_mult=1.0, blocks=(3, 4, 6, 3), *, useB
         the classifier", :12-14);
       * with lossType 'softmaxlog' getBatchFerPlus provides no 'hardlabel' (:215-220): the classerror head reads
         'label' then.
-    Weights are seeded synthetic ones, as elsewhere (the VGGFace2 .mat files are not available)."""
+    Weights are seeded synthetic ones, as elsewhere (the VGGFace2 .mat files are not available), unless `modelDir`
+    names the directory that holds the model files (the reference's vl_rootnn/data/models-import): then every name of
+    :37-71 is read from <modelDir>/[subfolder/]<name>.mat (ferPlusModelPath), `seed` only seeds the new classifier, and
+    `width_mult` / `blocks` mean nothing.  The pretrained names (ferPlusModels, ferModels, net-epoch-*) return as loaded
+    after fixInputVarnames (:103-114), every other name goes through prepareFromDagNN and configureForClassification
+    with the deviations above.  A missing file raises FileNotFoundError."""
+    if modelDir is not None:
+        path, fileName = ferPlusModelPath(modelName, modelDir)
+        net = load_model(path)                                                     # :98-100
+        if modelName in FERPLUS_MODELS or "net-epoch" in fileName or modelName in FER_MODELS:
+            return fixInputVarnames(net)                                           # :103-114
+        prepareFromDagNN(net, numOutputs, seed)                                    # :116
+        configureForClassification(net, finetuneLR, dropoutRate, lossType)         # :118-119
+        return fixInputVarnames(net)                                               # :124
     if modelName in FERPLUS_TRAINABLE:
         net = resnet50(FERPLUS_TRAINABLE[modelName], numOutputs, width_mult, blocks)
         synthetic_pretrained(net, seed)
@@ -383,9 +442,25 @@ def updatePooling(net, numSeconds):
 
 
 def emoVoxZoo(modelName="emovoxceleb-student", scratch=1, lossType="hot-cross-ent", numSeconds=4,
-              numOutputs=8, seed=200, width_mult=1.0, dropout=False):
+              numOutputs=8, seed=200, width_mult=1.0, dropout=False, modelDir=None):
     """dag = emoVoxZoo(name, 'scratch', 1, 'lossType', 'hot-cross-ent', 'numSeconds', 4,
-    'numOutputs', 8, 'dropout', rate) -- emoVoxZoo.m:1-62 (call site run_distillation.m:125-129)."""
+    'numOutputs', 8, 'dropout', rate) -- emoVoxZoo.m:1-62 (call site run_distillation.m:125-129).
+
+    `modelDir` (the reference's option of that name, :22): read <modelDir>/<modelName>.mat instead of building the
+    seeded stand-in.  scratch = 0 returns the file's network after fixInputVarnames (:41-48); scratch = 1 keeps its
+    architecture only: prepareFromDagNN, initParams, configureForRegression, updatePooling (:50-62).  The two teacher
+    names are accepted there as in the reference (:28-33).  A missing file raises FileNotFoundError."""
+    if modelDir is not None:
+        if modelName not in ("emovoxceleb-student", "vggvox-ver", "vggvox-ident") + tuple(FERPLUS_MODELS):
+            raise ValueError("%s is not a recognised student model" % modelName)            # :33-35
+        net = load_model(os.path.join(os.fspath(modelDir), modelName + ".mat"))                # :36-44
+        if not scratch:
+            return fixInputVarnames(net)                                                    # :45
+        prepareFromDagNN(net, numOutputs)                                                   # :50
+        net.initParams(seed)                                                                # :54
+        configureForRegression(net, lossType, numOutputs, dropout)                          # :57-58
+        updatePooling(net, numSeconds)                                                      # :61
+        return fixInputVarnames(net)                                                        # :62
     if modelName not in ("emovoxceleb-student", "vggvox-ver", "vggvox-ident"):
         raise ValueError("%s is not a recognised student model" % modelName)
     net = vggvox(1251, width_mult)
@@ -399,3 +474,42 @@ def emoVoxZoo(modelName="emovoxceleb-student", scratch=1, lossType="hot-cross-en
     updatePooling(net, numSeconds)
     net.meta["modelName"] = modelName
     return net
+
+
+def inference_student(modelName, modelDir=None):
+    """the student the evaluation drivers build when none is passed (external/compute_audio_feats.m:52, emoVoxZoo(opts.modelName)):
+    the seeded stand-in, or with `modelDir` the network of <modelDir>/<modelName>.mat with its weights (scratch = 0)"""
+    if modelDir is None:
+        return emoVoxZoo(modelName)
+    return emoVoxZoo(modelName, scratch=0, modelDir=modelDir)
+
+
+def ensure_compatibility(modelDir):
+    """misc/ensure_compatibility.m: every public model found in `modelDir` is loaded, the `exBackprop` field is taken out
+    of its block structs (MatConvNet versions before that property refuse it) and the struct is saved back in place,
+    at the top level of the file (save(modelPath, '-struct', 'net')).  Nothing else in the file changes: the struct is
+    rewritten as read, not through loadobj / saveobj.  A model without a file is skipped (the reference fails there).
+    Returns the paths written."""
+    from . import matfile
+    written = []
+    for modelName in PUBLIC_MODELS:
+        path = os.path.join(os.fspath(modelDir), modelName + ".mat")
+        if not os.path.isfile(path):
+            continue
+        net = matfile.read_mat(path)
+        if "net" in net:
+            net = net["net"][0, 0]
+            net = {f: net[f] for f in net.dtype.names}
+        layers = net.get("layers")
+        if layers is not None and layers.size and "block" in (layers.dtype.names or ()):
+            for idx in np.ndindex(*layers.shape):
+                b = layers[idx]["block"]
+                if isinstance(b, np.ndarray) and b.dtype.names and "exBackprop" in b.dtype.names:
+                    keep = [f for f in b.dtype.names if f != "exBackprop"]
+                    nb = np.empty(b.shape, dtype=[(f, object) for f in keep])
+                    for j in np.ndindex(*b.shape):
+                        nb[j] = tuple(b[j][f] for f in keep)
+                    layers[idx]["block"] = nb if keep else np.array([[None]], object)
+        matfile.write_mat(path, matfile.rewritable(net))
+        written.append(path)
+    return written
