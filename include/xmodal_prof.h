@@ -2,7 +2,9 @@
  * xmodal_prof.h -- measurement hooks of libxmodal_hip.so (NOT part of the drop-in operator ABI).
  * bench.py uses them to time each convolution kernel instantiation with HIP events recorded on
  * the stream the kernel is launched on, and to attach the algorithmic FLOPs of every launch
- * (2 * M * pixels * taps, un-padded), so that roofline.achieved is measured live.
+ * (2 * M * pixels * taps, un-padded), so that roofline.achieved is measured live; the tests read
+ * from them which kernel a call ran.  csrc/prof.h (ProfScope, the keys), csrc/prof.cpp (the table
+ * of keys and names); from Python: mcncrossmodalemotions_amd/prof.py.
  */
 /*
  * Environment the library reads (nothing else): every name is read once.
@@ -31,11 +33,13 @@ extern "C" {
 #endif
 /* on != 0: start recording (drops previous records); on == 0: stop recording, keep records */
 int xm_prof_enable(int on);
-/* after the stream has been synchronised: per-kernel totals; returns #distinct kernels */
+/* after the stream has been synchronised: per-kernel totals in first-launch order; writes at most cap entries (cap 0:
+ * none, the arrays may be NULL) and returns #distinct kernels */
 int xm_prof_collect(int cap, int *keys, double *total_ms, double *total_flops, long long *launches);
 /* algorithmic HBM bytes (x + f + y [+ residual], every operand once) of the recorded launches, per kernel */
 int xm_prof_collect_bytes(int cap, int *keys, double *total_bytes);
-/* name of a key, identical to the kernel name rocprofv3 --kernel-trace prints (sans namespace) */
+/* name of a key, identical to the kernel name rocprofv3 --kernel-trace prints (sans namespace); a key that no launch
+ * site records is XM_EINVAL and leaves buf empty */
 int xm_prof_kernel_name(int key, char *buf, int len);
 /* Test / tools switches: ONE entry (round 6; rounds 2-5 exported one xm_debug_force_* function per switch).  They select
  * between complete, parity-tested implementations of an operator (never what is computed) and are process-global: a host

@@ -11,6 +11,7 @@
 #include <vector>
 
 #include "conv_kernels.h"
+#include "prof.h"
 #include "stem_pool_kernels.h"
 
 namespace xm {
@@ -268,11 +269,11 @@ static const Cfg kCfgs[] = {
     // 2 % slower with it, 64 x 256 by eight waves is no faster than 64 x 128 by four, 96 x 256 by waves of 96 x 32 spills,
     // 96 x 128 by six waves stages 512 gather units with 384 threads: 75 against 117 TFLOP/s)
     {1, 2, 4, 2},  //  7
-    // LDS-DMA variants (conv_gemm_dma_kernel): forward / dgrad GEMMs of 1x1 unit-stride layers only
-    {2, 2, 2, 2},  //  8: 128 x 128, 3 LDS stages
-    {2, 2, 1, 4},  //  9:  64 x 256, 3 stages
-    {1, 2, 2, 2},  // 10:  64 x 128, 4 stages
-    {1, 1, 2, 2},  // 11:  64 x  64, 4 stages
+    // LDS-DMA variants (conv_gemm_dma_kernel): forward / dgrad GEMMs of 1x1 unit-stride layers only; LDS stages: kDmaStages
+    {2, 2, 2, 2},  //  8: 128 x 128
+    {2, 2, 1, 4},  //  9:  64 x 256
+    {1, 2, 2, 2},  // 10:  64 x 128
+    {1, 1, 2, 2},  // 11:  64 x  64
 };
 constexpr int kNumCfg = sizeof(kCfgs) / sizeof(kCfgs[0]);
 constexpr int kNumBaseCfg = 8;                       // configurations every forward / dgrad geometry can run
@@ -337,26 +338,39 @@ static int pick_cfg(long long M, long long NP, int nkt) {
   return bi;
 }
 
-#ifndef XM_DMA_NST7
-#define XM_DMA_NST7 4
-#endif
-#ifndef XM_DMA_NST9
-#define XM_DMA_NST9 4
-#endif
-#ifndef XM_DMA_NST10
-#define XM_DMA_NST10 4
+#ifndef XM_DMA_NST
+#define XM_DMA_NST {4, 3, 4, 4}
 #endif
 #ifndef XM_DMA_PERCU
 #define XM_DMA_PERCU {2, 2, 4, 4}
 #endif
+constexpr int kDmaStages[kNumCfg - kNumBaseCfg] = XM_DMA_NST;   // LDS stages of the LDS-DMA configurations (launch and name)
 static void launch_gemm_dma(int ci, const ConvGemmArgs &a, dim3 grid, hipStream_t st) {
   dim3 block(256);
   switch (ci) {
-    case kNumBaseCfg + 0: hipLaunchKernelGGL((conv_gemm_dma_kernel<2, 2, 2, 2, XM_DMA_NST7>), grid, block, 0, st, a); break;
-    case kNumBaseCfg + 1: hipLaunchKernelGGL((conv_gemm_dma_kernel<2, 2, 1, 4, 3>), grid, block, 0, st, a); break;
-    case kNumBaseCfg + 2: hipLaunchKernelGGL((conv_gemm_dma_kernel<1, 2, 2, 2, XM_DMA_NST9>), grid, block, 0, st, a); break;
-    default: hipLaunchKernelGGL((conv_gemm_dma_kernel<1, 1, 2, 2, XM_DMA_NST10>), grid, block, 0, st, a); break;
+    case kNumBaseCfg + 0: hipLaunchKernelGGL((conv_gemm_dma_kernel<2, 2, 2, 2, kDmaStages[0]>), grid, block, 0, st, a); break;
+    case kNumBaseCfg + 1: hipLaunchKernelGGL((conv_gemm_dma_kernel<2, 2, 1, 4, kDmaStages[1]>), grid, block, 0, st, a); break;
+    case kNumBaseCfg + 2: hipLaunchKernelGGL((conv_gemm_dma_kernel<1, 2, 2, 2, kDmaStages[2]>), grid, block, 0, st, a); break;
+    default: hipLaunchKernelGGL((conv_gemm_dma_kernel<1, 1, 2, 2, kDmaStages[3]>), grid, block, 0, st, a); break;
   }
+}
+
+// prof.h: the kernel behind a key of launch_gemm (sub = ci * 2 + mode), wgrad_run (ci * 4 + log2 of the vector width) or
+// launch_gemm_multi (ci * 2), for the values those sites can pass
+bool conv_cfg_kernel_name(ProfKind kind, int sub, char *buf, int len) {
+  const int per = kind == kProfWgrad ? 4 : 2, ci = sub / per, v = sub % per;
+  const int ncfg = kind == kProfGemm ? kNumCfg : kind == kProfWgrad ? kNumWgradCfg : kNumBaseCfg;
+  if (sub < 0 || ci >= ncfg || v > (kind == kProfGemm ? 1 : kind == kProfWgrad ? 2 : 0)) return false;
+  const Cfg &c = kCfgs[ci];
+  if (kind == kProfGemm && is_dma_cfg(ci))
+    snprintf(buf, len, "conv_gemm_dma_kernel<%d, %d, %d, %d, %d>", c.tm, c.tn, c.wgm, c.wgn, kDmaStages[ci - kNumBaseCfg]);
+  else if (kind == kProfGemm)
+    snprintf(buf, len, "conv_gemm_kernel<%d, %d, %d, %d, %d>", c.tm, c.tn, c.wgm, c.wgn, v);
+  else if (kind == kProfGemmMulti)
+    snprintf(buf, len, "conv_gemm_multi_kernel<%d, %d, %d, %d>", c.tm, c.tn, c.wgm, c.wgn);
+  else
+    snprintf(buf, len, "conv_wgrad_kernel<%d, %d, %d, %d, %d>", c.tm, c.tn, c.wgm, c.wgn, 1 << v);
+  return true;
 }
 
 template <int MODE>
@@ -385,51 +399,6 @@ static int g_force_wgrad_patch = -1; // test hook (xm_debug_force_wgrad_patch)
 static unsigned g_exec_hint = 0;
 static int g_force_halo = -1; // test hook (xm_debug_force_conv_halo): 1 = halo-patch kernel wherever it can run, 0 = never
 static unsigned long long *g_dbg_cycles = nullptr;  // device buffer, set by xm_debug_conv_cycles(1)
-
-// ---- per-kernel timing with HIP events on the launch stream (bench.py roofline leg) --------
-struct ProfRec {
-  hipEvent_t start, stop;
-  int key;  // kind * 100 + cfg * 2 + check
-  double flops;
-  double bytes;  // algorithmic HBM bytes of the launch: every operand once (x + f + y [+ residual])
-};
-static bool g_prof_on = false;
-static std::vector<ProfRec> g_prof;
-static std::vector<hipEvent_t> g_event_pool;
-
-static hipEvent_t prof_event() {
-  if (!g_event_pool.empty()) {
-    hipEvent_t e = g_event_pool.back();
-    g_event_pool.pop_back();
-    return e;
-  }
-  hipEvent_t e;
-  (void)hipEventCreate(&e);
-  return e;
-}
-struct ProfScope {
-  bool on;
-  ProfRec r;
-  hipStream_t st;
-  ProfScope(int key, double flops, hipStream_t s, double bytes = 0) : on(g_prof_on), st(s) {
-    if (!on) return;
-    r.key = key;
-    r.flops = flops;
-    r.bytes = bytes;
-    r.start = prof_event();
-    r.stop = prof_event();
-    (void)hipEventRecord(r.start, st);
-  }
-  ~ProfScope() {
-    if (!on) return;
-    (void)hipEventRecord(r.stop, st);
-    g_prof.push_back(r);
-  }
-};
-// the same scope for launches of the other translation units (spec.hip); nullptr while the profiler is off
-void *prof_open(int key, double flops, hipStream_t st) { return g_prof_on ? new ProfScope(key, flops, st) : nullptr; }
-void prof_close(void *scope) { delete (ProfScope *)scope; }
-
 
 // co-resident blocks per CU of the register-staged configurations (VGPR-limited: 222 / 232 / 186 / 140 / 116 / 134 / 122 /
 // 128 with eight waves)
@@ -512,7 +481,7 @@ static int launch_gemm(ConvGemmArgs &a, int mode, int ci, int splits, float *sla
   }
   {
     const double abytes = (double)a.xBytes + 4.0 * a.M * a.Rtrue + 4.0 * a.M * (double)a.NP * (a.resid ? 2 : 1);
-    ProfScope ps(0 * 100 + ci * 2 + mode, a.algoFlops > 0 ? a.algoFlops : 2.0 * a.M * (double)a.NP * a.Rtrue, st,
+    ProfScope ps(prof_key(kProfGemm, ci * 2 + mode), a.algoFlops > 0 ? a.algoFlops : 2.0 * a.M * (double)a.NP * a.Rtrue, st,
                  abytes);
     if (is_dma_cfg(ci)) {
       // persistent: one round of co-resident blocks (a multiple of 8 so that every XCD gets the same share)
@@ -580,7 +549,7 @@ static int launch_gemm_multi(const std::vector<ConvGemmArgs> &args, int ci, hipS
     m.c[i] = a;
   }
   {
-    ProfScope ps(2 * 100 + ci * 2, flops, st, abytes);
+    ProfScope ps(prof_key(kProfGemmMulti, ci * 2), flops, st, abytes);
     launch_gemm_multi_cfg(ci, m, dim3(maxTiles, 1, (unsigned)args.size()), st);
   }
   XM_LAUNCH_CHECK();
@@ -697,7 +666,7 @@ static int launch_halo(ConvGemmArgs a, int v, float *slab, hipStream_t st) {
   if (a.slab) a.statPart = nullptr;
   {
     const double abytes = (double)a.xBytes + 4.0 * a.M * a.Rtrue + 4.0 * a.M * (double)a.NP * (a.resid ? 2 : 1);
-    ProfScope ps(3 * 100 + v, a.algoFlops > 0 ? a.algoFlops : 2.0 * a.M * (double)a.NP * a.Rtrue, st, abytes);
+    ProfScope ps(prof_key(kProfHalo, v), a.algoFlops > 0 ? a.algoFlops : 2.0 * a.M * (double)a.NP * a.Rtrue, st, abytes);
     const dim3 grid(a.nbm * a.nbn, splits), block(256);
     if (v == 0) hipLaunchKernelGGL((conv_halo_kernel<2, 2, 2, 2, 512>), grid, block, 0, st, a);
     else if (v == 1) hipLaunchKernelGGL((conv_halo_kernel<3, 1, 1, 4, 512>), grid, block, 0, st, a);
@@ -725,7 +694,7 @@ static int launch_halo_multi(const std::vector<ConvGemmArgs> &args, int v, hipSt
     m.c[i] = a;
   }
   {
-    ProfScope ps(4 * 100 + v, flops, st, abytes);
+    ProfScope ps(prof_key(kProfHaloMulti, v), flops, st, abytes);
     const dim3 grid(maxTiles, 1, (unsigned)args.size()), block(256);
     if (v == 0) hipLaunchKernelGGL((conv_halo_multi_kernel<2, 2, 2, 2, 512>), grid, block, 0, st, m);
     else if (v == 1) hipLaunchKernelGGL((conv_halo_multi_kernel<3, 1, 1, 4, 512>), grid, block, 0, st, m);
@@ -1207,7 +1176,7 @@ static int launch_stem(ConvGemmArgs a, const float *f, int R, hipStream_t st) {
   a.hyS = 1, a.hyFull = 0, a.hyTps = 0, a.hyP0 = 0, a.piReal = 0;
   a.dbgCycles = g_dbg_cycles;
   const double abytes = (double)a.xBytes + 4.0 * a.M * a.Rtrue + 4.0 * a.M * (double)a.NP;
-  ProfScope ps(5 * 100, 2.0 * a.M * (double)a.NP * a.Rtrue, st, abytes);
+  ProfScope ps(prof_key(kProfStem), 2.0 * a.M * (double)a.NP * a.Rtrue, st, abytes);
   const int grid = stem_grid(a.NP);
   if (a.gsy == 2) hipLaunchKernelGGL(conv_stem_kernel<2>, dim3(grid), dim3(256), 0, st, a, a.nbn);
   else hipLaunchKernelGGL(conv_stem_kernel<1>, dim3(grid), dim3(256), 0, st, a, a.nbn);
@@ -1230,7 +1199,7 @@ static int launch_stem3(ConvGemmArgs a, const float *f, int R, hipStream_t st) {
   const int pij = (int)a.divPIJ.d, pi = (int)a.divPI.d;
   const bool wide = wide_on && pij % 256 == 0 && pi >= 86;
   if (wide) a.nbn = a.NP / 256;
-  ProfScope ps(12 * 100 + (wide ? 1 : 0), 2.0 * a.M * (double)a.NP * a.Rtrue, st, abytes);
+  ProfScope ps(prof_key(kProfStem3, wide ? 1 : 0), 2.0 * a.M * (double)a.NP * a.Rtrue, st, abytes);
   const int grid = std::min(512, (a.nbn + 7) / 8 * 8);
   if (wide) hipLaunchKernelGGL(conv_stem3_kernel<2>, dim3(grid), dim3(256), 0, st, a, a.nbn);
   else hipLaunchKernelGGL(conv_stem3_kernel<1>, dim3(grid), dim3(256), 0, st, a, a.nbn);
@@ -1491,7 +1460,7 @@ static int launch_dgrad_s2(const float *dzdy, const float *f, float *dxo, const 
                      Fd, g.C, g.K, a.nbm, a.nkg, g.pl);
   XM_LAUNCH_CHECK();
   {
-    ProfScope ps(11 * 100, 2.0 * g.K * (double)g.Ho * g.Wo * g.N * g.R, st,
+    ProfScope ps(prof_key(kProfDgradS2), 2.0 * g.K * (double)g.Ho * g.Wo * g.N * g.R, st,
                  (double)a.dyBytes + 4.0 * g.K * g.R + 4.0 * g.C * (double)g.H * g.W * g.N);
     hipLaunchKernelGGL(conv_dgrad_s2_kernel<1>, dim3((unsigned)(blocks * g.N)), dim3(256), 0, st, a);
   }
@@ -1801,7 +1770,7 @@ static int wgrad_run(const float *x, const float *dzdy, float *dfo, const Geo &g
     a.nbm = nbm, a.nbn = nbn, a.tilesPerSplit = tps, a.nkt = nkt, a.splitStride = slab;
     {
       const int av = wgrad_av(a);
-      ProfScope ps(1 * 100 + ci * 4 + (av == 4 ? 2 : av == 2 ? 1 : 0), 2.0 * g.Kg * (double)NP * g.R, st,
+      ProfScope ps(prof_key(kProfWgrad, ci * 4 + (av == 4 ? 2 : av == 2 ? 1 : 0)), 2.0 * g.Kg * (double)NP * g.R, st,
                    (double)a.xBytes + (double)a.dyBytes + 4.0 * g.Kg * g.R);
       launch_wgrad_cfg(ci, a, dim3(nbm * nbn, splits), st);
     }
@@ -1864,7 +1833,7 @@ static int launch_stem_wgrad(const float *x, const float *dzdy, float *dfo, cons
     // BNP reads the convolution's output once (as the plain kernel reads dY) + the pooled derivative and its table
     const double abytes = 4.0 * g.H * g.W * g.N + 4.0 * a.M * (double)a.NP + 4.0 * a.M * a.R +
                           (bnp ? 5.0 * bnp->pHo * bnp->pWo * (double)g.K * g.N : 0.0);
-    ProfScope ps(6 * 100 + (bnp ? 1 : 0), 2.0 * a.M * (double)a.NP * a.R, st, abytes);
+    ProfScope ps(prof_key(kProfStemWgrad, bnp ? 1 : 0), 2.0 * a.M * (double)a.NP * a.R, st, abytes);
     if (bnp) {
       const int ones = a.onesCol < 0 ? 0 : (a.onesCol < 32 ? 1 : 2);
 #define XM_BNP_LAUNCH(SY_, ON_) hipLaunchKernelGGL((conv_stem_wgrad_bnp_kernel<SY_, ON_>), dim3(grid), dim3(256), kStemWgSmemBnp, st, a, ntiles)
@@ -1921,7 +1890,7 @@ static int launch_wgrad_patch(const float *x, const float *dzdy, float *dfo, con
   a.splitStride = slab;
   a.out = splits > 1 ? part : dfo;
   {
-    ProfScope ps(9 * 100, 2.0 * g.Kg * (double)g.Ho * g.Wo * g.N * g.R, st, (double)a.xBytes + (double)a.dyBytes + 4.0 * slab);
+    ProfScope ps(prof_key(kProfWgradPatch), 2.0 * g.Kg * (double)g.Ho * g.Wo * g.N * g.R, st, (double)a.xBytes + (double)a.dyBytes + 4.0 * slab);
     hipLaunchKernelGGL(conv_wgrad_patch_kernel<30>, dim3(tiles, splits), dim3(256), 0, st, a);
   }
   XM_LAUNCH_CHECK();
@@ -1957,7 +1926,7 @@ static int launch_wgrad_patch_s2(const float *x, const float *dzdy, float *dfo, 
   a.splitStride = slab;
   a.out = splits > 1 ? part : dfo;
   {
-    ProfScope ps(10 * 100, 2.0 * g.Kg * (double)g.Ho * g.Wo * g.N * g.R, st, (double)a.xBytes + (double)a.dyBytes + 4.0 * slab);
+    ProfScope ps(prof_key(kProfWgradPatchS2), 2.0 * g.Kg * (double)g.Ho * g.Wo * g.N * g.R, st, (double)a.xBytes + (double)a.dyBytes + 4.0 * slab);
     hipLaunchKernelGGL((conv_wgrad_patch_s2_kernel<5, 2>), dim3(tiles * splits), dim3(256), 0, st, a);
   }
   XM_LAUNCH_CHECK();
@@ -2039,7 +2008,7 @@ static int launch_stem_gram(WsCarver &ws, const float *x, const Geo &g, double *
   }
   {
     // three of the four 32 x 32 tiles of the padded 64 x 64 product are computed
-    ProfScope ps(13 * 100, 2.0 * (g.R + 1) * (g.R + 1) * (double)g.Ho * g.Wo * g.N, st, 4.0 * g.H * g.W * g.N);
+    ProfScope ps(prof_key(kProfStemGram), 2.0 * (g.R + 1) * (g.R + 1) * (double)g.Ho * g.Wo * g.N, st, 4.0 * g.H * g.W * g.N);
     if (g.sy == 2) hipLaunchKernelGGL(stem_gram_kernel<2>, dim3(grid), dim3(256), kSpGramSmem, st, a, nunits);
     else hipLaunchKernelGGL(stem_gram_kernel<1>, dim3(grid), dim3(256), kSpGramSmem, st, a, nunits);
   }
@@ -2147,133 +2116,6 @@ int xm_debug_conv_cycles(int on, unsigned long long *out, int nblocks) {
   return XM_OK;
 }
 #endif
-
-// ---- include/xmodal_prof.h ------------------------------------------------------------------
-int xm_prof_enable(int on) {
-  if (on) {
-    for (auto &r : g_prof) {
-      g_event_pool.push_back(r.start);
-      g_event_pool.push_back(r.stop);
-    }
-    g_prof.clear();
-  }
-  g_prof_on = on != 0;
-  return XM_OK;
-}
-
-// index of `key` in the keys seen so far (appended when new): first-launch order
-static size_t prof_slot(std::vector<int> &ks, int key) {
-  const size_t i = std::find(ks.begin(), ks.end(), key) - ks.begin();
-  if (i == ks.size()) ks.push_back(key);
-  return i;
-}
-
-// Aggregates the recorded launches by kernel instantiation.  Caller must have synchronised the
-// stream(s).  Returns the number of distinct kernels; fills up to `cap` entries.
-int xm_prof_collect(int cap, int *keys, double *total_ms, double *total_flops, long long *launches) {
-  std::vector<int> ks;
-  std::vector<double> ms, fl;
-  std::vector<long long> cnt;
-  for (auto &r : g_prof) {
-    float t = 0.f;
-    if (hipEventElapsedTime(&t, r.start, r.stop) != hipSuccess) continue;
-    const size_t i = prof_slot(ks, r.key);
-    if (i == ms.size()) ms.push_back(0), fl.push_back(0), cnt.push_back(0);
-    ms[i] += t;
-    fl[i] += r.flops;
-    cnt[i] += 1;
-  }
-  for (size_t i = 0; i < ks.size() && (int)i < cap; ++i) {
-    keys[i] = ks[i];
-    total_ms[i] = ms[i];
-    total_flops[i] = fl[i];
-    launches[i] = cnt[i];
-  }
-  return (int)ks.size();
-}
-
-// algorithmic bytes (every operand once) summed per kernel instantiation, same order / keys as xm_prof_collect
-int xm_prof_collect_bytes(int cap, int *keys, double *total_bytes) {
-  std::vector<int> ks;
-  std::vector<double> by;
-  for (auto &r : g_prof) {
-    const size_t i = prof_slot(ks, r.key);
-    if (i == by.size()) by.push_back(0);
-    by[i] += r.bytes;
-  }
-  for (size_t i = 0; i < ks.size() && (int)i < cap; ++i) {
-    keys[i] = ks[i];
-    total_bytes[i] = by[i];
-  }
-  return (int)ks.size();
-}
-
-// human-readable kernel name of a profiler key, matching the rocprofv3 kernel-trace name
-int xm_prof_kernel_name(int key, char *buf, int len) {
-  int kind = key / 100;
-  if (kind == 20) {   // spec.hip
-    static const char *const names[4] = {"spec_bank_kernel", "spec_plan_kernel", "spec_gemm_kernel", "spec_finish_kernel"};
-    snprintf(buf, len, "%s", names[key % 100 < 4 ? key % 100 : 0]);
-    return XM_OK;
-  }
-  if (kind == 21) {   // jpeg.hip
-    static const char *const names[6] = {"jpeg_clear_kernel", "jpeg_entropy_kernel", "jpeg_idct_kernel", "jpeg_colour_kernel",
-                                         "crop_resize_face_ragged_kernel", "jpeg_entropy_split_kernel"};
-    snprintf(buf, len, "%s", names[key % 100 < 6 ? key % 100 : 0]);
-    return XM_OK;
-  }
-  if (kind == 22) {   // wav.hip
-    snprintf(buf, len, "wav_decode_kernel");
-    return XM_OK;
-  }
-  if (kind == 23) {   // pixcsv.hip
-    snprintf(buf, len, "pixcsv_decode_kernel");
-    return XM_OK;
-  }
-  if (kind == 3 || kind == 4) {
-    const int v = key % 100;
-    snprintf(buf, len, "%s<%s, %d>", kind == 3 ? "conv_halo_kernel" : "conv_halo_multi_kernel",
-             v == 0 ? "2, 2, 2, 2" : "3, 1, 1, 4", v == 2 ? 1024 : 512);
-    return XM_OK;
-  }
-  if (kind == 9) {
-    snprintf(buf, len, "conv_wgrad_patch_kernel<30>");
-    return XM_OK;
-  }
-  if (kind == 10) {
-    snprintf(buf, len, "conv_wgrad_patch_s2_kernel<5, 2>");
-    return XM_OK;
-  }
-  if (kind == 12) {
-    snprintf(buf, len, key % 100 ? "conv_stem3_kernel<2>" : "conv_stem3_kernel<1>");
-    return XM_OK;
-  }
-  if (kind == 11) {
-    snprintf(buf, len, "conv_dgrad_s2_kernel<1>");
-    return XM_OK;
-  }
-  if (kind == 13 || kind == 14 || kind == 15) {
-    snprintf(buf, len, kind == 13 ? "stem_gram_kernel<2>" : kind == 14 ? (key % 100 ? "conv_stem_wgrad_pool_kernel<2, true>" : "conv_stem_wgrad_pool_kernel<2, false>") : "conv_stem_bnpool_fwd_kernel");
-    return XM_OK;
-  }
-  if (kind == 5 || kind == 6) {
-    snprintf(buf, len, kind == 5 ? "conv_stem_kernel<2>" : (key % 100 ? "conv_stem_wgrad_bnp_kernel<2, 2>" : "conv_stem_wgrad_kernel<2>"));
-    return XM_OK;
-  }
-  int ci = (kind == 0 || kind == 2) ? (key % 100) / 2 : (key % 100) / 4;   // keys: ProfScope call sites (ci * 2 [+ mode] / ci * 4 + vec)
-  if (ci < 0 || ci >= kNumCfg) return XM_EINVAL;
-  const Cfg &c = kCfgs[ci];
-  if (kind == 0 && is_dma_cfg(ci))
-    snprintf(buf, len, "conv_gemm_dma_kernel<%d, %d, %d, %d, %d>", c.tm, c.tn, c.wgm, c.wgn,
-             ci == kNumBaseCfg ? XM_DMA_NST7 : ci == kNumBaseCfg + 1 ? 3 : ci == kNumBaseCfg + 2 ? XM_DMA_NST9 : XM_DMA_NST10);
-  else if (kind == 0)
-    snprintf(buf, len, "conv_gemm_kernel<%d, %d, %d, %d, %d>", c.tm, c.tn, c.wgm, c.wgn, key % 2);
-  else if (kind == 2)
-    snprintf(buf, len, "conv_gemm_multi_kernel<%d, %d, %d, %d>", c.tm, c.tn, c.wgm, c.wgn);
-  else
-    snprintf(buf, len, "conv_wgrad_kernel<%d, %d, %d, %d, %d>", c.tm, c.tn, c.wgm, c.wgn, 1 << (key % 4));
-  return XM_OK;
-}
 
 int xm_nnconv_forward_fused(const float *x, int H, int W, int C, int N, const float *f, int FH,
                             int FW, int FC, int K, const float *b, float *y, int sy, int sx,
@@ -2476,7 +2318,7 @@ int xm_nnconv_bnorm_relu_pool_forward(const float *x, int H, int W, int C, int N
   }
   const int grid = std::min(256 * XM_SF_OCC, (a.nunits + 3) / 4);
   {
-    ProfScope ps(15 * 100, 2.0 * g.K * (double)g.Ho * g.Wo * g.N * g.R, st, 4.0 * g.H * g.W * g.N + 5.0 * (double)pooled);
+    ProfScope ps(prof_key(kProfStemBnpoolFwd), 2.0 * g.K * (double)g.Ho * g.Wo * g.N * g.R, st, 4.0 * g.H * g.W * g.N + 5.0 * (double)pooled);
     hipLaunchKernelGGL(conv_stem_bnpool_fwd_kernel, dim3(grid), dim3(256), kSfSmem, st, a);
   }
   XM_LAUNCH_CHECK();
@@ -2542,7 +2384,7 @@ int xm_nnconv_backward_filter_bnrelupool_gram(const float *x, int H, int W, int 
   }
   {
     const double abytes = 4.0 * g.H * g.W * g.N + (y_pool ? 9.0 : 5.0) * (double)pooled + 4.0 * a.M * a.R;
-    ProfScope ps(14 * 100 + (y_pool ? 1 : 0), 2.0 * a.M * (double)g.Ho * g.Wo * g.N * a.R, st, abytes);
+    ProfScope ps(prof_key(kProfStemWgradPool, y_pool ? 1 : 0), 2.0 * a.M * (double)g.Ho * g.Wo * g.N * a.R, st, abytes);
 #define XM_SPW_LAUNCH(SY_, G_) hipLaunchKernelGGL((conv_stem_wgrad_pool_kernel<SY_, G_>), dim3(grid), dim3(256), kSp3Smem, st, a, nunits)
     if (g.sy == 2) {
       if (y_pool) XM_SPW_LAUNCH(2, true); else XM_SPW_LAUNCH(2, false);

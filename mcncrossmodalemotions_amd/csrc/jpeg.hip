@@ -26,6 +26,7 @@
 #include <algorithm>
 #include <vector>
 
+#include "prof.h"
 #include "xm_common.h"
 
 namespace xm {
@@ -1030,46 +1031,38 @@ static int jpeg_decode_launch(const unsigned char *bytes, long long nbytes, cons
   float *pix = pixels ? pixels : ws.take<float>((size_t)pixel_floats);
   const unsigned char *huff = tables + (size_t)nq * kQtBytes;
   {
-    void *ps = prof_open(2100, 0, st);
+    ProfScope ps(prof_key(kProfJpeg, 0), 0, st);
     const size_t n16 = (size_t)coef_elems / 8;
     hipLaunchKernelGGL(jpeg_clear_kernel, dim3((unsigned)std::min<size_t>((n16 + 255) / 256, 4096)), dim3(256), 0, st,
                        (uint4 *)coef, n16, status, N);
-    prof_close(ps);
-    XM_LAUNCH_CHECK();
   }
+  XM_LAUNCH_CHECK();
   {
-    void *ps = prof_open(seg_bytes ? 2105 : 2101, 0, st);
+    ProfScope ps(prof_key(kProfJpeg, seg_bytes ? 5 : 1), 0, st);
     if (seg_bytes)
       hipLaunchKernelGGL(jpeg_entropy_split_kernel, dim3((unsigned)nlanes), dim3(kJpegSplitThreads), 0, st,
                          (const uint4 *)bytes, nbytes, desc, N, lanes, nlanes, huff, nh, coef, status, seg_bytes, rounds);
     else
       hipLaunchKernelGGL(jpeg_entropy_kernel, dim3((unsigned)((nlanes + kJpegLanes - 1) / kJpegLanes)), dim3(64), 0, st,
                          (const uint4 *)bytes, nbytes, desc, N, lanes, nlanes, huff, nh, coef, status);
-    prof_close(ps);
-    XM_LAUNCH_CHECK();
   }
+  XM_LAUNCH_CHECK();
   {
-    void *ps = prof_open(2102, 0, st);
+    ProfScope ps(prof_key(kProfJpeg, 2), 0, st);
     const long long nb = coef_elems / 64;
     hipLaunchKernelGGL(jpeg_idct_kernel, dim3((unsigned)((nb + 255) / 256)), dim3(256), 0, st, coef, nb, desc, N, tables, nq,
                        planes);
-    prof_close(ps);
-    XM_LAUNCH_CHECK();
   }
+  XM_LAUNCH_CHECK();
   {
-    void *ps = prof_open(2103, 0, st);
+    ProfScope ps(prof_key(kProfJpeg, 3), 0, st);
     const long long np = pixel_floats / 3;
     hipLaunchKernelGGL(jpeg_colour_kernel, dim3((unsigned)((np + 255) / 256)), dim3(256), 0, st, planes, desc, N, np, pix);
-    prof_close(ps);
-    XM_LAUNCH_CHECK();
   }
-  if (faces) {
-    void *ps = prof_open(2104, 0, st);
-    rc = face_ragged_launch(pix, desc, kJpegDesc, D_H, D_W, D_PIX, N, crop, Ho, Wo, avg3, faces, st);
-    prof_close(ps);
-    if (rc) return rc;
-  }
-  return XM_OK;
+  XM_LAUNCH_CHECK();
+  if (!faces) return XM_OK;
+  ProfScope ps(prof_key(kProfJpeg, 4), 0, st);
+  return face_ragged_launch(pix, desc, kJpegDesc, D_H, D_W, D_PIX, N, crop, Ho, Wo, avg3, faces, st);
 }
 
 extern "C" {

@@ -20,6 +20,7 @@
 #include <algorithm>
 
 #include "pixcsv_plan.h"
+#include "prof.h"
 #include "xm_common.h"
 
 namespace xm {
@@ -200,10 +201,9 @@ int xm_pixcsv_decode_batch(const unsigned char *bytes, long long nbytes, const l
   if (out_floats < (long long)H * W)
     return fail(XM_EINVAL, "pixcsv_decode_batch: out_floats = %lld holds no image of %d x %d", out_floats, H, W);
   hipStream_t st = (hipStream_t)stream;
-  void *ps = prof_open(2300, 0, st);
+  ProfScope ps(prof_key(kProfPixcsv), 0, st);
   hipLaunchKernelGGL(pixcsv_decode_kernel, dim3((unsigned)N), dim3(kPixThreads), 0, st, (const uint4 *)bytes, nbytes, desc, H, W,
                      transpose, out, out_floats, status);
-  prof_close(ps);
   XM_LAUNCH_CHECK();
   return XM_OK;
 }

@@ -24,6 +24,7 @@
 // the tile list, and at most N + G of them -- and spec_finish_kernel merges a clip's slots in block order in fp64.  No
 // atomics anywhere: the result is the same run to run.  The magnitudes inside the crop wait in the workspace for their
 // statistics; frames outside it never leave the registers.
+#include "prof.h"
 #include "xm_common.h"
 
 namespace xm {
@@ -310,29 +311,25 @@ int xm_spec_bucket_batch(const float *wav, long long wav_len, const long long *d
   double *part = ws.take<double>(slots * 2 * B);
   float *raw = ws.take<float>((size_t)N * rsize * B);
   {
-    void *ps = prof_open(2000, 0, st);
+    ProfScope ps(prof_key(kProfSpec, 0), 0, st);
     hipLaunchKernelGGL(spec_bank_kernel, dim3((Kp + 31) / 32, 2 * B / 32), dim3(256), 0, st, bank, bT, taps, Kp, 2 * B);
-    prof_close(ps);
   }
   XM_LAUNCH_CHECK();
   {
-    void *ps = prof_open(2001, 0, st);
+    ProfScope ps(prof_key(kProfSpec, 1), 0, st);
     hipLaunchKernelGGL(spec_plan_kernel, dim3(1), dim3(1024), 0, st, desc, N, taps, hop, tile_start);
-    prof_close(ps);
   }
   XM_LAUNCH_CHECK();
   {
-    void *ps = prof_open(2002, 0, st);
+    ProfScope ps(prof_key(kProfSpec, 2), 0, st);
     hipLaunchKernelGGL(spec_gemm_kernel, dim3(G), dim3(256), lds, st, wav, wav_len, desc, N, rsize, bT, taps, hop,
                        tile_start, part, raw);
-    prof_close(ps);
   }
   XM_LAUNCH_CHECK();
   {
-    void *ps = prof_open(2003, 0, st);
+    ProfScope ps(prof_key(kProfSpec, 3), 0, st);
     hipLaunchKernelGGL(spec_finish_kernel, dim3((rsize + 15) / 16, N), dim3(256), 0, st, desc, N, rsize, taps, hop,
                        tile_start, part, G, raw, out);
-    prof_close(ps);
   }
   XM_LAUNCH_CHECK();
   return XM_OK;

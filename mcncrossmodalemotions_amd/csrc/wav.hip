@@ -17,6 +17,7 @@
 //                        No atomics, no workspace; every output float has exactly one writer.
 #include <algorithm>
 
+#include "prof.h"
 #include "wav_plan.h"
 #include "xm_common.h"
 
@@ -251,10 +252,9 @@ int xm_wav_decode_batch(const unsigned char *bytes, long long nbytes, const long
   if (nbytes == 0 || out_floats == 0) return XM_OK;   // no data chunk holds a byte: nothing to write
   hipStream_t st = (hipStream_t)stream;
   const long long tiles = (out_floats + 6 + kWavTile) / kWavTile;     // an upper bound of the kernel's tile count
-  void *ps = prof_open(2200, 0, st);
+  ProfScope ps(prof_key(kProfWav), 0, st);
   hipLaunchKernelGGL(wav_decode_kernel, dim3((unsigned)std::min<long long>(tiles, kWavMaxBlocks)), dim3(256), 0, st,
                      (const uint32_t *)bytes, nbytes, desc, N, (uint32_t *)out, out_floats);
-  prof_close(ps);
   XM_LAUNCH_CHECK();
   return XM_OK;
 }

@@ -94,11 +94,6 @@ int comm_force_single(int on);
 // spec.hip: test switch behind xm_debug_set("spec_blocks", v)
 extern int g_spec_blocks;
 
-// conv.hip: one record of the xm_prof_* hooks (include/xmodal_prof.h) around a launch of another translation unit;
-// prof_open returns nullptr while the profiler is off, prof_close(nullptr) does nothing
-void *prof_open(int key, double flops, hipStream_t stream);
-void prof_close(void *scope);
-
 // persistent small device objects keyed by content (tap tables)
 const void *cached_device_table(const void *host, size_t bytes);
 

@@ -5,7 +5,6 @@
     python tests/_dispatch_worker.py keys out.json        one launch per tune kind with find mode on: the table keys
 
 Only vl.* (the public C ABI) and the debug switches of _lib are used.  Inputs are seeded on the host."""
-import ctypes as C
 import hashlib
 import json
 import os
@@ -23,8 +22,8 @@ STEM = dict(H=268, W=13, N=2)          # 7 x 7 / stride 2, no padding: 131 x 4 o
 class Recorder:
     def __init__(self):
         import torch
-        from mcncrossmodalemotions_amd import _lib, vl
-        self.torch, self.vl, self.L = torch, vl, _lib.load()
+        from mcncrossmodalemotions_amd import _lib, prof, vl
+        self.torch, self.vl, self.prof, self.L = torch, vl, prof, _lib.load()
         self.cases = {}
         self.count = 0
 
@@ -41,28 +40,17 @@ class Recorder:
 
     def case(self, name, fn, **switches):
         """run fn() under the given debug switches; store the kernels it launched and the digests of what it returned"""
-        L, torch = self.L, self.torch
+        L = self.L
         old = {k: L.xm_debug_set(k.encode(), int(v)) for k, v in switches.items()}
-        L.xm_prof_enable(1)
         try:
-            out = fn()
-            torch.cuda.synchronize()
+            out, rows = self.prof.kernels_run(fn, L)
         finally:
-            L.xm_prof_enable(0)
             for k, v in old.items():
                 L.xm_debug_set(k.encode(), v)
-        cap = 64
-        keys, ms, fl, cnt = (C.c_int * cap)(), (C.c_double * cap)(), (C.c_double * cap)(), (C.c_longlong * cap)()
-        n = L.xm_prof_collect(cap, keys, ms, fl, cnt)
-        names = []
-        for i in range(min(n, cap)):
-            buf = C.create_string_buffer(128)
-            L.xm_prof_kernel_name(keys[i], buf, 128)
-            names.append("%s x%d" % (buf.value.decode(), cnt[i]))
         assert out is not None, name + ": the entry point refused the shape"
         outs = [t for t in (out if isinstance(out, (tuple, list)) else [out]) if t is not None]
         assert name not in self.cases, name
-        self.cases[name] = {"kernels": names, "sha256": [self.digest(t) for t in outs]}
+        self.cases[name] = {"kernels": ["%s x%d" % (r.name, r.launches) for r in rows], "sha256": [self.digest(t) for t in outs]}
         return out
 
 

@@ -21,7 +21,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 WORKER = os.path.join(ROOT, "tests", "_dispatch_worker.py")
 GOLDEN = os.path.join(ROOT, "tests", "golden", "conv_dispatch_digest.json")
 
-# every ProfScope kind of csrc/conv.hip has to occur in the record (and therefore in every later run)
+# every ProfKind (csrc/prof.h) that csrc/conv.hip records has to occur in the record (and therefore in every later run)
 KERNELS = ["conv_gemm_kernel<", "conv_gemm_dma_kernel<", "conv_gemm_multi_kernel<", "conv_wgrad_kernel<", "conv_halo_kernel<2, 2, 2, 2, 512>",
            "conv_halo_kernel<3, 1, 1, 4, 512>", "conv_halo_kernel<3, 1, 1, 4, 1024>", "conv_halo_multi_kernel<", "conv_stem_kernel<",
            "conv_stem_wgrad_kernel<", "conv_stem_wgrad_bnp_kernel<", "conv_wgrad_patch_kernel<", "conv_wgrad_patch_s2_kernel<",

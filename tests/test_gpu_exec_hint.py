@@ -16,11 +16,10 @@ pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 CHILD = r"""
-import sys, ctypes as C
+import sys
 import numpy as np, torch
 sys.path.insert(0, %(root)r)
-from mcncrossmodalemotions_amd import vl, _lib
-L = _lib.load()
+from mcncrossmodalemotions_amd import prof, vl
 hint, history, out = int(sys.argv[1]), sys.argv[2], sys.argv[3]
 vl.set_exec_hint(hint)
 rng = np.random.default_rng(5)
@@ -38,16 +37,9 @@ if history != "none":
         else:
             vl.vl_nnconv(xs, fs, None, pad=1)
     torch.cuda.synchronize()
-L.xm_prof_enable(1)
-_, df, _ = vl.vl_nnconv(x, f, None, dz, pad=1, no_der_data=True)
-torch.cuda.synchronize()
-L.xm_prof_enable(0)
-keys = (C.c_int * 16)(); ms = (C.c_double * 16)(); fl = (C.c_double * 16)(); cnt = (C.c_longlong * 16)()
-names = []
-for i in range(L.xm_prof_collect(16, keys, ms, fl, cnt)):
-    b = C.create_string_buffer(128); L.xm_prof_kernel_name(keys[i], b, 128); names.append(b.value.decode())
+(_, df, _), rows = prof.kernels_run(lambda: vl.vl_nnconv(x, f, None, dz, pad=1, no_der_data=True))
 np.save(out, vl.to_numpy(df))
-print("KERNELS", ";".join(names))
+print("KERNELS", ";".join(r.name for r in rows))
 """
 
 

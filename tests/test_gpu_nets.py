@@ -592,10 +592,9 @@ def test_profiler_names_are_the_kernels_that_exist(gpu):
     instantiated kernel of the library (the symbol rocprofv3 prints) -- round 3 decoded the merged strided-dgrad kernel's
     key with the wrong divisor and reported an instantiation that had not run.  A distillation step on narrow networks
     (every kernel family: implicit GEMM, LDS-DMA, halo, merged dgrad, wgrad, stem + its fused filter derivative)."""
-    import ctypes as C
     import subprocess
     import torch
-    from mcncrossmodalemotions_amd import _lib, batch as xbatch, train, vl, zoo
+    from mcncrossmodalemotions_amd import _lib, batch as xbatch, prof, train, vl, zoo
     L = _lib.load()
     syms = subprocess.run(["nm", "-C", _lib.SO_PATH], capture_output=True, text=True).stdout
     teacher = zoo.ferPlusZoo("resnet50-ferplus", seed=1, width_mult=0.25, blocks=(1, 1, 1, 1))
@@ -608,23 +607,15 @@ def test_profiler_names_are_the_kernels_that_exist(gpu):
     faces = xbatch.getImageBatch(8, seed=4)
     spec = vl.spec_rownorm(torch.randn((8, 1, 300, 512), device="cuda").abs_().permute(3, 2, 1, 0))
     opts = train.TrainOpts(batchSize=8)
-    L.xm_prof_enable(1)
-    teacher.eval(["data", faces])
-    tl = teacher.vars["prediction"].value
-    train.train_step(student, ["data", spec, "logitTarget", tl, "maxLabel", vl.max_label(tl)], opts, 0, None, 8)
-    torch.cuda.synchronize()
-    L.xm_prof_enable(0)
-    cap = 64
-    keys, ms, fl, cnt = (C.c_int * cap)(), (C.c_double * cap)(), (C.c_double * cap)(), (C.c_longlong * cap)()
-    n = L.xm_prof_collect(cap, keys, ms, fl, cnt)
-    assert n >= 6
-    names = set()
-    for i in range(min(n, cap)):
-        buf = C.create_string_buffer(128)
-        assert L.xm_prof_kernel_name(keys[i], buf, 128) == 0
-        name = buf.value.decode()
-        names.add(name)
-        assert ("xm::%s(" % name) in syms, "%r (key %d) is not a kernel of %s" % (name, keys[i], _lib.SO_PATH)
+    with prof.recording(L):
+        teacher.eval(["data", faces])
+        tl = teacher.vars["prediction"].value
+        train.train_step(student, ["data", spec, "logitTarget", tl, "maxLabel", vl.max_label(tl)], opts, 0, None, 8)
+    rows = prof.collect(L)      # a key without a name raises
+    assert len(rows) >= 6
+    names = {r.name for r in rows}
+    for r in rows:
+        assert ("xm::%s(" % r.name) in syms, "%r (key %d) is not a kernel of %s" % (r.name, r.key, _lib.SO_PATH)
     fam = {nm.split("<")[0] for nm in names}
     assert {"conv_gemm_kernel", "conv_wgrad_kernel", "conv_stem_bnpool_fwd_kernel", "conv_stem_wgrad_pool_kernel", "stem_gram_kernel"} <= fam \
         and len(fam) >= 6, fam
@@ -633,18 +624,10 @@ def test_profiler_names_are_the_kernels_that_exist(gpu):
     x = torch.randn((16, 96, 73, 126), device="cuda").permute(3, 2, 1, 0)
     f = (torch.randn((256, 96, 5, 5), device="cuda") * 0.05).permute(3, 2, 1, 0)
     dzdy = torch.randn((16, 256, 36, 62), device="cuda").permute(3, 2, 1, 0)
-    L.xm_prof_enable(1)
-    vl.vl_nnconv(x, f, None, dzdy, stride=2, pad=1, no_der_filters=True)
-    torch.cuda.synchronize()
-    L.xm_prof_enable(0)
-    n = L.xm_prof_collect(cap, keys, ms, fl, cnt)
-    merged = []
-    assert n <= cap
-    for i in range(n):
-        buf = C.create_string_buffer(128)
-        L.xm_prof_kernel_name(keys[i], buf, 128)
-        assert ("xm::%s(" % buf.value.decode()) in syms, buf.value.decode()
-        merged.append(buf.value.decode())
+    _, rows = prof.kernels_run(lambda: vl.vl_nnconv(x, f, None, dzdy, stride=2, pad=1, no_der_filters=True), L)
+    merged = [r.name for r in rows]
+    for m in merged:
+        assert ("xm::%s(" % m) in syms, m
     assert any("multi" in m for m in merged), merged
 
 

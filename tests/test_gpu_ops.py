@@ -431,21 +431,9 @@ HALO_CASES = [(30, 17, 16, 3, 40, (1, 1, 1, 1)),      # student conv3-5 geometry
 
 def _kernels_run(L, fn):
     """names of the convolution kernels `fn` launched (profiler hooks of the library)"""
-    import ctypes as C
-    import torch
-    L.xm_prof_enable(1)
-    out = fn()
-    torch.cuda.synchronize()
-    L.xm_prof_enable(0)
-    cap = 32
-    keys, ms, fl, cnt = (C.c_int * cap)(), (C.c_double * cap)(), (C.c_double * cap)(), (C.c_longlong * cap)()
-    n = L.xm_prof_collect(cap, keys, ms, fl, cnt)
-    names = []
-    for i in range(min(n, cap)):
-        buf = C.create_string_buffer(128)
-        L.xm_prof_kernel_name(keys[i], buf, 128)
-        names.append(buf.value.decode())
-    return out, names
+    from mcncrossmodalemotions_amd import prof
+    out, rows = prof.kernels_run(fn, L)
+    return out, [r.name for r in rows]
 
 
 @pytest.mark.parametrize("case", HALO_CASES)

@@ -160,20 +160,9 @@ def test_driver_bookkeeping(gpu):
 
 
 def _launches(L, fn):
-    import torch
-    L.xm_prof_enable(1)
-    out = fn()
-    torch.cuda.synchronize()
-    L.xm_prof_enable(0)
-    cap = 32
-    keys, ms, fl, cnt = (C.c_int * cap)(), (C.c_double * cap)(), (C.c_double * cap)(), (C.c_longlong * cap)()
-    n = L.xm_prof_collect(cap, keys, ms, fl, cnt)
-    names = {}
-    for i in range(min(n, cap)):
-        buf = C.create_string_buffer(128)
-        L.xm_prof_kernel_name(keys[i], buf, 128)
-        names[buf.value.decode()] = int(cnt[i])
-    return out, names
+    from mcncrossmodalemotions_amd import prof
+    out, rows = prof.kernels_run(fn, L)
+    return out, {r.name: r.launches for r in rows}
 
 
 def test_fixed_launch_count_no_tuning(gpu, nine):

@@ -173,19 +173,8 @@ def test_out_base_past_2_31(gpu, golden):
 
 
 def _launches(L, fn):
-    L.xm_prof_enable(1)
-    fn()
-    torch.cuda.synchronize()
-    L.xm_prof_enable(0)
-    cap = 32
-    keys, ms, fl, cnt = (C.c_int * cap)(), (C.c_double * cap)(), (C.c_double * cap)(), (C.c_longlong * cap)()
-    n = L.xm_prof_collect(cap, keys, ms, fl, cnt)
-    out = {}
-    for i in range(min(n, cap)):
-        b = C.create_string_buffer(128)
-        L.xm_prof_kernel_name(keys[i], b, 128)
-        out[b.value.decode()] = int(cnt[i])
-    return out
+    from mcncrossmodalemotions_amd import prof
+    return {r.name: r.launches for r in prof.kernels_run(fn, L)[1]}
 
 
 def test_one_launch_whatever_n(gpu, golden, names):

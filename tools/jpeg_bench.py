@@ -11,7 +11,6 @@ golden files of tests/golden/jpeg_small.npz repeated, and the PIL lines are left
 split=): the entropy kernel's time unsplit and at seg_bytes 64 / 128 / 256 / 512 with the mean and the maximum of the
 rounds per lane, the whole decode back to back, and buildImdb's loop unsplit, split and fed by PIL on 10 threads."""
 import argparse
-import ctypes as C
 import io
 import os
 import sys
@@ -23,7 +22,7 @@ import torch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
-from mcncrossmodalemotions_amd import _lib, fetch_emovoxceleb_imdb as fe, vl, zoo  # noqa: E402
+from mcncrossmodalemotions_amd import _lib, fetch_emovoxceleb_imdb as fe, prof, vl, zoo  # noqa: E402
 
 
 def timeit(fn, reps):
@@ -67,20 +66,10 @@ def pil_rate(files, threads):
 
 
 def kernel_ms(L, fn, reps):
-    L.xm_prof_enable(1)
-    for _ in range(reps):
-        fn()
-    torch.cuda.synchronize()
-    L.xm_prof_enable(0)
-    cap = 32
-    keys, ms, fl, cnt = (C.c_int * cap)(), (C.c_double * cap)(), (C.c_double * cap)(), (C.c_longlong * cap)()
-    n = L.xm_prof_collect(cap, keys, ms, fl, cnt)
-    out = {}
-    for i in range(min(n, cap)):
-        b = C.create_string_buffer(128)
-        L.xm_prof_kernel_name(keys[i], b, 128)
-        out[b.value.decode()] = ms[i] / max(cnt[i], 1)
-    return out
+    with prof.recording(L):
+        for _ in range(reps):
+            fn()
+    return {r.name: r.ms / max(r.launches, 1) for r in prof.collect(L)}
 
 
 def loop_rate(teacher, imdb, numIms, **src):

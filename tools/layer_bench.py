@@ -3,6 +3,7 @@
 usage: python tools/layer_bench.py [--net resnet50|senet50|vggvox] [--n 32] [--reps 20] [--bwd]
 Prints one row per dagnn.Conv layer: geometry, time, TFLOP/s, share of the summed conv time."""
 import argparse
+import contextlib
 import os
 import sys
 
@@ -10,36 +11,25 @@ import numpy as np
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-from mcncrossmodalemotions_amd import dagnn, vl, zoo  # noqa: E402
+from mcncrossmodalemotions_amd import _lib, dagnn, prof, vl, zoo  # noqa: E402
 
 
 def timeit(fn, reps, tag=None):
     for _ in range(3):
         fn()
     torch.cuda.synchronize()
-    prof = os.environ.get("LB_PROF") and tag
-    if prof:
-        import ctypes as C
-        from mcncrossmodalemotions_amd import _lib
-        L = _lib.load()
-        L.xm_prof_enable(1)
+    profiled = os.environ.get("LB_PROF") and tag
     s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    s.record()
-    for _ in range(reps):
-        fn()
-    e.record()
+    with prof.recording() if profiled else contextlib.nullcontext():
+        s.record()
+        for _ in range(reps):
+            fn()
+        e.record()
     torch.cuda.synchronize()
-    if prof:
-        L.xm_prof_enable(0)
-        cap = 64
-        keys = (C.c_int * cap)(); ms = (C.c_double * cap)(); fl = (C.c_double * cap)(); cnt = (C.c_longlong * cap)()
-        n = L.xm_prof_collect(cap, keys, ms, fl, cnt)
-        out = []
-        for i in range(n):
-            buf = C.create_string_buffer(128); L.xm_prof_kernel_name(keys[i], buf, 128)
-            out.append("%s x%d avg %.3f ms" % (buf.value.decode(), cnt[i], ms[i] / cnt[i]))
+    if profiled:
+        out = ["%s x%d avg %.3f ms" % (r.name, r.launches, r.ms / r.launches) for r in prof.collect()]
         print("[prof] %s: wall %.3f ms/call | %s | ws %d MB" % (tag, s.elapsed_time(e) / reps, "; ".join(out),
-                                                          L.xm_workspace_bytes() >> 20), file=sys.stderr)
+                                                          _lib.load().xm_workspace_bytes() >> 20), file=sys.stderr)
     return s.elapsed_time(e) / reps
 
 
@@ -52,7 +42,6 @@ def main():
     args = ap.parse_args()
     dev = torch.device("cuda:0")
     if os.environ.get("LB_RESERVE"):
-        from mcncrossmodalemotions_amd import _lib
         _lib.check(_lib.load().xm_workspace_reserve(int(os.environ["LB_RESERVE"]) << 20))
     rng = np.random.default_rng(0)
     if args.net == "vggvox":

@@ -21,7 +21,7 @@ import numpy as np
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-from mcncrossmodalemotions_amd import _lib, batch, external, vl  # noqa: E402
+from mcncrossmodalemotions_amd import _lib, batch, external, prof, vl  # noqa: E402
 
 FS, NW, NS = 16000, 400, 160
 
@@ -65,19 +65,7 @@ def batched(wav, offs):
 
 
 def gemm_ms(L, fn):
-    L.xm_prof_enable(1)
-    fn()
-    torch.cuda.synchronize()
-    L.xm_prof_enable(0)
-    cap = 32
-    keys, ms, fl, cnt = (C.c_int * cap)(), (C.c_double * cap)(), (C.c_double * cap)(), (C.c_longlong * cap)()
-    n = L.xm_prof_collect(cap, keys, ms, fl, cnt)
-    for i in range(min(n, cap)):
-        buf = C.create_string_buffer(128)
-        L.xm_prof_kernel_name(keys[i], buf, 128)
-        if buf.value.decode() == "spec_gemm_kernel":
-            return float(ms[i])
-    return float("nan")
+    return {r.name: r.ms for r in prof.kernels_run(fn, L)[1]}.get("spec_gemm_kernel", float("nan"))
 
 
 def main():

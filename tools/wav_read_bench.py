@@ -21,7 +21,7 @@ import torch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
-from mcncrossmodalemotions_amd import _lib, vl  # noqa: E402
+from mcncrossmodalemotions_amd import _lib, prof, vl  # noqa: E402
 
 FS = 16000
 DT = {vl.WAV_U8: "u1", vl.WAV_S16: "<i2", vl.WAV_S24: None, vl.WAV_S32: "<i4", vl.WAV_F32: "<f4", vl.WAV_F64: "<f8"}
@@ -54,20 +54,10 @@ def device_ms(fn, reps):
 
 
 def kernel_ms(L, fn, reps):
-    L.xm_prof_enable(1)
-    for _ in range(reps):
-        fn()
-    torch.cuda.synchronize()
-    L.xm_prof_enable(0)
-    cap = 32
-    keys, ms, fl, cnt = (C.c_int * cap)(), (C.c_double * cap)(), (C.c_double * cap)(), (C.c_longlong * cap)()
-    n = L.xm_prof_collect(cap, keys, ms, fl, cnt)
-    out = {}
-    for i in range(min(n, cap)):
-        b = C.create_string_buffer(128)
-        L.xm_prof_kernel_name(keys[i], b, 128)
-        out[b.value.decode()] = ms[i] / max(cnt[i], 1)
-    return out
+    with prof.recording(L):
+        for _ in range(reps):
+            fn()
+    return {r.name: r.ms / max(r.launches, 1) for r in prof.collect(L)}
 
 
 def host_clock(fn, reps):
