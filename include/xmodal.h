@@ -57,7 +57,7 @@ enum { XM_FUSE_RELU = 1, XM_BN_BATCH_MOMENTS = 2, XM_FUSE_SIGMOID = 4 };
 
 /* ABI revision: 100 = round 1; 101 = xm_nnbnorm_relu_pool_backward gained `y_pool`, exchange entry points return
  * XM_EINVAL without a communicator; 102 = + xm_nnconv_forward_moments, xm_nnbnorm_backward_dxsum, xm_nnconv_forward_gated;
- * 103 = + xm_nnpool_global_avg_backward_accum; 104 = + xm_nnconv_backward_filter_bnrelupool, xm_nndropout_forward / _apply, xm_resample, xm_se_tail_backward_reduce / _apply, xm_se_squeeze_bn, xm_scale_axpy_bn; 105 = + xm_set_exec_hint / xm_get_exec_hint; 106 = + xm_nnconv_bnorm_relu_pool_forward, xm_stem_gram, xm_stem_gram_moments, xm_nnconv_backward_filter_bnrelupool_gram; 107 = + xm_nnaffinegrid / _backward, xm_nnbilinearsampler / _backward, xm_ferplus_batch; 108 = + XM_AGG_PEAK, xm_mnrfit, xm_mnrval; 109 = + xm_roc, xm_roc_launches, xm_label_hist; 110 = + xm_group_rows, xm_gather_rows, xm_scatter_rows, xm_track_peaks; 111 = + xm_wav_batch; 112 = + xm_spec_bucket_batch; 113 = + xm_jpeg_plan, xm_jpeg_decode_batch; 114 = + xm_wav_plan, xm_wav_decode_batch; 115 = + xm_jpeg_decode_batch_split, xm_jpeg_split_geometry; 116 = + xm_pixcsv_plan, xm_pixcsv_decode_batch, xm_pixcsv_geometry (additions never change the revision's meaning for older bindings).  A binding checks xm_version() >= the revision it was written against. */
+ * 103 = + xm_nnpool_global_avg_backward_accum; 104 = + xm_nnconv_backward_filter_bnrelupool, xm_nndropout_forward / _apply, xm_resample, xm_se_tail_backward_reduce / _apply, xm_se_squeeze_bn, xm_scale_axpy_bn; 105 = + xm_set_exec_hint / xm_get_exec_hint; 106 = + xm_nnconv_bnorm_relu_pool_forward, xm_stem_gram, xm_stem_gram_moments, xm_nnconv_backward_filter_bnrelupool_gram; 107 = + xm_nnaffinegrid / _backward, xm_nnbilinearsampler / _backward, xm_ferplus_batch; 108 = + XM_AGG_PEAK, xm_mnrfit, xm_mnrval; 109 = + xm_roc, xm_roc_launches, xm_label_hist; 110 = + xm_group_rows, xm_gather_rows, xm_scatter_rows, xm_track_peaks; 111 = + xm_wav_batch; 112 = + xm_spec_bucket_batch; 113 = + xm_jpeg_plan, xm_jpeg_decode_batch; 114 = + xm_wav_plan, xm_wav_decode_batch; 115 = + xm_jpeg_decode_batch_split, xm_jpeg_split_geometry; 116 = + xm_pixcsv_plan, xm_pixcsv_decode_batch, xm_pixcsv_geometry; 117 = + xm_nnconv_forward_strided_residual (additions never change the revision's meaning for older bindings).  A binding checks xm_version() >= the revision it was written against. */
 int xm_version(void);
 const char *xm_last_error(void);
 /* Device memory for hosts that have no device-array type of their own (MATLAB's gpuArray is CUDA-only: on an
@@ -133,6 +133,23 @@ int xm_nnconv_forward_gated(const float *x, int H, int W, int C, int N, const fl
                             int FC, int K, const float *b, float *y, int sy, int sx, int pt, int pb,
                             int pl, int pr, int dy, int dx, const float *scale, const float *shift,
                             const float *gate, const float *residual, int flags, void *stream);
+/* Extension (ABI 117): xm_nnconv_forward_gated whose residual has an extent of its own, res_H x res_W x K x N, and is
+ * SAMPLED with a stride: output pixel (oy, ox) adds residual(oy * res_sy, ox * res_sx, k, n).  gate == NULL is the plain
+ * fused epilogue of xm_nnconv_forward_fused; both older entry points are this one with the residual at output extent and
+ * unit stride.  XM_EINVAL unless Ho == floor((res_H - 1) / res_sy) + 1 and Wo == floor((res_W - 1) / res_sx) + 1.
+ * What it is for: the last 1 x 1 expansion of a ResNet stage whose only readers are the 1 x 1 / stride-s convolutions that
+ * open the next stage (Caffe-style: stride on the first 1 x 1).  Run with stride s over its own input it computes exactly the
+ * pixels those readers look at; its shortcut operand still has the full extent and is read at every s-th row and column.
+ * Restriction: a call whose residual is really strided (not at output extent with unit stride) runs the register-staged
+ * implicit-GEMM kernel only and NEVER splits its reduction (no split-K, no hybrid remainder), so that, with a tile configuration
+ * of the same chain structure, its outputs are the bits the full-extent layer gives the same pixels.  The price: a problem
+ * with few output tiles and a deep reduction underfills the chip (the pruned res4f expansion at 32 faces: 208 blocks on 256
+ * CUs).  Only the "conv_splits" test switch (xmodal_prof.h) makes such a call split. */
+int xm_nnconv_forward_strided_residual(const float *x, int H, int W, int C, int N, const float *f, int FH, int FW,
+                                       int FC, int K, const float *b, float *y, int sy, int sx, int pt, int pb,
+                                       int pl, int pr, int dy, int dx, const float *scale, const float *shift,
+                                       const float *gate, const float *residual, int res_H, int res_W, int res_sy,
+                                       int res_sx, int flags, void *stream);
 /* Extension: Y = vl_nnconv(X, F, B, ...) AND the batch moments of Y that a train-mode vl_nnbnorm(Y, G, B) would
  * compute first -- moments_out (K x 2, column-major) = [mean_k, sqrt(var_k + epsilon)] over H x W x N, biased
  * variance (emoVoxZoo.m:118-123: every dagnn.Conv of the student is followed by dagnn.BatchNorm).  Hand them to

@@ -47,6 +47,8 @@ int xm_prof_kernel_name(int key, char *buf, int len);
  * one; INT_MIN = unknown key.
  *   "conv_cfg"       tile configuration of every implicit-GEMM launch, 0 .. xm_debug_get("num_conv_cfgs") - 1; -1 = measured / modelled choice
  *   "conv_splits"    split-K factor of the implicit-GEMM launches (0 = automatic)
+ *   "conv_last_combine"  (read only) what the most recent implicit-GEMM launch left to conv_splitk_epilogue_kernel: 0 = nothing,
+ *                    z > 0 = z partial slabs combined by its 16-byte form, z < 0 = |z| slabs by its scalar form
  *   "conv_halo"      1 + v: halo-patch kernel variant v (0: 128-row tiles, 1: 96-row tiles, 2: 96-row tiles / tall patch) wherever it
  *                    can run, another runnable variant otherwise; 0: never; -1: measured choice (default)
  *   "conv_stem"      1: the single-channel stem kernels (conv_stem_kernel, conv_stem_wgrad_*; also gates the Gram route's kernels)

@@ -299,6 +299,9 @@ static inline double cfg_eff(const Cfg &c) {
 }
 
 static int g_force_splits = 0;  // test hook
+// what the most recent launch_gemm left to conv_splitk_epilogue_kernel: 0 = nothing (the GEMM's own epilogue stored y), z > 0 =
+// z partial slabs combined by the 16-byte form, z < 0 = |z| slabs by the scalar form (xm_debug_get("conv_last_combine"): tests)
+static int g_last_combine = 0;
 
 // With few output tiles the reduction is split over grid.y; the split count fills ONE round of
 // 2 co-resident blocks per CU (no tail round).
@@ -411,6 +414,7 @@ static int hybrid_plan(const ConvGemmArgs &a, int ci, int *full_out) {
   const bool off = !path_on(kPathHybrid);
   *full_out = 0;
   if (off || is_dma_cfg(ci) || g_force_splits > 0) return 1;
+  if (a.rsOn) return 1;       // (a strided-residual launch keeps ONE reduction chain per output: see gemm_slab_floats)
   if (a.statPart && (!a.vecStore || a.relu || a.resid)) return 1;   // conv_splitk_epilogue_stats_kernel's case only
   const int tiles = a.nbm * a.nbn, slots = 256 * kCfgOcc[ci];
   if (tiles <= slots || a.nkt < 16) return 1;
@@ -428,6 +432,12 @@ static size_t gemm_slab_floats(const ConvGemmArgs &a, int ci, int *splits_out) {
   const Cfg &c = kCfgs[ci];
   int nbm = (a.M + c.bm() - 1) / c.bm(), nbn = (a.NP + c.bn() - 1) / c.bn();
   int splits = pick_splits(nbm * nbn, a.Rp / kBK);
+  // A strided-residual launch is the full-extent layer computed at a quarter (1 / s^2) of its pixels, and it has to give those
+  // pixels the values the full-extent launch gives them.  That launch has tiles enough to run unsplit, so neither the fewer
+  // tiles of the pruned launch (split-K) nor a partly filled last round (hybrid_plan) may cut its reduction into partial sums:
+  // with a configuration of the same chain structure (one accumulator chain, or the two of the 1 x 1 wave tiles) the results
+  // are then the same bits.  The launch is a few hundred short blocks either way.  (The test hook still forces a split.)
+  if (a.rsOn && g_force_splits <= 0) splits = 1;
   *splits_out = splits;
   size_t need = splits > 1 ? (size_t)splits * a.M * ((a.NP + 3) & ~3) : 0;
   if (splits == 1 && !is_dma_cfg(ci)) {
@@ -496,6 +506,7 @@ static int launch_gemm(ConvGemmArgs &a, int mode, int ci, int splits, float *sla
       launch_gemm_cfg<0>(ci, a, grid, st);
   }
   XM_LAUNCH_CHECK();
+  g_last_combine = 0;
   if (splits > 1 || hyS > 1) {
     const int z = splits > 1 ? splits : hyS;
     const int np = a.NP - a.hyP0;                       // pixels the slabs cover
@@ -508,6 +519,7 @@ static int launch_gemm(ConvGemmArgs &a, int mode, int ci, int splits, float *sla
       a.statNcg = statBase + chunks;
     } else
       launch_splitk_epilogue(a, z, np, vec, st);
+    g_last_combine = vec ? z : -z;
     XM_LAUNCH_CHECK();
   }
   return XM_OK;
@@ -1231,6 +1243,10 @@ struct FwdOperands {
   const int2 *taps;
   int lda, Rp, relu;
   bool bigTaps, dma_ok;
+  // the residual's own geometry: extent rH x rW (x K x N), sampled at (oy * rsy, ox * rsx).  rH == Ho, rW == Wo, unit strides
+  // is the plain residual at output extent.
+  int rH = 0, rW = 0, rsy = 1, rsx = 1;
+  bool resid_strided(const Geo &g) const { return resid && (rH != g.Ho || rW != g.Wo || rsy != 1 || rsx != 1); }
 };
 
 // the implicit-GEMM problem of filter group `grp`
@@ -1243,6 +1259,12 @@ static ConvGemmArgs forward_args(const Geo &g, int grp, const FwdOperands &o) {
   a.bias = o.b ? o.b + grp * g.Kg : nullptr;
   a.scale = o.scale ? o.scale + grp * g.Kg : nullptr, a.shift = o.shift ? o.shift + grp * g.Kg : nullptr;
   a.resid = o.resid ? o.resid + yoff : nullptr, a.relu = o.relu;
+  if (o.resid_strided(g)) {
+    // the residual's own group offset and strides; the epilogues fetch it pixel by pixel (ConvGemmArgs::rsOn)
+    a.resid = o.resid + (size_t)grp * g.Kg * o.rH * o.rW;
+    a.rsOn = 1, a.rsy = o.rsy, a.rsx = o.rsx, a.rH = o.rH;
+    a.rChanStride = o.rH * o.rW, a.rSampleStride = o.rH * o.rW * g.K;
+  }
   a.gate = o.gate ? o.gate + (size_t)grp * g.Kg : nullptr, a.gateStride = g.K;
   a.M = g.Kg, a.Rp = o.Rp, a.Rtrue = g.R;
   a.PI = g.Ho, a.PJ = g.Wo, a.NP = g.Ho * g.Wo * g.N;
@@ -1254,8 +1276,10 @@ static ConvGemmArgs forward_args(const Geo &g, int grp, const FwdOperands &o) {
   a.oChanStride = g.Ho * g.Wo, a.oSampleStride = g.Ho * g.Wo * g.K, a.divMU = make_fastdiv(1), a.oUStride = 0;
   // 4 consecutive output pixels are contiguous (same sample) and every tile starts on a multiple
   // of 32 pixels; 16-byte alignment of (y, residual) rows needs Ho*Wo % 4 == 0
-  a.vecStore = ((g.Ho * g.Wo) % 4 == 0 && (((uintptr_t)a.Y | (uintptr_t)a.resid) & 15) == 0) ? 1 : 0;
-  a.dmaOk = (o.dma_ok && a.vecStore) ? 1 : 0;   // the LDS-DMA kernel only carries the 16-byte-store epilogue
+  // (a strided residual is read with 4-byte loads: its alignment does not matter)
+  a.vecStore = ((g.Ho * g.Wo) % 4 == 0 && (((uintptr_t)a.Y | (a.rsOn ? 0 : (uintptr_t)a.resid)) & 15) == 0) ? 1 : 0;
+  // the LDS-DMA kernel only carries the 16-byte-store epilogue, and no strided residual
+  a.dmaOk = (o.dma_ok && a.vecStore && !a.rsOn) ? 1 : 0;
   return a;
 }
 
@@ -1305,17 +1329,18 @@ static int forward_run(const Geo &g, const ConvGemmArgs &a, const float *x, cons
   // longer epilogue, so whichever variant reached a shape first must not fix the choice for the other
   const TuneKey key = tune_key_forward(0, g, a.M, a.NP, a.Rp, mode + (s.ok ? 4 : 0));
   const int ci = tune_cfg(key, pick_cfg(a.M, a.NP, a.Rp / kBK), st, gemm, a.dmaOk ? kNumCfg : kNumBaseCfg, w8_skip(a.M, a.NP));
-  if (stem_ok(a, g, x, s.ok)) {     // the single-channel stem kernel: one partial row per (persistent) block
+  // a strided residual is known to the implicit-GEMM epilogue and the split-K combine only: no stem, no halo arm
+  if (!a.rsOn && stem_ok(a, g, x, s.ok)) {     // the single-channel stem kernel: one partial row per (persistent) block
     auto arm = [&](int h) { return h ? launch_stem(stats_args(a, s, s.ok ? stem_grid(a.NP) : 0), f, g.R, st) : gemm(ci); };
     return arm(select_arm(7, key, st, 2, kOneChallenger, kHaloMargin, g_force_stem, arm));
   }
-  if (stem3_ok(a, g, x, s.ok)) {    // the three-channel stem kernel
+  if (!a.rsOn && stem3_ok(a, g, x, s.ok)) {    // the three-channel stem kernel
     auto arm = [&](int h) { return h ? launch_stem3(a, f, g.R, st) : gemm(ci); };
     return arm(select_arm(12, key, st, 2, kOneChallenger, kHaloMargin, g_force_stem3, arm));
   }
   // <= 3 x 3 taps / unit stride: the halo-patch kernel variants
   ConvGemmArgs ah = a;
-  const int hneed = forced_tiling() ? 0 : halo_setup(ah, g.N);
+  const int hneed = (forced_tiling() || a.rsOn) ? 0 : halo_setup(ah, g.N);
   const bool hok[4] = {true, halo_var_ok(ah, hneed, 0), halo_var_ok(ah, hneed, 1), halo_var_ok(ah, hneed, 2)};
   auto arm = [&](int h) {
     if (!h) return gemm(ci);
@@ -1330,7 +1355,8 @@ static int forward_run(const Geo &g, const ConvGemmArgs &a, const float *x, cons
 // (16-byte-store epilogue, no split-K, no filter groups), else by a pass over Y.
 static int conv_forward(const float *x, const float *f, const float *b, float *y, const Geo &g,
                         const float *scale, const float *shift, const float *resid, int relu,
-                        hipStream_t st, float *moments_out = nullptr, float eps = 0.f, const float *gate = nullptr) {
+                        hipStream_t st, float *moments_out = nullptr, float eps = 0.f, const float *gate = nullptr,
+                        int res_H = 0, int res_W = 0, int res_sy = 1, int res_sx = 1) {
   // The (u,v) validity mask has 63 bits.  Without spatial padding every tap is inside the image, so
   // larger filters (the 1 x 401 STFT bank of batch.runSpec) simply do not use it.
   const bool padded = (g.pt | g.pb | g.pl | g.pr) != 0;
@@ -1359,6 +1385,7 @@ static int conv_forward(const float *x, const float *f, const float *b, float *y
   if (rc) return rc;
   FwdOperands o{x, f, b, scale, shift, resid, gate, y, device_taps(fwd_tap_table(g, Rp, bigTaps)), g.R, Rp, relu, bigTaps, dma_ok};
   if (!o.taps) return fail(XM_ENOMEM, "vl_nnconv: tap table allocation failed");
+  if (resid) o.rH = res_H > 0 ? res_H : g.Ho, o.rW = res_W > 0 ? res_W : g.Wo, o.rsy = res_sy, o.rsx = res_sx;
   if (need_pad) {
     float *Ap = ws.take<float>((size_t)g.K * Rp);
     size_t n = (size_t)g.K * Rp;
@@ -2058,6 +2085,7 @@ int xm_debug_set(const char *key, int value) {
 }
 int xm_debug_get(const char *key) {
   if (key && strcmp(key, "num_conv_cfgs") == 0) return kNumCfg;
+  if (key && strcmp(key, "conv_last_combine") == 0) return g_last_combine;
   const DebugSwitch *s = debug_switch(key);
   return s ? *s->value : INT_MIN;
 }
@@ -2117,25 +2145,57 @@ int xm_debug_conv_cycles(int on, unsigned long long *out, int nblocks) {
 }
 #endif
 
-int xm_nnconv_forward_fused(const float *x, int H, int W, int C, int N, const float *f, int FH,
-                            int FW, int FC, int K, const float *b, float *y, int sy, int sx,
-                            int pt, int pb, int pl, int pr, int dy, int dx, const float *scale,
-                            const float *shift, const float *residual, int flags, void *stream) {
+// The fused forward behind xm_nnconv_forward_fused (gate == NULL) / _gated / _strided_residual: the residual has the
+// extent res_H x res_W x K x N and is read at (oy * res_sy, ox * res_sx); res_H == 0: at output extent, unit stride.
+static int fused_forward(const float *x, int H, int W, int C, int N, const float *f, int FH, int FW,
+                         int FC, int K, const float *b, float *y, int sy, int sx, int pt, int pb,
+                         int pl, int pr, int dy, int dx, const float *scale, const float *shift,
+                         const float *gate, const float *residual, int res_H, int res_W, int res_sy,
+                         int res_sx, int flags, void *stream) {
   Geo g;
   int rc = make_geo(g, H, W, C, N, FH, FW, FC, K, sy, sx, pt, pb, pl, pr, dy, dx);
   if (rc) return rc;
+  if (res_H == 0) res_H = g.Ho, res_W = g.Wo, res_sy = res_sx = 1;
   if (!x || !f || !y) return fail(XM_EINVAL, "vl_nnconv: NULL tensor");
   if ((scale == nullptr) != (shift == nullptr))
     return fail(XM_EINVAL, "vl_nnconv(fused): scale and shift must be given together");
   if ((flags & XM_FUSE_RELU) && (flags & XM_FUSE_SIGMOID))
     return fail(XM_EINVAL, "vl_nnconv(fused): relu and sigmoid are exclusive");
+  if (gate && (flags & XM_FUSE_SIGMOID)) return fail(XM_ENOTSUP, "vl_nnconv(gated): sigmoid epilogue is not built");
+  if (residual) {
+    if (res_sy < 1 || res_sx < 1 || res_H < 1 || res_W < 1 || g.Ho != (res_H - 1) / res_sy + 1 ||
+        g.Wo != (res_W - 1) / res_sx + 1)
+      return fail(XM_EINVAL, "vl_nnconv(fused): a %d x %d residual sampled with stride [%d %d] does not give the %d x %d output",
+                  res_H, res_W, res_sy, res_sx, g.Ho, g.Wo);
+    if ((long long)res_H * res_W * g.K * g.N >= (1LL << 30))
+      return fail(XM_ETOOBIG, "vl_nnconv(fused): residual with >= 2^30 elements (4 GiB)");
+  }
   hipStream_t st = (hipStream_t)stream;
-  if (!residual && fc_skinny_ok(g))
+  if (!gate && !residual && fc_skinny_ok(g))
     return fc_skinny_forward(x, f, b, y, g, (flags & XM_FUSE_SIGMOID) ? 2 : ((flags & XM_FUSE_RELU) ? 1 : 0), st, scale,
                              shift);
-  rc = conv_forward(x, f, b, y, g, scale, shift, residual, (flags & XM_FUSE_RELU) ? 1 : 0, st);
+  rc = conv_forward(x, f, b, y, g, scale, shift, residual, (flags & XM_FUSE_RELU) ? 1 : 0, st, nullptr, 0.f, gate, res_H,
+                    res_W, res_sy, res_sx);
   if (rc || !(flags & XM_FUSE_SIGMOID)) return rc;
   return xm_nnsigmoid(y, (size_t)g.Ho * g.Wo * g.K * g.N, nullptr, y, stream);  // in place (elementwise)
+}
+
+int xm_nnconv_forward_fused(const float *x, int H, int W, int C, int N, const float *f, int FH,
+                            int FW, int FC, int K, const float *b, float *y, int sy, int sx,
+                            int pt, int pb, int pl, int pr, int dy, int dx, const float *scale,
+                            const float *shift, const float *residual, int flags, void *stream) {
+  return fused_forward(x, H, W, C, N, f, FH, FW, FC, K, b, y, sy, sx, pt, pb, pl, pr, dy, dx, scale, shift, nullptr, residual,
+                       0, 0, 1, 1, flags, stream);
+}
+
+int xm_nnconv_forward_strided_residual(const float *x, int H, int W, int C, int N, const float *f, int FH, int FW,
+                                       int FC, int K, const float *b, float *y, int sy, int sx, int pt, int pb,
+                                       int pl, int pr, int dy, int dx, const float *scale, const float *shift,
+                                       const float *gate, const float *residual, int res_H, int res_W, int res_sy,
+                                       int res_sx, int flags, void *stream) {
+  if (residual && res_H < 1) return fail(XM_EINVAL, "vl_nnconv(fused): residual extent must be positive");
+  return fused_forward(x, H, W, C, N, f, FH, FW, FC, K, b, y, sy, sx, pt, pb, pl, pr, dy, dx, scale, shift, gate, residual,
+                       residual ? res_H : 0, res_W, res_sy, res_sx, flags, stream);
 }
 
 int xm_nnconv_forward_moments(const float *x, int H, int W, int C, int N, const float *f, int FH, int FW,
@@ -2157,15 +2217,9 @@ int xm_nnconv_forward_gated(const float *x, int H, int W, int C, int N, const fl
                             int FC, int K, const float *b, float *y, int sy, int sx, int pt, int pb,
                             int pl, int pr, int dy, int dx, const float *scale, const float *shift,
                             const float *gate, const float *residual, int flags, void *stream) {
-  Geo g;
-  int rc = make_geo(g, H, W, C, N, FH, FW, FC, K, sy, sx, pt, pb, pl, pr, dy, dx);
-  if (rc) return rc;
-  if (!x || !f || !y || !gate) return fail(XM_EINVAL, "vl_nnconv(gated): NULL tensor");
-  if ((scale == nullptr) != (shift == nullptr))
-    return fail(XM_EINVAL, "vl_nnconv(gated): scale and shift must be given together");
-  if (flags & XM_FUSE_SIGMOID) return fail(XM_ENOTSUP, "vl_nnconv(gated): sigmoid epilogue is not built");
-  return conv_forward(x, f, b, y, g, scale, shift, residual, (flags & XM_FUSE_RELU) ? 1 : 0, (hipStream_t)stream,
-                      nullptr, 0.f, gate);
+  if (!gate) return fail(XM_EINVAL, "vl_nnconv(gated): NULL tensor");     // (every other check: fused_forward)
+  return fused_forward(x, H, W, C, N, f, FH, FW, FC, K, b, y, sy, sx, pt, pb, pl, pr, dy, dx, scale, shift, gate, residual,
+                       0, 0, 1, 1, flags, stream);
 }
 
 int xm_nnconv_forward(const float *x, int H, int W, int C, int N, const float *f, int FH, int FW,

@@ -48,6 +48,11 @@ struct ConvGemmArgs {
   // sample] -- the SE excite a .* x folded into the 1 x 1 projection that produces x (xm_nnconv_forward_gated)
   const float *gate;
   int gateStride;
+  // rsOn != 0 (forward, oMU == 1, register-staged implicit-GEMM kernel and the split-K combine only): the residual has an
+  // extent of its own, rH x rW x M x N, and is SAMPLED with a stride: output pixel (i, j) of row m and sample n adds
+  // resid[i * rsy + rH * (j * rsx) + m * rChanStride + n * rSampleStride] -- a 1 x 1 expansion computed only at the pixels
+  // a strided reader will look at, while its shortcut operand still has the full extent (xm_nnconv_forward_strided_residual)
+  int rsOn, rsy, rsx, rH, rChanStride, rSampleStride;
   int relu;
   unsigned xBytes;    // size of the gather source in bytes (buffer bounds check)
   unsigned aBytes;    // size of A in bytes (LDS-DMA variant: A is read through a buffer descriptor too)
@@ -226,7 +231,18 @@ __device__ __forceinline__ void xm_st4(float *p, float v) {
     *p = v;
 }
 
-template <int TM, int TN, int WGM, int WGN, bool ASMST = false>
+// offset of flat output pixel p inside a strided residual (ConvGemmArgs::rsOn), without the row term
+__device__ __forceinline__ int resid_pixel_off(const ConvGemmArgs &a, uint32_t p) {
+  const uint32_t n = xm_div(p, a.divPIJ);
+  const uint32_t q = p - n * a.divPIJ.d;
+  const uint32_t jj = xm_div(q, a.divPI);
+  const uint32_t ii = q - jj * a.divPI.d;
+  return (int)ii * a.rsy + a.rH * ((int)jj * a.rsx) + (int)n * a.rSampleStride;
+}
+
+// RSTR: the instantiation also knows a strided residual (a.rsOn) -- a template flag, so that the kernels that are never
+// dispatched with one (LDS-DMA, halo, the dgrad multi launch) keep their code and registers
+template <int TM, int TN, int WGM, int WGN, bool ASMST = false, bool RSTR = false>
 __device__ __forceinline__ void conv_gemm_epilogue(const ConvGemmArgs &a, f32x16 (&acc)[TM][TN], int bm, int bn,
                                                    int split, int wm, int wn, int half, int l31,
                                                    float *sred = nullptr /* LDS, >= 2 * WGN * BM floats (statPart) */,
@@ -371,7 +387,17 @@ __device__ __forceinline__ void conv_gemm_epilogue(const ConvGemmArgs &a, f32x16
             if (a.resid) {
               if constexpr (ASMST)
                 o += rv[g4 % (ASMST ? 4 : 1)][j % (ASMST ? TN : 1)];
-              else
+              else if (RSTR && a.rsOn) {
+                // the quad's four pixels are neither neighbours in the residual (stride) nor always in one output
+                // column (Ho % 4 != 0): one fetch per pixel, the 16-byte store of y stays.  NP % 4 == 0 with vecStore,
+                // so the whole quad exists whenever its lane's pixel does.
+                const uint32_t p0 = (uint32_t)(bn * BN + (wn * TN + j) * 32 + l31 - iq);
+                const float *rr = a.resid + min(wbase + i * 32 + 8 * g4 + 4 * half + iq, a.M - 1) * a.rChanStride;
+                o.x += rr[resid_pixel_off(a, p0)];
+                o.y += rr[resid_pixel_off(a, p0 + 1)];
+                o.z += rr[resid_pixel_off(a, p0 + 2)];
+                o.w += rr[resid_pixel_off(a, p0 + 3)];
+              } else
                 o += *reinterpret_cast<const f32x4 *>(a.resid + offs[g4][j]);
             }
             if (!ASMST && a.statPart) {
@@ -447,7 +473,12 @@ __device__ __forceinline__ void conv_gemm_epilogue(const ConvGemmArgs &a, f32x16
           int off = obase[j] + moff;
           float v = acc[i][j][r] * rmul[r] + radd[r];
           if (a.gate) v *= a.gate[min(m, a.M - 1) + gbase[j]];
-          if (a.resid) v += a.resid[off];
+          if (a.resid) {
+            int roff = off;
+            if (RSTR && a.rsOn)
+              roff = resid_pixel_off(a, (uint32_t)(bn * BN + (wn * TN + j) * 32 + l31)) + min(m, a.M - 1) * a.rChanStride;
+            v += a.resid[roff];
+          }
           if (a.relu) v = fmaxf(v, 0.f);
           xm_st4<ASMST>(a.Y + off, v);
         }
@@ -457,7 +488,7 @@ __device__ __forceinline__ void conv_gemm_epilogue(const ConvGemmArgs &a, f32x16
 }
 
 // MODE 0: every tap is inside the image (pad == 0, Rp == R);  MODE 1: (u,v) validity mask.
-template <int TM, int TN, int WGM, int WGN, int MODE>
+template <int TM, int TN, int WGM, int WGN, int MODE, bool RSTR = false>
 __device__ __forceinline__ void conv_gemm_body(const ConvGemmArgs &a) {
   constexpr int BM = 32 * TM * WGM, BN = 32 * TN * WGN;
   constexpr int NT = 64 * WGM * WGN;                 // 4 waves per block; 8 in the low-register configuration (kCfgs[7])
@@ -695,7 +726,7 @@ __device__ __forceinline__ void conv_gemm_body(const ConvGemmArgs &a) {
 #undef XM_STAGE_LAST
 
   if (TM * TN == 1) acc[0][0] += accx;
-  conv_gemm_epilogue<TM, TN, WGM, WGN>(a, acc, bm, bn, split, wm, wn, half, l31, smem, toSlab);
+  conv_gemm_epilogue<TM, TN, WGM, WGN, false, RSTR>(a, acc, bm, bn, split, wm, wn, half, l31, smem, toSlab);
 }
 
 template <int TM, int TN, int WGM, int WGN, int MODE>
@@ -706,7 +737,7 @@ conv_gemm_kernel(const ConvGemmArgs a) {
   // branch it cost the whole step 4 % (the start-clock value stays live across the main loop).
   const unsigned long long c0 = __builtin_readcyclecounter();
 #endif
-  conv_gemm_body<TM, TN, WGM, WGN, MODE>(a);
+  conv_gemm_body<TM, TN, WGM, WGN, MODE, true>(a);   // (the forward launches: a strided residual may arrive here)
 #ifdef XM_DEBUG_CYCLES
   if (a.dbgCycles && threadIdx.x == 0) {
     const unsigned b = blockIdx.x + gridDim.x * blockIdx.y;
@@ -2192,7 +2223,16 @@ conv_splitk_epilogue_kernel(const ConvGemmArgs a, int splits, FastDiv divCols) {
     if (a.bias) v += a.bias[m];
     if (a.scale) v = v * a.scale[m] + a.shift[m];
     if (a.gate) v *= a.gate[m + (int)n * a.gateStride];
-    if (a.resid) v += *reinterpret_cast<const f32x4 *>(a.resid + off);
+    if (a.resid) {
+      if (a.rsOn) {     // strided residual: one fetch per pixel of the quad (see conv_gemm_epilogue)
+        const float *rr = a.resid + m * a.rChanStride;
+        v.x += rr[resid_pixel_off(a, (uint32_t)p)];
+        v.y += rr[resid_pixel_off(a, (uint32_t)p + 1)];
+        v.z += rr[resid_pixel_off(a, (uint32_t)p + 2)];
+        v.w += rr[resid_pixel_off(a, (uint32_t)p + 3)];
+      } else
+        v += *reinterpret_cast<const f32x4 *>(a.resid + off);
+    }
     if (a.relu) {
       v.x = fmaxf(v.x, 0.f);
       v.y = fmaxf(v.y, 0.f);
@@ -2206,7 +2246,7 @@ conv_splitk_epilogue_kernel(const ConvGemmArgs a, int splits, FastDiv divCols) {
     if (a.bias) v += a.bias[m];
     if (a.scale) v = v * a.scale[m] + a.shift[m];
     if (a.gate) v *= a.gate[m + (int)n * a.gateStride];
-    if (a.resid) v += a.resid[off];
+    if (a.resid) v += a.resid[a.rsOn ? resid_pixel_off(a, (uint32_t)p) + m * a.rChanStride : off];
     if (a.relu) v = fmaxf(v, 0.f);
     a.Y[off] = v;
   }

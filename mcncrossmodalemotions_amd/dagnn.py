@@ -485,6 +485,9 @@ class DagNN:
         self.foldSEReduce = os.environ.get("XM_NO_SE_FOLD_FC") is None   # ... and the projection folded into the SE reduction layer
         # training plans: relu mask + excite + squeeze + bnorm backward of an SE block's tail in two fused calls
         self.fuseSETrain = os.environ.get("XM_NO_FUSED_SE_BWD") is None
+        # test-mode plans: a 1 x 1 expansion whose output is read only by 1 x 1 / stride-s convolutions (the end of a
+        # Caffe-style ResNet stage) computes the pixels those readers look at and nothing else (_prune_strided_boundaries)
+        self.stridePrune = os.environ.get("XM_STRIDE_PRUNE", "1") != "0"
         self.wgradStream = None  # optional side HIP stream for the filter / bias derivatives
         self.gradHook = None     # callable(layer name): called right after a conv layer's parameter
                                  # derivatives were enqueued, on the stream they were enqueued on
@@ -585,7 +588,7 @@ class DagNN:
         import copy
         r = DagNN()
         r.meta, r.mode, r.fuse, r.device = self.meta, self.mode, self.fuse, self.device
-        r.conserveMemory = self.conserveMemory
+        r.conserveMemory, r.stridePrune = self.conserveMemory, self.stridePrune
         for l in self.layers:
             r.layers.append(_LayerRec(l.name, copy.copy(l.block), l.inputs, l.outputs, l.params))
         r.params = self.params
@@ -800,7 +803,7 @@ class DagNN:
     def _plan(self, training):
         # the set of precious variables is part of the key: a fused step never materialises the intermediate
         # variables it swallows, so marking one precious after a plan was built must rebuild the plan
-        key = (training, self.mode, self.fuse, len(self.layers),
+        key = (training, self.mode, self.fuse, self.stridePrune, len(self.layers),
                tuple(n for n, v in self.vars.items() if v.precious))
         if getattr(self, "_plan_key", None) == key and getattr(self, "_plan_layers", None) == [
                 id(l) for l in self.layers]:
@@ -842,6 +845,13 @@ class _Step:
         self.bias_conv_done = False
         self.se_bn = None        # training plans: the _SEBnTrainStep whose fused backward covers this step (its squeeze / excite)
         self.stem_into = None    # training plans: the _BnReluPoolStep that can run this (first-layer) convolution inside its own kernel
+        # forward-only test-mode plans (_prune_strided_boundaries): the stride this convolution step runs with instead of its
+        # block's -- (s, s) on a pruned stage-end expansion (its shortcut operand is then sampled with the same stride),
+        # (1, 1) on the stride-s readers of its output
+        self.run_stride = None
+
+    def _stride(self):
+        return self.rec.block.stride if self.run_stride is None else self.run_stride
 
     def _bias_der_slot(self, net):
         """flat derivative slot of the producing convolution's bias when this bnorm step may fill it (sum of dx)"""
@@ -890,6 +900,10 @@ class _Step:
             outs = [vl.vl_nnconv(ins[0], prm[0], prm[1] if blk.hasBias else None, stride=blk.stride, pad=blk.pad,
                                  dilate=blk.dilate, moments_out=mo, epsilon=bn.block.epsilon)]
             bn.block._pre_moments = mo
+        elif self.run_stride is not None:
+            prm, blk = self._params(net), r.block
+            outs = [vl.vl_nnconv(ins[0], prm[0], prm[1] if blk.hasBias else None, stride=self.run_stride, pad=blk.pad,
+                                 dilate=blk.dilate)]
         else:
             outs = r.block.forward(ins, self._params(net))
         for v, t in zip(r.outputs, outs):
@@ -1308,7 +1322,7 @@ class _ConvActStep(_Step):
         r, blk = self.rec, self.rec.block
         par = self._params(net)
         sig = isinstance(self.act_rec.block, Sigmoid)
-        y = vl.vl_nnconv(net.vars[r.inputs[0]].value, par[0], par[1] if blk.hasBias else None, stride=blk.stride,
+        y = vl.vl_nnconv(net.vars[r.inputs[0]].value, par[0], par[1] if blk.hasBias else None, stride=self._stride(),
                          pad=blk.pad, dilate=blk.dilate, relu=not sig, sigmoid=sig)
         net.vars[self.act_rec.outputs[0]].value = y
 
@@ -1347,8 +1361,9 @@ class _ConvFoldStep(_Step):
         if self.sum_rec is not None:
             other = [v for v in self.sum_rec.inputs if v != self.bn_rec.outputs[0]][0]
             resid = net.vars[other].value
-        y = vl.vl_nnconv(x, prm[0], prm[1] if blk.hasBias else None, stride=blk.stride, pad=blk.pad,
-                         dilate=blk.dilate, scale=sc, shift=sh, residual=resid,
+        pruned = self.run_stride if (resid is not None and self.run_stride != (1, 1)) else None
+        y = vl.vl_nnconv(x, prm[0], prm[1] if blk.hasBias else None, stride=self._stride(), pad=blk.pad,
+                         dilate=blk.dilate, scale=sc, shift=sh, residual=resid, residual_stride=pruned,
                          relu=self.relu_rec is not None)
         net.vars[self.out_name].value = y
 
@@ -1414,8 +1429,10 @@ class _SEFoldStep(_ConvFoldStep):
             z = vl.vl_nnconv(ubar, prm[0], bias, scale=sc, shift=sh)
             h = vl.vl_nnconv(z, f1[0], b1, relu=True)
         a = vl.vl_nnconv(h, f2[0], f2[1] if se["fc2"].block.hasBias else None, sigmoid=True)
-        y = vl.vl_nnconv(u, prm[0], bias, stride=blk.stride, pad=blk.pad, dilate=blk.dilate, scale=sc, shift=sh,
-                         gate=a, residual=net.vars[se["shortcut"]].value, relu=se["relu"] is not None)
+        # (a pruned step samples only the excite's write: the squeeze above is a mean over ALL pixels of u)
+        y = vl.vl_nnconv(u, prm[0], bias, stride=self._stride(), pad=blk.pad, dilate=blk.dilate, scale=sc, shift=sh,
+                         gate=a, residual=net.vars[se["shortcut"]].value, residual_stride=self.run_stride,
+                         relu=se["relu"] is not None)
         net.vars[self.out_name].value = y
 
 
@@ -1473,6 +1490,41 @@ def _link_bias_conv(bn_step, steps, r, consumers, training):
             len(consumers.get(r.inputs[0], [])) == 1:
         bn_step.bias_conv = prod[0]
         prod[0].bias_from = bn_step
+
+
+def _plain_1x1(blk):
+    return isinstance(blk, Conv) and blk.size[0] == 1 and blk.size[1] == 1 and not any(vl._pad4(blk.pad)) and \
+        tuple(vl._pair(blk.dilate, "DILATE")) == (1, 1)
+
+
+def _prune_strided_boundaries(net, steps, consumers):
+    """forward-only test-mode plans: skip the pixels no layer reads.
+
+    A folded 1 x 1 / stride-1 convolution step (the C/4 -> C expansion that ends a stage, with its bnorm, shortcut add or SE
+    excite, and ReLU) whose output variable is not precious and is read ONLY by 1 x 1, pad-0 convolutions that all have
+    the same stride (s, s), s > 1 (Caffe-style stages put the stride on their first 1 x 1: branch1 and branch2a), runs with
+    stride (s, s) over its own input, its shortcut operand sampled with the same stride; the readers then run with unit
+    stride over the smaller tensor.  Both sides have floor((H - 1) / s) + 1 rows, and a 1 x 1 convolution of a sampled
+    tensor is the sampled 1 x 1 convolution, so every later variable has the values it had."""
+    head = {id(st.rec): st for st in steps}
+    for st in steps:
+        blk = st.rec.block
+        if not isinstance(st, _ConvFoldStep) or st.run_stride is not None or not _plain_1x1(blk) or \
+                tuple(vl._pair(blk.stride, "STRIDE")) != (1, 1) or net.vars[st.out_name].precious:
+            continue
+        readers = [head.get(id(c)) for c in consumers.get(st.out_name, [])]
+        if not readers or any(q is None or type(q) not in (_Step, _ConvActStep, _ConvFoldStep) or
+                              not _plain_1x1(q.rec.block) or q.run_stride is not None for q in readers):
+            continue
+        strides = {tuple(vl._pair(q.rec.block.stride, "STRIDE")) for q in readers}
+        if len(strides) != 1:
+            continue
+        s = strides.pop()
+        if s[0] != s[1] or s[0] <= 1:
+            continue
+        st.run_stride = s
+        for q in readers:
+            q.run_stride = (1, 1)
 
 
 def build_plan(net, training):
@@ -1565,6 +1617,8 @@ def build_plan(net, training):
     # a fused step may now sit before the producer of one of its operands is scheduled; the
     # `ready` test above guarantees producers precede the conv, so plain order is still valid.
     del produced_before
+    if fold_ok and net.stridePrune:
+        _prune_strided_boundaries(net, steps, consumers)
     if training:
         # Conv -> BatchNorm (train mode): the convolution's epilogue computes the batch moments (vl_nnconv
         # moments_out), the bnorm step -- plain, +relu or +relu+pool -- takes them instead of re-reading its input

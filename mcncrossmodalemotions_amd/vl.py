@@ -151,7 +151,7 @@ def out_size(n, pa, pb, f, d, s):
 def vl_nnconv(x, f, b=None, dzdy=None, stride=1, pad=0, dilate=1, no_der_data=False,
               no_der_filters=False, no_der_biases=False, scale=None, shift=None, residual=None,
               relu=False, df_out=None, db_out=None, dx_accum=None, sigmoid=False, moments_out=None, epsilon=1e-4,
-              gate=None):
+              gate=None, residual_stride=None):
     """Y = VL_NNCONV(X, F, B) / [DX, DF, DB] = VL_NNCONV(X, F, B, DZDY).
 
     `gate` (forward, extension; 1 x 1 x K x N): per-(channel, sample) multiplier between scale / shift and the residual --
@@ -159,6 +159,8 @@ def vl_nnconv(x, f, b=None, dzdy=None, stride=1, pad=0, dilate=1, no_der_data=Fa
     `moments_out` (forward, extension; a K x 2 device matrix): also receives the batch moments [mean, sqrt(var +
     epsilon)] of Y -- the statistics pass of the train-mode vl_nnbnorm that follows (xm_nnconv_forward_moments).
     `scale/shift/residual/relu/sigmoid` select the fused forward epilogue (extension; see xmodal.h);
+    `residual_stride=(sy, sx)` (forward, extension): RESIDUAL has an extent of its own, RH x RW x K x N, and is sampled at
+    (oy * sy, ox * sx); Ho must equal floor((RH - 1) / sy) + 1, likewise Wo (xm_nnconv_forward_strided_residual);
     `dx_accum` (backward, extension): DX = dgrad + dx_accum in the dgrad epilogue."""
     x, f = _chk(x, "X"), _chk(f, "F")
     H, W, Cc, N = _shape4(x)
@@ -177,7 +179,25 @@ def vl_nnconv(x, f, b=None, dzdy=None, stride=1, pad=0, dilate=1, no_der_data=Fa
     if dzdy is None:
         y = mat_empty(max(Ho, 0), max(Wo, 0), K, N, device=x.device)
         fused = scale is not None or residual is not None or relu or sigmoid
-        if gate is not None:
+        if residual_stride is not None:
+            if residual is None:
+                raise ValueError("vl_nnconv: residual_stride without a residual")
+            if moments_out is not None or sigmoid:
+                raise ValueError("vl_nnconv: residual_stride cannot be combined with moments_out or sigmoid")
+            rsy, rsx = _pair(residual_stride, "RESIDUAL_STRIDE")
+            RH, RW, RK, RN = _shape4(_chk(residual, "RESIDUAL"))
+            if [RK, RN] != [K, N]:
+                raise ValueError("vl_nnconv: residual shape mismatch")
+            gt = None
+            if gate is not None:
+                gt = _chk(gate, "GATE")
+                if gt.numel() != K * N:
+                    raise ValueError("vl_nnconv: GATE must be 1 x 1 x %d x %d" % (K, N))
+            # (the extents are checked by the library: XM_EINVAL unless the sampled residual has the output's size)
+            _lib.check(L.xm_nnconv_forward_strided_residual(
+                _ptr(x), H, W, Cc, N, _ptr(f), FH, FW, FC, K, _ptr(bb), _ptr(y), sy, sx, pt, pb, pl, pr, dy, dx,
+                _ptr(scale), _ptr(shift), _ptr(gt), _ptr(residual), RH, RW, rsy, rsx, 1 if relu else 0, _stream()))
+        elif gate is not None:
             gt = _chk(gate, "GATE")
             if gt.numel() != K * N:
                 raise ValueError("vl_nnconv: GATE must be 1 x 1 x %d x %d" % (K, N))

@@ -1,6 +1,7 @@
 #!/bin/bash
 # Regenerates mcncrossmodalemotions_amd/tune_gfx950.txt: run through gpurun, then copy gpurun_out/tune_gfx950.txt
-# over the tracked file.  Every workload of bench.py, the inference buckets and the GPU tests leave their shapes.
+# over the tracked file, THEN put back the entries listed in mcncrossmodalemotions_amd/tune_gfx950.pinned.txt (pinned by reduction
+# structure, not by speed: DESIGN.md 2.2g; tests/test_stride_prune_plan.py compares the two files).  Every workload of bench.py, the inference buckets and the GPU tests leave their shapes.
 cd "$GRAFT_REPO_ROOT" || exit 1
 export XM_TUNE_FILE=$PWD/gpurun_out/tune_gfx950.txt XM_TUNE_SAVE=1 XM_TUNE_REPS=8   # best of 8 launches per configuration
 rm -f $XM_TUNE_FILE
