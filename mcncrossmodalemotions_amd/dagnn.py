@@ -503,6 +503,8 @@ class DagNN:
         # xm_average_update on the flat buffers, checkpoint loads, pack_params): cached derived quantities
         # (folded test-mode bnorm scale / shift) are keyed on it.  Shared with replica()s (same parameters).
         self._gen = [0]
+        self._plan_key = self._plan_layers = self._plan_cache = None   # _plan; `_plan_key = None` forces a rebuild
+        self._der_consts = {}    # eval: scalar output derivatives as cached device tensors
 
     @property
     def paramGeneration(self):
@@ -726,13 +728,10 @@ class DagNN:
         mark("fwd0")
         for step in plan:
             if pending:
-                recs = [step.rec] + [getattr(step, n) for n in ("relu_rec", "pool_rec", "bn_rec", "sum_rec")
-                                     if getattr(step, n, None) is not None]
-                for rec in recs:
-                    for v in rec.inputs:
-                        ev = pending.pop(v, None)
-                        if ev is not None:
-                            torch.cuda.current_stream().wait_event(ev)
+                for v in step.reads:
+                    ev = pending.pop(v, None)
+                    if ev is not None:
+                        torch.cuda.current_stream().wait_event(ev)
             step.forward(self)
         mark("fwd1")
         if derOutputs is None:
@@ -741,7 +740,7 @@ class DagNN:
             if not isinstance(d, torch.Tensor):
                 # cached device scalar: a fresh host->device copy here would block the host until the
                 # queued forward pass has drained
-                cache = self.__dict__.setdefault("_der_consts", {})
+                cache = self._der_consts
                 key = (float(d), str(self.device))
                 if key not in cache:
                     cache[key] = vl.from_numpy(np.array([[float(d)]], np.float32), self.device)
@@ -805,13 +804,10 @@ class DagNN:
         # variables it swallows, so marking one precious after a plan was built must rebuild the plan
         key = (training, self.mode, self.fuse, self.stridePrune, len(self.layers),
                tuple(n for n, v in self.vars.items() if v.precious))
-        if getattr(self, "_plan_key", None) == key and getattr(self, "_plan_layers", None) == [
-                id(l) for l in self.layers]:
-            return self._plan_cache
-        steps = build_plan(self, training)
-        self._plan_key, self._plan_cache = key, steps
-        self._plan_layers = [id(l) for l in self.layers]
-        return steps
+        layers = [id(l) for l in self.layers]
+        if self._plan_key != key or self._plan_layers != layers:
+            self._plan_key, self._plan_layers, self._plan_cache = key, layers, build_plan(self, training)
+        return self._plan_cache
 
 
 def load_mat(path):
@@ -834,17 +830,26 @@ class FlatParams:
 # ---------------------------------------------------------------------------------------------
 # execution plan with peephole fusion
 # ---------------------------------------------------------------------------------------------
-class _Step:
-    """plain step: one dagnn layer."""
+def _release_der(net, var):
+    """conserveMemory: a step that has consumed the derivative of its output drops it"""
+    if net.conserveMemory and not var.precious:
+        var.der = None
 
-    def __init__(self, rec):
+
+class _Step:
+    """generic step: one dagnn layer, run by its block.  Every step lists `recs`, the layer records it executes (head
+    first; the last one's outputs are the step's `outputs`), and `reads`, the variables those layers read that none of them
+    produces."""
+
+    # True: the head convolution is the step's only read of its input (what _prune_strided_boundaries asks of a reader)
+    reads_through_conv = False
+
+    def __init__(self, rec, *swallowed):
         self.rec = rec
-        self.bias_from = None  # fused consumer step that already produced this conv's bias derivative
-        self.moments_for = None  # _LayerRec of the train-mode BatchNorm this conv step computes the batch moments for
-        self.bias_conv = None    # bnorm steps: _Step of the biased Conv that produced the input (its dzdb = sum of our dx)
-        self.bias_conv_done = False
-        self.se_bn = None        # training plans: the _SEBnTrainStep whose fused backward covers this step (its squeeze / excite)
-        self.stem_into = None    # training plans: the _BnReluPoolStep that can run this (first-layer) convolution inside its own kernel
+        self.recs = [rec] + [q for q in swallowed if q is not None]
+        self.outputs = self.recs[-1].outputs
+        made = {v for q in self.recs for v in q.outputs}
+        self.reads = tuple(dict.fromkeys(v for q in self.recs for v in q.inputs if v not in made))
         # forward-only test-mode plans (_prune_strided_boundaries): the stride this convolution step runs with instead of its
         # block's -- (s, s) on a pruned stage-end expansion (its shortcut operand is then sampled with the same stride),
         # (1, 1) on the stride-s readers of its output
@@ -853,12 +858,147 @@ class _Step:
     def _stride(self):
         return self.rec.block.stride if self.run_stride is None else self.run_stride
 
+    def _params(self, net):
+        return [net.params[p].value for p in self.rec.params]
+
+    def _values(self, net, ins):
+        """the step's outputs: the part of forward that differs by kind"""
+        return self.rec.block.forward(ins, self._params(net))
+
+    def _derivatives(self, net, ins, douts):
+        """(derivatives of the inputs, derivatives of the parameters): the part of backward that differs by kind"""
+        return self.rec.block.backward(ins, self._params(net), douts)
+
+    def forward(self, net):
+        outs = self._values(net, [net.vars[v].value for v in self.rec.inputs])
+        for v, t in zip(self.outputs, outs):
+            net.vars[v].value = t
+
+    def backward(self, net):
+        r = self.rec
+        douts = [net.vars[v].der for v in self.outputs]
+        if all(d is None for d in douts):
+            return
+        dins, dpar = self._derivatives(net, [net.vars[v].value for v in r.inputs], douts)
+        for v, d in zip(r.inputs, dins):
+            net._set_var_der(v, d)
+        for p, d in zip(r.params, dpar):
+            net._set_param_der(p, d)
+        for v in self.outputs:
+            _release_der(net, net.vars[v])
+
+
+class _ConvStep(_Step):
+    """an unfused Conv, and what a training plan hangs on it (_link_training)."""
+
+    reads_through_conv = True
+
+    def __init__(self, rec):
+        super().__init__(rec)
+        self.bias_from = None    # the bnorm step whose backward may already have produced this conv's bias derivative
+        self.moments_for = None  # _LayerRec of the train-mode BatchNorm this conv step computes the batch moments for
+        self.stem_into = None    # the _BnReluPoolStep that can run this (first-layer) convolution inside its own kernel
+
+    def forward(self, net):
+        if self.stem_into is not None and self.stem_into.stem_forward(net, self):
+            return      # conv -> bnorm -> relu -> pool ran as one kernel; this convolution's output is never written
+        super().forward(net)
+
+    def _values(self, net, ins):
+        r, blk = self.rec, self.rec.block
+        prm = self._params(net)
+        if net._training and net.wgradStream is not None and net.vars[r.inputs[0]].fanin > 0 and net.prepareBackward:
+            # the backward pass of this layer will need the transposed filters: build them now on the idle side
+            # stream instead of on the critical path of the backward pass (vl.conv_prepare_backward)
+            with torch.cuda.stream(net.wgradStream):
+                vl.conv_prepare_backward(ins[0], prm[0], stride=blk.stride, pad=blk.pad, dilate=blk.dilate)
+        bn = self.moments_for
+        if bn is not None and net._training and net.mode != "test" and net.fuseStats:
+            # the train-mode bnorm that consumes this convolution needs the batch moments of its output: the GEMM
+            # epilogue leaves them (straight in the flat derivative slot of the moments parameter when there is one)
+            do = net._direct_der(bn)
+            mo = do[2] if do else vl.mat_empty(bn.block.numChannels, 2, device=ins[0].device)
+            y = vl.vl_nnconv(ins[0], prm[0], prm[1] if blk.hasBias else None, stride=blk.stride, pad=blk.pad,
+                             dilate=blk.dilate, moments_out=mo, epsilon=bn.block.epsilon)
+            bn.block._pre_moments = mo
+            return [y]
+        if self.run_stride is not None:
+            return [vl.vl_nnconv(ins[0], prm[0], prm[1] if blk.hasBias else None, stride=self.run_stride, pad=blk.pad,
+                                 dilate=blk.dilate)]
+        return blk.forward(ins, prm)
+
+    def _derivatives(self, net, ins, douts):
+        r = self.rec
+        need_dx = net.vars[r.inputs[0]].fanin > 0  # network inputs need no derivative
+        skip_db = self.bias_from is not None and self.bias_from.bias_conv_done
+        side = net.wgradStream if need_dx else None
+        if side is not None and net._flat is not None and net._direct_der(r) is None:
+            side = None  # the derivative would need a copy on this stream
+        # fork: another consumer of the input already left its derivative -> add it in the dgrad
+        # epilogue (dx = dgrad + existing) instead of a separate sum2 pass
+        xin = net.vars[r.inputs[0]]
+        accum = xin.der if need_dx else None
+        if accum is not None:
+            xin.der = None   # replaced by the accumulated result below
+        if side is None:
+            dins, dpar = r.block.backward(ins, self._params(net), douts, need_dx=need_dx,
+                                          der_out=net._direct_der(r), skip_db=skip_db, dx_accum=accum)
+            if net.gradHook is not None:
+                if net._side_pending:
+                    # the hook may push a bucket that also covers layers whose filter derivatives were
+                    # enqueued on the side stream: the push is ordered against THIS stream only
+                    torch.cuda.current_stream().wait_stream(net.wgradStream)
+                net.gradHook(r.name)
+        else:
+            # dzdw / dzdb are off the critical path of the backward pass: they run on the side
+            # stream next to the (HBM-bound) bnorm / pooling derivatives of the layers below
+            main = torch.cuda.current_stream()
+            defer = net.wgradAfterDgrad
+            if defer:
+                # the dgrad of this layer first, alone on the chip; its wgrad starts when it has finished and
+                # then runs next to the HBM-bound bnorm / pooling derivatives of the layers below (two
+                # MFMA-bound kernels side by side only slow each other down)
+                dins, _ = r.block.backward(ins, self._params(net), douts, need_dx=True, need_df=False,
+                                           dx_accum=accum)
+            side.wait_stream(main)
+            with torch.cuda.stream(side):
+                _, dpar = r.block.backward(ins, self._params(net), douts, need_dx=False,
+                                           der_out=net._direct_der(r), skip_db=skip_db)
+                if net.gradHook is not None:
+                    net.gradHook(r.name)
+            douts[0].record_stream(side)
+            ins[0].record_stream(side)
+            net._side_pending = True
+            if not defer:
+                dins, _ = r.block.backward(ins, self._params(net), douts, need_dx=True, need_df=False,
+                                           dx_accum=accum)
+        if skip_db:
+            dpar = [dpar[0], net.params[r.params[1]].der]
+        return dins, dpar
+
+
+class _BnStep(_Step):
+    """an unfused BatchNorm, and the base of every step a BatchNorm heads.  In training plans a biased Conv whose only
+    consumer is this bnorm gets its dzdb from the bnorm backward (sum of dx) instead of a pass of its own over dzdy."""
+
+    # True: the step fills the bias slot whenever there is one, without consulting net.fuseBiasDer or the side-stream rule
+    bias_der_always = False
+    relu = False             # True: the block rectifies in the same kernel, each way (_BnReluStep)
+
+    def __init__(self, rec, *swallowed):
+        super().__init__(rec, *swallowed)
+        self.bias_conv = None        # _ConvStep of the biased Conv that produced the input (its dzdb = sum of our dx)
+        self.bias_conv_done = False
+
+    def take_bias_of(self, conv_step):
+        self.bias_conv, conv_step.bias_from = conv_step, self
+
     def _bias_der_slot(self, net):
         """flat derivative slot of the producing convolution's bias when this bnorm step may fill it (sum of dx)"""
         self.bias_conv_done = False
-        if self.bias_conv is None or net._flat is None or net.accumulateParamDers or not net.fuseBiasDer:
+        if self.bias_conv is None or net._flat is None or net.accumulateParamDers:
             return None
-        if net.wgradStream is not None and type(self) is not _BnReluPoolStep:
+        if not self.bias_der_always and (not net.fuseBiasDer or net.wgradStream is not None):
             # measured (default step, three A/B pairs): with a side stream the convolution's own dzdb pass runs there,
             # next to the main stream's dgrad, for free; pulling it into the bnorm backward lengthens the main stream
             # (the critical path) and cost 1 % -- although it removes 20 us of kernel time per layer.  One-stream hosts
@@ -870,158 +1010,60 @@ class _Step:
             return bp.der
         return None
 
-    def _params(self, net):
-        return [net.params[p].value for p in self.rec.params]
+    def _values(self, net, ins):
+        return self.rec.block.forward(ins, self._params(net), relu=self.relu)
 
-    def forward(self, net):
-        r = self.rec
-        if self.se_bn is not None and self.se_bn.fwd is not None and isinstance(r.block, GlobalPooling):
-            f = self.se_bn.fwd      # the squeeze of a fused SE tail: straight from the bnorm's input
-            net.vars[r.outputs[0]].value = vl.se_squeeze_bn(f["u"], f["g"], f["b"], f["moments"])
-            return
-        if self.stem_into is not None and self.stem_into.stem_forward(net, self):
-            return      # conv -> bnorm -> relu -> pool ran as one kernel; this convolution's output is never written
-        ins = [net.vars[v].value for v in r.inputs]
-        if net._training and net.wgradStream is not None and isinstance(r.block, Conv) and \
-                net.vars[r.inputs[0]].fanin > 0 and net.prepareBackward:
-            # the backward pass of this layer will need the transposed filters: build them now on the idle side
-            # stream instead of on the critical path of the backward pass (vl.conv_prepare_backward)
-            with torch.cuda.stream(net.wgradStream):
-                vl.conv_prepare_backward(ins[0], self._params(net)[0], stride=r.block.stride, pad=r.block.pad,
-                                         dilate=r.block.dilate)
-        bn = self.moments_for
-        if bn is not None and net._training and net.mode != "test" and net.fuseStats:
-            # the train-mode bnorm that consumes this convolution needs the batch moments of its output: the GEMM
-            # epilogue leaves them (straight in the flat derivative slot of the moments parameter when there is one)
-            do = net._direct_der(bn)
-            mo = do[2] if do else vl.mat_empty(bn.block.numChannels, 2, device=ins[0].device)
-            prm = self._params(net)
-            blk = r.block
-            outs = [vl.vl_nnconv(ins[0], prm[0], prm[1] if blk.hasBias else None, stride=blk.stride, pad=blk.pad,
-                                 dilate=blk.dilate, moments_out=mo, epsilon=bn.block.epsilon)]
-            bn.block._pre_moments = mo
-        elif self.run_stride is not None:
-            prm, blk = self._params(net), r.block
-            outs = [vl.vl_nnconv(ins[0], prm[0], prm[1] if blk.hasBias else None, stride=self.run_stride, pad=blk.pad,
-                                 dilate=blk.dilate)]
-        else:
-            outs = r.block.forward(ins, self._params(net))
-        for v, t in zip(r.outputs, outs):
-            net.vars[v].value = t
+    def _derivatives(self, net, ins, douts):
+        y = net.vars[self.outputs[0]].value if self.relu else None
+        return self.rec.block.backward(ins, self._params(net), douts, relu=self.relu, y=y,
+                                       der_out=net._direct_der(self.rec), dxsum_out=self._bias_der_slot(net))
 
-    def backward(self, net):
-        r = self.rec
-        douts = [net.vars[v].der for v in r.outputs]
-        if all(d is None for d in douts):
-            return
-        ins = [net.vars[v].value for v in r.inputs]
-        if isinstance(r.block, Conv):
-            need_dx = net.vars[r.inputs[0]].fanin > 0  # network inputs need no derivative
-            skip_db = self.bias_from is not None and self.bias_from.bias_conv_done
-            side = net.wgradStream if need_dx else None
-            if side is not None and net._flat is not None and net._direct_der(r) is None:
-                side = None  # the derivative would need a copy on this stream
-            # fork: another consumer of the input already left its derivative -> add it in the dgrad
-            # epilogue (dx = dgrad + existing) instead of a separate sum2 pass
-            xin = net.vars[r.inputs[0]]
-            accum = xin.der if need_dx else None
-            if accum is not None:
-                xin.der = None   # replaced by the accumulated result below
-            if side is None:
-                dins, dpar = r.block.backward(ins, self._params(net), douts, need_dx=need_dx,
-                                              der_out=net._direct_der(r), skip_db=skip_db, dx_accum=accum)
-                if net.gradHook is not None:
-                    if net._side_pending:
-                        # the hook may push a bucket that also covers layers whose filter derivatives were
-                        # enqueued on the side stream: the push is ordered against THIS stream only
-                        torch.cuda.current_stream().wait_stream(net.wgradStream)
-                    net.gradHook(r.name)
-            else:
-                # dzdw / dzdb are off the critical path of the backward pass: they run on the side
-                # stream next to the (HBM-bound) bnorm / pooling derivatives of the layers below
-                main = torch.cuda.current_stream()
-                defer = net.wgradAfterDgrad
-                if defer:
-                    # the dgrad of this layer first, alone on the chip; its wgrad starts when it has finished and
-                    # then runs next to the HBM-bound bnorm / pooling derivatives of the layers below (two
-                    # MFMA-bound kernels side by side only slow each other down)
-                    dins, _ = r.block.backward(ins, self._params(net), douts, need_dx=True, need_df=False,
-                                               dx_accum=accum)
-                side.wait_stream(main)
-                with torch.cuda.stream(side):
-                    _, dpar = r.block.backward(ins, self._params(net), douts, need_dx=False,
-                                               der_out=net._direct_der(r), skip_db=skip_db)
-                    if net.gradHook is not None:
-                        net.gradHook(r.name)
-                douts[0].record_stream(side)
-                ins[0].record_stream(side)
-                net._side_pending = True
-                if not defer:
-                    dins, _ = r.block.backward(ins, self._params(net), douts, need_dx=True, need_df=False,
-                                               dx_accum=accum)
-            if skip_db:
-                dpar = [dpar[0], net.params[r.params[1]].der]
-        elif isinstance(r.block, BatchNorm):
-            dins, dpar = r.block.backward(ins, self._params(net), douts, der_out=net._direct_der(r),
-                                          dxsum_out=self._bias_der_slot(net))
-        elif isinstance(r.block, GlobalPooling) and self.se_bn is not None and self.se_bn.stash is not None:
+
+class _PoolStep(_Step):
+    """an unfused Pooling: the backward call may use the forward result."""
+
+    def _derivatives(self, net, ins, douts):
+        outs = [net.vars[v].value for v in self.rec.outputs]
+        return self.rec.block.backward(ins, self._params(net), douts, outputs=outs if outs[0] is not None else None)
+
+
+class _GlobalPoolStep(_PoolStep):
+    """an unfused GlobalPooling: the squeeze of an SE block, one of the two readers of the block's widest tensor."""
+
+    def __init__(self, rec):
+        super().__init__(rec)
+        self.se_bn = None        # training plans: the _SEBnTrainStep whose fused calls cover this squeeze
+
+    def _values(self, net, ins):
+        f = self.se_bn.fwd if self.se_bn is not None else None
+        if f is None:
+            return super()._values(net, ins)
+        # the squeeze of a fused SE tail: straight from the bnorm's input
+        return [vl.se_squeeze_bn(f["u"], f["g"], f["b"], f["moments"])]
+
+    def _derivatives(self, net, ins, douts):
+        if self.se_bn is not None and self.se_bn.stash is not None:
             # the squeeze of a fused SE tail: its derivative is a per-plane constant that the bnorm's fused backward adds
             self.se_bn.stash["dgp"] = douts[0]
-            if net.conserveMemory:
-                for v in r.outputs:
-                    if not net.vars[v].precious:
-                        net.vars[v].der = None
-            return
-        elif isinstance(r.block, GlobalPooling) and r.block.method == "avg" and net.vars[r.inputs[0]].der is not None \
-                and net.fuseForkSums:
-            # fork: the other consumer of X (the SE excite) already left its derivative -> one pass instead of a
-            # broadcast pass + a sum pass over the widest tensors of the block
-            xin = net.vars[r.inputs[0]]
-            acc, xin.der = xin.der, None
-            dins, dpar = [vl.vl_nnpool(ins[0], [int(ins[0].shape[0]), int(ins[0].shape[1])], douts[0], method="avg",
-                                       dx_accum=acc)], []
-        elif isinstance(r.block, Pooling):
-            outs = [net.vars[v].value for v in r.outputs]
-            dins, dpar = r.block.backward(ins, self._params(net), douts,
-                                          outputs=outs if outs[0] is not None else None)
-        else:
-            dins, dpar = r.block.backward(ins, self._params(net), douts)
-        for v, d in zip(r.inputs, dins):
-            net._set_var_der(v, d)
-        for p, d in zip(r.params, dpar):
-            net._set_param_der(p, d)
-        if net.conserveMemory:
-            for v in r.outputs:
-                if not net.vars[v].precious:
-                    net.vars[v].der = None
+            return [], []
+        xin = net.vars[self.rec.inputs[0]]
+        if self.rec.block.method != "avg" or xin.der is None or not net.fuseForkSums:
+            return super()._derivatives(net, ins, douts)
+        # fork: the other consumer of X (the SE excite) already left its derivative -> one pass instead of a
+        # broadcast pass + a sum pass over the widest tensors of the block
+        acc, xin.der = xin.der, None
+        return [vl.vl_nnpool(ins[0], [int(ins[0].shape[0]), int(ins[0].shape[1])], douts[0], method="avg",
+                             dx_accum=acc)], []
 
 
-class _BnReluStep(_Step):
+class _BnReluStep(_BnStep):
     """BatchNorm -> ReLU executed as one kernel each way (train or test mode)."""
 
+    relu = True
+
     def __init__(self, bn_rec, relu_rec):
-        super().__init__(bn_rec)
+        super().__init__(bn_rec, relu_rec)
         self.relu_rec = relu_rec
-
-    def forward(self, net):
-        r = self.rec
-        ins = [net.vars[v].value for v in r.inputs]
-        y = r.block.forward(ins, self._params(net), relu=True)[0]
-        net.vars[self.relu_rec.outputs[0]].value = y
-
-    def backward(self, net):
-        r = self.rec
-        out = net.vars[self.relu_rec.outputs[0]]
-        if out.der is None:
-            return
-        ins = [net.vars[v].value for v in r.inputs]
-        dins, dpar = r.block.backward(ins, self._params(net), [out.der], relu=True, y=out.value,
-                                      der_out=net._direct_der(r), dxsum_out=self._bias_der_slot(net))
-        net._set_var_der(r.inputs[0], dins[0])
-        for p, d in zip(r.params, dpar):
-            net._set_param_der(p, d)
-        if net.conserveMemory and not out.precious:
-            out.der = None
 
 
 class _AddReluStep(_Step):
@@ -1029,49 +1071,35 @@ class _AddReluStep(_Step):
     (y = relu(a + b) or relu(s .* x + r)); backward masks dzdy by (y > 0) first."""
 
     def __init__(self, rec, relu_rec):
-        super().__init__(rec)
+        super().__init__(rec, relu_rec)
         self.relu_rec = relu_rec
+        self.se_bn = None        # training plans: the _SEBnTrainStep whose fused calls cover this excite
 
-    def forward(self, net):
-        r = self.rec
-        ins = [net.vars[v].value for v in r.inputs]
+    def _values(self, net, ins):
         if self.se_bn is not None and self.se_bn.fwd is not None:
             f = self.se_bn.fwd      # the excite of a fused SE tail: a .* bnorm(u) + shortcut, relu
-            y = vl.scale_axpy_bn(f["u"], ins[0], ins[2], f["g"], f["b"], f["moments"], relu=True)
-        else:
-            y = r.block.forward(ins, [], relu=True)[0]
-        net.vars[self.relu_rec.outputs[0]].value = y
+            return [vl.scale_axpy_bn(f["u"], ins[0], ins[2], f["g"], f["b"], f["moments"], relu=True)]
+        return self.rec.block.forward(ins, [], relu=True)
 
-    def backward(self, net):
-        r = self.rec
-        out = net.vars[self.relu_rec.outputs[0]]
-        if out.der is None:
-            return
-        if self.se_bn is not None and self.se_bn.begin(net, self, out):
-            return      # the fused SE-tail backward: da is out, everything else follows at the bnorm's position
-        dz = vl.vl_nnrelu(out.value, out.der)  # y = relu(.) > 0  <=>  pre-activation > 0
-        ins = [net.vars[v].value for v in r.inputs]
-        dins, _ = r.block.backward(ins, [], [dz])
-        for v, d in zip(r.inputs, dins):
-            net._set_var_der(v, d)
-        if net.conserveMemory and not out.precious:
-            out.der = None
+    def _derivatives(self, net, ins, douts):
+        out = net.vars[self.outputs[0]]
+        if self.se_bn is not None and self.se_bn.begin(net, out):
+            return [], []   # the fused SE-tail backward: da is out, everything else follows at the bnorm's position
+        dz = vl.vl_nnrelu(out.value, douts[0])  # y = relu(.) > 0  <=>  pre-activation > 0
+        return self.rec.block.backward(ins, [], [dz])
 
 
-class _SEBnTrainStep(_Step):
+class _SEBnTrainStep(_BnStep):
     """Training plans: the plain BatchNorm whose output X feeds exactly the squeeze (GlobalPooling 'avg') and the
     excite (Axpy(gate, X, shortcut) -> ReLU) of an SE block.  Forward: unchanged.  Backward: two fused calls
     (vl.se_tail_backward_reduce at the Axpy's position -> the gate's derivative; vl.se_tail_backward_apply here, once
     the gate's backward has produced the squeeze's derivative) instead of relu mask, scale backward, squeeze backward
     and bnorm backward over the block's widest tensors."""
 
-    def __init__(self, bn_rec, axpy_step, gp_step):
+    def __init__(self, bn_rec, axpy_rec, gp_rec):
         super().__init__(bn_rec)
-        self.axpy_step, self.gp_step = axpy_step, gp_step
-        self.stash = None
-        self.fwd = None
-        axpy_step.se_bn = self
-        gp_step.se_bn = self
+        self.axpy_rec, self.gp_rec = axpy_rec, gp_rec    # their steps point back here through se_bn (_link_training)
+        self.stash = self.fwd = None
 
     def forward(self, net):
         """X has exactly two readers, the squeeze and the excite, and the fused backward never reads it: both recompute
@@ -1091,7 +1119,7 @@ class _SEBnTrainStep(_Step):
                 return
         super().forward(net)
 
-    def begin(self, net, axpy_step, out):
+    def begin(self, net, out):
         """called by the Axpy+ReLU step's backward; False = run the separate operators"""
         self.stash = None
         # the fused backward writes no bias-derivative slot: a value left from an unfused pass (fuseSETrain toggled
@@ -1101,7 +1129,7 @@ class _SEBnTrainStep(_Step):
             if self.fwd is not None:
                 raise RuntimeError("fused SE tail: fuseSETrain was switched off between the forward and the backward pass")
             return False
-        r, ax = self.rec, axpy_step.rec
+        r, ax = self.rec, self.axpy_rec
         gate_v, x_v, sc_v = (net.vars[v] for v in ax.inputs)
         if x_v.precious or net.vars[r.outputs[0]] is not x_v:
             if self.fwd is not None:
@@ -1117,8 +1145,6 @@ class _SEBnTrainStep(_Step):
         net._set_var_der(ax.inputs[0], da)
         self.stash = {"y": out.value, "dzdy": out.der, "u": u, "sums": sums, "gate": gate_v.value, "moments": moments,
                       "test": test, "shortcut": ax.inputs[2], "dgp": None}
-        if net.conserveMemory and not out.precious:
-            out.der = None
         return True
 
     def backward(self, net):
@@ -1139,22 +1165,20 @@ class _SEBnTrainStep(_Step):
             net._set_param_der(p, d)
 
 
-class _BnReluPoolStep(_Step):
+class _BnReluPoolStep(_BnStep):
     """BatchNorm -> ReLU -> Pooling('max') as one fused operator pair (train or test mode): the
     normalised / rectified tensor is never written to HBM (vl.bnorm_relu_pool)."""
 
-    def __init__(self, bn_rec, relu_rec, pool_rec, bias_conv=None):
-        super().__init__(bn_rec)
+    bias_der_always = True
+
+    def __init__(self, bn_rec, relu_rec, pool_rec):
+        super().__init__(bn_rec, relu_rec, pool_rec)
         self.relu_rec, self.pool_rec = relu_rec, pool_rec
         self._saved = None
-        self.bias_conv = bias_conv        # _Step of the biased Conv feeding this BN (or None)
-        self.bias_conv_done = False
-        self.producer_conv = None         # _Step of the Conv whose ONLY consumer is this BN (training plans, build_plan)
+        self.producer_conv = None         # _ConvStep of the Conv whose ONLY consumer is this BN (_link_training)
         self._stem_fused = True           # cleared when the library reports the shapes as not covered
         self._stem_fwd_ok = True          # ... the fused forward (conv + bnorm + relu + pool in one kernel)
         self._stem_fwd = None             # set by stem_forward: {"gram": G or None} -- the convolution's output does not exist
-        if bias_conv is not None:
-            bias_conv.bias_from = self
 
     def _stem_conditions(self, net):
         """what both fused directions need from the plan: the producing convolution is a first layer that feeds only this
@@ -1235,26 +1259,17 @@ class _BnReluPoolStep(_Step):
         do = net._direct_der(r)
         if self._stem_backward(net, x, g, b, mom if test else mo, am, out, do, test):
             net._set_param_der(r.params[2], mo)
-            if net.conserveMemory and not out.precious:
-                out.der = None
+            _release_der(net, out)
             return
         # the producing convolution's bias derivative (= per-channel sum of this dx) comes for free
-        bias_der = None
-        if self.bias_conv is not None and net._flat is not None and not net.accumulateParamDers:
-            bp = net.params[self.bias_conv.rec.params[1]]
-            if bp.fanout == 1 and bp.der is not None:
-                bias_der = bp.der
-        self.bias_conv_done = bias_der is not None
         dx, dg, db = vl.bnorm_relu_pool_backward(x, g, b, mom if test else mo, am, out.der, pb.poolSize,
                                                  stride=pb.stride, pad=pb.pad, train=not test,
                                                  dg_out=do[0] if do else None, db_out=do[1] if do else None,
-                                                 dxsum_out=bias_der, y_pool=out.value)
+                                                 dxsum_out=self._bias_der_slot(net), y_pool=out.value)
         net._set_var_der(r.inputs[0], dx)
         for p, d in zip(r.params, [dg, db, mo]):
             net._set_param_der(p, d)
-        if net.conserveMemory and not out.precious:
-            out.der = None
-
+        _release_der(net, out)
 
     def _stem_backward(self, net, x, g, b, moments, am, out, do, test):
         """The producing convolution is a first layer (its input needs no derivative) and feeds only this step: one
@@ -1314,17 +1329,17 @@ class _ConvActStep(_Step):
     """forward-only plans: Conv -> ReLU / Sigmoid with the activation in the producing kernel (the SE gate's
     fc1 -> relu and fc2 -> sigmoid: four launches become two skinny-FC kernels, see xm_nnconv_forward_fused)."""
 
+    reads_through_conv = True
+
     def __init__(self, conv_rec, act_rec):
-        super().__init__(conv_rec)
+        super().__init__(conv_rec, act_rec)
         self.act_rec = act_rec
 
-    def forward(self, net):
-        r, blk = self.rec, self.rec.block
-        par = self._params(net)
+    def _values(self, net, ins):
+        blk, par = self.rec.block, self._params(net)
         sig = isinstance(self.act_rec.block, Sigmoid)
-        y = vl.vl_nnconv(net.vars[r.inputs[0]].value, par[0], par[1] if blk.hasBias else None, stride=self._stride(),
-                         pad=blk.pad, dilate=blk.dilate, relu=not sig, sigmoid=sig)
-        net.vars[self.act_rec.outputs[0]].value = y
+        return [vl.vl_nnconv(ins[0], par[0], par[1] if blk.hasBias else None, stride=self._stride(),
+                             pad=blk.pad, dilate=blk.dilate, relu=not sig, sigmoid=sig)]
 
     def backward(self, net):
         raise RuntimeError("dagnn: a forward-only plan was asked for derivatives")
@@ -1334,9 +1349,11 @@ class _ConvFoldStep(_Step):
     """test mode only: Conv -> BatchNorm [-> Sum(shortcut)] [-> ReLU] in the conv epilogue.
     scale_k = g_k / sigma_k, shift_k = b_k - mu_k * scale_k  (frozen moments)."""
 
-    def __init__(self, conv_rec, bn_rec, sum_rec, relu_rec, out_name):
-        super().__init__(conv_rec)
-        self.bn_rec, self.sum_rec, self.relu_rec, self.out_name = bn_rec, sum_rec, relu_rec, out_name
+    reads_through_conv = True
+
+    def __init__(self, conv_rec, bn_rec, sum_rec, relu_rec, between=()):
+        super().__init__(conv_rec, bn_rec, *between, sum_rec, relu_rec)
+        self.bn_rec, self.sum_rec, self.relu_rec = bn_rec, sum_rec, relu_rec
         self._folded = None
 
     def _fold(self, net):
@@ -1351,21 +1368,17 @@ class _ConvFoldStep(_Step):
                             vl.from_numpy(sh.reshape(-1, 1), g.device))
         return self._folded[1], self._folded[2]
 
-    def forward(self, net):
-        r = self.rec
-        blk = r.block
-        x = net.vars[r.inputs[0]].value
-        prm = self._params(net)
+    def _values(self, net, ins):
+        blk, prm = self.rec.block, self._params(net)
         sc, sh = self._fold(net)
         resid = None
         if self.sum_rec is not None:
             other = [v for v in self.sum_rec.inputs if v != self.bn_rec.outputs[0]][0]
             resid = net.vars[other].value
         pruned = self.run_stride if (resid is not None and self.run_stride != (1, 1)) else None
-        y = vl.vl_nnconv(x, prm[0], prm[1] if blk.hasBias else None, stride=self._stride(), pad=blk.pad,
-                         dilate=blk.dilate, scale=sc, shift=sh, residual=resid, residual_stride=pruned,
-                         relu=self.relu_rec is not None)
-        net.vars[self.out_name].value = y
+        return [vl.vl_nnconv(ins[0], prm[0], prm[1] if blk.hasBias else None, stride=self._stride(), pad=blk.pad,
+                             dilate=blk.dilate, scale=sc, shift=sh, residual=resid, residual_stride=pruned,
+                             relu=self.relu_rec is not None)]
 
     def backward(self, net):
         raise RuntimeError("folded conv+bn steps exist only in forward-only test-mode plans")
@@ -1383,8 +1396,11 @@ class _SEFoldStep(_ConvFoldStep):
     (vl_nnconv(..., gate=a, residual=shortcut)): x is never materialised -- no write, no squeeze read, no excite
     read / write of the widest tensors of the network."""
 
+    reads_through_conv = False      # the squeeze is a mean over every pixel of the input
+
     def __init__(self, conv_rec, bn_rec, se):
-        super().__init__(conv_rec, bn_rec, None, se["relu"], se["out"])
+        super().__init__(conv_rec, bn_rec, None, se["relu"],
+                         between=[se[k] for k in ("gp", "fc1", "relu1", "fc2", "sig", "axpy")])
         self.se = se
         self._reduce = None
 
@@ -1408,9 +1424,8 @@ class _SEFoldStep(_ConvFoldStep):
                             vl.from_numpy(b10.astype(np.float32).reshape(-1, 1), F.device))
         return self._reduce[1], self._reduce[2]
 
-    def forward(self, net):
-        r, blk, se = self.rec, self.rec.block, self.se
-        u = net.vars[r.inputs[0]].value
+    def _values(self, net, ins):
+        blk, se, u = self.rec.block, self.se, ins[0]
         prm = self._params(net)
         bias = prm[1] if blk.hasBias else None
         sc, sh = self._fold(net)
@@ -1430,74 +1445,168 @@ class _SEFoldStep(_ConvFoldStep):
             h = vl.vl_nnconv(z, f1[0], b1, relu=True)
         a = vl.vl_nnconv(h, f2[0], f2[1] if se["fc2"].block.hasBias else None, sigmoid=True)
         # (a pruned step samples only the excite's write: the squeeze above is a mean over ALL pixels of u)
-        y = vl.vl_nnconv(u, prm[0], bias, stride=self._stride(), pad=blk.pad, dilate=blk.dilate, scale=sc, shift=sh,
-                         gate=a, residual=net.vars[se["shortcut"]].value, residual_stride=self.run_stride,
-                         relu=se["relu"] is not None)
-        net.vars[self.out_name].value = y
+        return [vl.vl_nnconv(u, prm[0], bias, stride=self._stride(), pad=blk.pad, dilate=blk.dilate, scale=sc, shift=sh,
+                             gate=a, residual=net.vars[se["shortcut"]].value, residual_stride=self.run_stride,
+                             relu=se["relu"] is not None)]
 
 
-def _match_se_tail(net, recs, consumers, order, conv_rec, bn_rec, keep_values=False):
+# ---- building a plan: who reads and writes what, the fusions by kind of plan, the links, the pruning --------------------
+class _Wiring:
+    """who reads and who writes each variable of net.layers, for one build_plan call"""
+
+    def __init__(self, net):
+        self.net = net
+        self.order = {id(r): i for i, r in enumerate(net.layers)}
+        self.consumers, self.producers = {}, {}
+        for r in net.layers:
+            for v in r.inputs:
+                self.consumers.setdefault(v, []).append(r)
+            for v in r.outputs:
+                self.producers.setdefault(v, []).append(r)
+
+    def sole_consumer(self, var, cls, keep_value=False):
+        """the only layer that reads `var` when it is a `cls` -- and, unless the caller still materialises `var`
+        (`keep_value`), when `var` is not precious"""
+        cs = self.consumers.get(var, [])
+        ok = len(cs) == 1 and isinstance(cs[0].block, cls) and (keep_value or not self.net.vars[var].precious)
+        return cs[0] if ok else None
+
+    def fused_relu(self, var, keep_value=False):
+        """the plain ReLU that is the sole consumer of `var`: the producing kernel can rectify"""
+        rl = self.sole_consumer(var, ReLU, keep_value)
+        return rl if rl is not None and rl.block.leak == 0.0 else None
+
+    def produced_before(self, var, rec):
+        """every layer that writes `var` runs before `rec` (nothing writes a network input): a fused step headed by `rec`
+        can take it as an operand, and the plain order of the heads is still a valid schedule"""
+        return all(self.order[id(q)] < self.order[id(rec)] for q in self.producers.get(var, ()))
+
+    def feeding_conv(self, rec):
+        """the Conv whose output is the first input of `rec` and is read by nothing else"""
+        var = rec.inputs[0]
+        prod = self.producers.get(var, [])
+        ok = prod and isinstance(prod[0].block, Conv) and len(self.consumers.get(var, [])) == 1
+        return prod[0] if ok else None
+
+
+def _conv_1x1(blk, unit_stride=False, unit_dilate=True):
+    """a 1 x 1, pad-0 Conv; the call sites differ in whether they also ask for unit stride and unit dilation"""
+    return isinstance(blk, Conv) and blk.size[0] == 1 and blk.size[1] == 1 and not any(vl._pad4(blk.pad)) and \
+        (not unit_stride or tuple(vl._pair(blk.stride, "STRIDE")) == (1, 1)) and \
+        (not unit_dilate or tuple(vl._pair(blk.dilate, "DILATE")) == (1, 1))
+
+
+def _match_se_tail(w, conv_rec, bn_rec, keep_values=False):
     """the SE tail behind a 1 x 1 / stride-1 projection + bnorm: {GlobalPooling('avg') -> Conv -> ReLU -> Conv -> Sigmoid}
     and Axpy(gate, x, shortcut) [-> ReLU] as the only consumers of x, nothing precious in between (`keep_values`: the
     caller still materialises every variable of the gate path -- training plans -- so precious ones there are fine)"""
-    blk = conv_rec.block
-    if blk.size[0] != 1 or blk.size[1] != 1 or tuple(vl._pair(blk.stride, "STRIDE")) != (1, 1) or any(vl._pad4(blk.pad)):
+    if not _conv_1x1(conv_rec.block, unit_stride=True, unit_dilate=False):
         return None
     x = bn_rec.outputs[0]
-    cs = consumers.get(x, [])
-    if len(cs) != 2 or net.vars[x].precious:
+    cs = w.consumers.get(x, [])
+    if len(cs) != 2 or w.net.vars[x].precious:
         return None
     gp = [c for c in cs if isinstance(c.block, GlobalPooling) and c.block.method == "avg"]
     ax = [c for c in cs if isinstance(c.block, Axpy)]
     if len(gp) != 1 or len(ax) != 1:
         return None
     gp, ax = gp[0], ax[0]
-
-    def only(var, cls):
-        c = consumers.get(var, [])
-        return c[0] if len(c) == 1 and isinstance(c[0].block, cls) and (keep_values or not net.vars[var].precious) else None
-    fc1 = only(gp.outputs[0], Conv)
-    r1 = only(fc1.outputs[0], ReLU) if fc1 else None
-    fc2 = only(r1.outputs[0], Conv) if r1 else None
-    sg = only(fc2.outputs[0], Sigmoid) if fc2 else None
-    if sg is None or r1.block.leak != 0.0 or only(sg.outputs[0], Axpy) is not ax:
+    fc1 = w.sole_consumer(gp.outputs[0], Conv, keep_values)
+    r1 = w.sole_consumer(fc1.outputs[0], ReLU, keep_values) if fc1 else None
+    fc2 = w.sole_consumer(r1.outputs[0], Conv, keep_values) if r1 else None
+    sg = w.sole_consumer(fc2.outputs[0], Sigmoid, keep_values) if fc2 else None
+    if sg is None or r1.block.leak != 0.0 or w.sole_consumer(sg.outputs[0], Axpy, keep_values) is not ax:
         return None
-    for fc in (fc1, fc2):
-        b = fc.block
-        if b.size[0] != 1 or b.size[1] != 1 or tuple(vl._pair(b.stride, "STRIDE")) != (1, 1) or any(vl._pad4(b.pad)):
-            return None
+    if not all(_conv_1x1(fc.block, unit_stride=True, unit_dilate=False) for fc in (fc1, fc2)):
+        return None
     if len(ax.inputs) != 3 or ax.inputs[0] != sg.outputs[0] or ax.inputs[1] != x:
         return None
     shortcut = ax.inputs[2]
-    prod = [q for q in recs if shortcut in q.outputs]
-    if prod and not all(order[id(q)] < order[id(conv_rec)] for q in prod):
+    if not w.produced_before(shortcut, conv_rec):
         return None
-    out, relu = ax.outputs[0], None
-    rl = only(out, ReLU)
-    if rl is not None and rl.block.leak == 0.0:
-        relu, out = rl, rl.outputs[0]
-    return {"gp": gp, "fc1": fc1, "relu1": r1, "fc2": fc2, "sig": sg, "axpy": ax, "relu": relu, "out": out,
-            "shortcut": shortcut}
+    return {"gp": gp, "fc1": fc1, "relu1": r1, "fc2": fc2, "sig": sg, "axpy": ax,
+            "relu": w.fused_relu(ax.outputs[0], keep_values), "shortcut": shortcut}
 
 
-def _link_bias_conv(bn_step, steps, r, consumers, training):
-    """training plans: a biased Conv whose only consumer is this bnorm gets its dzdb from the bnorm backward (sum of
-    dx) instead of a pass of its own over dzdy"""
-    if not training:
-        return
-    prod = [q for q in steps if type(q) is _Step and r.inputs[0] in q.rec.outputs]
-    if prod and isinstance(prod[0].rec.block, Conv) and prod[0].rec.block.hasBias and \
-            len(consumers.get(r.inputs[0], [])) == 1:
-        bn_step.bias_conv = prod[0]
-        prod[0].bias_from = bn_step
+def _fold_forward_only(w, r):
+    """forward-only test-mode plans: a Conv takes its frozen bnorm -- with the SE tail, or the shortcut add, and the ReLU
+    behind it -- or else its activation into its own kernel"""
+    if not isinstance(r.block, Conv):
+        return None
+    bn = w.sole_consumer(r.outputs[0], BatchNorm)
+    if bn is None:
+        act = w.sole_consumer(r.outputs[0], (ReLU, Sigmoid))
+        if act is not None and (isinstance(act.block, Sigmoid) or act.block.leak == 0.0):
+            return _ConvActStep(r, act)
+        return None
+    se = _match_se_tail(w, r, bn) if w.net.fuseSE else None
+    if se is not None:
+        return _SEFoldStep(r, bn, se)
+    out = bn.outputs[0]
+    sm = w.sole_consumer(out, Sum)
+    # the shortcut operand must already be computed when the conv runs
+    if sm is not None and len(sm.inputs) == 2 and w.produced_before([v for v in sm.inputs if v != out][0], r):
+        out = sm.outputs[0]
+    else:
+        sm = None
+    return _ConvFoldStep(r, bn, sm, w.fused_relu(out))
 
 
-def _plain_1x1(blk):
-    return isinstance(blk, Conv) and blk.size[0] == 1 and blk.size[1] == 1 and not any(vl._pad4(blk.pad)) and \
-        tuple(vl._pair(blk.dilate, "DILATE")) == (1, 1)
+def _fuse_common(w, r):
+    """the peephole fusions of every plan: Sum / Axpy -> ReLU and BatchNorm -> ReLU [-> Pooling('max')]"""
+    if isinstance(r.block, Axpy) or (isinstance(r.block, Sum) and len(r.inputs) == 2):
+        rl = w.fused_relu(r.outputs[0])
+        return _AddReluStep(r, rl) if rl is not None else None
+    if isinstance(r.block, BatchNorm):
+        rl = w.fused_relu(r.outputs[0])
+        pl = w.sole_consumer(rl.outputs[0], Pooling) if rl is not None else None
+        if pl is not None and not isinstance(pl.block, GlobalPooling) and _BnReluPoolStep.eligible(pl.block):
+            return _BnReluPoolStep(r, rl, pl)
+        return _BnReluStep(r, rl) if rl is not None else None
+    return None
 
 
-def _prune_strided_boundaries(net, steps, consumers):
+def _se_train_head(w, r):
+    """training plans: the plain bnorm behind an SE block's projection; its squeeze and its excite (+ relu) share one
+    fused backward with it (_link_training ties the three steps together once the later two exist)"""
+    conv = w.feeding_conv(r) if isinstance(r.block, BatchNorm) else None
+    se = _match_se_tail(w, conv, r, keep_values=True) if conv is not None else None
+    # the excite has to become one Axpy+ReLU step: _fuse_common asks the same of its output
+    if se is None or w.fused_relu(se["axpy"].outputs[0]) is None:
+        return None
+    return _SEBnTrainStep(r, se["axpy"], se["gp"])
+
+
+def _unfused(r):
+    for cls, step in ((Conv, _ConvStep), (BatchNorm, _BnStep), (GlobalPooling, _GlobalPoolStep), (Pooling, _PoolStep)):
+        if isinstance(r.block, cls):
+            return step(r)
+    return _Step(r)
+
+
+def _link_training(w, steps):
+    """training plans.  Conv -> BatchNorm (train mode) with nothing else reading the convolution: its epilogue computes
+    the batch moments (vl_nnconv moments_out) and the bnorm step -- plain, +relu or +relu+pool -- takes them instead of
+    re-reading its input; a biased one gets its dzdb from that step; a +relu+pool step can run the convolution itself."""
+    by_rec = {id(st.rec): st for st in steps}
+    for st in steps:
+        if isinstance(st, _SEBnTrainStep):
+            ax, gp = by_rec[id(st.axpy_rec)], by_rec[id(st.gp_rec)]
+            assert type(ax) is _AddReluStep and type(gp) is _GlobalPoolStep, st.rec.name     # _se_train_head saw to it
+            ax.se_bn = gp.se_bn = st
+        conv = w.feeding_conv(st.rec) if isinstance(st, _BnStep) else None
+        if conv is None:
+            continue
+        cs = by_rec[id(conv)]
+        assert isinstance(cs, _ConvStep), conv.name      # only forward-only plans fold a convolution
+        cs.moments_for = st.rec
+        if conv.block.hasBias:
+            st.take_bias_of(cs)
+        if isinstance(st, _BnReluPoolStep):
+            st.producer_conv, cs.stem_into = cs, st
+
+
+def _prune_strided_boundaries(w, steps):
     """forward-only test-mode plans: skip the pixels no layer reads.
 
     A folded 1 x 1 / stride-1 convolution step (the C/4 -> C expansion that ends a stage, with its bnorm, shortcut add or SE
@@ -1508,13 +1617,12 @@ def _prune_strided_boundaries(net, steps, consumers):
     tensor is the sampled 1 x 1 convolution, so every later variable has the values it had."""
     head = {id(st.rec): st for st in steps}
     for st in steps:
-        blk = st.rec.block
-        if not isinstance(st, _ConvFoldStep) or st.run_stride is not None or not _plain_1x1(blk) or \
-                tuple(vl._pair(blk.stride, "STRIDE")) != (1, 1) or net.vars[st.out_name].precious:
+        if not isinstance(st, _ConvFoldStep) or st.run_stride is not None or \
+                not _conv_1x1(st.rec.block, unit_stride=True) or w.net.vars[st.outputs[0]].precious:
             continue
-        readers = [head.get(id(c)) for c in consumers.get(st.out_name, [])]
-        if not readers or any(q is None or type(q) not in (_Step, _ConvActStep, _ConvFoldStep) or
-                              not _plain_1x1(q.rec.block) or q.run_stride is not None for q in readers):
+        readers = [head.get(id(c)) for c in w.consumers.get(st.outputs[0], [])]
+        if not readers or any(q is None or not q.reads_through_conv or not _conv_1x1(q.rec.block) or
+                              q.run_stride is not None for q in readers):
             continue
         strides = {tuple(vl._pair(q.rec.block.stride, "STRIDE")) for q in readers}
         if len(strides) != 1:
@@ -1528,129 +1636,19 @@ def _prune_strided_boundaries(net, steps, consumers):
 
 
 def build_plan(net, training):
-    recs = net.layers
-    if not net.fuse:
-        return [_Step(r) for r in recs]
-    consumers = {}
-    for r in recs:
-        for v in r.inputs:
-            consumers.setdefault(v, []).append(r)
-    produced_before = {}
-    order = {id(r): i for i, r in enumerate(recs)}
-
-    def sole_consumer(var, cls):
-        cs = consumers.get(var, [])
-        if len(cs) == 1 and isinstance(cs[0].block, cls) and not net.vars[var].precious:
-            return cs[0]
-        return None
-
-    steps, skip = [], set()
-    fold_ok = (not training) and net.mode == "test"
-    for r in recs:
-        if id(r) in skip:
+    w = _Wiring(net)
+    fold = net.fuse and not training and net.mode == "test"
+    steps, taken = [], set()
+    for r in net.layers:
+        if id(r) in taken:
             continue
-        if fold_ok and isinstance(r.block, Conv):
-            bn = sole_consumer(r.outputs[0], BatchNorm)
-            se = _match_se_tail(net, recs, consumers, order, r, bn) if (bn is not None and net.fuseSE) else None
-            if se is not None:
-                steps.append(_SEFoldStep(r, bn, se))
-                skip.update(id(q) for q in (bn, se["gp"], se["fc1"], se["relu1"], se["fc2"], se["sig"], se["axpy"],
-                                            se["relu"]) if q is not None)
-                continue
-            if bn is not None:
-                out = bn.outputs[0]
-                sm = sole_consumer(out, Sum)
-                # the shortcut operand must already be computed when the conv runs
-                if sm is not None and len(sm.inputs) == 2:
-                    other = [v for v in sm.inputs if v != out][0]
-                    prod = [q for q in recs if other in q.outputs]
-                    ready = (not prod) or all(order[id(q)] < order[id(r)] for q in prod)
-                    if ready:
-                        out = sm.outputs[0]
-                    else:
-                        sm = None
-                else:
-                    sm = None
-                rl = sole_consumer(out, ReLU)
-                if rl is not None and rl.block.leak == 0.0:
-                    out = rl.outputs[0]
-                else:
-                    rl = None
-                steps.append(_ConvFoldStep(r, bn, sm, rl, out))
-                skip.update(id(q) for q in (bn, sm, rl) if q is not None)
-                continue
-            act = sole_consumer(r.outputs[0], (ReLU, Sigmoid))
-            if act is not None and (isinstance(act.block, Sigmoid) or act.block.leak == 0.0):
-                steps.append(_ConvActStep(r, act))
-                skip.add(id(act))
-                continue
-        if isinstance(r.block, (Sum, Axpy)) and (not isinstance(r.block, Sum) or len(r.inputs) == 2):
-            rl = sole_consumer(r.outputs[0], ReLU)
-            if rl is not None and rl.block.leak == 0.0:
-                steps.append(_AddReluStep(r, rl))
-                skip.add(id(rl))
-                continue
-        if isinstance(r.block, BatchNorm):
-            rl = sole_consumer(r.outputs[0], ReLU)
-            if rl is not None and rl.block.leak == 0.0:
-                pl = sole_consumer(rl.outputs[0], Pooling)
-                if pl is not None and not isinstance(pl.block, GlobalPooling) and \
-                        _BnReluPoolStep.eligible(pl.block):
-                    bias_conv = None
-                    prod = [q for q in steps if type(q) is _Step and r.inputs[0] in q.rec.outputs]
-                    if training and prod and isinstance(prod[0].rec.block, Conv) and prod[0].rec.block.hasBias \
-                            and len(consumers.get(r.inputs[0], [])) == 1:
-                        bias_conv = prod[0]
-                    steps.append(_BnReluPoolStep(r, rl, pl, bias_conv))
-                    skip.update((id(rl), id(pl)))
-                    continue
-                st_ = _BnReluStep(r, rl)
-                _link_bias_conv(st_, steps, r, consumers, training)
-                steps.append(st_)
-                skip.add(id(rl))
-                continue
-            st_ = _Step(r)
-            _link_bias_conv(st_, steps, r, consumers, training)
-            steps.append(st_)
-            continue
-        steps.append(_Step(r))
-    # a fused step may now sit before the producer of one of its operands is scheduled; the
-    # `ready` test above guarantees producers precede the conv, so plain order is still valid.
-    del produced_before
-    if fold_ok and net.stridePrune:
-        _prune_strided_boundaries(net, steps, consumers)
-    if training:
-        # Conv -> BatchNorm (train mode): the convolution's epilogue computes the batch moments (vl_nnconv
-        # moments_out), the bnorm step -- plain, +relu or +relu+pool -- takes them instead of re-reading its input
-        conv_of = {st.rec.outputs[0]: st for st in steps if type(st) is _Step and isinstance(st.rec.block, Conv)}
-        for st in steps:
-            r = st.rec
-            if isinstance(r.block, BatchNorm) and type(st) in (_Step, _BnReluStep, _BnReluPoolStep):
-                cs = conv_of.get(r.inputs[0])
-                if cs is not None and len(consumers.get(r.inputs[0], [])) == 1:
-                    cs.moments_for = r
-                    if type(st) is _BnReluPoolStep:
-                        st.producer_conv = cs
-                        cs.stem_into = st
-        # SE blocks: the plain bnorm behind the projection, its squeeze and its excite (+ relu) share one fused backward
-        by_rec = {id(st.rec): st for st in steps}
-        for i, st in enumerate(steps):
-            r = st.rec
-            if type(st) is not _Step or not isinstance(r.block, BatchNorm):
-                continue
-            cs = conv_of.get(r.inputs[0])
-            if cs is None or len(consumers.get(r.inputs[0], [])) != 1:
-                continue
-            se = _match_se_tail(net, recs, consumers, order, cs.rec, r, keep_values=True)
-            if se is None or se["relu"] is None:
-                continue
-            ax_step, gp_step = by_rec.get(id(se["axpy"])), by_rec.get(id(se["gp"]))
-            if type(ax_step) is not _AddReluStep or type(gp_step) is not _Step:
-                continue
-            new_st = _SEBnTrainStep(r, ax_step, gp_step)
-            new_st.bias_conv, new_st.bias_from, new_st.moments_for = st.bias_conv, st.bias_from, st.moments_for
-            for q in steps:
-                if q.bias_from is st:
-                    q.bias_from = new_st
-            steps[i] = new_st
+        st = _fold_forward_only(w, r) if fold else None
+        if st is None and net.fuse:
+            st = _fuse_common(w, r) or (_se_train_head(w, r) if training else None)
+        steps.append(st or _unfused(r))
+        taken.update(id(q) for q in steps[-1].recs[1:])
+    if net.fuse and training:
+        _link_training(w, steps)
+    if fold and net.stridePrune:
+        _prune_strided_boundaries(w, steps)
     return steps
