@@ -57,7 +57,7 @@ enum { XM_FUSE_RELU = 1, XM_BN_BATCH_MOMENTS = 2, XM_FUSE_SIGMOID = 4 };
 
 /* ABI revision: 100 = round 1; 101 = xm_nnbnorm_relu_pool_backward gained `y_pool`, exchange entry points return
  * XM_EINVAL without a communicator; 102 = + xm_nnconv_forward_moments, xm_nnbnorm_backward_dxsum, xm_nnconv_forward_gated;
- * 103 = + xm_nnpool_global_avg_backward_accum; 104 = + xm_nnconv_backward_filter_bnrelupool, xm_nndropout_forward / _apply, xm_resample, xm_se_tail_backward_reduce / _apply, xm_se_squeeze_bn, xm_scale_axpy_bn; 105 = + xm_set_exec_hint / xm_get_exec_hint; 106 = + xm_nnconv_bnorm_relu_pool_forward, xm_stem_gram, xm_stem_gram_moments, xm_nnconv_backward_filter_bnrelupool_gram; 107 = + xm_nnaffinegrid / _backward, xm_nnbilinearsampler / _backward, xm_ferplus_batch; 108 = + XM_AGG_PEAK, xm_mnrfit, xm_mnrval; 109 = + xm_roc, xm_roc_launches, xm_label_hist; 110 = + xm_group_rows, xm_gather_rows, xm_scatter_rows, xm_track_peaks; 111 = + xm_wav_batch; 112 = + xm_spec_bucket_batch; 113 = + xm_jpeg_plan, xm_jpeg_decode_batch; 114 = + xm_wav_plan, xm_wav_decode_batch; 115 = + xm_jpeg_decode_batch_split, xm_jpeg_split_geometry; 116 = + xm_pixcsv_plan, xm_pixcsv_decode_batch, xm_pixcsv_geometry; 117 = + xm_nnconv_forward_strided_residual (additions never change the revision's meaning for older bindings).  A binding checks xm_version() >= the revision it was written against. */
+ * 103 = + xm_nnpool_global_avg_backward_accum; 104 = + xm_nnconv_backward_filter_bnrelupool, xm_nndropout_forward / _apply, xm_resample, xm_se_tail_backward_reduce / _apply, xm_se_squeeze_bn, xm_scale_axpy_bn; 105 = + xm_set_exec_hint / xm_get_exec_hint; 106 = + xm_nnconv_bnorm_relu_pool_forward, xm_stem_gram, xm_stem_gram_moments, xm_nnconv_backward_filter_bnrelupool_gram; 107 = + xm_nnaffinegrid / _backward, xm_nnbilinearsampler / _backward, xm_ferplus_batch; 108 = + XM_AGG_PEAK, xm_mnrfit, xm_mnrval; 109 = + xm_roc, xm_roc_launches, xm_label_hist; 110 = + xm_group_rows, xm_gather_rows, xm_scatter_rows, xm_track_peaks; 111 = + xm_wav_batch; 112 = + xm_spec_bucket_batch; 113 = + xm_jpeg_plan, xm_jpeg_decode_batch; 114 = + xm_wav_plan, xm_wav_decode_batch; 115 = + xm_jpeg_decode_batch_split, xm_jpeg_split_geometry; 116 = + xm_pixcsv_plan, xm_pixcsv_decode_batch, xm_pixcsv_geometry; 117 = + xm_nnconv_forward_strided_residual; 118 = + xm_solver_update (additions never change the revision's meaning for older bindings).  A binding checks xm_version() >= the revision it was written against. */
 int xm_version(void);
 const char *xm_last_error(void);
 /* Device memory for hosts that have no device-array type of their own (MATLAB's gpuArray is CUDA-only: on an
@@ -400,6 +400,37 @@ int xm_nnloss(const float *x, const float *labels, int C, int N, int loss, const
  * trainMethod 'gradient':  m <- momentum*m - (wd*w + der/batch);  w <- w + lr*m */
 int xm_sgd_update(float *w, float *m, const float *der, size_t n, float lr, float momentum,
                   float weight_decay, float batch, void *stream);
+/* cnn_train_dag's 'solver' option and the 'nesterovUpdate' arm of its default solver (ABI 118).  One launch updates one flat
+ * segment in place.  The formulas are restated from MatConvNet's +solver package and cnn_train_dag.m [EXT]; MatConvNet is
+ * not part of this tree, so parity with it is not pinned by a test (the tests hold the kernel to a numpy restatement of
+ * the lines below).  First  g = der * (1/batch) + weight_decay * w  (vl_taccum(1/batchSize, parDer, thisDecay, value)),
+ * then, in fp32 and in this order of operations:
+ *   XM_SOLVER_ADAGRAD   s1 = g_sqr                  g_sqr = g_sqr*rho + g.^2;  w = w - lr*g ./ (sqrt(g_sqr) + epsilon)
+ *   XM_SOLVER_RMSPROP   s1 = g_sqr                  g_sqr = g_sqr*rho + g.^2*(1-rho);  w = w - lr*g ./ (sqrt(g_sqr) + epsilon)
+ *   XM_SOLVER_ADADELTA  s1 = g_sqr, s2 = delta_sqr  g_sqr = g_sqr*rho + g.^2*(1-rho);
+ *                                                   delta = -sqrt((delta_sqr + epsilon) ./ (g_sqr + epsilon)) .* g;
+ *                                                   delta_sqr = delta_sqr*rho + delta.^2*(1-rho);  w = w + lr*delta
+ *   XM_SOLVER_ADAM      s1 = m, s2 = v              m = m + (1-beta1)*(g - m);  v = v + (1-beta2)*(g.^2 - v);
+ *                                                   w = w - lr_t * m ./ (sqrt(v) + epsilon),
+ *                                                   lr_t = lr*sqrt(1 - beta2^t)/(1 - beta1^t), t = updates so far, this one
+ *                                                   included (the HOST counts t and computes lr_t; `lr` is not read)
+ *   XM_SOLVER_NESTEROV  s1 = momentum state         m = mom*m - g;  w = w + lr*(mom*m - g)
+ * States start at zero (MatConvNet's empty state).  s2 is read and written by ADADELTA and ADAM only; the other kinds
+ * accept NULL there and leave a passed buffer untouched.
+ * `coef`: HOST pointer to 4 floats, read during the call.  MATLAB evaluates a double scalar expression such as
+ * (1 - opts.beta2) in double and only then multiplies the single array, so the host forms these in double and rounds once
+ * (1 - 0.999f in fp32 is 1.3e-5 off):
+ *                       coef[0]     coef[1]     coef[2]     coef[3]
+ *   ADAGRAD             epsilon     rho         -           -          defaults 1e-10, 1
+ *   RMSPROP             epsilon     rho         1 - rho     -          defaults 1e-8, 0.99
+ *   ADADELTA            epsilon     rho         1 - rho     -          defaults 1e-6, 0.9
+ *   ADAM                epsilon     1 - beta1   1 - beta2   lr_t       defaults 1e-8, beta1 0.9, beta2 0.999
+ *   NESTEROV            momentum    -           -           -          cnn_train_dag's 'momentum'
+ * Unused slots are not read.  XM_EINVAL, before anything touches the device: unknown kind, batch <= 0, NULL coef, and for
+ * n > 0 a NULL w, der or s1, or a NULL s2 for ADADELTA / ADAM.  n == 0: XM_OK without a launch. */
+enum { XM_SOLVER_ADAGRAD = 0, XM_SOLVER_RMSPROP = 1, XM_SOLVER_ADADELTA = 2, XM_SOLVER_ADAM = 3, XM_SOLVER_NESTEROV = 4 };
+int xm_solver_update(int kind, float *w, float *s1, float *s2, const float *der, size_t n, float lr,
+                     float weight_decay, float batch, const float *coef, void *stream);
 /* trainMethod 'average' (BN moments):  w <- (1-lr)*w + lr*der/denom.
  * MatConvNet [EXT]: dagnn.BatchNorm hands back moments * (its worker's batch size), the workers' values are summed
  * and accumulateGradients divides by the GLOBAL batch size -- workers with ragged shards are weighted by their

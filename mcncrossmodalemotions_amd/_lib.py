@@ -95,6 +95,7 @@ SIGNATURES = {
     "xm_nnsoftmaxceloss": [c_fp, c_fp, _i, _i, _f, _i, c_fp, c_fp, c_fp, _vp],
     "xm_nnloss": [c_fp, c_fp, _i, _i, _i, c_fp, c_fp, _vp],
     "xm_sgd_update": [c_fp, c_fp, c_fp, _sz, _f, _f, _f, _f, _vp],
+    "xm_solver_update": [_i, c_fp, c_fp, c_fp, c_fp, _sz, _f, _f, _f, C.POINTER(C.c_float), _vp],
     "xm_average_update": [c_fp, c_fp, _sz, _f, _f, _vp],
     "xm_comm_unique_id": [_vp],
     "xm_comm_init": [_vp, _i, _i],

@@ -1,7 +1,7 @@
 // Elementwise operators, losses, optimiser update and the batch-provider arithmetic on gfx950.
 // vl_nnrelu / vl_nnsigmoid / dagnn.Sum / mcnExtraLayers Scale+Axpy, vl_nnsoftmaxt,
 // vl_nnsoftmaxceloss (emoVoxZoo.m:152), vl_nnloss (emoVoxZoo.m:149,160), the SGD-momentum step of
-// cnn_train_dag (run_distillation.m:170-182) and the device side of getBatchEmoVoxCeleb /
+// cnn_train_dag (run_distillation.m:170-182), its 'solver' option and the device side of getBatchEmoVoxCeleb /
 // getImageBatch.  All HBM- or latency-bound; float4 grid-stride loops, no atomics.
 #include "xm_common.h"
 
@@ -471,6 +471,79 @@ sgd_kernel(float *__restrict__ w, float *__restrict__ m, const float *__restrict
   }
 }
 
+// ---- cnn_train_dag's 'solver' option (MatConvNet +solver package [EXT]) and the nesterovUpdate arm of its default solver --
+// One element of one update, in fp32, operation by operation in the order of the MATLAB source (xmodal.h has the formulas
+// and the coef slots).  g = vl_taccum(1 / batchSize, parDer, thisDecay, value).  The scalar coefficients arrive rounded as
+// MATLAB rounds them (a double expression such as 1 - beta2 is evaluated in double, then meets the single array).
+struct SolverArgs {
+  float lr, wd, inv_batch, c0, c1, c2, c3;
+};
+
+template <int KIND>
+__device__ __forceinline__ void solver_step(float &w, float &s1, float &s2, float d, const SolverArgs &a) {
+  const float g = d * a.inv_batch + a.wd * w;
+  if (KIND == XM_SOLVER_ADAGRAD) {            // c0 = epsilon, c1 = rho
+    s1 = s1 * a.c1 + g * g;
+    w = w - a.lr * g / (sqrtf(s1) + a.c0);
+  } else if (KIND == XM_SOLVER_RMSPROP) {     // c0 = epsilon, c1 = rho, c2 = 1 - rho
+    s1 = s1 * a.c1 + g * g * a.c2;
+    w = w - a.lr * g / (sqrtf(s1) + a.c0);
+  } else if (KIND == XM_SOLVER_ADADELTA) {    // c0 = epsilon, c1 = rho, c2 = 1 - rho; s1 = g_sqr, s2 = delta_sqr
+    s1 = s1 * a.c1 + g * g * a.c2;
+    const float delta = -sqrtf((s2 + a.c0) / (s1 + a.c0)) * g;
+    s2 = s2 * a.c1 + delta * delta * a.c2;
+    w = w + a.lr * delta;
+  } else if (KIND == XM_SOLVER_ADAM) {        // c0 = epsilon, c1 = 1 - beta1, c2 = 1 - beta2, c3 = lr_t; s1 = m, s2 = v
+    s1 = s1 + a.c1 * (g - s1);
+    s2 = s2 + a.c2 * (g * g - s2);
+    w = w - a.c3 * s1 / (sqrtf(s2) + a.c0);
+  } else {                                    // XM_SOLVER_NESTEROV: c0 = momentum; s1 = momentum state
+    s1 = a.c0 * s1 - g;
+    w = w + a.lr * (a.c0 * s1 - g);
+  }
+}
+
+template <int KIND>
+__global__ void __launch_bounds__(256)
+solver_kernel(float *__restrict__ w, float *__restrict__ s1, float *__restrict__ s2, const float *__restrict__ der,
+              size_t n, SolverArgs a, int vec) {
+  constexpr bool TWO = KIND == XM_SOLVER_ADADELTA || KIND == XM_SOLVER_ADAM;   // one-state kinds never touch s2
+  size_t stride = (size_t)gridDim.x * 256;
+  size_t i0 = blockIdx.x * (size_t)256 + threadIdx.x;
+  size_t tail = 0;
+  if (vec) {
+    size_t n4 = n >> 2;
+    for (size_t i = i0; i < n4; i += stride) {
+      float4 wv = reinterpret_cast<float4 *>(w)[i], av = reinterpret_cast<float4 *>(s1)[i];
+      float4 bv = TWO ? reinterpret_cast<float4 *>(s2)[i] : make_float4(0, 0, 0, 0);
+      float4 dv = reinterpret_cast<const float4 *>(der)[i];
+      solver_step<KIND>(wv.x, av.x, bv.x, dv.x, a);
+      solver_step<KIND>(wv.y, av.y, bv.y, dv.y, a);
+      solver_step<KIND>(wv.z, av.z, bv.z, dv.z, a);
+      solver_step<KIND>(wv.w, av.w, bv.w, dv.w, a);
+      reinterpret_cast<float4 *>(s1)[i] = av;
+      if (TWO) reinterpret_cast<float4 *>(s2)[i] = bv;
+      reinterpret_cast<float4 *>(w)[i] = wv;
+    }
+    tail = n4 << 2;
+  }
+  for (size_t i = tail + i0; i < n; i += stride) {
+    float ww = w[i], aa = s1[i], bb = TWO ? s2[i] : 0.f;
+    solver_step<KIND>(ww, aa, bb, der[i], a);
+    s1[i] = aa;
+    if (TWO) s2[i] = bb;
+    w[i] = ww;
+  }
+}
+
+template <int KIND>
+static void solver_launch(float *w, float *s1, float *s2, const float *der, size_t n, const SolverArgs &a,
+                          hipStream_t st) {
+  int vec = ((((uintptr_t)w | (uintptr_t)s1 | (uintptr_t)s2 | (uintptr_t)der) & 15) == 0) ? 1 : 0;
+  hipLaunchKernelGGL(solver_kernel<KIND>, dim3(ew_grid(vec ? n / 4 + 1 : n)), dim3(256), 0, st, w, s1, s2,
+                     der, n, a, vec);
+}
+
 __global__ void scale_kernel(float *__restrict__ x, size_t n, float a) {
   size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x;
   if (i < n) x[i] *= a;
@@ -842,6 +915,31 @@ int xm_sgd_update(float *w, float *m, const float *der, size_t n, float lr, floa
   int vec = ((((uintptr_t)w | (uintptr_t)m | (uintptr_t)der) & 15) == 0) ? 1 : 0;
   hipLaunchKernelGGL(sgd_kernel, dim3(ew_grid(vec ? n / 4 + 1 : n)), dim3(256), 0, (hipStream_t)stream,
                      w, m, der, n, lr, momentum, weight_decay, 1.0f / batch, vec);
+  XM_LAUNCH_CHECK();
+  return XM_OK;
+}
+
+int xm_solver_update(int kind, float *w, float *s1, float *s2, const float *der, size_t n, float lr,
+                     float weight_decay, float batch, const float *coef, void *stream) {
+  static const char *const names[] = {"adagrad", "rmsprop", "adadelta", "adam", "nesterov"};
+  if (kind < XM_SOLVER_ADAGRAD || kind > XM_SOLVER_NESTEROV)
+    return fail(XM_EINVAL, "solver: unknown kind %d (0 adagrad, 1 rmsprop, 2 adadelta, 3 adam, 4 nesterov)", kind);
+  if (!(batch > 0.f)) return fail(XM_EINVAL, "solver %s: batch must be > 0", names[kind]);
+  if (!coef) return fail(XM_EINVAL, "solver %s: NULL coefficient array", names[kind]);
+  const bool two = kind == XM_SOLVER_ADADELTA || kind == XM_SOLVER_ADAM;
+  if (n > 0 && (!w || !der || !s1)) return fail(XM_EINVAL, "solver %s: NULL tensor (w, der or state 1)", names[kind]);
+  if (n > 0 && two && !s2) return fail(XM_EINVAL, "solver %s: needs a second state buffer, s2 is NULL", names[kind]);
+  ++xm::g_param_version;
+  if (n == 0) return XM_OK;
+  const xm::SolverArgs a = {lr, weight_decay, 1.0f / batch, coef[0], coef[1], coef[2], coef[3]};
+  hipStream_t st = (hipStream_t)stream;
+  switch (kind) {
+    case XM_SOLVER_ADAGRAD: solver_launch<XM_SOLVER_ADAGRAD>(w, s1, s2, der, n, a, st); break;
+    case XM_SOLVER_RMSPROP: solver_launch<XM_SOLVER_RMSPROP>(w, s1, s2, der, n, a, st); break;
+    case XM_SOLVER_ADADELTA: solver_launch<XM_SOLVER_ADADELTA>(w, s1, s2, der, n, a, st); break;
+    case XM_SOLVER_ADAM: solver_launch<XM_SOLVER_ADAM>(w, s1, s2, der, n, a, st); break;
+    default: solver_launch<XM_SOLVER_NESTEROV>(w, s1, s2, der, n, a, st); break;
+  }
   XM_LAUNCH_CHECK();
   return XM_OK;
 }

@@ -825,6 +825,10 @@ def save_mat(net, path, wrap=None):
 class FlatParams:
     def __init__(self, val, der, mom, segments):
         self.val, self.der, self.mom, self.segments = val, der, mom, segments
+        # cnn_train_dag's 'solver' option (train.solver_state): mom is the solver's first state; a second buffer of the same
+        # size (adadelta, adam) and adam's update count per segment are made on first use
+        self.state2 = None
+        self.solver_t = None
 
 
 # ---------------------------------------------------------------------------------------------

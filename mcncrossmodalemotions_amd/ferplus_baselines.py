@@ -83,7 +83,8 @@ def ferplus_baselines(dev=False, useBnorm=1, dataAug=True, dataType="CNTK", loss
                       modelName="senet50_ft-dag", dataDir="data/datasets/fer2013+", evaluateOnly=None, gpus=1,
                       finetuneLR=0.1, dropoutRate=0.5, cont=True, batchSize=128, learningRate=None, numEpochs=300,
                       *, imdb=None, expRoot="data/grimaces/fer2013+", widthMult=1.0, blocks=(3, 4, 6, 3), seed=0,
-                      numImages=512, verbose=False, modelDir=None):
+                      numImages=512, verbose=False, modelDir=None, solver=None, solverOpts=None, nesterovUpdate=False,
+                      momentum=0.9, weightDecay=5e-4):
     """Options as in ferplus_baselines.m:59-80 (`cont` is opts.train.continue, `gpus` / `batchSize` /
     `learningRate` are opts.train.*; `numEpochs` is cnn_train_dag's default, 300, with the last rate held after
     epoch 180).  `evaluateOnly` = {'subset': '' | 'val' | 'test', 'fromCkpt': bool}.  `dataDir` holds the FER2013 and
@@ -91,7 +92,9 @@ def ferplus_baselines(dev=False, useBnorm=1, dataAug=True, dataType="CNTK", loss
     Extensions (keyword-only): `imdb` (a prepared imdb; without it and without the CSVs a SyntheticFerPlusImdb of
     `numImages` images), `expRoot` (root of the experiment directories), `widthMult` / `blocks` (narrow networks for
     tests), `seed` (synthetic weights, imdb and batch draws), `modelDir` (zoo.ferPlusZoo reads the model file from there
-    instead of building the seeded stand-in)."""
+    instead of building the seeded stand-in), `solver` / `solverOpts` / `nesterovUpdate` / `momentum` / `weightDecay`
+    (further fields of opts.train, handed to cnn_train_dag as :140-141 hands the whole struct; the defaults are
+    cnn_train_dag's)."""
     ev = {"subset": "", "fromCkpt": False}
     ev.update(evaluateOnly or {})
     if learningRate is None:
@@ -148,4 +151,5 @@ def ferplus_baselines(dev=False, useBnorm=1, dataAug=True, dataType="CNTK", loss
     return train.cnn_train_dag(dag, imdb, getBatch, learningRate=learningRate, batchSize=batchSize,
                                numEpochs=numEpochs, train=trainSamples, val=valSamples, cont=cont,
                                expDir=None if evaluating else expDir, extractStatsFn=train.extractStats,
-                               verbose=verbose)
+                               verbose=verbose, solver=solver, solverOpts=solverOpts, nesterovUpdate=nesterovUpdate,
+                               momentum=momentum, weightDecay=weightDecay)

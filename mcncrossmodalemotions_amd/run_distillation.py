@@ -24,14 +24,17 @@ def run_distillation(gpus=(2,), cont=True, miniVal=0.2, numSeconds=4, batchSize=
                      lossType="hot-cross-ent", temperature=2, fixedSegments=False, learningRate=None,
                      parameterServer="tmove", wavDir=None,
                      *, imdb=None, dataDir="data/xEmo18", numTracks=256, widthMult=1.0, seed=0, verbose=False,
-                     useWav=False, transformation="I", modelDir=None):
+                     useWav=False, transformation="I", modelDir=None, solver=None, solverOpts=None,
+                     nesterovUpdate=False, momentum=0.9, weightDecay=5e-4):
     """Options as in run_distillation.m:72-90.  Extensions (keyword-only): `imdb` (a prepared imdb),
     `dataDir` (root of the experiment directories), `numTracks` / `seed` (synthetic imdb), `widthMult`
     (narrow student for tests), `useWav` (the batches come from the imdb's waveforms through the batched device
     front-end, batch.getBatchEmoVoxCeleb(use_wav, wavBatch), instead of the seeded spectrogram generator) and
     `transformation` (net.meta.augmentation.transformation, :130: 'I', 'IS', 'ISN' ...; 'S' / 'N' need useWav) and
     `modelDir` (emoVoxZoo's option: the student comes from <modelDir>/<student>.mat -- with fromScratch its architecture,
-    without it the network as saved, loss heads included -- instead of the seeded stand-in)."""
+    without it the network as saved, loss heads included -- instead of the seeded stand-in); `solver`, `solverOpts`,
+    `nesterovUpdate`, `momentum`, `weightDecay`: cnn_train_dag's options of those names (the defaults are the values the
+    call at :170-182 leaves to cnn_train_dag)."""
     gpus = list(np.atleast_1d(gpus))
     if miniEpochRatio is None:
         miniEpochRatio = 0.05 * len(gpus)                      # :77
@@ -91,4 +94,6 @@ def run_distillation(gpus=(2,), cont=True, miniVal=0.2, numSeconds=4, batchSize=
                                numEpochs=numEpochs, train=trainSamples, val=valSamples, cont=cont,
                                expDir=expDir, epochSize=epochSize,
                                parameterServer=parserv,
-                               extractStatsFn=train.extractStats, verbose=verbose)
+                               extractStatsFn=train.extractStats, verbose=verbose, solver=solver,
+                               solverOpts=solverOpts, nesterovUpdate=nesterovUpdate, momentum=momentum,
+                               weightDecay=weightDecay)

@@ -6,6 +6,7 @@ Reference call: cnn_train_dag(net, imdb, getBatchFn, 'learningRate', logspace(-4
     net.eval(inputs, {'objective', 1})          -> HIP kernels
     parserv.push / sync / pull                  -> one RCCL sum-all-reduce of the flat der buffer
     accumulateGradients (momentum 0.9, wd 5e-4) -> fused HIP SGD / moving-average kernels
+                                                   ('solver' / 'nesterovUpdate': fused HIP solver kernel)
 Data parallelism follows MatConvNet: each worker takes a shard of the minibatch, BN statistics
 are per worker, gradients are summed and divided by the GLOBAL batch size.
 """
@@ -17,16 +18,27 @@ import torch
 
 from . import _lib, vl
 
+# @solver.<name> of MatConvNet's +solver package [EXT] (vl.SOLVERS also lists the default solver's nesterovUpdate arm)
+SOLVER_NAMES = tuple(k for k in vl.SOLVERS if k != "nesterov")
+
 
 class TrainOpts:
     def __init__(self, learningRate=None, momentum=0.9, weightDecay=5e-4, batchSize=64,
-                 derOutputs=("objective", 1)):
+                 derOutputs=("objective", 1), solver=None, solverOpts=None, nesterovUpdate=False):
         # run_distillation.m:76,87: 300 mini-epochs, logspace(-4, -5, 300)
         self.learningRate = np.logspace(-4, -5, 300) if learningRate is None else np.atleast_1d(learningRate)
         self.momentum = momentum
         self.weightDecay = weightDecay
         self.batchSize = batchSize
         self.derOutputs = list(derOutputs)
+        # cnn_train_dag's 'solver' (None = its default, SGD with momentum), 'solverOpts' and 'nesterovUpdate' [EXT]
+        if solver is not None and solver not in SOLVER_NAMES:
+            raise ValueError("unknown solver %r (None or one of %s)" % (solver, ", ".join(SOLVER_NAMES)))
+        if solver is None and solverOpts:
+            raise ValueError("solverOpts without a solver (the default solver takes momentum / nesterovUpdate)")
+        self.solver = solver
+        self.solverOpts = vl.solver_opts(solver, solverOpts) if solver is not None else {}
+        self.nesterovUpdate = bool(nesterovUpdate)     # as in MatConvNet: read by the default solver only
 
 
 class ParameterServer:
@@ -366,19 +378,46 @@ def shard_batch(batch, rank, world):
     return list(batch)[rank::world]
 
 
+def solver_state(flat, solver):
+    """the solver's state beyond flat.mom (state slot 1), made on first use: adam's update count per segment on the host
+    and, for adadelta and adam only, a second flat buffer; all zero, MatConvNet's empty state"""
+    if flat.solver_t is None:
+        flat.solver_t = [0] * len(flat.segments)
+    if vl.SOLVERS[solver][2] and flat.state2 is None:
+        flat.state2 = torch.zeros_like(flat.mom)
+
+
 def accumulate_gradients(net, opts, lr, global_batch, moments_denom=1.0):
-    """accumulateGradients of cnn_train_dag (solver = []): per flat segment one fused launch.
+    """accumulateGradients of cnn_train_dag: per flat segment one fused launch -- xm_sgd_update for the default solver
+    (solver = []), xm_solver_update for opts.solver (@solver.adagrad / rmsprop / adadelta / adam) and for the default
+    solver's nesterovUpdate arm.
     `moments_denom`: 1 for a single worker (der = the batch moments); the global batch size when the exchanged der
     is sum_w moments_w * batch_w (train_step does that weighting)."""
     flat = net._flat
-    for (method, lr_mult, wd_mult), a, b in flat.segments:
+    kind = opts.solver if opts.solver is not None else ("nesterov" if opts.nesterovUpdate else None)
+    if opts.solver is not None:
+        solver_state(flat, opts.solver)
+    for k, ((method, lr_mult, wd_mult), a, b) in enumerate(flat.segments):
         if b == a:
             continue
         if method == "average":
             vl.average_update(flat.val[a:b], flat.der[a:b], lr_mult, moments_denom)
-        else:
+        elif kind is None:
             vl.sgd_update(flat.val[a:b], flat.mom[a:b], flat.der[a:b], lr * lr_mult, opts.momentum,
                           opts.weightDecay * wd_mult, global_batch)
+        else:
+            this_lr, this_decay = lr * lr_mult, opts.weightDecay * wd_mult
+            if not (this_lr > 0 or this_decay > 0):      # cnn_train_dag: if thisLR > 0 || thisDecay > 0
+                continue
+            if kind == "nesterov":
+                vl.solver_update(kind, flat.val[a:b], flat.mom[a:b], None, flat.der[a:b], this_lr, this_decay,
+                                 global_batch, momentum=opts.momentum)
+                continue
+            if kind == "adam":
+                flat.solver_t[k] += 1
+            s2 = flat.state2[a:b] if vl.SOLVERS[kind][2] else None
+            vl.solver_update(kind, flat.val[a:b], flat.mom[a:b], s2, flat.der[a:b], this_lr, this_decay,
+                             global_batch, t=max(flat.solver_t[k], 1), **opts.solverOpts)
     net.paramGeneration = getattr(net, "paramGeneration", 0) + 1   # folded / cached views of the parameters are stale
 
 
@@ -556,34 +595,66 @@ def process_epoch(net, imdb, getBatch, subset, opts, epoch, mode, parserv=None, 
     return stats
 
 
-def save_checkpoint(net, path, info, epoch):
+def _segment_of(flat, off):
+    """index of the flat segment that holds offset `off`"""
+    return next(k for k, (_, a, b) in enumerate(flat.segments) if a <= off < b)
+
+
+def save_checkpoint(net, path, info, epoch, opts=None):
     """net-epoch-<n>.pt: {parameter name: value / momentum} (self-describing: loadable into any net that has
     parameters of those names and shapes, e.g. emoVoxZoo(scratch=0) for inference), written to a temporary file and
-    renamed into place so that a crash cannot leave a truncated file that `cont` would pick up."""
+    renamed into place so that a crash cannot leave a truncated file that `cont` would pick up.
+    "momentum" is the first solver state whatever the solver.  With opts.solver set the file also carries "solver":
+    {name, opts, state2: {parameter name: second state} (adadelta, adam), t: {parameter name: update count}}."""
     import os
-    vals, moms = {}, {}
+    flat = net._flat
+    solver = getattr(opts, "solver", None)
+    vals, moms, st2, ts = {}, {}, {}, {}
     for name, p in net.params.items():
         n = int(p.value.numel())
         off = p._flat_off
-        vals[name] = net._flat.val[off:off + n].reshape(tuple(reversed(p.value.shape))).clone()
-        moms[name] = net._flat.mom[off:off + n].reshape(tuple(reversed(p.value.shape))).clone()
+        vals[name] = flat.val[off:off + n].reshape(tuple(reversed(p.value.shape))).clone()
+        moms[name] = flat.mom[off:off + n].reshape(tuple(reversed(p.value.shape))).clone()
+        if solver is not None:
+            if flat.state2 is not None:
+                st2[name] = flat.state2[off:off + n].reshape(tuple(reversed(p.value.shape))).clone()
+            ts[name] = int(flat.solver_t[_segment_of(flat, off)]) if flat.solver_t is not None and n else 0
     # counter offsets of the dropout layers' Philox streams (training state: a resumed run must not repeat masks)
     rng = {l.name: int(l.block._offset) for l in net.layers if hasattr(l.block, "_offset")}
+    ck = {"format": "xmodal-params-v2", "params": vals, "momentum": moms, "info": info, "epoch": epoch, "rng": rng}
+    if solver is not None:
+        ck["solver"] = {"name": solver, "opts": {k: float(v) for k, v in opts.solverOpts.items()}, "state2": st2,
+                        "t": ts}
     tmp = path + ".tmp"
-    torch.save({"format": "xmodal-params-v2", "params": vals, "momentum": moms, "info": info, "epoch": epoch,
-                "rng": rng}, tmp)
+    torch.save(ck, tmp)
     os.replace(tmp, path)
 
 
-def load_checkpoint(net, path, strict=True):
+_ANY_SOLVER = object()
+
+
+def load_checkpoint(net, path, strict=True, solver=_ANY_SOLVER):
     """inverse of save_checkpoint (values stored in the flat buffers' memory order: reversed MATLAB shape).
-    The whole file is validated against the net BEFORE anything is copied: a mismatch leaves the net untouched."""
+    The whole file is validated against the net BEFORE anything is copied: a mismatch leaves the net untouched.
+    `solver`: the solver of the run that resumes from the file (None = the default solver); a file written under another
+    one is a CheckpointMismatch.  Not given (loading for evaluation): any file is accepted."""
     ck = torch.load(path, map_location=net.device, weights_only=True)
     if not isinstance(ck, dict) or ck.get("format") != "xmodal-params-v2" or not isinstance(ck.get("params"), dict):
         # an older-format or foreign file: unreadable for `cont` (skipped with a warning), not a mismatch
         raise CheckpointUnreadable("%s: not an xmodal-params-v2 checkpoint" % path)
+    sv = ck.get("solver")
+    if sv is not None and not (isinstance(sv, dict) and isinstance(sv.get("name"), str)):
+        raise CheckpointUnreadable("%s: malformed solver state" % path)
+    if solver is not _ANY_SOLVER and (sv["name"] if sv else None) != solver:
+        raise CheckpointMismatch("%s was written with solver %r, this run uses solver %r" %
+                                 (path, sv["name"] if sv else None, solver))
     if net._flat is None:
         net.pack_params()
+    st2, ts = (sv.get("state2") or {}, sv.get("t") or {}) if sv else ({}, {})
+    for name, p in net.params.items():
+        if name in st2 and int(st2[name].numel()) != int(p.value.numel()):
+            raise CheckpointMismatch("second solver state of %r: %d values in the checkpoint, %d in the net" %
+                                     (name, st2[name].numel(), p.value.numel()))
     todo = []
     for name, p in net.params.items():
         if name not in ck["params"]:
@@ -604,6 +675,16 @@ def load_checkpoint(net, path, strict=True):
         net._flat.val[off:off + n].copy_(src.reshape(-1))
         if mom is not None:
             net._flat.mom[off:off + n].copy_(mom.reshape(-1))
+    if sv is not None and sv["name"] in vl.SOLVERS:
+        flat = net._flat
+        flat.state2 = flat.solver_t = None          # the file's solver state replaces the net's, whole
+        solver_state(flat, sv["name"])
+        for name, p in net.params.items():
+            n = int(p.value.numel())
+            if name in st2:
+                flat.state2[p._flat_off:p._flat_off + n].copy_(st2[name].reshape(-1))
+            if n and name in ts:
+                flat.solver_t[_segment_of(flat, p._flat_off)] = int(ts[name])
     for l in net.layers:
         if hasattr(l.block, "_offset") and l.name in (ck.get("rng") or {}):
             l.block._offset = int(ck["rng"][l.name])
@@ -621,10 +702,14 @@ class CheckpointUnreadable(OSError):
 
 def cnn_train_dag(net, imdb, getBatch, learningRate=None, batchSize=64, numEpochs=300, train=None, val=None,
                   cont=True, expDir=None, epochSize=float("inf"), parameterServer=None, extractStatsFn=extractStats,
-                  momentum=0.9, weightDecay=5e-4, derOutputs=("objective", 1), randomSeed=0, verbose=False):
+                  momentum=0.9, weightDecay=5e-4, derOutputs=("objective", 1), randomSeed=0, verbose=False,
+                  solver=None, solverOpts=None, nesterovUpdate=False):
     """[net, info] = cnn_train_dag(net, imdb, getBatch, 'learningRate', ..., 'batchSize', ..., 'numEpochs', ...,
     'train', ..., 'val', ..., 'continue', ..., 'expDir', ..., 'epochSize', ..., 'parameterServer', ...,
     'extractStatsFn', ...) -- the MatConvNet driver [EXT] as run_distillation.m:170-182 calls it.
+    'solver' (None | 'adagrad' | 'rmsprop' | 'adadelta' | 'adam': @solver.<name>), 'solverOpts' (a dict; the solver's
+    defaults fill the rest) and 'nesterovUpdate' (default solver only) are the driver's options of those names, as
+    ferplus_baselines.m:70-80,140-141 can pass them through opts.train.
 
     Per epoch: shuffle `train` with the epoch's seed, keep the first `epochSize` samples (the reference's
     "mini-epochs"), one training pass, one validation pass in test mode, then a checkpoint
@@ -632,7 +717,7 @@ def cnn_train_dag(net, imdb, getBatch, learningRate=None, batchSize=64, numEpoch
     `gpus` is implicit: one process per GPU (torchrun), the process group gives the worker count."""
     import os
     opts = TrainOpts(learningRate=learningRate, momentum=momentum, weightDecay=weightDecay, batchSize=batchSize,
-                     derOutputs=derOutputs)
+                     derOutputs=derOutputs, solver=solver, solverOpts=solverOpts, nesterovUpdate=nesterovUpdate)
     if len(opts.learningRate) < numEpochs:   # MatConvNet indexes min(epoch, numel(learningRate))
         pass
     parserv = parameterServer if isinstance(parameterServer, ParameterServer) else ParameterServer("torch")
@@ -650,7 +735,7 @@ def cnn_train_dag(net, imdb, getBatch, learningRate=None, batchSize=64, numEpoch
         done = sorted(e for e in range(1, numEpochs + 1) if os.path.exists(path(e)))
         while done:                      # newest readable checkpoint wins; unreadable ones are skipped
             try:
-                ck = load_checkpoint(net, path(done[-1]))
+                ck = load_checkpoint(net, path(done[-1]), solver=opts.solver)
             except CheckpointMismatch:   # readable, but of another net: restarting would overwrite those files
                 raise
             except (OSError, EOFError, RuntimeError, pickle.UnpicklingError, KeyError, ValueError, TypeError,
@@ -671,6 +756,6 @@ def cnn_train_dag(net, imdb, getBatch, learningRate=None, batchSize=64, numEpoch
         if verbose and parserv.rank == 0:
             print("epoch %d: train %s | val %s" % (epoch + 1, info["train"][-1], info["val"][-1]), flush=True)
         if path and parserv.rank == 0:
-            save_checkpoint(net, path(epoch + 1), info, epoch + 1)
+            save_checkpoint(net, path(epoch + 1), info, epoch + 1, opts)
     parserv.stop()
     return net, info

@@ -787,6 +787,59 @@ def sgd_update(w, m, der, lr, momentum=0.9, weight_decay=5e-4, batch=1.0):
                                   float(momentum), float(weight_decay), float(batch), _stream()))
 
 
+# cnn_train_dag's 'solver' / 'solverOpts' (MatConvNet +solver [EXT]) and the nesterovUpdate arm of its default solver:
+# name -> (XM_SOLVER_* kind, option defaults, uses the second state)
+SOLVERS = {
+    "adagrad": (0, {"epsilon": 1e-10, "rho": 1.0}, False),
+    "rmsprop": (1, {"epsilon": 1e-8, "rho": 0.99}, False),
+    "adadelta": (2, {"epsilon": 1e-6, "rho": 0.9}, True),
+    "adam": (3, {"beta1": 0.9, "beta2": 0.999, "epsilon": 1e-8}, True),
+    "nesterov": (4, {"momentum": 0.9}, False),
+}
+
+
+def solver_opts(kind, solverOpts=None):
+    """the solver's options with its defaults filled in; unknown solver or option names raise ValueError"""
+    if kind not in SOLVERS:
+        raise ValueError("unknown solver %r (one of %s)" % (kind, ", ".join(sorted(SOLVERS))))
+    defaults = SOLVERS[kind][1]
+    unknown = sorted(set(solverOpts or {}) - set(defaults))
+    if unknown:
+        raise ValueError("solver %r has no option %s (its options: %s)" %
+                         (kind, ", ".join(map(repr, unknown)), ", ".join(sorted(defaults))))
+    return dict(defaults, **{k: float(v) for k, v in (solverOpts or {}).items()})
+
+
+def solver_coef(kind, lr, t=1, **solverOpts):
+    """the four coefficient slots of xm_solver_update (include/xmodal.h) as float32.  Formed in double and rounded once, as
+    MATLAB does with a double scalar expression that meets a single array: 1 - beta2 is float32(0.001), not
+    1 - float32(0.999).  `t` (adam): updates so far, this one included."""
+    o = solver_opts(kind, solverOpts)
+    if kind == "adagrad":
+        c = [o["epsilon"], o["rho"], 0.0, 0.0]
+    elif kind in ("rmsprop", "adadelta"):
+        c = [o["epsilon"], o["rho"], 1.0 - o["rho"], 0.0]
+    elif kind == "adam":
+        t = int(t)
+        if t < 1:
+            raise ValueError("solver 'adam': t counts the updates from 1")
+        lr_t = float(lr) * np.sqrt(1.0 - o["beta2"] ** t) / (1.0 - o["beta1"] ** t)
+        c = [o["epsilon"], 1.0 - o["beta1"], 1.0 - o["beta2"], lr_t]
+    else:
+        c = [o["momentum"], 0.0, 0.0, 0.0]
+    return np.asarray(c, np.float64).astype(np.float32)
+
+
+def solver_update(kind, w, s1, s2, der, lr, weight_decay, batch, t=1, **solverOpts):
+    """in-place accumulateGradients step of cnn_train_dag with 'solver', @solver.<kind> (or, kind 'nesterov', with
+    'nesterovUpdate'): one launch of xm_solver_update.  s1: g_sqr / adam's m / the momentum; s2: adadelta's delta_sqr /
+    adam's v (None for the other kinds).  `t`: adam's update count, this update included (the caller keeps it)."""
+    coef = solver_coef(kind, lr, t, **solverOpts)
+    _lib.check(_L().xm_solver_update(SOLVERS[kind][0], _ptr(w), _ptr(s1), _ptr(s2), _ptr(der), w.numel(), float(lr),
+                                     float(weight_decay), float(batch),
+                                     coef.ctypes.data_as(_lib.C.POINTER(_lib.C.c_float)), _stream()))
+
+
 def scale_(x, a):
     """x <- a * x in place (worker-batch weighting of the BN moments before the ParameterServer exchange)."""
     _lib.check(_L().xm_scale_f32(_ptr(x), x.numel(), float(a), _stream()))
