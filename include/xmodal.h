@@ -57,7 +57,7 @@ enum { XM_FUSE_RELU = 1, XM_BN_BATCH_MOMENTS = 2, XM_FUSE_SIGMOID = 4 };
 
 /* ABI revision: 100 = round 1; 101 = xm_nnbnorm_relu_pool_backward gained `y_pool`, exchange entry points return
  * XM_EINVAL without a communicator; 102 = + xm_nnconv_forward_moments, xm_nnbnorm_backward_dxsum, xm_nnconv_forward_gated;
- * 103 = + xm_nnpool_global_avg_backward_accum; 104 = + xm_nnconv_backward_filter_bnrelupool, xm_nndropout_forward / _apply, xm_resample, xm_se_tail_backward_reduce / _apply, xm_se_squeeze_bn, xm_scale_axpy_bn; 105 = + xm_set_exec_hint / xm_get_exec_hint; 106 = + xm_nnconv_bnorm_relu_pool_forward, xm_stem_gram, xm_stem_gram_moments, xm_nnconv_backward_filter_bnrelupool_gram; 107 = + xm_nnaffinegrid / _backward, xm_nnbilinearsampler / _backward, xm_ferplus_batch; 108 = + XM_AGG_PEAK, xm_mnrfit, xm_mnrval; 109 = + xm_roc, xm_roc_launches, xm_label_hist; 110 = + xm_group_rows, xm_gather_rows, xm_scatter_rows, xm_track_peaks; 111 = + xm_wav_batch; 112 = + xm_spec_bucket_batch; 113 = + xm_jpeg_plan, xm_jpeg_decode_batch; 114 = + xm_wav_plan, xm_wav_decode_batch; 115 = + xm_jpeg_decode_batch_split, xm_jpeg_split_geometry; 116 = + xm_pixcsv_plan, xm_pixcsv_decode_batch, xm_pixcsv_geometry; 117 = + xm_nnconv_forward_strided_residual; 118 = + xm_solver_update (additions never change the revision's meaning for older bindings).  A binding checks xm_version() >= the revision it was written against. */
+ * 103 = + xm_nnpool_global_avg_backward_accum; 104 = + xm_nnconv_backward_filter_bnrelupool, xm_nndropout_forward / _apply, xm_resample, xm_se_tail_backward_reduce / _apply, xm_se_squeeze_bn, xm_scale_axpy_bn; 105 = + xm_set_exec_hint / xm_get_exec_hint; 106 = + xm_nnconv_bnorm_relu_pool_forward, xm_stem_gram, xm_stem_gram_moments, xm_nnconv_backward_filter_bnrelupool_gram; 107 = + xm_nnaffinegrid / _backward, xm_nnbilinearsampler / _backward, xm_ferplus_batch; 108 = + XM_AGG_PEAK, xm_mnrfit, xm_mnrval; 109 = + xm_roc, xm_roc_launches, xm_label_hist; 110 = + xm_group_rows, xm_gather_rows, xm_scatter_rows, xm_track_peaks; 111 = + xm_wav_batch; 112 = + xm_spec_bucket_batch; 113 = + xm_jpeg_plan, xm_jpeg_decode_batch; 114 = + xm_wav_plan, xm_wav_decode_batch; 115 = + xm_jpeg_decode_batch_split, xm_jpeg_split_geometry; 116 = + xm_pixcsv_plan, xm_pixcsv_decode_batch, xm_pixcsv_geometry; 117 = + xm_nnconv_forward_strided_residual; 118 = + xm_solver_update; 119 = + xm_nnnormalize_forward / _backward, xm_nnnormalize_geometry (additions never change the revision's meaning for older bindings).  A binding checks xm_version() >= the revision it was written against. */
 int xm_version(void);
 const char *xm_last_error(void);
 /* Device memory for hosts that have no device-array type of their own (MATLAB's gpuArray is CUDA-only: on an
@@ -850,6 +850,27 @@ int xm_pixcsv_plan(const unsigned char *bytes, long long nbytes, long long *desc
 int xm_pixcsv_decode_batch(const unsigned char *bytes, long long nbytes, const long long *desc, int N, int H, int W,
                            int transpose, float *out, long long out_floats, int *status, void *stream);
 int xm_pixcsv_geometry(int *bytes_per_pass, int *launches);
+
+/* ---- vl_nnnormalize [EXT: vl_nnnormalize.m, normalize_cpu]: cross-channel (local response) normalisation, the norm1 /
+ * norm2 layers of the VGG-M / VGG-F / AlexNet family (dagnn.LRN) ----
+ *   Y = vl_nnnormalize(X, PARAM), DZDX = vl_nnnormalize(X, PARAM, DZDY), PARAM = [N KAPPA ALPHA BETA], X H x W x C x S:
+ *     m1 = floor((N - 1) / 2), m2 = N - 1 - m1, G(k) = [k - m1, k + m2] within the C channels
+ *     L(i,j,k,s) = KAPPA + ALPHA * sum_{t in G(k)} X(i,j,t,s)^2,   Y = X .* L.^(-BETA)
+ *     DX(k) = DZDY(k) L(k)^(-BETA) - 2 ALPHA BETA X(k) sum_{t: k in G(t)} DZDY(t) X(t) L(t)^(-BETA - 1)
+ *   (the adjoint window is the mirrored one, [k - m2, k + m1]; for even N it differs from G(k)).
+ * Any N >= 1 (N > 2 C included) and any H * W * C * S the address space holds.  y / dx may NOT alias x or dzdy: a block
+ * reads channels that another block writes.  One launch, no scratch, no synchronisation.
+ * XM_EINVAL before any device work: N < 1, a negative dimension, a NULL or aliasing pointer; a tensor with a zero
+ * dimension is a no-op (XM_OK).
+ * xm_nnnormalize_geometry: host only, the constants of the kernels.  pixels_per_block: pixels of one sample a block owns;
+ * channels_per_pass: the shortest chunk of a split channel axis (planes with few pixels split it until the launch fills
+ * the device; a chunk re-reads the m1 + m2 channels its windows need on each side); window_in_registers: the widest N
+ * of the register arm, wider windows take the general arm.  A kernel without one of these notions reports 0. */
+int xm_nnnormalize_forward(const float *x, int H, int W, int C, int S, int N, float kappa, float alpha, float beta,
+                           float *y, void *stream);
+int xm_nnnormalize_backward(const float *x, const float *dzdy, int H, int W, int C, int S, int N, float kappa,
+                            float alpha, float beta, float *dx, void *stream);
+int xm_nnnormalize_geometry(int *pixels_per_block, int *channels_per_pass, int *window_in_registers);
 
 #ifdef __cplusplus
 }

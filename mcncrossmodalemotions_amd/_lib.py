@@ -140,6 +140,9 @@ SIGNATURES = {
     "xm_pixcsv_plan": [_vp, C.c_longlong, _vp, C.c_longlong, _vp],
     "xm_pixcsv_decode_batch": [c_fp, C.c_longlong, c_fp, _i, _i, _i, _i, c_fp, C.c_longlong, c_fp, _vp],
     "xm_pixcsv_geometry": [C.POINTER(C.c_int), C.POINTER(C.c_int)],
+    "xm_nnnormalize_forward": [c_fp] + [_i] * 5 + [_f, _f, _f, c_fp, _vp],
+    "xm_nnnormalize_backward": [c_fp, c_fp] + [_i] * 5 + [_f, _f, _f, c_fp, _vp],
+    "xm_nnnormalize_geometry": [C.POINTER(C.c_int)] * 3,
 }
 _RESTYPES = {"xm_get_exec_hint": C.c_uint, "xm_last_error": C.c_char_p, "xm_workspace_bytes": C.c_size_t,
              "xm_workspace_generation": C.c_ulonglong}

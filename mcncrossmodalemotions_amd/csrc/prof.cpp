@@ -61,6 +61,9 @@ static const ProfRow kProfRows[] = {
                     "crop_resize_face_ragged_kernel", "jpeg_entropy_split_kernel"}},
     {kProfWav, 1, {"wav_decode_kernel"}},
     {kProfPixcsv, 1, {"pixcsv_decode_kernel"}},
+    // inexact: the register-window rows name the N = 5 instantiation (the VGG-M family's) for every window width
+    {kProfLrn, 6, {"lrn_forward_kernel<5, false>", "lrn_forward_kernel<5, true>", "lrn_backward_kernel<5, false>",
+                   "lrn_backward_kernel<5, true>", "lrn_general_kernel<false>", "lrn_general_kernel<true>"}},
 };
 
 // index of `key` in the keys seen so far (appended when new): first-launch order

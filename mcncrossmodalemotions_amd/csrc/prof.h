@@ -26,6 +26,7 @@ enum ProfKind {
   kProfJpeg = 21,           // jpeg.hip, sub = stage of the decode
   kProfWav = 22,            // wav.hip
   kProfPixcsv = 23,         // pixcsv.hip
+  kProfLrn = 25,            // lrn.hip, sub = 2 * backward + 16-byte arm; 4 / 5: the general arm, forward / backward
 };
 constexpr int prof_key(ProfKind kind, int sub = 0) { return kind * 100 + sub; }
 

@@ -160,6 +160,25 @@ class ReLU(Layer):
         return [vl.vl_nnrelu(inputs[0], derOutputs[0], leak=self.leak)], []
 
 
+class LRN(Layer):
+    """dagnn.LRN [EXT]: cross-channel normalisation, vl_nnnormalize(x, param) with param = [N KAPPA ALPHA BETA] (the norm1 /
+    norm2 layers of the VGG-M / VGG-F / AlexNet family).  No parameters; runs as a generic plan step and no fusion reaches
+    across it."""
+
+    def __init__(self, param=(5, 1, 1e-4 / 5, 0.75)):
+        super().__init__()
+        param = [float(v) for v in np.asarray(param, dtype=np.float64).ravel()]
+        if len(param) != 4:
+            raise ValueError("dagnn.LRN: param must have four elements [N KAPPA ALPHA BETA]")
+        self.param = param
+
+    def forward(self, inputs, params):
+        return [vl.vl_nnnormalize(inputs[0], self.param)]
+
+    def backward(self, inputs, params, derOutputs):
+        return [vl.vl_nnnormalize(inputs[0], self.param, derOutputs[0])], []
+
+
 class Sigmoid(Layer):
     def forward(self, inputs, params):
         return [vl.vl_nnsigmoid(inputs[0])]
@@ -638,19 +657,23 @@ class DagNN:
         """dag.initParams(): re-randomise every parameter (emoVoxZoo.m:54)."""
         rng = np.random.default_rng(seed)
         for l in self.layers:
-            vals = l.block.initParams(rng)
-            for pname, v in zip(l.params, vals):
-                self.params[pname].value = v  # host array until move('gpu')
-                if isinstance(l.block, BatchNorm):
-                    k = l.params.index(pname)
-                    p = self.params[pname]
-                    # [EXT] MatConvNet convention for BN params: g lr 2, b lr 1, moments 'average' 0.1
-                    p.weightDecay = 0.0
-                    p.learningRate = (2.0, 1.0, 0.1)[k]
-                    p.trainMethod = "average" if k == 2 else "gradient"
-                elif isinstance(l.block, Conv) and l.params.index(pname) == 1:
-                    self.params[pname].weightDecay = 0.0
-                    self.params[pname].learningRate = 2.0
+            self.initLayerParams(l, rng)
+
+    def initLayerParams(self, l, rng):
+        """initParams for the one layer record `l` (a layer added to a network whose other parameters must stay)"""
+        vals = l.block.initParams(rng)
+        for pname, v in zip(l.params, vals):
+            self.params[pname].value = v  # host array until move('gpu')
+            if isinstance(l.block, BatchNorm):
+                k = l.params.index(pname)
+                p = self.params[pname]
+                # [EXT] MatConvNet convention for BN params: g lr 2, b lr 1, moments 'average' 0.1
+                p.weightDecay = 0.0
+                p.learningRate = (2.0, 1.0, 0.1)[k]
+                p.trainMethod = "average" if k == 2 else "gradient"
+            elif isinstance(l.block, Conv) and l.params.index(pname) == 1:
+                self.params[pname].weightDecay = 0.0
+                self.params[pname].learningRate = 2.0
         self._flat = None
         self.paramGeneration += 1
 

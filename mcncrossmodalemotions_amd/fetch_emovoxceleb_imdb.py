@@ -192,8 +192,7 @@ def buildImdb(teacher, imdb, frames=None, *, read=None, limit=math.inf, batchSiz
     firstId = int(ids[0])
     numKeep = int((wavIds <= firstId + limit).sum())
     numIms = min(len(images["denseFrames"]), numKeep)
-    E = NUM_EMOTIONS
-    logits = vl.mat_zeros(max(numIms, 1), E, device=device)                              # zeros(numIms, numEmotions), :119
+    E, logits = NUM_EMOTIONS, None
     for start in range(0, numIms, int(batchSize)):                                       # :122-136
         batch = range(start, min(start + int(batchSize), numIms))
         paths = [images["denseFrames"][i] for i in batch]
@@ -203,7 +202,14 @@ def buildImdb(teacher, imdb, frames=None, *, read=None, limit=math.inf, batchSiz
             data = frames(paths, device)                                                 # vl_imreadjpeg (:160-172)
             faces = vl.crop_resize_face(data, avg, imageSize)                            # getImageBatch (:152-193)
         out = model.logits(faces)                                                        # dag.eval, vars(end) (:129-130)
+        if logits is None:
+            # zeros(numIms, numEmotions) (:119), as wide as the teacher's output: the FER teachers have 7 classes, not the
+            # 8 that :64 writes down for the FER+ ones
+            E = int(out.shape[2])
+            logits = vl.mat_zeros(numIms, E, device=device)
         vl.scatter_rows(out, logits, row0=start)                                         # logits(batch, :) = out' (:131)
+    if logits is None:
+        logits = vl.mat_zeros(1, E, device=device)
     numWavs = len(images["name"])
     numLogits = int(min(numWavs, limit))                                                 # :140-142
     dids = torch.from_numpy(wavIds[:numIms].astype(np.int32)).to(device)
@@ -255,7 +261,9 @@ def load_imdb(path):
         v = rec[k].reshape(-1)
         images[k] = [str(x.reshape(-1)[0]) if x.size else "" for x in v] if v.dtype == object else v.astype(np.int64)
     E = NUM_EMOTIONS
-    wav = [np.asfortranarray(np.asarray(c, dtype=np.float32).reshape(-1, E)) for c in m["wavLogits"].reshape(-1)]
+    cells = [np.asarray(c, dtype=np.float32) for c in m["wavLogits"].reshape(-1)]
+    E = next((int(c.shape[1]) for c in cells if c.ndim == 2 and c.size), E)          # the width the teacher wrote
+    wav = [np.asfortranarray(c.reshape(-1, E)) for c in cells]
     return EmoVoxImdb(images, fs=int(m["fs"].ravel()[0]), seed=int(m["seed"].ravel()[0]), wavLogits=wav)
 
 

@@ -34,6 +34,7 @@ BLOCKS = {
     "dagnn.Conv": (dagnn.Conv, ("size", "hasBias", "pad", "stride", "dilate")),
     "dagnn.BatchNorm": (dagnn.BatchNorm, ("numChannels", "epsilon")),
     "dagnn.ReLU": (dagnn.ReLU, ("leak",)),
+    "dagnn.LRN": (dagnn.LRN, ("param",)),
     "dagnn.Sigmoid": (dagnn.Sigmoid, ()),
     "dagnn.SoftMax": (dagnn.SoftMax, ()),
     "dagnn.Sum": (dagnn.Sum, ()),
@@ -245,6 +246,13 @@ def _make_block(lname, ltype, b, nparams):
         return dagnn.BatchNorm(int(_number(b["numChannels"], "numChannels")), **kw)
     if ltype == "dagnn.ReLU":
         return dagnn.ReLU(_number(b["leak"], "leak") if has("leak") else 0.0)
+    if ltype == "dagnn.LRN":
+        if not has("param"):
+            return dagnn.LRN()
+        param = _numbers(b["param"])                  # 1 x 4 or 4 x 1
+        if len(param) != 4:
+            raise err("`param` has %d values, [N KAPPA ALPHA BETA] are four" % len(param))
+        return dagnn.LRN(param)
     if ltype == "dagnn.Scale":
         if nparams:
             raise err("only the two-input form without parameters (SE blocks) is built")
@@ -296,7 +304,7 @@ def _block_struct(block):
         elif f in ("stride", "dilate"):
             from . import vl
             v = _row(vl._pair(v, f))
-        elif f in ("size", "poolSize"):
+        elif f in ("size", "poolSize", "param"):
             v = _row(v)
         elif isinstance(v, (bool, np.bool_)):
             v = bool(v)

@@ -554,6 +554,39 @@ def vl_nnrelu(x, dzdy=None, leak=0.0):
     return y
 
 
+def nnnormalize_geometry():
+    """(pixels_per_block, channels_per_pass, window_in_registers) of the vl_nnnormalize kernels (host only)"""
+    v = [C.c_int(0) for _ in range(3)]
+    _lib.check(_L().xm_nnnormalize_geometry(*[C.byref(t) for t in v]))
+    return tuple(int(t.value) for t in v)
+
+
+def vl_nnnormalize(x, param, dzdy=None, out=None):
+    """Y = vl_nnnormalize(X, PARAM) / DZDX = vl_nnnormalize(X, PARAM, DZDY) [EXT], PARAM = [N KAPPA ALPHA BETA]: cross-channel
+    normalisation Y = X .* (KAPPA + ALPHA * sum of X.^2 over N neighbouring channels).^(-BETA) (include/xmodal.h).
+    `out` (extension): the array that receives the result; it may not overlap X or DZDY."""
+    x = _chk(x, "X")
+    param = [float(v) for v in np.asarray(param, dtype=np.float64).ravel()]
+    if len(param) != 4:
+        raise ValueError("PARAM must have four elements [N KAPPA ALPHA BETA]")
+    if param[0] != int(param[0]):
+        raise ValueError("PARAM(1) = N must be a positive integer")
+    H, W, Cc, S = _shape4(x)
+    y = mat_empty(*x.shape, device=x.device) if out is None else _chk(out, "OUT")
+    if tuple(y.shape) != tuple(x.shape):
+        raise ValueError("OUT and X do not have the same size")
+    # (a window of 2^31 - 1 channels already covers every tensor the ABI's int C can describe)
+    N, kappa, alpha, beta = min(int(param[0]), 2 ** 31 - 1), param[1], param[2], param[3]
+    if dzdy is None:
+        _lib.check(_L().xm_nnnormalize_forward(_ptr(x), H, W, Cc, S, N, kappa, alpha, beta, _ptr(y), _stream()))
+        return y
+    d = _chk(dzdy, "DZDY")
+    if tuple(d.shape) != tuple(x.shape):
+        raise ValueError("DZDY and X do not have the same size")
+    _lib.check(_L().xm_nnnormalize_backward(_ptr(x), _ptr(d), H, W, Cc, S, N, kappa, alpha, beta, _ptr(y), _stream()))
+    return y
+
+
 def vl_nndropout(x, dzdy=None, rate=0.5, mask=None, seed=0, offset=0):
     """[Y, MASK] = vl_nndropout(X, 'rate', r) / Y = vl_nndropout(X, 'mask', M) / DZDX = vl_nndropout(X, DZDY, 'mask', M).
     Without a mask one is drawn from the library's stateless Philox stream (seed, offset: include/xmodal.h)."""

@@ -12,6 +12,8 @@ Net surgery follows the reference line by line where it exists:
     prepareFromDagNN        emoVoxZoo.m:187-253   strip Loss/SoftMax, last FC -> numOutputs
     configureForRegression  emoVoxZoo.m:105-183   loss + classerror + ErrorStats layers
     updatePooling           emoVoxZoo.m:256-269   pool6 <- [1 p1] from the bucket table
+    insertBNLayers          ferPlusZoo.m:123      called there, missing from the reference: built from what
+                                                  ferplus_baselines.m:14-17 documents
 """
 import os
 
@@ -133,6 +135,115 @@ def resnet50(se=False, num_classes=8, width_mult=1.0, blocks=(3, 4, 6, 3)):
     return net
 
 
+VGG_FACE_AVERAGE = [129.1863, 104.7624, 93.5940]        # [EXT] the VGG-Face models' meta.normalization.averageImage
+
+
+def _vgg_tail(net, x, cin, span, width, num_classes):
+    """fc6 (spans the final map) -> relu6 -> dropout6 -> fc7 -> relu7 -> dropout7 -> fc8 -> prob of the VGG families"""
+    net.addLayer("fc6", dagnn.Conv([span, span, cin, width], True), x, "fc6", ["fc6f", "fc6b"])
+    net.addLayer("relu6", dagnn.ReLU(), "fc6", "relu6")
+    net.addLayer("dropout6", dagnn.DropOut(rate=0.5, seed=len(net.layers)), "relu6", "dropout6")
+    net.addLayer("fc7", dagnn.Conv([1, 1, width, width], True), "dropout6", "fc7", ["fc7f", "fc7b"])
+    net.addLayer("relu7", dagnn.ReLU(), "fc7", "relu7")
+    net.addLayer("dropout7", dagnn.DropOut(rate=0.5, seed=len(net.layers)), "relu7", "dropout7")
+    net.addLayer("fc8", dagnn.Conv([1, 1, width, num_classes], True), "dropout7", "fc8", ["fc8f", "fc8b"])
+    net.addLayer("prob", dagnn.SoftMax(), "fc8", "prob")
+
+
+def vgg_vd_face(num_classes=2622, width_mult=1.0, image_size=224):
+    """VGG-Face, the 16-layer VGG-VD [EXT: the vgg-face model of the MatConvNet model zoo]: conv1_1 .. conv5_3, 3 x 3 / pad 1
+    with 64-64 / 128-128 / 256 x 3 / 512 x 3 / 512 x 3 channels, each followed by a ReLU; 2 x 2 / stride 2 max pooling after
+    every stage; fc6 spans the final map (7 x 7 x 512 x 4096 at 224), dropout 0.5 behind relu6 and relu7, fc8, softmax.  No
+    batch norm anywhere (insertBNLayers).  `width_mult` < 1 and `image_size` (a multiple of 32; fc6 spans image_size / 32)
+    are for tests."""
+    if image_size % 32 or image_size <= 0:
+        raise ValueError("vgg_vd_face: image_size must be a positive multiple of 32")
+
+    def c(n):
+        return max(4, int(round(n * width_mult)))
+
+    net = dagnn.DagNN()
+    x, cin = "input", 3
+    for stage, (n, ch) in enumerate([(2, 64), (2, 128), (3, 256), (3, 512), (3, 512)], 1):
+        for i in range(1, n + 1):
+            tag = "%d_%d" % (stage, i)
+            net.addLayer("conv" + tag, dagnn.Conv([3, 3, cin, c(ch)], True, (1, 1), (1, 1, 1, 1)), x, "conv" + tag,
+                         ["conv%sf" % tag, "conv%sb" % tag])
+            net.addLayer("relu" + tag, dagnn.ReLU(), "conv" + tag, "relu" + tag)
+            x, cin = "relu" + tag, c(ch)
+        net.addLayer("pool%d" % stage, dagnn.Pooling([2, 2], (2, 2), (0, 0, 0, 0), "max"), x, "pool%d" % stage)
+        x = "pool%d" % stage
+    _vgg_tail(net, x, cin, image_size // 32, c(4096), num_classes)
+    net.meta = {"normalization": {"imageSize": [image_size, image_size, 3], "averageImage": list(VGG_FACE_AVERAGE)}}
+    return net
+
+
+def vgg_m_face(bn=True, num_classes=2622, width_mult=1.0):
+    """VGG-M trained on faces [EXT: Chatfield et al.'s VGG-M, imagenet-vgg-m of the MatConvNet model zoo], input 224 x 224 x 3:
+    conv1 7 x 7 x 96 / stride 2, conv2 5 x 5 x 256 / stride 2 / pad 1, conv3 .. conv5 3 x 3 x 512 / pad 1, 3 x 3 / stride 2 max
+    pooling behind stages 1, 2 and 5, fc6 6 x 6 x 512 x 4096, fc7, fc8.  `bn`: BatchNorm + ReLU behind conv1 .. fc7 (the
+    -bn models); otherwise ReLU, with norm1 / norm2 = dagnn.LRN([5 2 1e-4 0.75]) behind relu1 / relu2 (the classic file).
+    The pools pad one row / column at the bottom / right ([0 1 0 1]): 224 -> 109 -> 54 -> 26 -> 13 -> 6, so fc6 lands on a
+    6 x 6 map and gives 1 x 1 (the geometry pin; tests/test_lrn_cpu.py)."""
+    def c(n):
+        return max(4, int(round(n * width_mult)))
+
+    net = dagnn.DagNN()
+    spec = [("1", 7, 3, c(96), 2, 0), ("2", 5, c(96), c(256), 2, 1), ("3", 3, c(256), c(512), 1, 1),
+            ("4", 3, c(512), c(512), 1, 1), ("5", 3, c(512), c(512), 1, 1), ("6", 6, c(512), c(4096), 1, 0),
+            ("7", 1, c(4096), c(4096), 1, 0)]
+    x = "input"
+    for name, f, ci, co, s, p in spec:
+        lname = ("conv" if int(name) < 6 else "fc") + name
+        net.addLayer(lname, dagnn.Conv([f, f, ci, co], True, (s, s), (p, p, p, p)), x, lname, [lname + "f", lname + "b"])
+        x = lname
+        if bn:
+            net.addLayer("bn" + name, dagnn.BatchNorm(co), x, "bn" + name, ["bn%sm" % name, "bn%sb" % name, "bn%sx" % name])
+            x = "bn" + name
+        net.addLayer("relu" + name, dagnn.ReLU(), x, "relu" + name)
+        x = "relu" + name
+        if not bn and name in ("1", "2"):
+            net.addLayer("norm" + name, dagnn.LRN([5, 2, 1e-4, 0.75]), x, "norm" + name)
+            x = "norm" + name
+        if name in ("1", "2", "5"):
+            net.addLayer("pool" + name, dagnn.Pooling([3, 3], (2, 2), (0, 1, 0, 1), "max"), x, "pool" + name)
+            x = "pool" + name
+    net.addLayer("fc8", dagnn.Conv([1, 1, c(4096), num_classes], True), x, "fc8", ["fc8f", "fc8b"])
+    net.addLayer("prob", dagnn.SoftMax(), "fc8", "prob")
+    net.meta = {"normalization": {"imageSize": [224, 224, 3], "averageImage": list(VGG_FACE_AVERAGE)}}
+    return net
+
+
+def insertBNLayers(net):
+    """dag = insertBNLayers(dag): ferPlusZoo.m:123 calls this function and the reference does not contain it; this is what
+    ferplus_baselines.m:14-17 documents for `useBnorm`: "inserts batch norm layers into a model after each convolution.  If
+    the model already contains any batch norm layers, this option does nothing".  One BatchNorm(K) goes directly behind
+    every Conv except the one that produces 'prediction' (a normalised classifier output would pin the logits' scale), and
+    the convolution's consumers read the bnorm's output instead.  Layer and variable <conv>_bn, parameters
+    <conv>_bn_mult / _bias / _moments with the values and rates DagNN.initParams gives a BatchNorm (g = 1 at rate 2, b = 0,
+    moments (0, 1) with trainMethod 'average' at 0.1, no weight decay).  The convolutions keep their biases.  DropOut layers
+    take their new position as seed (insert_dropout's and loadobj's rule), so a saved and reloaded net draws the same masks."""
+    if any(isinstance(l.block, dagnn.BatchNorm) for l in net.layers):
+        return net
+    for l in list(net.layers):
+        if not isinstance(l.block, dagnn.Conv) or l.outputs[0] == "prediction":
+            continue
+        src, name = l.outputs[0], l.name + "_bn"
+        if name in net.vars or net.getLayerIndex(name) is not None:
+            raise ValueError("insertBNLayers: the network already has a '%s'" % name)
+        readers = [q.name for q in net.layers if src in q.inputs]
+        net.insertLayerAfter(l.name, name, dagnn.BatchNorm(l.block.size[3]), src, name,
+                             [name + "_mult", name + "_bias", name + "_moments"])
+        for q in readers:
+            net.setLayerInputs(q, [name if v == src else v for v in net.getLayer(q).inputs])
+        net.initLayerParams(net.getLayer(name), None)
+    for pos, l in enumerate(net.layers):
+        if isinstance(l.block, dagnn.DropOut):
+            l.block.seed = pos          # the layers moved: insert_dropout's and loadobj's rule, seed = position
+    net._flat = None
+    return net
+
+
 def synthetic_pretrained(net, seed):
     """Seeded stand-in for downloaded weights: He-normal filters, zero biases,
     BN g = 1, b = 0, stored moments mean ~ N(0, .1), sigma ~ U(.5, 1.5)."""
@@ -195,6 +306,9 @@ FERPLUS_MODELS_DEV = {"resnet50_ft-dag-dropout-0.1": "net-epoch-17",            
                       "resnet50_ft-dag-dropout-0.5": "net-epoch-122",
                       "senet50_ft-dag-distributions-dropout-0.5-aug": "net-epoch-98",
                       "senet50_ft-dag-distributions-CNTK-dropout-0.5-aug": "net-epoch-90"}
+# the VGG face teachers that have a seeded stand-in (the SFEW names have none)
+VGG_STANDINS = {"vgg-vd-face": vgg_vd_face, "vgg_face": vgg_vd_face, "vgg-vd-face-fer": vgg_vd_face,
+                "vgg-m-face-bn": vgg_m_face, "vgg-m-face-bn-fer": vgg_m_face}
 PUBLIC_MODELS = ["resnet50-ferplus", "senet50-ferplus", "emovoxceleb-student"]         # ensure_compatibility.m:13-15
 
 
@@ -229,7 +343,7 @@ def ferPlusModelPath(modelName, modelDir):
 
 
 def ferPlusZoo(modelName, seed=100, width_mult=1.0, blocks=(3, 4, 6, 3), *, useBnorm=False, finetuneLR=1,
-               dropoutRate=0, lossType="distributions", numOutputs=7, modelDir=None):
+               dropoutRate=0, lossType="distributions", numOutputs=7, modelDir=None, image_size=224):
     """dag = ferPlusZoo(modelName, 'useBnorm', .., 'finetuneLR', .., 'dropoutRate', .., 'lossType', ..,
     'numOutputs', ..) -- teacher/ferPlusZoo.m (option defaults :30-36).
 
@@ -239,8 +353,9 @@ def ferPlusZoo(modelName, seed=100, width_mult=1.0, blocks=(3, 4, 6, 3), *, useB
     intent, and these are the deviations:
       * `numOutputs` is undefined at :116 -- opts.numOutputs is used;
       * `opts.dropoout` at :119 does not exist (opts.dropooutRate is a typo'd second default) -- opts.dropoutRate is used;
-      * `insertBNLayers` (:122) is not in the reference; both architectures carry batch norm after every convolution
-        already, so useBnorm changes nothing (as ferplus_baselines.m:14-17 documents for such models);
+      * `insertBNLayers` (:122) is not in the reference; zoo.insertBNLayers builds what ferplus_baselines.m:14-17 documents
+        (a BatchNorm behind every convolution but the classifier, nothing when the model has batch norm already: the
+        ResNets and vgg-m-face-bn are unchanged by useBnorm, the VGG-VD networks get 15 BatchNorms);
       * fixInputVarnames (:127-133) renames the input to 'input' although getBatchFerPlus feeds 'data'; it is 'data'
         here, as in the pretrained branch;
       * MATLAB's addLayer APPENDS the dropout layers, so layers(1:end-2) at :236 would be every layer but the two
@@ -254,7 +369,13 @@ def ferPlusZoo(modelName, seed=100, width_mult=1.0, blocks=(3, 4, 6, 3), *, useB
     :37-71 is read from <modelDir>/[subfolder/]<name>.mat (ferPlusModelPath), `seed` only seeds the new classifier, and
     `width_mult` / `blocks` mean nothing.  The pretrained names (ferPlusModels, ferModels, net-epoch-*) return as loaded
     after fixInputVarnames (:103-114), every other name goes through prepareFromDagNN and configureForClassification
-    with the deviations above.  A missing file raises FileNotFoundError."""
+    with the deviations above, and then insertBNLayers when `useBnorm` (:123).  A missing file raises FileNotFoundError.
+    The VGG face teachers without `modelDir` (architectures restated from the public models [EXT]):
+    'vgg-vd-face' / 'vgg_face' (vgg_vd_face; `image_size`, a multiple of 32, shrinks it for tests) and 'vgg-m-face-bn'
+    (vgg_m_face(bn=True)) go through the training branch above; 'vgg-vd-face-fer' / 'vgg-m-face-bn-fer' are the
+    pretrained FER stand-ins: the same graphs with 7 classes, as a FER training leaves them for inference -- up to the
+    classifier's output 'prediction', neither loss heads nor the softmax (fetch_emovoxceleb_imdb.m:130 takes the last
+    variable as the logits) -- returned after fixInputVarnames.  The SFEW names have no stand-in."""
     if modelDir is not None:
         path, fileName = ferPlusModelPath(modelName, modelDir)
         net = load_model(path)                                                     # :98-100
@@ -262,6 +383,24 @@ def ferPlusZoo(modelName, seed=100, width_mult=1.0, blocks=(3, 4, 6, 3), *, useB
             return fixInputVarnames(net)                                           # :103-114
         prepareFromDagNN(net, numOutputs, seed)                                    # :116
         configureForClassification(net, finetuneLR, dropoutRate, lossType)         # :118-119
+        if useBnorm:
+            insertBNLayers(net)                                                    # :123
+        return fixInputVarnames(net)                                               # :124
+    if modelName in VGG_STANDINS:
+        pretrained = modelName in FER_MODELS
+        build = VGG_STANDINS[modelName]
+        kw = {"image_size": image_size} if build is vgg_vd_face else {}
+        net = build(num_classes=7 if pretrained else 2622, width_mult=width_mult, **kw)
+        synthetic_pretrained(net, seed)
+        net.meta["modelName"] = modelName
+        if pretrained:                                                             # :103-114
+            net.removeLayer([l.name for l in net.layers if isinstance(l.block, dagnn.SoftMax)])
+            net.renameVar(net.getOutputs()[-1], "prediction")
+            return fixInputVarnames(net)
+        prepareFromDagNN(net, numOutputs, seed)                                    # :116
+        configureForClassification(net, finetuneLR, dropoutRate, lossType)         # :118-119
+        if useBnorm:
+            insertBNLayers(net)                                                    # :123
         return fixInputVarnames(net)                                               # :124
     if modelName in FERPLUS_TRAINABLE:
         net = resnet50(FERPLUS_TRAINABLE[modelName], numOutputs, width_mult, blocks)
