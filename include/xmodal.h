@@ -93,8 +93,10 @@ int xm_device_synchronize(void);
 enum { XM_EXEC_SINGLE_STREAM = 1 };
 int xm_set_exec_hint(unsigned flags);
 unsigned xm_get_exec_hint(void);
-int xm_tune_load(const char *path);   /* NULL / "" = the default file; returns the number of entries read */
-int xm_tune_save(const char *path);   /* merges with the file on disk, writes atomically */
+int xm_tune_load(const char *path);   /* NULL / "" = the default file; returns the number of entries ADDED: an entry the
+                                         table already holds keeps its value and is not counted */
+int xm_tune_save(const char *path);   /* NULL / "" = the default file; the table written is the process's merged with the
+                                         DEFAULT file (loaded first if it was not yet), not with `path`; atomic (rename) */
 int xm_tune_entries(int *total, int *unsaved);
 /* optional: pre-size the internal scratch (split-K partials, filter transposes, tap tables). */
 int xm_workspace_reserve(size_t bytes);

@@ -11,8 +11,8 @@
 #include <vector>
 
 #include "conv_kernels.h"
+#include "conv_tune.h"
 #include "prof.h"
-#include "stem_pool_kernels.h"
 
 namespace xm {
 
@@ -250,39 +250,7 @@ conv_stats_finalize2_kernel(const double *__restrict__ part2, float *__restrict_
   mom[M + c] = (float)sqrt(var + (double)eps);
 }
 
-// ---- tile configuration ---------------------------------------------------------------------
-struct Cfg {
-  int tm, tn, wgm, wgn;
-  int bm() const { return 32 * tm * wgm; }
-  int bn() const { return 32 * tn * wgn; }
-};
-static const Cfg kCfgs[] = {
-    {2, 2, 2, 2},  // 128 x 128
-    {2, 2, 1, 4},  //  64 x 256
-    {3, 1, 1, 4},  //  96 x 128
-    {1, 2, 2, 2},  //  64 x 128
-    {1, 1, 2, 2},  //  64 x  64
-    {1, 1, 4, 1},  // 128 x  32
-    {1, 1, 1, 4},  //  32 x 128
-    // EIGHT waves per block: the 128 x 128 tile by waves of 32 x 64 -- 128 VGPRs, so two blocks per CU are four waves per
-    // SIMD instead of two: +3 ... 4 % on the long-reduction forward / dgrad layers (the filter derivative is
-    // 2 % slower with it, 64 x 256 by eight waves is no faster than 64 x 128 by four, 96 x 256 by waves of 96 x 32 spills,
-    // 96 x 128 by six waves stages 512 gather units with 384 threads: 75 against 117 TFLOP/s)
-    {1, 2, 4, 2},  //  7
-    // LDS-DMA variants (conv_gemm_dma_kernel): forward / dgrad GEMMs of 1x1 unit-stride layers only; LDS stages: kDmaStages
-    {2, 2, 2, 2},  //  8: 128 x 128
-    {2, 2, 1, 4},  //  9:  64 x 256
-    {1, 2, 2, 2},  // 10:  64 x 128
-    {1, 1, 2, 2},  // 11:  64 x  64
-};
-constexpr int kNumCfg = sizeof(kCfgs) / sizeof(kCfgs[0]);
-constexpr int kNumBaseCfg = 8;                       // configurations every forward / dgrad geometry can run
-constexpr int kCfgW8 = 7;                            // the eight-wave configuration (XM_NO_W8 runs configuration 0 in its place)
-constexpr int kNumWgradCfg = 7;                      // ... and the filter derivative (four-wave configurations only)
-static const int kDmaBase[] = {0, 1, 3, 4};          // the register-staged configuration of the same tile shape
-static inline bool is_dma_cfg(int ci) { return ci >= kNumBaseCfg; }
-static inline int base_cfg(int ci) { return is_dma_cfg(ci) ? kDmaBase[ci - kNumBaseCfg] : ci; }
-static inline int wgrad_cfg(int ci) { ci = base_cfg(ci); return ci >= kNumWgradCfg ? 0 : ci; }
+// ---- tile configuration (the list itself: conv_tune.h) ----------------------------------------
 // The eight-wave configuration is a candidate for launches of at least XM_W8_MIN_TILES 128 x 128 tiles (default: two rounds
 // of the chip).  Measured (profiles/r04/schedule_experiments.txt): alone it is 3 ... 4 % faster at every size, but next to the
 // filter derivatives of the side stream the shorter launches lose more than that (student step at 64 spectrograms - 3 %).
@@ -392,7 +360,7 @@ static void launch_gemm_cfg(int ci, const ConvGemmArgs &a, dim3 grid, hipStream_
 }
 
 static int g_force_cfg = -1;  // test hook (xm_debug_force_conv_cfg)
-static int g_force_stem = -1; // test hook (xm_debug_force_conv_stem): 1 = conv_stem_kernel wherever it can run, 0 = never
+int g_force_stem = -1;        // test hook (xm_debug_force_conv_stem): 1 = conv_stem_kernel wherever it can run, 0 = never (xm_common.h: stem_pool.hip reads it)
 static int g_force_wgrad_patch = -1; // test hook (xm_debug_force_wgrad_patch)
 // Execution hint of the HOST (xm_set_exec_hint, include/xmodal.h): XM_EXEC_SINGLE_STREAM = every operator call of the
 // process arrives on one stream, so a kernel has the chip to itself -- conv_wgrad_patch_kernel (48 KB of LDS per block,
@@ -721,34 +689,7 @@ static int launch_halo_multi(const std::vector<ConvGemmArgs> &args, int v, hipSt
 // caller's stream (HIP events, 2 launches each, best of) and the winner is cached for the life of
 // the process.  Happens during warm-up; results are identical for every configuration.
 // XM_AUTOTUNE=0 falls back to the analytic model above.
-struct TuneKey {
-  int kind, M, NP, Rp, mode, a, b, c, d;
-  bool operator<(const TuneKey &o) const { return memcmp(this, &o, sizeof(TuneKey)) < 0; }
-};
-// one builder per key family (the kinds: DESIGN.md 2.0); the fields are what the shipped table was written with
-static TuneKey tune_key_forward(int kind, const Geo &g, int M, int NP, int Rp, int tmode) {
-  return TuneKey{kind, M, NP, Rp, tmode, g.sy * 16 + g.sx, g.FH * 64 + g.FW, g.H, g.W};
-}
-static TuneKey tune_key_class_dgrad(int kind, const Geo &g, const DgradClass &c, int M, int NP, int PI) {
-  return TuneKey{kind, M, NP, c.Rp, c.nU * 64 + c.nV, g.sy * 16 + g.sx, PI, c.PJ, g.Ho};
-}
-static TuneKey tune_key_merged_dgrad(int kind, const Geo &g, int M, long long npSum, int rpMax, int classes) {
-  return TuneKey{kind, M, (int)std::min<long long>(npSum, 1 << 30), rpMax, classes, g.sy * 16 + g.sx, g.FH * 64 + g.FW, g.H, g.W};
-}
-static TuneKey tune_key_wgrad(int kind, const Geo &g) {
-  return TuneKey{kind, g.Kg, g.Ho * g.Wo * g.N, g.R, g.G, g.sy * 16 + g.sx, g.FH * 64 + g.FW, g.H, g.W};
-}
-static std::map<TuneKey, int> g_tuned;
-
-// ---- persistent tuning table ------------------------------------------------------------------
-// The measured choices are kept in a text file next to the library (tune_gfx950.txt, or $XM_TUNE_FILE) and
-// loaded before the first lookup: tile choices -- and therefore the summation order of every convolution --
-// are then the same in every process, and shapes already in the table pay no timed launches on the caller's
-// stream.  Shapes that are not in the table are still measured once per process (and written back by
-// xm_tune_save).  The header carries XM_TUNE_REV, bumped whenever the kernels or the configuration list change.
-constexpr int XM_TUNE_REV = 7;   // 7: configuration 7 = 128 x 128 by eight waves (the LDS-DMA ones moved to 8 ... 11); 6: fused-statistics launches are their own entries (mode + 4)
-static bool g_tune_loaded = false;
-static int g_tune_new = 0;  // entries measured in this process (not yet saved)
+static TuneTable g_tune;   // the process-wide table (keys, file format, load / save: conv_tune.h)
 
 static std::string tune_default_path() {
   if (const char *e = getenv("XM_TUNE_FILE")) return e;
@@ -760,30 +701,12 @@ static std::string tune_default_path() {
   }
   return "tune_gfx950.txt";
 }
-static int tune_load_file(const char *path) {
-  FILE *fp = fopen(path, "r");
-  if (!fp) return 0;
-  int ver = 0, rev = 0, ncfg = 0, n = 0;
-  if (fscanf(fp, "xmodal-tune %d rev=%d cfgs=%d\n", &ver, &rev, &ncfg) == 3 && ver == 1 && rev == XM_TUNE_REV &&
-      ncfg == kNumCfg) {
-    TuneKey k;
-    int cfg;
-    while (fscanf(fp, "%d %d %d %d %d %d %d %d %d %d\n", &k.kind, &k.M, &k.NP, &k.Rp, &k.mode, &k.a, &k.b, &k.c, &k.d,
-                  &cfg) == 10)
-      if (cfg >= 0 && cfg < kNumCfg && !g_tuned.count(k)) {
-        g_tuned[k] = cfg;
-        ++n;
-      }
-  }
-  fclose(fp);
-  return n;
-}
 static void tune_load_once() {
-  if (g_tune_loaded) return;
-  g_tune_loaded = true;
+  if (g_tune.loaded) return;
+  g_tune.loaded = true;
   const char *e = getenv("XM_TUNE_FILE");
   if (e && !e[0]) return;  // XM_TUNE_FILE="" : no persistent table
-  int n = tune_load_file(tune_default_path().c_str());
+  int n = g_tune.load(tune_default_path().c_str());
   if (getenv("XM_TUNE_VERBOSE")) fprintf(stderr, "[xm tune] %d entries from %s\n", n, tune_default_path().c_str());
 }
 static int autotune_enabled() {
@@ -794,39 +717,67 @@ static int autotune_enabled() {
   }
   return on;
 }
+// The gate in front of both measuring routines.  true: nothing is recorded under `key` and the candidates may be timed now.
+// false: *pick is the answer -- the table's entry, or what the caller put there (find mode off, or `st` is being captured).
+static bool tune_must_measure(const TuneKey &key, hipStream_t st, int *pick) {
+  if (!autotune_enabled()) return false;
+  tune_load_once();
+  if (const int *hit = g_tune.find(key)) {
+    *pick = *hit;
+    return false;
+  }
+  hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+  return !(hipStreamIsCapturing(st, &cs) == hipSuccess && cs != hipStreamCaptureStatusNone);
+}
+// The event pair of a measurement.
+struct TuneTimer {
+  hipEvent_t e0 = nullptr, e1 = nullptr;
+  bool ok;
+  TuneTimer() {
+    ok = hipEventCreate(&e0) == hipSuccess && hipEventCreate(&e1) == hipSuccess;
+    // The candidates are timed on an otherwise idle device: whatever the other streams of the step had queued is drained first
+    // (the host thread is in here, so nothing new arrives).  Timed next to a neighbour's kernels the choice depended on what
+    // happened to be running -- the shipped table differed from one generation to the next.
+    if (ok) (void)hipDeviceSynchronize();
+  }
+  ~TuneTimer() {
+    if (e0) (void)hipEventDestroy(e0);
+    if (e1) (void)hipEventDestroy(e1);
+  }
+  // milliseconds of one launch() on `st`; negative: it failed, or could not be timed
+  template <class L>
+  float time_once(hipStream_t st, L &&launch) {
+    float ms = 0.f;
+    (void)hipEventRecord(e0, st);
+    if (launch() != XM_OK) return -1.f;
+    (void)hipEventRecord(e1, st);
+    if (hipEventSynchronize(e1) != hipSuccess || hipEventElapsedTime(&ms, e0, e1) != hipSuccess) return -1.f;
+    return ms;
+  }
+};
+
+// XM_TUNE_REPS (default 2) consecutive launches per configuration, best of; one that fails disqualifies its configuration.
 template <class F>
 static int tune_cfg(const TuneKey &key, int fallback, hipStream_t st, F &&launch, int ncfg = kNumBaseCfg,
                     unsigned skip = 0 /* bit ci: configuration not eligible for this launch */) {
   if (g_force_cfg >= 0) return g_force_cfg < ncfg ? g_force_cfg : base_cfg(g_force_cfg);
-  if (!autotune_enabled()) return fallback;
-  tune_load_once();
-  auto it = g_tuned.find(key);
-  if (it != g_tuned.end()) return it->second;
-  hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-  if (hipStreamIsCapturing(st, &cs) == hipSuccess && cs != hipStreamCaptureStatusNone) return fallback;
-  hipEvent_t e0, e1;
-  if (hipEventCreate(&e0) != hipSuccess || hipEventCreate(&e1) != hipSuccess) return fallback;
+  int bi = fallback;
+  if (!tune_must_measure(key, st, &bi)) return bi;
+  TuneTimer timer;
+  if (!timer.ok) return fallback;
   static const bool verbose = getenv("XM_TUNE_VERBOSE") != nullptr;
   static const int reps = getenv("XM_TUNE_REPS") ? std::max(1, atoi(getenv("XM_TUNE_REPS"))) : 2;
   float best = 1e30f;
-  int bi = fallback;
-  // The candidates are timed on an otherwise idle device: whatever the other streams of the step had queued is drained first
-  // (the host thread is in here, so nothing new arrives).  Timed next to a neighbour's kernels the choice depended on what
-  // happened to be running -- the shipped table differed from one generation to the next.
-  (void)hipDeviceSynchronize();
   for (int ci = 0; ci < ncfg; ++ci) {
     if (skip >> ci & 1u) continue;
     float tmin = 1e30f;
     for (int rep = 0; rep < reps; ++rep) {
-      (void)hipEventRecord(e0, st);
-      if (launch(ci) != XM_OK) {
+      const float ms = timer.time_once(st, [&] { return launch(ci); });
+      if (ms < 0.f) {
         tmin = 1e30f;
         break;
       }
-      (void)hipEventRecord(e1, st);
-      if (hipEventSynchronize(e1) != hipSuccess) break;
-      float ms = 0.f;
-      if (hipEventElapsedTime(&ms, e0, e1) == hipSuccess) tmin = std::min(tmin, ms);
+      tmin = std::min(tmin, ms);
     }
     if (verbose) fprintf(stderr, " cfg%d %.3f", ci, tmin);
     if (tmin < best) {
@@ -834,10 +785,7 @@ static int tune_cfg(const TuneKey &key, int fallback, hipStream_t st, F &&launch
       bi = ci;
     }
   }
-  (void)hipEventDestroy(e0);
-  (void)hipEventDestroy(e1);
-  g_tuned[key] = bi;
-  ++g_tune_new;
+  g_tune.record(key, bi);
   if (verbose)
     fprintf(stderr, "  -> [xm tune] kind %d M %d NP %d Rp %d (%d %d %d %d %d): cfg%d %.3f ms\n", key.kind, key.M,
             key.NP, key.Rp, key.mode, key.a, key.b, key.c, key.d, bi, best);
@@ -850,35 +798,22 @@ static int tune_cfg(const TuneKey &key, int fallback, hipStream_t st, F &&launch
 // (larger LDS footprint).  `ok[i]` = false skips a challenger.
 template <class F>
 static int tune_challengers(const TuneKey &key, hipStream_t st, F &&launch, int n, const bool *ok, float margin) {
-  if (!autotune_enabled()) return 0;
-  tune_load_once();
-  auto it = g_tuned.find(key);
-  if (it != g_tuned.end()) return (it->second < n && (it->second == 0 || ok[it->second])) ? it->second : 0;
-  hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-  if (hipStreamIsCapturing(st, &cs) == hipSuccess && cs != hipStreamCaptureStatusNone) return 0;
-  hipEvent_t e0, e1;
-  if (hipEventCreate(&e0) != hipSuccess || hipEventCreate(&e1) != hipSuccess) return 0;
+  int pick = 0;
+  if (!tune_must_measure(key, st, &pick)) return (pick < n && (pick == 0 || ok[pick])) ? pick : 0;   // a stored arm has to be runnable still
+  TuneTimer timer;
+  if (!timer.ok) return 0;
   float tmin[8];
   for (int i = 0; i < 8; ++i) tmin[i] = 1e30f;
-  (void)hipDeviceSynchronize();   // see tune_cfg: the candidates are timed on an otherwise idle device
   for (int rep = 0; rep < 4; ++rep)
     for (int ci = 0; ci < n && ci < 8; ++ci) {
       if (ci > 0 && !ok[ci]) continue;
-      (void)hipEventRecord(e0, st);
-      if (launch(ci) != XM_OK) continue;
-      (void)hipEventRecord(e1, st);
-      if (hipEventSynchronize(e1) != hipSuccess) continue;
-      float ms = 0.f;
-      if (rep > 0 && hipEventElapsedTime(&ms, e0, e1) == hipSuccess) tmin[ci] = std::min(tmin[ci], ms);
+      const float ms = timer.time_once(st, [&] { return launch(ci); });
+      if (rep > 0 && ms >= 0.f) tmin[ci] = std::min(tmin[ci], ms);
     }
-  (void)hipEventDestroy(e0);
-  (void)hipEventDestroy(e1);
-  int pick = 0;
   float best = (1.f - margin) * tmin[0];
   for (int ci = 1; ci < n && ci < 8; ++ci)
     if (tmin[ci] < best) best = tmin[ci], pick = ci;
-  g_tuned[key] = pick;
-  ++g_tune_new;
+  g_tune.record(key, pick);
   if (getenv("XM_TUNE_VERBOSE"))
     fprintf(stderr, "[xm tune] kind %d M %d NP %d Rp %d: incumbent %.3f ms, challengers %.3f %.3f %.3f -> %d\n", key.kind,
             key.M, key.NP, key.Rp, tmin[0], tmin[1], tmin[2], tmin[3], pick);
@@ -933,8 +868,8 @@ static void launch_wgrad_cfg(int ci, const WgradArgs &a, dim3 grid, hipStream_t 
 static_assert(sizeof(Tap2) == sizeof(int2) && alignof(Tap2) <= alignof(int2), "Tap2 has the layout of int2: {x, y}");
 static_assert(sizeof(Tap4) == sizeof(int4) && alignof(Tap4) <= alignof(int4), "Tap4 has the layout of int4: {x, y, z, w}");
 
-static int make_geo(Geo &g, int H, int W, int C, int N, int FH, int FW, int FC, int K, int sy,
-                    int sx, int pt, int pb, int pl, int pr, int dy, int dx) {
+int make_geo(Geo &g, int H, int W, int C, int N, int FH, int FW, int FC, int K, int sy,
+             int sx, int pt, int pb, int pl, int pr, int dy, int dx) {
   if (H <= 0 || W <= 0 || C <= 0 || N <= 0 || FH <= 0 || FW <= 0 || FC <= 0 || K <= 0)
     return fail(XM_EINVAL, "vl_nnconv: empty tensor (X %dx%dx%dx%d, F %dx%dx%dx%d)", H, W, C, N, FH,
                 FW, FC, K);
@@ -2005,46 +1940,6 @@ static int conv_wgrad(const float *x, const float *dzdy, float *dfo, const Geo &
   return run(ci);
 }
 
-// ---- conv1 -> bnorm -> relu -> pool through the Gram matrix of the input patches (stem_pool_kernels.h) -------------------
-static bool stem_pool_ok(const Geo &g, const float *x) { return path_on(kPathStem) && stem_pool_can(g, (uintptr_t)x); }
-
-static int stem_pool_units(const Geo &g) { return g.N * ((g.Wo + 1) / 2) * ((g.Ho + 255) / 256); }
-static void stem_pool_args(StemPoolArgs &a, const float *x, const Geo &g) {
-  a.X = x, a.M = g.Kg, a.R = g.R, a.nU = g.FH, a.nV = g.FW, a.PI = g.Ho, a.PJ = g.Wo;
-  const int G = (g.Ho + 255) / 256;
-  a.divJG = make_fastdiv((uint32_t)(((g.Wo + 1) / 2) * G)), a.divG = make_fastdiv((uint32_t)G);
-  a.gsx = g.sx, a.gh0 = -g.pt, a.gw0 = -g.pl, a.LimH = g.H, a.LimW = g.W, a.xSampleStride = g.H * g.W;
-}
-
-static int stem_pool_grid(int nunits, int occ) { return std::min(256 * occ, (nunits + 7) / 8 * 8); }
-static size_t stem_gram_need(const Geo &g) {
-  return WsCarver::need((size_t)stem_pool_grid(stem_pool_units(g), 3) * 64 * 64, 4);
-}
-
-// G (fp64 [64][64]) of the patches of x; scratch from the caller's carver
-static int launch_stem_gram(WsCarver &ws, const float *x, const Geo &g, double *gram, hipStream_t st) {
-  StemPoolArgs a{};
-  stem_pool_args(a, x, g);
-  const int nunits = stem_pool_units(g), grid = stem_pool_grid(nunits, 3);
-  a.part = ws.take<float>((size_t)grid * 64 * 64);
-  static bool attr_done = false;
-  if (!attr_done) {
-    XM_HIP(hipFuncSetAttribute((const void *)stem_gram_kernel<2>, hipFuncAttributeMaxDynamicSharedMemorySize, kSpGramSmem));
-    XM_HIP(hipFuncSetAttribute((const void *)stem_gram_kernel<1>, hipFuncAttributeMaxDynamicSharedMemorySize, kSpGramSmem));
-    attr_done = true;
-  }
-  {
-    // three of the four 32 x 32 tiles of the padded 64 x 64 product are computed
-    ProfScope ps(prof_key(kProfStemGram), 2.0 * (g.R + 1) * (g.R + 1) * (double)g.Ho * g.Wo * g.N, st, 4.0 * g.H * g.W * g.N);
-    if (g.sy == 2) hipLaunchKernelGGL(stem_gram_kernel<2>, dim3(grid), dim3(256), kSpGramSmem, st, a, nunits);
-    else hipLaunchKernelGGL(stem_gram_kernel<1>, dim3(grid), dim3(256), kSpGramSmem, st, a, nunits);
-  }
-  XM_LAUNCH_CHECK();
-  hipLaunchKernelGGL(stem_gram_reduce_kernel, dim3(64), dim3(1024), 0, st, a.part, gram, grid);
-  XM_LAUNCH_CHECK();
-  return XM_OK;
-}
-
 }  // namespace xm
 
 using namespace xm;
@@ -2100,29 +1995,20 @@ unsigned xm_get_exec_hint(void) { return g_exec_hint; }
 
 // ---- persistent tuning table (include/xmodal.h) ----------------------------------------------
 int xm_tune_load(const char *path) {
-  g_tune_loaded = true;
-  return tune_load_file(path && path[0] ? path : tune_default_path().c_str());
+  return g_tune.load(path && path[0] ? path : tune_default_path().c_str());
 }
 int xm_tune_save(const char *path) {
-  tune_load_once();   // merge with what is on disk
-  std::string p = path && path[0] ? std::string(path) : tune_default_path();
-  std::string tmp = p + ".tmp";
-  FILE *fp = fopen(tmp.c_str(), "w");
-  if (!fp) return fail(XM_EINVAL, "xm_tune_save: cannot write %s", tmp.c_str());
-  fprintf(fp, "xmodal-tune 1 rev=%d cfgs=%d\n", XM_TUNE_REV, kNumCfg);
-  for (auto &kv : g_tuned) {
-    const TuneKey &k = kv.first;
-    fprintf(fp, "%d %d %d %d %d %d %d %d %d %d\n", k.kind, k.M, k.NP, k.Rp, k.mode, k.a, k.b, k.c, k.d, kv.second);
-  }
-  fclose(fp);
-  if (rename(tmp.c_str(), p.c_str()) != 0) return fail(XM_EINVAL, "xm_tune_save: rename to %s failed", p.c_str());
-  g_tune_new = 0;
+  tune_load_once();   // merge with the default file
+  const std::string p = path && path[0] ? std::string(path) : tune_default_path();
+  const int rc = g_tune.save(p.c_str());
+  if (rc == 1) return fail(XM_EINVAL, "xm_tune_save: cannot write %s.tmp", p.c_str());
+  if (rc) return fail(XM_EINVAL, "xm_tune_save: rename to %s failed", p.c_str());
   return XM_OK;
 }
 int xm_tune_entries(int *total, int *unsaved) {
   tune_load_once();
-  if (total) *total = (int)g_tuned.size();
-  if (unsaved) *unsaved = g_tune_new;
+  if (total) *total = g_tune.size();
+  if (unsaved) *unsaved = g_tune.unsaved;
   return XM_OK;
 }
 // on = 1: every block (< 4096) of every later conv_gemm launch records {first clock, last clock, HW_ID, XCC_ID};
@@ -2278,180 +2164,6 @@ int xm_nnconv_backward_filter_bnrelupool(const float *x, int H, int W, int C, in
   if (rc) return rc;
   StemBnp bnp{dzdy_pool, argmax, rowc, pHo, pWo, dbias_out};
   return launch_stem_wgrad(x, y, df_out, g, spart, grid, st, &bnp);
-}
-
-// G = P~' P~ of the im2col patches (+ a column of ones) of a single-channel first-layer convolution: fp64 [64][64],
-// row / column t = u + FH v (t < FH FW), t = FH FW: the ones column; entries beyond are zero.
-int xm_stem_gram(const float *x, int H, int W, int N, int FH, int FW, int sy, int sx, int pt, int pb, int pl, int pr,
-                 double *gram, void *stream) {
-  Geo g;
-  int rc = make_geo(g, H, W, 1, N, FH, FW, 1, 1, sy, sx, pt, pb, pl, pr, 1, 1);
-  if (rc) return rc;
-  if (!x || !gram) return fail(XM_EINVAL, "xm_stem_gram: NULL tensor");
-  if (!stem_pool_ok(g, x)) return fail(XM_ENOTSUP, "xm_stem_gram: geometry not covered");
-  hipStream_t st = (hipStream_t)stream;
-  WsCarver ws;
-  rc = ws.init(stem_gram_need(g), st);
-  if (rc) return rc;
-  return launch_stem_gram(ws, x, g, gram, st);
-}
-
-// Batch moments [mean, sqrt(var + eps)] of Y = vl_nnconv(X, F, B) for a single-channel first layer, from G alone
-int xm_stem_gram_moments(const double *gram, const float *f, const float *b, int FH, int FW, int K, float epsilon,
-                         float *moments_out, void *stream) {
-  if (!gram || !f || !moments_out) return fail(XM_EINVAL, "xm_stem_gram_moments: NULL tensor");
-  if (FH * FW < 1 || FH * FW > 63 || K < 1) return fail(XM_EINVAL, "xm_stem_gram_moments: bad shape");
-  hipLaunchKernelGGL(stem_gram_moments_kernel, dim3(K), dim3(64), 0, (hipStream_t)stream, gram, f, b, K, FH * FW,
-                     (double)epsilon, moments_out);
-  XM_LAUNCH_CHECK();
-  return XM_OK;
-}
-
-// Y_POOL, ARGMAX, MOMENTS of vl_nnpool(vl_nnrelu(vl_nnbnorm(vl_nnconv(X, F, B), G, BB)), [3 3], 'stride', 2) for a
-// single-channel first layer in one kernel (conv_stem_bnpool_fwd_kernel): the convolution's output is never written.
-// Train mode (moments_in NULL): G = xm_stem_gram(X) is left in `gram` (fp64 [64][64], caller-owned: the backward call
-// takes it) and the batch moments come from it.  The table marks windows whose maximum did not pass the ReLU with 255.
-int xm_nnconv_bnorm_relu_pool_forward(const float *x, int H, int W, int C, int N, const float *f, int FH, int FW, int FC,
-                                      int K, const float *bias, int sy, int sx, int pt, int pb, int pl, int pr, int dy, int dx,
-                                      const float *bn_g, const float *bn_b, float epsilon, const float *moments_in, int ph,
-                                      int pw, int psy, int psx, int ppt, int ppb, int ppl, int ppr, double *gram,
-                                      float *y_pool, unsigned char *argmax, float *moments_out, void *stream) {
-  Geo g;
-  int rc = make_geo(g, H, W, C, N, FH, FW, FC, K, sy, sx, pt, pb, pl, pr, dy, dx);
-  if (rc) return rc;
-  if (!x || !f || !bn_g || !bn_b || !y_pool || !argmax || (!moments_in && (!gram || !moments_out)))
-    return fail(XM_EINVAL, "vl_nnconv + bnorm + relu + pool (fused forward): NULL tensor");
-  hipStream_t st = (hipStream_t)stream;
-  const int pHo = out_size(g.Ho, ppt, ppb, ph, 1, psy), pWo = out_size(g.Wo, ppl, ppr, pw, 1, psx);
-  const long long pooled = (long long)pHo * pWo * g.K * g.N;
-  const bool ok = path_on(kPathStem) && g_force_stem != 0 &&
-                  fused_stem_can(kFusedStemForward, g, (uintptr_t)x, ph, pw, psy, psx, ppt, ppb, ppl, ppr, pHo, pWo, (uintptr_t)y_pool);
-  if (!ok)
-    return fail(XM_ENOTSUP, "vl_nnconv + bnorm + relu + pool (fused forward): geometry not covered by the fused kernel");
-  const float *moments = moments_in;
-  if (!moments_in) {
-    WsCarver ws;
-    rc = ws.init(stem_gram_need(g), st);
-    if (rc) return rc;
-    rc = launch_stem_gram(ws, x, g, gram, st);
-    if (rc) return rc;
-    hipLaunchKernelGGL(stem_gram_moments_kernel, dim3(g.K), dim3(64), 0, st, gram, f, bias, g.K, g.R, (double)epsilon,
-                       moments_out);
-    XM_LAUNCH_CHECK();
-    moments = moments_out;
-  }
-  StemFwdArgs a{};
-  a.X = x, a.F = f, a.bias = bias, a.bn_g = bn_g, a.bn_b = bn_b, a.moments = moments;
-  a.Y = y_pool, a.amax = argmax;
-  a.M = g.K, a.R = g.R, a.nU = g.FH, a.nV = g.FW;
-  a.PI = g.Ho, a.PJ = g.Wo, a.pHo = pHo, a.pWo = pWo;
-  a.NS = (pHo + 62) / 63;
-  const int slots = 256 * XM_SF_OCC * 4;
-  // segments of window columns per (sample, strip, row tile): the count that minimises (rounds of the resident waves) x
-  // (output columns of a unit, one of them computed twice per segment).  A partly filled last round costs a whole one:
-  // 11 segments at 32 spectrograms = 2112 units for 2048 waves ran 285 us, 10 segments 206 us; at 256 spectrograms one
-  // segment leaves a quarter of the waves idle and two make 1.5 rounds, four make exactly three.
-  {
-    const long long base = (long long)g.N * a.NS * 3;
-    long long best = -1;
-    a.SG = 1;
-    for (int sg = 1; sg <= std::min(16, pWo); ++sg) {
-      const long long rounds = (base * sg + slots - 1) / slots;
-      const long long cost = rounds * (2 * ((pWo + sg - 1) / sg) + 1);
-      if (best < 0 || cost < best) best = cost, a.SG = sg;
-    }
-  }
-  a.nunits = g.N * a.NS * a.SG * 3;
-  a.div3 = make_fastdiv(3u), a.divSG = make_fastdiv((uint32_t)a.SG), a.divNS = make_fastdiv((uint32_t)a.NS);
-  a.gh0 = -g.pt, a.gw0 = -g.pl, a.LimH = g.H, a.LimW = g.W, a.xSampleStride = g.H * g.W;
-  a.yBytes = (unsigned)(pooled * 4), a.amBytes = (unsigned)pooled;
-  static bool attr_done = false;
-  if (!attr_done) {
-    XM_HIP(hipFuncSetAttribute((const void *)conv_stem_bnpool_fwd_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, kSfSmem));
-    attr_done = true;
-  }
-  const int grid = std::min(256 * XM_SF_OCC, (a.nunits + 3) / 4);
-  {
-    ProfScope ps(prof_key(kProfStemBnpoolFwd), 2.0 * g.K * (double)g.Ho * g.Wo * g.N * g.R, st, 4.0 * g.H * g.W * g.N + 5.0 * (double)pooled);
-    hipLaunchKernelGGL(conv_stem_bnpool_fwd_kernel, dim3(grid), dim3(256), kSfSmem, st, a);
-  }
-  XM_LAUNCH_CHECK();
-  return XM_OK;
-}
-
-// xm_nnconv_backward_filter_bnrelupool without a pass over the convolution's output (stem_pool_kernels.h): the
-// filter bank F (and bias B) take Y's place; `gram` = xm_stem_gram of X (NULL: computed here).
-int xm_nnconv_backward_filter_bnrelupool_gram(const float *x, int H, int W, int C, int N, const float *f, int FH, int FW,
-                                              int FC, int K, const float *bias, int sy, int sx, int pt, int pb, int pl,
-                                              int pr, int dy, int dx, const float *bn_g, const float *moments, int train,
-                                              int ph, int pw, int psy, int psx, int ppt, int ppb, int ppl, int ppr,
-                                              const unsigned char *argmax, const float *y_pool, const float *dzdy_pool,
-                                              const double *gram, float *df_out, float *dbias_out, float *dg_out,
-                                              float *db_out, void *stream) {
-  Geo g;
-  int rc = make_geo(g, H, W, C, N, FH, FW, FC, K, sy, sx, pt, pb, pl, pr, dy, dx);
-  if (rc) return rc;
-  if (!x || !f || !bn_g || !moments || !argmax || !dzdy_pool || !df_out)
-    return fail(XM_EINVAL, "vl_nnconv(filter derivative through bnorm+relu+pool, gram): NULL tensor");
-  hipStream_t st = (hipStream_t)stream;
-  const int pHo = out_size(g.Ho, ppt, ppb, ph, 1, psy), pWo = out_size(g.Wo, ppl, ppr, pw, 1, psx);
-  const long long pooled = (long long)pHo * pWo * g.K * g.N;
-  const bool ok = path_on(kPathStem) && g_force_stem != 0 &&      // (y_pool NULL: the table marks closed windows itself)
-                  fused_stem_can(kFusedStemBackward, g, (uintptr_t)x, ph, pw, psy, psx, ppt, ppb, ppl, ppr, pHo, pWo,
-                                 (uintptr_t)dzdy_pool | (uintptr_t)y_pool);
-  if (!ok)
-    return fail(XM_ENOTSUP, "vl_nnconv(filter derivative through bnorm+relu+pool, gram): geometry not covered by the fused kernel");
-  StemPoolArgs a{};
-  stem_pool_args(a, x, g);
-  // wave units (sample, column pair, 64-row chunk pair) x 3 row tiles of filters; grid: whole XCD rows of blocks whose
-  // waves split evenly over the row tiles (a multiple of 24 blocks), two blocks per CU
-  const int ncp = (g.Ho + 63) / 64, npair = (g.Wo + 1) / 2;
-  const int nunits = g.N * npair * ncp;
-  a.divJG = make_fastdiv((uint32_t)npair);
-  a.divG = make_fastdiv((uint32_t)ncp);
-  const int grid = std::min(504, ((nunits * 3 + 3) / 4 + 23) / 24 * 24);      // two blocks per CU, 63 per XCD
-  const int nwc = grid * 4 / 3;
-  WsCarver ws;
-  rc = ws.init(WsCarver::need((size_t)grid * 4 * 32 * 64, 4) + WsCarver::need(64 * 64, 8) + stem_gram_need(g), st);
-  if (rc) return rc;
-  a.part = ws.take<float>((size_t)grid * 4 * 32 * 64);
-  double *gr = ws.take<double>(64 * 64);
-  if (train && !gram) {
-    rc = launch_stem_gram(ws, x, g, gr, st);
-    if (rc) return rc;
-    gram = gr;
-  }
-  a.dP = dzdy_pool;
-  a.yP = y_pool ? y_pool : dzdy_pool;
-  a.amax = argmax;
-  a.pHo = pHo;
-  a.pWo = pWo;
-  a.dpBytes = (unsigned)(pooled * 4);
-  a.amBytes = (unsigned)pooled;
-  static bool attr_done = false;
-  if (!attr_done) {
-    XM_HIP(hipFuncSetAttribute((const void *)conv_stem_wgrad_pool_kernel<2, true>, hipFuncAttributeMaxDynamicSharedMemorySize, kSp3Smem));
-    XM_HIP(hipFuncSetAttribute((const void *)conv_stem_wgrad_pool_kernel<1, true>, hipFuncAttributeMaxDynamicSharedMemorySize, kSp3Smem));
-    XM_HIP(hipFuncSetAttribute((const void *)conv_stem_wgrad_pool_kernel<2, false>, hipFuncAttributeMaxDynamicSharedMemorySize, kSp3Smem));
-    XM_HIP(hipFuncSetAttribute((const void *)conv_stem_wgrad_pool_kernel<1, false>, hipFuncAttributeMaxDynamicSharedMemorySize, kSp3Smem));
-    attr_done = true;
-  }
-  {
-    const double abytes = 4.0 * g.H * g.W * g.N + (y_pool ? 9.0 : 5.0) * (double)pooled + 4.0 * a.M * a.R;
-    ProfScope ps(prof_key(kProfStemWgradPool, y_pool ? 1 : 0), 2.0 * a.M * (double)g.Ho * g.Wo * g.N * a.R, st, abytes);
-#define XM_SPW_LAUNCH(SY_, G_) hipLaunchKernelGGL((conv_stem_wgrad_pool_kernel<SY_, G_>), dim3(grid), dim3(256), kSp3Smem, st, a, nunits)
-    if (g.sy == 2) {
-      if (y_pool) XM_SPW_LAUNCH(2, true); else XM_SPW_LAUNCH(2, false);
-    } else {
-      if (y_pool) XM_SPW_LAUNCH(1, true); else XM_SPW_LAUNCH(1, false);
-    }
-#undef XM_SPW_LAUNCH
-  }
-  XM_LAUNCH_CHECK();
-  hipLaunchKernelGGL(stem_pool_finalize_kernel, dim3(g.K), dim3(1024), 0, st, a.part, nwc, gram, f, bias, bn_g, moments, g.K,
-                     g.R, train ? 1 : 0, df_out, dbias_out, dg_out, db_out);
-  XM_LAUNCH_CHECK();
-  return XM_OK;
 }
 
 int xm_nnconv_backward(const float *x, int H, int W, int C, int N, const float *f, int FH, int FW,

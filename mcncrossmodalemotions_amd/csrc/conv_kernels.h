@@ -34,9 +34,6 @@
 
 namespace xm {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-
 struct ConvGemmArgs {
   const float *A;     // [M][lda], lda % 4 == 0, 16-byte aligned, zero padded to Rp columns
   const float *X;     // gather source

@@ -19,7 +19,7 @@ enum ProfKind {
   kProfWgradPatchS2 = 10,
   kProfDgradS2 = 11,
   kProfStem3 = 12,          //           sub = 1: 256-pixel block tiles
-  kProfStemGram = 13,
+  kProfStemGram = 13,       // stem_pool.hip
   kProfStemWgradPool = 14,  //           sub = 1: with the pooled output
   kProfStemBnpoolFwd = 15,
   kProfSpec = 20,           // spec.hip, sub = launch of xm_spec_bucket_batch
@@ -55,7 +55,7 @@ struct ProfScope {
   ~ProfScope() { if (on) prof_end(r, st); }
 };
 
-// conv.hip, next to kCfgs and the launch switches: name of the instantiation behind a kProfGemm / kProfWgrad /
+// conv.hip, next to the launch switches over kCfgs (conv_tune.h): name of the instantiation behind a kProfGemm / kProfWgrad /
 // kProfGemmMulti sub-key; false when no launch site produces `sub`
 bool conv_cfg_kernel_name(ProfKind kind, int sub, char *buf, int len);
 

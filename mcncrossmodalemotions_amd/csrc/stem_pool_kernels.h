@@ -24,7 +24,8 @@
 // contributions to a pixel are added in registers in a fixed order.  The forward half of the layer
 // (conv_stem_bnpool_fwd_kernel, second part of this file) writes the pooled output and the table without writing x either.
 #pragma once
-#include "conv_kernels.h"
+#include "conv_plan.h"
+#include "xm_common.h"
 
 namespace xm {
 

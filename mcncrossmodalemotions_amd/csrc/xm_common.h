@@ -77,7 +77,7 @@ enum Path {
   kPathPoolLds,         // XM_NO_POOL_LDS        LDS-staged fused bnorm + relu + pool forward
   kPathPoolPatch,       // XM_NO_POOL_PATCH      stride-cell variant of its backward apply
   kPathPoolPooled,      // XM_NO_POOL_POOLED     backward sums from the pooled tensors
-  kPathW8,              // XM_NO_W8              128 x 128 tiles by eight waves of 128 VGPRs (conv.hip kCfgs[7]); off = four waves of 222
+  kPathW8,              // XM_NO_W8              128 x 128 tiles by eight waves of 128 VGPRs (conv_tune.h kCfgs[7]); off = four waves of 222
   kPathWgradPatch,      // XM_NO_WGRAD_PATCH     filter derivative of 3 x 3 / stride 1 layers from an input patch (conv_wgrad_patch_kernel)
   kPathWgradPatchS2,    // XM_NO_WGRAD_PATCH_S2  filter derivative of 5 x 5 / stride 2 layers from an input patch (conv_wgrad_patch_s2_kernel)
   kPathDgradS2,         // XM_NO_DGRAD_S2        dgrad of 5 x 5 / stride 2 layers with both row parities per wave (conv_dgrad_s2_kernel)
@@ -93,6 +93,12 @@ double env_double(const char *name, double dflt);
 int comm_force_single(int on);
 // spec.hip: test switch behind xm_debug_set("spec_blocks", v)
 extern int g_spec_blocks;
+// conv.hip: test switch behind xm_debug_set("conv_stem", v), and the checked geometry of a vl_nnconv call (struct Geo:
+// conv_plan.h) -- stem_pool.hip needs both
+extern int g_force_stem;
+struct Geo;
+int make_geo(Geo &g, int H, int W, int C, int N, int FH, int FW, int FC, int K, int sy, int sx, int pt, int pb, int pl,
+             int pr, int dy, int dx);
 
 // persistent small device objects keyed by content (tap tables)
 const void *cached_device_table(const void *host, size_t bytes);
@@ -140,6 +146,12 @@ static inline FastDiv make_fastdiv(uint32_t d) {
   f.m = (uint32_t)(((1ull << f.s) + d - 1) / d);
   return f;
 }
+
+#ifdef __HIPCC__
+// MFMA accumulator and 16-byte access vectors of the kernel headers (conv_kernels.h, stem_pool_kernels.h)
+typedef float f32x16 __attribute__((ext_vector_type(16)));
+typedef float f32x4 __attribute__((ext_vector_type(4)));
+#endif
 
 }  // namespace xm
 

@@ -1,6 +1,7 @@
 #!/usr/bin/env python
 """VGPR / AGPR / SGPR / spill / LDS / occupancy of every kernel of a csrc/*.hip file (compiles it with
--Rpass-analysis=kernel-resource-usage; nothing is written).  usage: python tools/kernel_regs.py conv.hip [filter] [-D...]"""
+-Rpass-analysis=kernel-resource-usage; nothing is written).  usage: python tools/kernel_regs.py conv.hip [filter] [-D...]
+(the Gram-route stem kernels: stem_pool.hip)"""
 import os
 import re
 import subprocess
