@@ -110,7 +110,10 @@ unsigned long long xm_workspace_generation(void);
 int xm_out_size(int in, int pad_a, int pad_b, int f, int dilate, int stride);
 
 /* ---- vl_nnconv  (MatConvNet matlab/vl_nnconv.m; dagnn.Conv at emoVoxZoo.m:118) -------------
- * Y = vl_nnconv(X, F, B, 'stride', [sy sx], 'pad', [t b l r], 'dilate', [dy dx]) */
+ * Y = vl_nnconv(X, F, B, 'stride', [sy sx], 'pad', [t b l r], 'dilate', [dy dx])
+ * Every pointer of the xm_nnconv_* entry points need only be 4-byte aligned (a float boundary): the alignment of an
+ * operand selects between kernels (16- / 8-byte accesses where every operand they touch allows them, 4-byte ones
+ * otherwise) and never changes what is computed. */
 int xm_nnconv_forward(const float *x, int H, int W, int C, int N, const float *f, int FH, int FW,
                       int FC, int K, const float *b, float *y, int sy, int sx, int pt, int pb,
                       int pl, int pr, int dy, int dx, void *stream);

@@ -49,6 +49,13 @@ int xm_prof_kernel_name(int key, char *buf, int len);
  *   "conv_splits"    split-K factor of the implicit-GEMM launches (0 = automatic)
  *   "conv_last_combine"  (read only) what the most recent implicit-GEMM launch left to conv_splitk_epilogue_kernel: 0 = nothing,
  *                    z > 0 = z partial slabs combined by its 16-byte form, z < 0 = |z| slabs by its scalar form
+ *   "wgrad_last_splits"  (read only) the final split count of the most recent filter-derivative launch (generic or patch kernel):
+ *                    the number of partial slabs reduce_splits_kernel added, 1 = none
+ *   "bias_grad_last_splits"  (read only) sample splits S of the most recent bias-derivative launch
+ *   "stats_last_splits"  (read only) tile splits S of the most recent reduction of the forward epilogue's batch statistics;
+ *                    0: the most recent forward with batch moments took them from a pass over Y instead
+ *   "dgrad_last_transpose"  (read only) 1: the most recent dgrad filter operand came from transpose_filter_kernel, 0: from
+ *                    prep_dgrad_filter_kernel (neither is profiled)
  *   "conv_halo"      1 + v: halo-patch kernel variant v (0: 128-row tiles, 1: 96-row tiles, 2: 96-row tiles / tall patch) wherever it
  *                    can run, another runnable variant otherwise; 0: never; -1: measured choice (default)
  *   "conv_stem"      1: the single-channel stem kernels (conv_stem_kernel, conv_stem_wgrad_*; also gates the Gram route's kernels)

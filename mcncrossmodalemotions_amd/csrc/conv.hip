@@ -159,13 +159,13 @@ static void launch_reduce_splits(const float *part, float *out, size_t total, in
 }
 
 // dzdb(k) = sum over pixels and samples of dzdy(:,:,k,:): grid (K, S) partial sums, then a
-// fixed-order finalize (deterministic)
+// fixed-order finalize (deterministic).  vec (the host's: HW % 4 == 0 and dy 16-byte aligned): 16-byte loads, divRun
+// divides by HW / 4; else 4-byte loads and divRun divides by HW.
 __global__ void __launch_bounds__(256)
 bias_grad_partial_kernel(const float *__restrict__ dy, double *__restrict__ part, int HW, int K, int N,
-                         int S, FastDiv divRun) {
+                         int S, int vec, FastDiv divRun) {
   int k = blockIdx.x, sp = blockIdx.y;
   double s = 0.0;
-  const bool vec = (HW & 3) == 0;
   // flat (sample, position) index: FC-shaped layers (H*W = 8) keep all lanes busy
   const int nper = (N - sp + S - 1) / S;
   const int run = vec ? HW >> 2 : HW;
@@ -270,6 +270,12 @@ static int g_force_splits = 0;  // test hook
 // what the most recent launch_gemm left to conv_splitk_epilogue_kernel: 0 = nothing (the GEMM's own epilogue stored y), z > 0 =
 // z partial slabs combined by the 16-byte form, z < 0 = |z| slabs by the scalar form (xm_debug_get("conv_last_combine"): tests)
 static int g_last_combine = 0;
+// read-only, for the tests of the reduction helpers (xm_debug_get): the final split count of the last wgrad_run /
+// launch_wgrad_patch / launch_wgrad_patch_s2 ("wgrad_last_splits"), S of the last bias-derivative launch
+// ("bias_grad_last_splits") and of the last forward_stats_reduce ("stats_last_splits": 0 when the most recent forward with
+// batch moments took them from a pass over Y instead); "dgrad_last_transpose": 1 when the
+// last dgrad filter operand was built by transpose_filter_kernel, 0 by prep_dgrad_filter_kernel
+static int g_last_wgrad_splits = 0, g_last_bias_splits = 0, g_last_stats_splits = 0, g_last_dgrad_transpose = 0;
 
 // With few output tiles the reduction is split over grid.y; the split count fills ONE round of
 // 2 co-resident blocks per CU (no tail round).
@@ -1235,6 +1241,7 @@ static ConvGemmArgs stats_args(const ConvGemmArgs &a, FwdStats &s, int ncg) {
 // [mean, sqrt(var + eps)] from the partial sums (fp64 across the partial rows, fixed order)
 static int forward_stats_reduce(const FwdStats &s, double *part2, float *moments_out, int K, int NP, float eps, hipStream_t st) {
   const int S = std::max(1, std::min(64, s.ncg / 768));   // one launch up to ~1500 partial rows per channel
+  g_last_stats_splits = S;
   hipLaunchKernelGGL(conv_stats_reduce_kernel, dim3((K + 7) / 8, S), dim3(256), 0, st, s.part, moments_out, part2, K, s.ncg, S,
                      (double)NP, eps);
   XM_LAUNCH_CHECK();
@@ -1334,6 +1341,7 @@ static int conv_forward(const float *x, const float *f, const float *b, float *y
   float *statp = statf ? ws.take<float>(statf) : nullptr;
   double *statp2 = stat2 ? ws.take<double>(stat2) : nullptr;
   bool stats_done = false;
+  if (moments_out) g_last_stats_splits = 0;   // stays 0 when the moments come from the pass over Y below
   for (int grp = 0; grp < g.G; ++grp) {
     ConvGemmArgs a = forward_args(g, grp, o);
     FwdStats s{want_stats && a.vecStore && !relu && !resid, statp, 0};
@@ -1448,7 +1456,8 @@ static bool dgrad_pure_transpose(const Geo &g, const DgradClass &c, bool foldH, 
          path_on(kPathFastTranspose);
 }
 static int launch_dgrad_filter(const float *f, float *Ag, const Geo &g, const DgradClass &c, int grp, bool foldH, hipStream_t st) {
-  if (dgrad_pure_transpose(g, c, foldH, f, Ag)) {
+  g_last_dgrad_transpose = dgrad_pure_transpose(g, c, foldH, f, Ag) ? 1 : 0;
+  if (g_last_dgrad_transpose) {
     const int Rrows = g.FC * (foldH ? g.FH : 1);
     hipLaunchKernelGGL(transpose_filter_kernel, dim3((Rrows + 63) / 64, (g.Kg + 63) / 64), dim3(256), 0, st, f, Ag,
                        g.Kg, Rrows, c.Rp);
@@ -1714,6 +1723,7 @@ static int wgrad_run(const float *x, const float *dzdy, float *dfo, const Geo &g
   splits = std::min(splits, 1024);
   int tps = (nkt + splits - 1) / splits;
   splits = (nkt + tps - 1) / tps;
+  g_last_wgrad_splits = splits;
   const int4 *taps = device_taps(wgrad_tap_table(g, Rn));
   if (!taps) return fail(XM_ENOMEM, "vl_nnconv: tap table allocation failed");
   const size_t slab = (size_t)g.Kg * g.R;
@@ -1849,6 +1859,7 @@ static int launch_wgrad_patch(const float *x, const float *dzdy, float *dfo, con
   a.nbm = (g.Kg + 127) / 128, a.nbn = (g.R + 127) / 128;
   const int tiles = a.nbm * a.nbn, splits = patch_splits(a.nStages, tiles, max_splits, &a.stagesPerSplit);
   const size_t slab = (size_t)g.Kg * g.R;
+  g_last_wgrad_splits = splits;
   a.splitStride = slab;
   a.out = splits > 1 ? part : dfo;
   {
@@ -1884,6 +1895,7 @@ static int launch_wgrad_patch_s2(const float *x, const float *dzdy, float *dfo, 
   a.nbm = (g.Kg + 127) / 128, a.nbn = (g.R + 127) / 128;
   const int tiles = a.nbm * a.nbn, splits = patch_splits(a.nStages, tiles, max_splits, &a.stagesPerSplit);
   a.splits = splits;
+  g_last_wgrad_splits = splits;
   const size_t slab = (size_t)g.Kg * g.R;
   a.splitStride = slab;
   a.out = splits > 1 ? part : dfo;
@@ -1981,6 +1993,10 @@ int xm_debug_set(const char *key, int value) {
 int xm_debug_get(const char *key) {
   if (key && strcmp(key, "num_conv_cfgs") == 0) return kNumCfg;
   if (key && strcmp(key, "conv_last_combine") == 0) return g_last_combine;
+  if (key && strcmp(key, "wgrad_last_splits") == 0) return g_last_wgrad_splits;
+  if (key && strcmp(key, "bias_grad_last_splits") == 0) return g_last_bias_splits;
+  if (key && strcmp(key, "stats_last_splits") == 0) return g_last_stats_splits;
+  if (key && strcmp(key, "dgrad_last_transpose") == 0) return g_last_dgrad_transpose;
   const DebugSwitch *s = debug_switch(key);
   return s ? *s->value : INT_MIN;
 }
@@ -2093,6 +2109,7 @@ int xm_nnconv_forward_moments(const float *x, int H, int W, int C, int N, const 
   if (!x || !f || !y || !moments_out) return fail(XM_EINVAL, "vl_nnconv(+moments): NULL tensor");
   hipStream_t st = (hipStream_t)stream;
   if (fc_skinny_ok(g)) {
+    g_last_stats_splits = 0;
     rc = fc_skinny_forward(x, f, b, y, g, 0, st);
     return rc ? rc : bn_batch_moments(y, g.Ho, g.Wo, g.K, g.N, epsilon, moments_out, st);
   }
@@ -2191,8 +2208,10 @@ int xm_nnconv_backward_accum(const float *x, int H, int W, int C, int N, const f
     if (rc) return rc;
     double *part = ws.take<double>((size_t)K * S);
     const int HWo = g.Ho * g.Wo;
-    hipLaunchKernelGGL(bias_grad_partial_kernel, dim3(K, S), dim3(256), 0, st, dzdy, part, HWo, K, N, S,
-                       make_fastdiv((uint32_t)((HWo & 3) == 0 ? HWo >> 2 : HWo)));
+    const bool vec = (HWo & 3) == 0 && ((uintptr_t)dzdy & 15) == 0;   // 16-byte loads of whole pixel quads
+    g_last_bias_splits = S;
+    hipLaunchKernelGGL(bias_grad_partial_kernel, dim3(K, S), dim3(256), 0, st, dzdy, part, HWo, K, N, S, vec ? 1 : 0,
+                       make_fastdiv((uint32_t)(vec ? HWo >> 2 : HWo)));
     XM_LAUNCH_CHECK();
     hipLaunchKernelGGL(bias_grad_finalize_kernel, dim3((K + 3) / 4), dim3(256), 0, st, part, db_out,
                        K, S);

@@ -31,11 +31,10 @@ __device__ __forceinline__ void block_reduce2(double &a, double &b, double *red 
 // threads busy and cost 30 us per call.
 __global__ void __launch_bounds__(256)
 bn_stats_partial_kernel(const float *__restrict__ x, double *__restrict__ part, int HW, int C, int N,
-                        int S, FastDiv divRun) {
+                        int S, int vec, FastDiv divRun) {
   const int c = blockIdx.x, s = blockIdx.y;
   const float shift = x[(size_t)HW * c];
   double a = 0.0, b = 0.0;
-  const bool vec = (HW & 3) == 0;
   const int nper = (N - s + S - 1) / S;  // samples s, s + S, ...
   if (vec) {
     const int run = HW >> 2;
@@ -295,6 +294,10 @@ bn_bwd_apply_ch_kernel(const float *__restrict__ x, const float *__restrict__ dy
 
 // run length of one sample inside the flat (sample, position) index of the reduction kernels
 static FastDiv bn_run_div(int HW) { return make_fastdiv((uint32_t)((HW & 3) == 0 ? HW >> 2 : HW)); }
+// bn_stats_partial_kernel takes 16-byte loads of whole pixel quads only from a 16-byte aligned tensor (the caller of
+// vl_nnconv with batch moments may hand in an output that is 4-byte aligned only)
+static bool bn_stats_vec(int HW, const float *x) { return (HW & 3) == 0 && ((uintptr_t)x & 15) == 0; }
+static FastDiv bn_stats_run_div(int HW, const float *x) { return make_fastdiv((uint32_t)(bn_stats_vec(HW, x) ? HW >> 2 : HW)); }
 static int bn_splits(int C, int N) {
   int s = 2048 / (C > 0 ? C : 1);
   if (s < 1) s = 1;
@@ -323,7 +326,8 @@ int bn_batch_moments(const float *x, int H, int W, int C, int N, float eps, floa
   rc = ws.init(WsCarver::need((size_t)2 * C * S, 8), st);
   if (rc) return rc;
   double *part = ws.take<double>((size_t)2 * C * S);
-  hipLaunchKernelGGL(bn_stats_partial_kernel, dim3(C, S), dim3(256), 0, st, x, part, HW, C, N, S, bn_run_div(HW));
+  hipLaunchKernelGGL(bn_stats_partial_kernel, dim3(C, S), dim3(256), 0, st, x, part, HW, C, N, S, bn_stats_vec(HW, x) ? 1 : 0,
+                     bn_stats_run_div(HW, x));
   XM_LAUNCH_CHECK();
   hipLaunchKernelGGL(bn_finalize_kernel, dim3((C + 3) / 4), dim3(256), 0, st, x, part, moments_out, HW, C, S,
                      (double)HW * N, eps);
@@ -346,7 +350,8 @@ static int bnorm_forward(const float *x, int H, int W, int C, int N, const float
     if (rc) return rc;
     double *part = ws.take<double>((size_t)2 * C * S);
     float *momw = moments_out ? moments_out : ws.take<float>((size_t)2 * C);
-    hipLaunchKernelGGL(bn_stats_partial_kernel, dim3(C, S), dim3(256), 0, st, x, part, HW, C, N, S, bn_run_div(HW));
+    hipLaunchKernelGGL(bn_stats_partial_kernel, dim3(C, S), dim3(256), 0, st, x, part, HW, C, N, S, bn_stats_vec(HW, x) ? 1 : 0,
+                         bn_stats_run_div(HW, x));
     XM_LAUNCH_CHECK();
     hipLaunchKernelGGL(bn_finalize_kernel, dim3((C + 3) / 4), dim3(256), 0, st, x, part, momw, HW,
                        C, S, (double)HW * N, eps);
@@ -393,7 +398,8 @@ static int bnorm_backward(const float *x, const float *yfwd, int H, int W, int C
   const float *mom = moments_in;
   if (!moments_in) {
     float *momw = moments_out ? moments_out : ws.take<float>((size_t)2 * C);
-    hipLaunchKernelGGL(bn_stats_partial_kernel, dim3(C, S), dim3(256), 0, st, x, part, HW, C, N, S, bn_run_div(HW));
+    hipLaunchKernelGGL(bn_stats_partial_kernel, dim3(C, S), dim3(256), 0, st, x, part, HW, C, N, S, bn_stats_vec(HW, x) ? 1 : 0,
+                         bn_stats_run_div(HW, x));
     XM_LAUNCH_CHECK();
     hipLaunchKernelGGL(bn_finalize_kernel, dim3((C + 3) / 4), dim3(256), 0, st, x, part, momw, HW,
                        C, S, (double)HW * N, eps);
@@ -1173,7 +1179,8 @@ static int bnrelupool_forward(const float *x, int H, int W, int C, int N, const 
     rc = ws.init(WsCarver::need((size_t)2 * C * S, 8), st);
     if (rc) return rc;
     double *part = ws.take<double>((size_t)2 * C * S);
-    hipLaunchKernelGGL(bn_stats_partial_kernel, dim3(C, S), dim3(256), 0, st, x, part, HW, C, N, S, bn_run_div(HW));
+    hipLaunchKernelGGL(bn_stats_partial_kernel, dim3(C, S), dim3(256), 0, st, x, part, HW, C, N, S, bn_stats_vec(HW, x) ? 1 : 0,
+                         bn_stats_run_div(HW, x));
     XM_LAUNCH_CHECK();
     hipLaunchKernelGGL(bn_finalize_kernel, dim3((C + 3) / 4), dim3(256), 0, st, x, part, moments_out,
                        HW, C, S, (double)HW * N, eps);

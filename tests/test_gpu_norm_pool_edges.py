@@ -40,23 +40,13 @@ import numpy as np
 import pytest
 
 import pool_routing as PR
+from aligned_views import misaligned
 from oracle import oracle as O
 from test_gpu_ops import TOL, close, rnd, test_bnorm as _bnorm_sequence
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 WORKER = os.path.join(ROOT, "tests", "_pool_edges_worker.py")
-
-
-def misaligned(t):
-    """copy of the MATLAB-layout device tensor `t` that starts one float past a 16-byte boundary: buf[1:] of a flat buffer,
-    reshaped and permuted to MATLAB layout (what a sample slice x[..., k:] of a tensor with an odd plane size looks like)"""
-    import torch
-    flat = torch.empty(t.numel() + 1, dtype=t.dtype, device=t.device)
-    v = flat[1:].view(*reversed(t.shape)).permute(*reversed(range(t.dim())))
-    v.copy_(t)
-    assert v.data_ptr() % 16 == 4
-    return v
 
 
 def table_of(am, shape):
