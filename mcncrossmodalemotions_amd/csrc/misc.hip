@@ -3,6 +3,7 @@
 // vl_nnsoftmaxceloss (emoVoxZoo.m:152), vl_nnloss (emoVoxZoo.m:149,160), the SGD-momentum step of
 // cnn_train_dag (run_distillation.m:170-182), its 'solver' option and the device side of getBatchEmoVoxCeleb /
 // getImageBatch.  All HBM- or latency-bound; float4 grid-stride loops, no atomics.
+#include "norm_pool_plan.h"
 #include "xm_common.h"
 
 namespace xm {
@@ -10,13 +11,6 @@ extern unsigned long long g_param_version;   // conv.hip: prepared dgrad operand
 }
 
 namespace xm {
-
-static unsigned ew_grid(size_t work_items) {
-  size_t b = (work_items + 255) / 256;
-  if (b > 256 * 8) b = 256 * 8;
-  if (b < 1) b = 1;
-  return (unsigned)b;
-}
 
 enum { OP_RELU_F, OP_RELU_B, OP_SIG_F, OP_SIG_B, OP_SUM, OP_SUM_RELU };
 
@@ -62,7 +56,7 @@ template <int OP, bool BINARY>
 static int ew_launch(const float *a, const float *b, float *y, size_t n, float leak, hipStream_t st) {
   if (n == 0) return XM_OK;
   if (!a || !y || (BINARY && !b)) return fail(XM_EINVAL, "elementwise op: NULL tensor");
-  int vec = ((((uintptr_t)a | (uintptr_t)b | (uintptr_t)y) & 15) == 0) ? 1 : 0;
+  int vec = aligned16(a, b, y) ? 1 : 0;
   hipLaunchKernelGGL((ew_kernel<OP, BINARY>), dim3(ew_grid(vec ? n / 4 + 1 : n)), dim3(256), 0, st, a,
                      b, y, n, leak, vec);
   XM_LAUNCH_CHECK();
@@ -539,7 +533,7 @@ solver_kernel(float *__restrict__ w, float *__restrict__ s1, float *__restrict__
 template <int KIND>
 static void solver_launch(float *w, float *s1, float *s2, const float *der, size_t n, const SolverArgs &a,
                           hipStream_t st) {
-  int vec = ((((uintptr_t)w | (uintptr_t)s1 | (uintptr_t)s2 | (uintptr_t)der) & 15) == 0) ? 1 : 0;
+  int vec = aligned16(w, s1, s2, der) ? 1 : 0;
   hipLaunchKernelGGL(solver_kernel<KIND>, dim3(ew_grid(vec ? n / 4 + 1 : n)), dim3(256), 0, st, w, s1, s2,
                      der, n, a, vec);
 }
@@ -818,7 +812,7 @@ int xm_se_tail_backward_apply(const float *y, const float *dzdy, const float *u,
   XM_LAUNCH_CHECK();
   const size_t total = (size_t)HW * C * N;
   const double m = (double)HW * N;
-  const bool vec = (HW & 3) == 0 && ((((uintptr_t)y | (uintptr_t)dzdy | (uintptr_t)u | (uintptr_t)dz_out | (uintptr_t)du_out) & 15) == 0);
+  const bool vec = (HW & 3) == 0 && aligned16(y, dzdy, u, dz_out, du_out);
   const size_t items = vec ? total / 4 : total;
   const unsigned grid = (unsigned)std::min<size_t>((items + 255) / 256, (size_t)256 * 64);
   if (vec)
@@ -912,7 +906,7 @@ int xm_sgd_update(float *w, float *m, const float *der, size_t n, float lr, floa
   if (n == 0) return XM_OK;
   if (!w || !m || !der) return fail(XM_EINVAL, "sgd: NULL tensor");
   if (!(batch > 0.f)) return fail(XM_EINVAL, "sgd: batch must be > 0");
-  int vec = ((((uintptr_t)w | (uintptr_t)m | (uintptr_t)der) & 15) == 0) ? 1 : 0;
+  int vec = aligned16(w, m, der) ? 1 : 0;
   hipLaunchKernelGGL(sgd_kernel, dim3(ew_grid(vec ? n / 4 + 1 : n)), dim3(256), 0, (hipStream_t)stream,
                      w, m, der, n, lr, momentum, weight_decay, 1.0f / batch, vec);
   XM_LAUNCH_CHECK();

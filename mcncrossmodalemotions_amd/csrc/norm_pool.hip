@@ -2,8 +2,7 @@
 // fastest axis), float4 where the plane size allows, wave-shuffle + LDS tree reductions, fixed
 // reduction order (no atomics) so results are run-to-run identical.
 // Replaces MatConvNet's vl_nnbnorm / vl_nnpool MEX (bits/nnbnorm.cu, bits/nnpooling.cu).
-#include <algorithm>
-
+#include "norm_pool_plan.h"
 #include "xm_common.h"
 
 namespace xm {
@@ -292,47 +291,41 @@ bn_bwd_apply_ch_kernel(const float *__restrict__ x, const float *__restrict__ dy
   if (threadIdx.x == 0) part2[(size_t)c * S2 + s] = (red[0] + red[1]) + (red[2] + red[3]);
 }
 
-// run length of one sample inside the flat (sample, position) index of the reduction kernels
-static FastDiv bn_run_div(int HW) { return make_fastdiv((uint32_t)((HW & 3) == 0 ? HW >> 2 : HW)); }
-// bn_stats_partial_kernel takes 16-byte loads of whole pixel quads only from a 16-byte aligned tensor (the caller of
-// vl_nnconv with batch moments may hand in an output that is 4-byte aligned only)
-static bool bn_stats_vec(int HW, const float *x) { return (HW & 3) == 0 && ((uintptr_t)x & 15) == 0; }
-static FastDiv bn_stats_run_div(int HW, const float *x) { return make_fastdiv((uint32_t)(bn_stats_vec(HW, x) ? HW >> 2 : HW)); }
-static int bn_splits(int C, int N) {
-  int s = 2048 / (C > 0 ? C : 1);
-  if (s < 1) s = 1;
-  if (s > N) s = N;
-  return s;
-}
-
-static unsigned ew_grid(size_t work_items) {
-  size_t b = (work_items + 255) / 256;
-  if (b > 256 * 8) b = 256 * 8;
-  if (b < 1) b = 1;
-  return (unsigned)b;
-}
-
 static int bn_check(int H, int W, int C, int N) {
   if (H <= 0 || W <= 0 || C <= 0 || N <= 0) return fail(XM_EINVAL, "vl_nnbnorm: empty tensor");
   if (too_big(H, W, C, N)) return fail(XM_ETOOBIG, "vl_nnbnorm: tensor with >= 2^31 elements");
   return XM_OK;
 }
 
+template <class T>
+static T *take(WsCarver &ws, WsSeg<T> seg) { return seg.count ? ws.take<T>(seg.count) : nullptr; }
+
+// The moments of this call: the batch's, reduced into `dst` through `part` (moments_in == NULL), or the caller's, copied
+// to `dst` when that is another buffer
+static int bn_moments(const float *x, int HW, int C, int N, float eps, const float *moments_in, float *dst, double *part,
+                      hipStream_t st) {
+  if (!moments_in) {
+    const int S = bn_splits(C, N);
+    const bool vec = bn_vec(HW, x);
+    hipLaunchKernelGGL(bn_stats_partial_kernel, dim3(C, S), dim3(256), 0, st, x, part, HW, C, N, S, vec ? 1 : 0,
+                       make_fastdiv((uint32_t)bn_run(HW, vec)));
+    XM_LAUNCH_CHECK();
+    hipLaunchKernelGGL(bn_finalize_kernel, dim3((C + 3) / 4), dim3(256), 0, st, x, part, dst, HW, C, S, (double)HW * N, eps);
+    XM_LAUNCH_CHECK();
+  } else if (dst && dst != moments_in) {
+    XM_HIP(hipMemcpyAsync(dst, moments_in, sizeof(float) * 2 * C, hipMemcpyDeviceToDevice, st));
+  }
+  return XM_OK;
+}
+
 int bn_batch_moments(const float *x, int H, int W, int C, int N, float eps, float *moments_out, hipStream_t st) {
   int rc = bn_check(H, W, C, N);
   if (rc) return rc;
-  const int HW = H * W, S = bn_splits(C, N);
+  const BnWs w = bn_ws(C, bn_splits(C, N), false, 0, false);
   WsCarver ws;
-  rc = ws.init(WsCarver::need((size_t)2 * C * S, 8), st);
+  rc = ws.init(w.bytes(), st);
   if (rc) return rc;
-  double *part = ws.take<double>((size_t)2 * C * S);
-  hipLaunchKernelGGL(bn_stats_partial_kernel, dim3(C, S), dim3(256), 0, st, x, part, HW, C, N, S, bn_stats_vec(HW, x) ? 1 : 0,
-                     bn_stats_run_div(HW, x));
-  XM_LAUNCH_CHECK();
-  hipLaunchKernelGGL(bn_finalize_kernel, dim3((C + 3) / 4), dim3(256), 0, st, x, part, moments_out, HW, C, S,
-                     (double)HW * N, eps);
-  XM_LAUNCH_CHECK();
-  return XM_OK;
+  return bn_moments(x, H * W, C, N, eps, nullptr, moments_out, take(ws, w.part), st);
 }
 
 static int bnorm_forward(const float *x, int H, int W, int C, int N, const float *g, const float *b,
@@ -342,32 +335,18 @@ static int bnorm_forward(const float *x, int H, int W, int C, int N, const float
   if (rc) return rc;
   if (!x || !g || !b || !y) return fail(XM_EINVAL, "vl_nnbnorm: NULL tensor");
   const int HW = H * W;
-  const int S = bn_splits(C, N);
-  const float *mom = moments_in;
+  const BnWs w = bn_ws(C, moments_in ? 0 : bn_splits(C, N), false, 0, !moments_in && !moments_out);
   WsCarver ws;
-  if (!moments_in) {
-    rc = ws.init(WsCarver::need((size_t)2 * C * S, 8) + WsCarver::need((size_t)2 * C, 4), st);
-    if (rc) return rc;
-    double *part = ws.take<double>((size_t)2 * C * S);
-    float *momw = moments_out ? moments_out : ws.take<float>((size_t)2 * C);
-    hipLaunchKernelGGL(bn_stats_partial_kernel, dim3(C, S), dim3(256), 0, st, x, part, HW, C, N, S, bn_stats_vec(HW, x) ? 1 : 0,
-                         bn_stats_run_div(HW, x));
-    XM_LAUNCH_CHECK();
-    hipLaunchKernelGGL(bn_finalize_kernel, dim3((C + 3) / 4), dim3(256), 0, st, x, part, momw, HW,
-                       C, S, (double)HW * N, eps);
-    XM_LAUNCH_CHECK();
-    mom = momw;
-  } else if (moments_out && moments_out != moments_in) {
-    XM_HIP(hipMemcpyAsync(moments_out, moments_in, sizeof(float) * 2 * C, hipMemcpyDeviceToDevice, st));
-  }
-  size_t total = (size_t)HW * C * N;
-  FastDiv d = make_fastdiv((uint32_t)HW);
-  if ((HW & 3) == 0 && (((uintptr_t)x | (uintptr_t)y) & 15) == 0)
-    hipLaunchKernelGGL(bn_apply_kernel<true>, dim3(ew_grid(total / 4)), dim3(256), 0, st, x, y, g, b,
-                       mom, d, C, total, relu);
-  else
-    hipLaunchKernelGGL(bn_apply_kernel<false>, dim3(ew_grid(total)), dim3(256), 0, st, x, y, g, b,
-                       mom, d, C, total, relu);
+  if (w.bytes() && (rc = ws.init(w.bytes(), st))) return rc;   // given moments: no scratch
+  double *part = take(ws, w.part);
+  float *momw = moments_out ? moments_out : take(ws, w.mom);
+  rc = bn_moments(x, HW, C, N, eps, moments_in, momw, part, st);
+  if (rc) return rc;
+  const float *mom = moments_in ? moments_in : momw;
+  const size_t total = (size_t)HW * C * N;
+  const bool vec = bn_vec(HW, x, y);
+  hipLaunchKernelGGL(vec ? bn_apply_kernel<true> : bn_apply_kernel<false>, dim3(ew_grid(vec ? total / 4 : total)), dim3(256),
+                     0, st, x, y, g, b, mom, make_fastdiv((uint32_t)HW), C, total, relu);
   XM_LAUNCH_CHECK();
   return XM_OK;
 }
@@ -384,102 +363,44 @@ static int bnorm_backward(const float *x, const float *yfwd, int H, int W, int C
   if (!x || !g || !dzdy) return fail(XM_EINVAL, "vl_nnbnorm: NULL tensor");
   if (batch_moments && !moments_in) return fail(XM_EINVAL, "vl_nnbnorm: XM_BN_BATCH_MOMENTS needs moments");
   if (dxsum_out && !dx_out) return fail(XM_EINVAL, "vl_nnbnorm: dxsum needs dx");
-  const int HW = H * W;
-  const int S = bn_splits(C, N);
-  // apply blocks per channel of the dxsum path: enough blocks to fill the chip, at most one per sample
-  const int S2 = std::max(1, std::min(N, 4096 / std::max(1, C)));
+  const int HW = H * W, S = bn_splits(C, N), S2 = bn_dxsum_splits(C, N);
+  const BnWs w = bn_ws(C, S, true, dxsum_out ? S2 : 0, !moments_in && !moments_out);
   WsCarver ws;
-  rc = ws.init(WsCarver::need((size_t)2 * C * S, 8) + WsCarver::need((size_t)2 * C, 8) +
-                   WsCarver::need((size_t)2 * C, 4) + WsCarver::need(dxsum_out ? (size_t)C * S2 : 0, 8), st);
+  rc = ws.init(w.bytes(), st);
   if (rc) return rc;
-  double *part = ws.take<double>((size_t)2 * C * S);
-  double *sums = ws.take<double>((size_t)2 * C);
-  double *part2 = dxsum_out ? ws.take<double>((size_t)C * S2) : nullptr;
-  const float *mom = moments_in;
-  if (!moments_in) {
-    float *momw = moments_out ? moments_out : ws.take<float>((size_t)2 * C);
-    hipLaunchKernelGGL(bn_stats_partial_kernel, dim3(C, S), dim3(256), 0, st, x, part, HW, C, N, S, bn_stats_vec(HW, x) ? 1 : 0,
-                         bn_stats_run_div(HW, x));
-    XM_LAUNCH_CHECK();
-    hipLaunchKernelGGL(bn_finalize_kernel, dim3((C + 3) / 4), dim3(256), 0, st, x, part, momw, HW,
-                       C, S, (double)HW * N, eps);
-    XM_LAUNCH_CHECK();
-    mom = momw;
-  } else if (moments_out && moments_out != moments_in) {
-    XM_HIP(hipMemcpyAsync(moments_out, moments_in, sizeof(float) * 2 * C, hipMemcpyDeviceToDevice, st));
-  }
-  hipLaunchKernelGGL(bn_bwd_partial_kernel, dim3(C, S), dim3(256), 0, st, x, dzdy, yfwd, mom, part, HW,
-                     C, N, S, bn_run_div(HW));
+  double *part = take(ws, w.part), *sums = take(ws, w.sums), *part2 = take(ws, w.part2);
+  float *momw = moments_out ? moments_out : take(ws, w.mom);
+  rc = bn_moments(x, HW, C, N, eps, moments_in, momw, part, st);
+  if (rc) return rc;
+  const float *mom = moments_in ? moments_in : momw;
+  hipLaunchKernelGGL(bn_bwd_partial_kernel, dim3(C, S), dim3(256), 0, st, x, dzdy, yfwd, mom, part, HW, C, N, S,
+                     make_fastdiv((uint32_t)bn_run(HW, (HW & 3) == 0)));   // quads from any alignment
   XM_LAUNCH_CHECK();
+  const double m = (double)HW * N;
+  const int train = (moments_in && !batch_moments) ? 0 : 1;
+  const bool vec = bn_vec(HW, x, dzdy, dx_out, yfwd);
   if (dxsum_out) {
     // partial sums -> [finalize + apply + sum(dx) partials] -> dzdb of the producing convolution: three launches
-    const double m = (double)HW * N;
-    const int train = (moments_in && !batch_moments) ? 0 : 1;
-    const bool al = ((((uintptr_t)x | (uintptr_t)dzdy | (uintptr_t)dx_out | (uintptr_t)yfwd) & 15) == 0);
-    if ((HW & 3) == 0 && al)
-      hipLaunchKernelGGL(bn_bwd_apply_ch_kernel<true>, dim3(C, S2), dim3(256), 0, st, x, dzdy, yfwd, dx_out, g, mom,
-                         part, S, dg_out, db_out, part2, HW, C, N, S2, bn_run_div(HW), m, train);
-    else
-      hipLaunchKernelGGL(bn_bwd_apply_ch_kernel<false>, dim3(C, S2), dim3(256), 0, st, x, dzdy, yfwd, dx_out, g, mom,
-                         part, S, dg_out, db_out, part2, HW, C, N, S2, make_fastdiv((uint32_t)HW), m, train);
+    hipLaunchKernelGGL(vec ? bn_bwd_apply_ch_kernel<true> : bn_bwd_apply_ch_kernel<false>, dim3(C, S2), dim3(256), 0, st, x,
+                       dzdy, yfwd, dx_out, g, mom, part, S, dg_out, db_out, part2, HW, C, N, S2,
+                       make_fastdiv((uint32_t)bn_run(HW, vec)), m, train);
     XM_LAUNCH_CHECK();
     hipLaunchKernelGGL(sum_partials_kernel, dim3((C + 3) / 4), dim3(256), 0, st, part2, dxsum_out, C, S2);
     XM_LAUNCH_CHECK();
     return XM_OK;
   }
-  hipLaunchKernelGGL(bn_bwd_finalize_kernel, dim3((C + 3) / 4), dim3(256), 0, st, part, mom, sums,
-                     dg_out, db_out, C, S);
+  hipLaunchKernelGGL(bn_bwd_finalize_kernel, dim3((C + 3) / 4), dim3(256), 0, st, part, mom, sums, dg_out, db_out, C, S);
   XM_LAUNCH_CHECK();
   if (dx_out) {
-    size_t total = (size_t)HW * C * N;
-    FastDiv d = make_fastdiv((uint32_t)HW);
-    double m = (double)HW * N;
-    int train = (moments_in && !batch_moments) ? 0 : 1;
-    bool al = ((((uintptr_t)x | (uintptr_t)dzdy | (uintptr_t)dx_out | (uintptr_t)yfwd) & 15) == 0);
-    if ((HW & 3) == 0 && al)
-      hipLaunchKernelGGL(bn_bwd_apply_kernel<true>, dim3(ew_grid(total / 4)), dim3(256), 0, st, x,
-                         dzdy, yfwd, dx_out, g, mom, sums, d, C, total, m, train);
-    else
-      hipLaunchKernelGGL(bn_bwd_apply_kernel<false>, dim3(ew_grid(total)), dim3(256), 0, st, x, dzdy,
-                         yfwd, dx_out, g, mom, sums, d, C, total, m, train);
+    const size_t total = (size_t)HW * C * N;
+    hipLaunchKernelGGL(vec ? bn_bwd_apply_kernel<true> : bn_bwd_apply_kernel<false>, dim3(ew_grid(vec ? total / 4 : total)),
+                       dim3(256), 0, st, x, dzdy, yfwd, dx_out, g, mom, sums, make_fastdiv((uint32_t)HW), C, total, m, train);
     XM_LAUNCH_CHECK();
   }
   return XM_OK;
 }
 
 // ===================================== pooling ===============================================
-struct PoolGeo {
-  int H, W, Ho, Wo, ph, pw, sy, sx, pt, pl;
-};
-
-// 2-D indexing shared by the pooling kernels: threadIdx.x runs along the contiguous H axis,
-// (blockIdx.x * blockDim.y + threadIdx.y) along W, blockIdx.y (+ grid-stride) over C*N planes --
-// no per-element integer division.
-struct PoolLaunch {
-  dim3 grid, block;
-};
-static int pow2_ge(int v, int cap) {
-  int p = 1;
-  while (p < v && p < cap) p <<= 1;
-  return p;
-}
-static PoolLaunch pool_launch(int rows, int cols, long long planes) {
-  // 256 threads = bx (rows, contiguous) x by (cols) x bz (planes): small planes pack several
-  // planes into one block instead of idling lanes
-  int bx = pow2_ge(rows, 256);
-  int by = pow2_ge(cols, 256 / bx);
-  int bz = 256 / (bx * by);
-  PoolLaunch l;
-  l.block = dim3(bx, by, bz);
-  // ~8k blocks in total: each block then strides over several planes (amortises block start-up)
-  int gx = (cols + by - 1) / by, gz = (rows + bx - 1) / bx;
-  long long pg = (planes + bz - 1) / bz;
-  long long gy = std::max<long long>(1, 8192 / ((long long)gx * gz));
-  gy = std::min<long long>(std::min<long long>(gy, pg), 65535);
-  l.grid = dim3(gx, (unsigned)gy, gz);
-  return l;
-}
-
 // one thread per output element; window scan is column-major.
 // `amax` (optional, max pooling): position of the FIRST maximum inside the un-clipped window,
 // code = dh + ph * dw -- the routing table of the backward pass.
@@ -780,52 +701,33 @@ static int pool_geo(PoolGeo &g, int H, int W, int C, int N, int ph, int pw, int 
   return XM_OK;
 }
 
-static int pool_forward(const float *x, int H, int W, int C, int N, int ph, int pw, int sy, int sx,
-                        int pt, int pb, int pl, int pr, int method, float *y, unsigned char *amax,
+// g: the checked geometry (pool_geo)
+static int pool_forward(const float *x, const PoolGeo &g, int C, int N, int method, float *y, unsigned char *amax,
                         hipStream_t st, const float *bn_g = nullptr, const float *bn_b = nullptr,
                         const float *bn_mom = nullptr) {
-  PoolGeo g;
-  int rc = pool_geo(g, H, W, C, N, ph, pw, sy, sx, pt, pb, pl, pr, method);
-  if (rc) return rc;
   if (!x || (!y && !amax)) return fail(XM_EINVAL, "vl_nnpool: NULL tensor");
-  if (amax && ph * pw > 255) return fail(XM_ENOTSUP, "vl_nnpool: windows above 255 elements are not built");
-  if (!amax && !bn_g && g.Ho == 1 && g.Wo == 1 && ph >= H && pw >= W && !(pt | pl)) {
-    int planes = C * N;
-    hipLaunchKernelGGL(pool_global_kernel, dim3((planes + 3) / 4), dim3(256), 0, st, x, y, H * W,
-                       planes, method);
+  if (amax && g.ph * g.pw > 255) return fail(XM_ENOTSUP, "vl_nnpool: windows above 255 elements are not built");
+  const int planes = C * N;
+  if (pool_is_global(g, amax, bn_g)) {
+    hipLaunchKernelGGL(pool_global_kernel, dim3((planes + 3) / 4), dim3(256), 0, st, x, y, g.H * g.W, planes, method);
     XM_LAUNCH_CHECK();
     return XM_OK;
   }
-  // LDS-staged kernel: max pooling, 3x3 window, planes large enough to fill a block, 16-byte aligned tensor
-  if (method == XM_POOL_MAX && ph == 3 && pw == 3 && ((uintptr_t)x & 15) == 0 && g.Ho * g.Wo >= 256 && path_on(kPathPoolLds)) {
-    const int maxcols = 16 * 256 / H;  // 16 KB of LDS per block: 10 blocks per CU, measured best of 8 / 16 / 32 / 64
-    int wob = maxcols >= pw ? (maxcols - pw) / sx + 1 : 0;
-    wob = std::min(wob, g.Wo);
-    if (wob >= 4 || (wob >= 1 && wob == g.Wo)) {
-      // even out the column groups (the last block would otherwise hold a sliver)
-      const int groups = (g.Wo + wob - 1) / wob;
-      wob = (g.Wo + groups - 1) / groups;
-      const int ncols = (wob - 1) * sx + pw;
-      const size_t lds = ((size_t)ncols * H + 8) * sizeof(float);
-      hipLaunchKernelGGL((pool_fwd_lds_kernel<3, 3>), dim3(C * N, groups), dim3(256), lds, st, x, y, amax, g,
-                         make_fastdiv((uint32_t)g.Ho), wob, (size_t)H * W * C * N, bn_g, bn_b, bn_mom, C);
-      XM_LAUNCH_CHECK();
-      return XM_OK;
-    }
+  const PoolLds lds = pool_lds_plan(g, method == XM_POOL_MAX, (uintptr_t)x);
+  if (lds.run && path_on(kPathPoolLds)) {
+    hipLaunchKernelGGL((pool_fwd_lds_kernel<3, 3>), dim3(planes, lds.groups), dim3(256), lds.lds_bytes, st, x, y, amax, g,
+                       make_fastdiv((uint32_t)g.Ho), lds.wob, (size_t)g.H * g.W * planes, bn_g, bn_b, bn_mom, C);
+    XM_LAUNCH_CHECK();
+    return XM_OK;
   }
-  PoolLaunch pl_ = pool_launch(g.Ho, g.Wo, (long long)C * N);
-  if (ph == 3 && pw == 3)
-    hipLaunchKernelGGL((pool_fwd_kernel<3, 3>), pl_.grid, pl_.block, 0, st, x, y, amax, g, C * N, method, bn_g, bn_b,
-                       bn_mom, C);
-  else if (ph == 5 && pw == 3)
-    hipLaunchKernelGGL((pool_fwd_kernel<5, 3>), pl_.grid, pl_.block, 0, st, x, y, amax, g, C * N, method, bn_g, bn_b,
-                       bn_mom, C);
-  else if (ph == 2 && pw == 2)
-    hipLaunchKernelGGL((pool_fwd_kernel<2, 2>), pl_.grid, pl_.block, 0, st, x, y, amax, g, C * N, method, bn_g, bn_b,
-                       bn_mom, C);
-  else
-    hipLaunchKernelGGL((pool_fwd_kernel<0, 0>), pl_.grid, pl_.block, 0, st, x, y, amax, g, C * N, method, bn_g, bn_b,
-                       bn_mom, C);
+  const PoolLaunch l = pool_launch(g.Ho, g.Wo, planes);
+  decltype(&pool_fwd_kernel<0, 0>) kernel;
+  if (g.ph == 3 && g.pw == 3) kernel = pool_fwd_kernel<3, 3>;
+  else if (g.ph == 5 && g.pw == 3) kernel = pool_fwd_kernel<5, 3>;
+  else if (g.ph == 2 && g.pw == 2) kernel = pool_fwd_kernel<2, 2>;
+  else kernel = pool_fwd_kernel<0, 0>;
+  hipLaunchKernelGGL(kernel, dim3(l.gx, l.gy, l.gz), dim3(l.bx, l.by, l.bz), 0, st, x, y, amax, g, planes, method, bn_g, bn_b,
+                     bn_mom, C);
   XM_LAUNCH_CHECK();
   return XM_OK;
 }
@@ -1133,139 +1035,93 @@ sum_partials_kernel(const double *__restrict__ part, float *__restrict__ out, in
   if (lane == 0) out[c] = (float)s;
 }
 
-static int pool_backward(const float *x, const unsigned char *amax, int H, int W, int C, int N, int ph,
-                         int pw, int sy, int sx, int pt, int pb, int pl, int pr, int method,
+static int pool_backward(const float *x, const unsigned char *amax, const PoolGeo &g, int C, int N, int method,
                          const float *dzdy, float *dx_out, hipStream_t st) {
-  PoolGeo g;
-  int rc = pool_geo(g, H, W, C, N, ph, pw, sy, sx, pt, pb, pl, pr, method);
-  if (rc) return rc;
   if (!dzdy || !dx_out) return fail(XM_EINVAL, "vl_nnpool: NULL tensor");
   if (method == XM_POOL_MAX && !amax) {
     // plain MatConvNet signature: recompute the routing table from X into scratch first
     if (!x) return fail(XM_EINVAL, "vl_nnpool: X is NULL");
-    size_t ny = (size_t)g.Ho * g.Wo * C * N;
+    const WsSeg<unsigned char> table{(size_t)g.Ho * g.Wo * C * N};
     WsCarver ws;
-    rc = ws.init(WsCarver::need(ny, 1), st);
+    int rc = ws.init(ws_bytes(table), st);
     if (rc) return rc;
-    unsigned char *aw = ws.take<unsigned char>(ny);
-    rc = pool_forward(x, H, W, C, N, ph, pw, sy, sx, pt, pb, pl, pr, method, nullptr, aw, st);
+    unsigned char *aw = take(ws, table);
+    rc = pool_forward(x, g, C, N, method, nullptr, aw, st);
     if (rc) return rc;
     amax = aw;
   }
-  PoolLaunch pl_ = pool_launch(H, W, (long long)C * N);
-  const bool fast = (ph + sy - 1) / sy <= 2 && (pw + sx - 1) / sx <= 2;
-  if (fast)
-    hipLaunchKernelGGL(pool_bwd_kernel<true>, pl_.grid, pl_.block, 0, st, amax, dzdy, dx_out, g,
-                       make_fastdiv((uint32_t)sy), make_fastdiv((uint32_t)sx), C * N, method);
-  else
-    hipLaunchKernelGGL(pool_bwd_kernel<false>, pl_.grid, pl_.block, 0, st, amax, dzdy, dx_out, g,
-                       make_fastdiv((uint32_t)sy), make_fastdiv((uint32_t)sx), C * N, method);
+  const PoolLaunch l = pool_launch(g.H, g.W, (long long)C * N);
+  hipLaunchKernelGGL(pool_cover_2x2(g) ? pool_bwd_kernel<true> : pool_bwd_kernel<false>, dim3(l.gx, l.gy, l.gz),
+                     dim3(l.bx, l.by, l.bz), 0, st, amax, dzdy, dx_out, g, make_fastdiv((uint32_t)g.sy),
+                     make_fastdiv((uint32_t)g.sx), C * N, method);
   XM_LAUNCH_CHECK();
   return XM_OK;
 }
 
-static int bnrelupool_forward(const float *x, int H, int W, int C, int N, const float *g,
-                              const float *b, float eps, const float *moments_in, int ph, int pw,
-                              int sy, int sx, int pt, int pb, int pl, int pr, float *y_pool,
-                              unsigned char *amax, float *moments_out, hipStream_t st) {
+static int bnrelupool_forward(const float *x, int H, int W, int C, int N, const float *g, const float *b, float eps,
+                              const float *moments_in, int ph, int pw, int sy, int sx, int pt, int pb, int pl, int pr,
+                              float *y_pool, unsigned char *amax, float *moments_out, hipStream_t st) {
   int rc = bn_check(H, W, C, N);
   if (rc) return rc;
-  if (!x || !g || !b || !y_pool || !amax || !moments_out)
-    return fail(XM_EINVAL, "bnorm+relu+pool: NULL tensor");
-  const int HW = H * W;
-  if (!moments_in) {
-    const int S = bn_splits(C, N);
-    WsCarver ws;
-    rc = ws.init(WsCarver::need((size_t)2 * C * S, 8), st);
-    if (rc) return rc;
-    double *part = ws.take<double>((size_t)2 * C * S);
-    hipLaunchKernelGGL(bn_stats_partial_kernel, dim3(C, S), dim3(256), 0, st, x, part, HW, C, N, S, bn_stats_vec(HW, x) ? 1 : 0,
-                         bn_stats_run_div(HW, x));
-    XM_LAUNCH_CHECK();
-    hipLaunchKernelGGL(bn_finalize_kernel, dim3((C + 3) / 4), dim3(256), 0, st, x, part, moments_out,
-                       HW, C, S, (double)HW * N, eps);
-    XM_LAUNCH_CHECK();
-  } else if (moments_out != moments_in) {
-    XM_HIP(hipMemcpyAsync(moments_out, moments_in, sizeof(float) * 2 * C, hipMemcpyDeviceToDevice, st));
-  }
-  return pool_forward(x, H, W, C, N, ph, pw, sy, sx, pt, pb, pl, pr, XM_POOL_MAX, y_pool, amax, st, g, b,
-                      moments_out);
+  if (!x || !g || !b || !y_pool || !amax || !moments_out) return fail(XM_EINVAL, "bnorm+relu+pool: NULL tensor");
+  PoolGeo pg;
+  rc = pool_geo(pg, H, W, C, N, ph, pw, sy, sx, pt, pb, pl, pr, XM_POOL_MAX);
+  if (rc) return rc;
+  const BnWs w = bn_ws(C, moments_in ? 0 : bn_splits(C, N), false, 0, false);
+  WsCarver ws;
+  if (w.bytes() && (rc = ws.init(w.bytes(), st))) return rc;   // given moments: no scratch
+  rc = bn_moments(x, H * W, C, N, eps, moments_in, moments_out, take(ws, w.part), st);
+  if (rc) return rc;
+  return pool_forward(x, pg, C, N, XM_POOL_MAX, y_pool, amax, st, g, b, moments_out);
 }
 
-static int bnrelupool_backward(const float *x, int H, int W, int C, int N, const float *g,
-                               const float *b, const float *moments, int train, int ph, int pw, int sy,
-                               int sx, int pt, int pb, int pl, int pr, const unsigned char *amax,
-                               const float *y_pool, const float *dzdy_pool, float *dx_out, float *dg_out,
-                               float *db_out, float *dxsum_out, hipStream_t st) {
+static int bnrelupool_backward(const float *x, int H, int W, int C, int N, const float *g, const float *b,
+                               const float *moments, int train, int ph, int pw, int sy, int sx, int pt, int pb, int pl,
+                               int pr, const unsigned char *amax, const float *y_pool, const float *dzdy_pool,
+                               float *dx_out, float *dg_out, float *db_out, float *dxsum_out, hipStream_t st) {
   PoolGeo pg;
   int rc = pool_geo(pg, H, W, C, N, ph, pw, sy, sx, pt, pb, pl, pr, XM_POOL_MAX);
   if (rc) return rc;
-  if (!x || !g || !b || !moments || !amax || !dzdy_pool)
-    return fail(XM_EINVAL, "bnorm+relu+pool: NULL tensor");
-  if ((ph + sy - 1) / sy > 2 || (pw + sx - 1) / sx > 2)
+  if (!x || !g || !b || !moments || !amax || !dzdy_pool) return fail(XM_EINVAL, "bnorm+relu+pool: NULL tensor");
+  if (!pool_cover_2x2(pg))
     return fail(XM_ENOTSUP, "bnorm+relu+pool backward: more than 2x2 windows cover an element");
   if (dxsum_out && !dx_out) return fail(XM_EINVAL, "bnorm+relu+pool backward: dxsum needs dx");
-  const bool no_patch = !path_on(kPathPoolPatch);
-  const bool no_pooled = !path_on(kPathPoolPooled);
-  // element kernels: (bx, by) threads own (h, w); grid.y = channel; the N samples are split S ways
-  int bx = pow2_ge(H, 256), by = 256 / bx;
-  by = pow2_ge(W, by);
-  int gx = (W + by - 1) / by, gz = (H + bx - 1) / bx;
-  int S = std::max(1, std::min(N, 4096 / std::max(1, C * gx * gz)));
-  const size_t nb = (size_t)gx * gz * S;
-  // patch kernel (apply): threads own stride cells
-  const bool patch = !no_patch && dx_out && ((sy == 2 && sx == 2) || (sy == 3 && sx == 2));
-  const int KH = (H + pt + sy - 1) / sy, KW = (W + pl + sx - 1) / sx;
-  int pbx = pow2_ge(KH, 256), pby = pow2_ge(KW, 256 / pbx);
-  int pgx = (KW + pby - 1) / pby, pgz = (KH + pbx - 1) / pbx;
-  int pS = std::max(1, std::min(N, 16384 / std::max(1, C * pgx * pgz)));   // >= 16 k blocks (4 k and 64 k measured worse)
-  const size_t pnb = (size_t)pgx * pgz * pS;
-  // pooled-domain sums
-  const bool pooled = !no_pooled && y_pool != nullptr;
-  const int S2 = bn_splits(C, N);
-  const size_t npart = pooled ? (size_t)S2 : nb;
-  const size_t npart2 = patch ? pnb : nb;
+  const BnPoolBwd p = bnpool_bwd_plan(pg, C, N, (uintptr_t)x, (uintptr_t)dx_out, y_pool);
+  const bool patch = p.patch_can && path_on(kPathPoolPatch), pooled = p.pooled_can && path_on(kPathPoolPooled);
+  const size_t npart = p.npart(pooled), npart2 = p.npart2(patch);
+  const BnWs w = bn_ws(C, npart, true, dxsum_out ? npart2 : 0, false);
   WsCarver ws;
-  rc = ws.init(WsCarver::need((size_t)2 * C * npart, 8) + WsCarver::need((size_t)2 * C, 8) +
-                   WsCarver::need((size_t)C * npart2, 8), st);
+  rc = ws.init(w.bytes(), st);
   if (rc) return rc;
-  double *part = ws.take<double>((size_t)2 * C * npart);
-  double *sums = ws.take<double>((size_t)2 * C);
-  double *part2 = dxsum_out ? ws.take<double>((size_t)C * npart2) : nullptr;
-  dim3 grid(gx, C, gz * S), block(bx, by);
+  double *part = take(ws, w.part), *sums = take(ws, w.sums), *part2 = take(ws, w.part2);
+  dim3 grid(p.gx, C, p.gz * p.S), block(p.bx, p.by);
   FastDiv dsy = make_fastdiv((uint32_t)sy), dsx = make_fastdiv((uint32_t)sx);
   if (pooled)
-    hipLaunchKernelGGL(bnpool_bwd_partial_pooled_kernel, dim3(C, S2), dim3(256), 0, st, x, y_pool, dzdy_pool, amax,
-                       g, b, moments, part, pg, make_fastdiv((uint32_t)pg.Ho), C, N, S2);
+    hipLaunchKernelGGL(bnpool_bwd_partial_pooled_kernel, dim3(C, p.S2), dim3(256), 0, st, x, y_pool, dzdy_pool, amax,
+                       g, b, moments, part, pg, make_fastdiv((uint32_t)pg.Ho), C, N, p.S2);
   else
-    hipLaunchKernelGGL(bnpool_bwd_partial_kernel, grid, block, 0, st, x, g, b, moments, amax, dzdy_pool,
-                       part, pg, dsy, dsx, C, N, S, gz);
+    hipLaunchKernelGGL(bnpool_bwd_partial_kernel, grid, block, 0, st, x, g, b, moments, amax, dzdy_pool, part, pg, dsy, dsx,
+                       C, N, p.S, p.gz);
   XM_LAUNCH_CHECK();
-  hipLaunchKernelGGL(bn_bwd_finalize_kernel, dim3((C + 3) / 4), dim3(256), 0, st, part, moments, sums,
-                     dg_out, db_out, C, (int)npart);
+  hipLaunchKernelGGL(bn_bwd_finalize_kernel, dim3((C + 3) / 4), dim3(256), 0, st, part, moments, sums, dg_out, db_out, C,
+                     (int)npart);
   XM_LAUNCH_CHECK();
   if (dx_out) {
     const double m = (double)H * W * N;
     if (patch) {
-      dim3 pgrid(pgx, C, pgz * pS), pblock(pbx, pby);
-      const bool vec2 = sy == 2 && (H & 1) == 0 && (pt & 1) == 0 && (((uintptr_t)x | (uintptr_t)dx_out) & 7) == 0;
-      if (sy == 2 && vec2)
-        hipLaunchKernelGGL((bnpool_bwd_apply_patch_kernel<2, 2, true>), pgrid, pblock, 0, st, x, g, b, moments, sums,
-                           amax, dzdy_pool, dx_out, part2, pg, KH, KW, C, N, pS, m, train);
-      else if (sy == 2)
-        hipLaunchKernelGGL((bnpool_bwd_apply_patch_kernel<2, 2, false>), pgrid, pblock, 0, st, x, g, b, moments,
-                           sums, amax, dzdy_pool, dx_out, part2, pg, KH, KW, C, N, pS, m, train);
-      else
-        hipLaunchKernelGGL((bnpool_bwd_apply_patch_kernel<3, 2, false>), pgrid, pblock, 0, st, x, g, b, moments,
-                           sums, amax, dzdy_pool, dx_out, part2, pg, KH, KW, C, N, pS, m, train);
+      decltype(&bnpool_bwd_apply_patch_kernel<2, 2, true>) kernel;
+      if (p.vec2) kernel = bnpool_bwd_apply_patch_kernel<2, 2, true>;
+      else if (sy == 2) kernel = bnpool_bwd_apply_patch_kernel<2, 2, false>;
+      else kernel = bnpool_bwd_apply_patch_kernel<3, 2, false>;
+      hipLaunchKernelGGL(kernel, dim3(p.pgx, C, p.pgz * p.pS), dim3(p.pbx, p.pby), 0, st, x, g, b, moments, sums, amax,
+                         dzdy_pool, dx_out, part2, pg, p.KH, p.KW, C, N, p.pS, m, train);
     } else {
-      hipLaunchKernelGGL(bnpool_bwd_apply_kernel, grid, block, 0, st, x, g, b, moments, sums, amax,
-                         dzdy_pool, dx_out, part2, pg, dsy, dsx, C, N, S, m, train);
+      hipLaunchKernelGGL(bnpool_bwd_apply_kernel, grid, block, 0, st, x, g, b, moments, sums, amax, dzdy_pool, dx_out,
+                         part2, pg, dsy, dsx, C, N, p.S, m, train);
     }
     XM_LAUNCH_CHECK();
     if (part2) {
-      hipLaunchKernelGGL(sum_partials_kernel, dim3((C + 3) / 4), dim3(256), 0, st, part2, dxsum_out, C,
-                         (int)npart2);
+      hipLaunchKernelGGL(sum_partials_kernel, dim3((C + 3) / 4), dim3(256), 0, st, part2, dxsum_out, C, (int)npart2);
       XM_LAUNCH_CHECK();
     }
   }
@@ -1295,9 +1151,8 @@ bnpool_rowconst_kernel(const float *__restrict__ gg, const float *__restrict__ b
   o[5] = (float)k2;
 }
 
-size_t bnpool_sums_need(int C, int N) {
-  return WsCarver::need((size_t)2 * C * bn_splits(C, N), 8) + WsCarver::need((size_t)2 * C, 8);
-}
+static BnWs bnpool_sums_ws(int C, int N) { return bn_ws(C, bn_splits(C, N), true, 0, false); }
+size_t bnpool_sums_need(int C, int N) { return bnpool_sums_ws(C, N).bytes(); }
 
 int bnpool_backward_sums(WsCarver &ws, const float *x, int H, int W, int C, int N, const float *g, const float *b,
                          const float *moments, int train, int ph, int pw, int sy, int sx, int pt, int pb, int pl, int pr,
@@ -1309,8 +1164,8 @@ int bnpool_backward_sums(WsCarver &ws, const float *x, int H, int W, int C, int 
   if (!x || !g || !b || !moments || !amax || !y_pool || !dzdy_pool || !rowc_out)
     return fail(XM_EINVAL, "bnorm+relu+pool sums: NULL tensor");
   const int S2 = bn_splits(C, N);
-  double *part = ws.take<double>((size_t)2 * C * S2);
-  double *sums = ws.take<double>((size_t)2 * C);
+  const BnWs w = bnpool_sums_ws(C, N);
+  double *part = take(ws, w.part), *sums = take(ws, w.sums);
   hipLaunchKernelGGL(bnpool_bwd_partial_pooled_kernel, dim3(C, S2), dim3(256), 0, st, x, y_pool, dzdy_pool, amax, g, b,
                      moments, part, pg, make_fastdiv((uint32_t)pg.Ho), C, N, S2);
   XM_LAUNCH_CHECK();
@@ -1376,11 +1231,8 @@ int xm_nnbnorm_backward_fused(const float *x, const float *y, int H, int W, int 
                               const float *g, const float *b, const float *dzdy, float epsilon,
                               const float *moments_in, float *dx_out, float *dg_out, float *db_out,
                               float *moments_out, int flags, void *stream) {
-  (void)b;
-  if ((flags & XM_FUSE_RELU) && !y) return fail(XM_EINVAL, "vl_nnbnorm(fused bwd): y is NULL");
-  return bnorm_backward(x, (flags & XM_FUSE_RELU) ? y : nullptr, H, W, C, N, g, dzdy, epsilon,
-                        moments_in, dx_out, dg_out, db_out, moments_out, (hipStream_t)stream,
-                        (flags & XM_BN_BATCH_MOMENTS) != 0);
+  return xm_nnbnorm_backward_dxsum(x, y, H, W, C, N, g, b, dzdy, epsilon, moments_in, dx_out, dg_out, db_out, moments_out,
+                                   nullptr, flags, stream);
 }
 
 int xm_nnbnorm_backward_dxsum(const float *x, const float *y, int H, int W, int C, int N,
@@ -1396,16 +1248,18 @@ int xm_nnbnorm_backward_dxsum(const float *x, const float *y, int H, int W, int 
 
 int xm_nnpool_forward(const float *x, int H, int W, int C, int N, int ph, int pw, int sy, int sx,
                       int pt, int pb, int pl, int pr, int method, float *y, void *stream) {
-  return pool_forward(x, H, W, C, N, ph, pw, sy, sx, pt, pb, pl, pr, method, y, nullptr,
-                      (hipStream_t)stream);
+  PoolGeo g;
+  int rc = pool_geo(g, H, W, C, N, ph, pw, sy, sx, pt, pb, pl, pr, method);
+  return rc ? rc : pool_forward(x, g, C, N, method, y, nullptr, (hipStream_t)stream);
 }
 
 int xm_nnpool_forward_argmax(const float *x, int H, int W, int C, int N, int ph, int pw, int sy,
                              int sx, int pt, int pb, int pl, int pr, float *y, unsigned char *argmax,
                              void *stream) {
   if (!y || !argmax) return fail(XM_EINVAL, "vl_nnpool: NULL tensor");
-  return pool_forward(x, H, W, C, N, ph, pw, sy, sx, pt, pb, pl, pr, XM_POOL_MAX, y, argmax,
-                      (hipStream_t)stream);
+  PoolGeo g;
+  int rc = pool_geo(g, H, W, C, N, ph, pw, sy, sx, pt, pb, pl, pr, XM_POOL_MAX);
+  return rc ? rc : pool_forward(x, g, C, N, XM_POOL_MAX, y, argmax, (hipStream_t)stream);
 }
 
 int xm_nnpool_global_avg_backward_accum(const float *dzdy, const float *accum, float *dx_out, int H, int W, int C, int N,
@@ -1416,13 +1270,10 @@ int xm_nnpool_global_avg_backward_accum(const float *dzdy, const float *accum, f
   const size_t n = (size_t)H * W * C * N;
   const xm::FastDiv d = xm::make_fastdiv((uint32_t)(H * W));
   const float scale = 1.0f / (float)(H * W);   // correctly rounded, as pool_bwd_kernel's
-  const bool vec = (H * W) % 4 == 0 && ((((uintptr_t)accum | (uintptr_t)dx_out)) & 15) == 0;
-  if (vec)
-    hipLaunchKernelGGL(pool_global_avg_bwd_accum_kernel<true>, dim3((unsigned)((n / 4 + 255) / 256)), dim3(256), 0,
-                       (hipStream_t)stream, dzdy, accum, dx_out, n, d, scale);
-  else
-    hipLaunchKernelGGL(pool_global_avg_bwd_accum_kernel<false>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0,
-                       (hipStream_t)stream, dzdy, accum, dx_out, n, d, scale);
+  const bool vec = (H * W) % 4 == 0 && aligned16(accum, dx_out);
+  hipLaunchKernelGGL(vec ? pool_global_avg_bwd_accum_kernel<true> : pool_global_avg_bwd_accum_kernel<false>,
+                     dim3((unsigned)(((vec ? n / 4 : n) + 255) / 256)), dim3(256), 0, (hipStream_t)stream, dzdy, accum, dx_out,
+                     n, d, scale);
   XM_LAUNCH_CHECK();
   return XM_OK;
 }
@@ -1430,16 +1281,18 @@ int xm_nnpool_global_avg_backward_accum(const float *dzdy, const float *accum, f
 int xm_nnpool_backward(const float *x, int H, int W, int C, int N, int ph, int pw, int sy, int sx,
                        int pt, int pb, int pl, int pr, int method, const float *dzdy, float *dx_out,
                        void *stream) {
-  return pool_backward(x, nullptr, H, W, C, N, ph, pw, sy, sx, pt, pb, pl, pr, method, dzdy, dx_out,
-                       (hipStream_t)stream);
+  PoolGeo g;
+  int rc = pool_geo(g, H, W, C, N, ph, pw, sy, sx, pt, pb, pl, pr, method);
+  return rc ? rc : pool_backward(x, nullptr, g, C, N, method, dzdy, dx_out, (hipStream_t)stream);
 }
 
 int xm_nnpool_backward_argmax(const unsigned char *argmax, int H, int W, int C, int N, int ph, int pw,
                               int sy, int sx, int pt, int pb, int pl, int pr, const float *dzdy,
                               float *dx_out, void *stream) {
   if (!argmax) return fail(XM_EINVAL, "vl_nnpool: argmax table is NULL");
-  return pool_backward(nullptr, argmax, H, W, C, N, ph, pw, sy, sx, pt, pb, pl, pr, XM_POOL_MAX, dzdy,
-                       dx_out, (hipStream_t)stream);
+  PoolGeo g;
+  int rc = pool_geo(g, H, W, C, N, ph, pw, sy, sx, pt, pb, pl, pr, XM_POOL_MAX);
+  return rc ? rc : pool_backward(nullptr, argmax, g, C, N, XM_POOL_MAX, dzdy, dx_out, (hipStream_t)stream);
 }
 
 int xm_nnbnorm_relu_pool_forward(const float *x, int H, int W, int C, int N, const float *g,

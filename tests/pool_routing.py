@@ -109,7 +109,9 @@ def scatter(code, dzdy, H, W, pool, stride=1, pad=0):
     return np.asfortranarray(dxp[g.pt:g.pt + H, g.pl:g.pl + W])
 
 
-# ---- the geometries of the LDS-staged 3 x 3 max pooling and of its gate (pool_forward in csrc/norm_pool.hip) -----------------
+# ---- the geometries of the LDS-staged 3 x 3 max pooling and of its gate (pool_lds_plan in csrc/norm_pool_plan.h) -------------
+# The figures beside each case are asserted against that header by tests/norm_pool_plan_check.cpp (kLdsCases; run by
+# tests/test_norm_pool_plan_cpu.py), which is the evidence that a case reaches the branch it is written for.
 # maxcols = 4096 / H (integer); wob = min((maxcols - 3) / sx + 1, Wo) (0 if maxcols < 3); the LDS kernel runs iff
 # Ho * Wo >= 256 and (wob >= 4 or wob == Wo); then groups = ceil(Wo / wob), wob = ceil(Wo / groups); a block's run starts at
 # base = plane * H * W + wlo * H and lead = base % 4.

@@ -8,7 +8,9 @@ derived: vl.scale_ is one fp32 multiply (bit for bit), the magnitude is sqrtf(re
 (|got - ref| <= 1e-6 |ref| per element).
 
 The derived quantities beside each case are recomputed from the launch code; the library's profiler hooks do not count these
-kernels, so that derivation is the evidence of which branch a case reaches.  ew_grid(items) = min(ceil(items / 256), 2048).
+kernels, so that derivation is the evidence of which branch a case reaches.  ew_grid(items) = min(ceil(items / 256), 2048) and
+the 16-byte gate aligned16(...) of the launchers are csrc/norm_pool_plan.h's, checked without a GPU by
+tests/norm_pool_plan_check.cpp.
 
 Kernel / branch -> the case that reaches it, and through which condition:
   ew_kernel<OP> vec arm, second trip + tail        n = 2,100,003 aligned: n4 = 525,000 > 2,048 * 256 = 524,288 (blocks 0 .. 2 take a

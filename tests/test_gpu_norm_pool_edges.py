@@ -8,9 +8,11 @@ Max pooling of a plain tensor copies inputs, its table is a pure function of the
 oracle's own order (wo outer, ho inner, fp32, from 0): Y, the table and DX are compared BIT FOR BIT.  Average pooling and the
 bnorm modes use the bounds of tests/test_gpu_ops.py (test_pool, test_bnorm, test_fused_bnorm_relu_pool).
 
-The derived quantities beside each shape are recomputed from the dispatch code (pool_forward, pool_launch, bn_splits,
-bnorm_backward, bnrelupool_backward); the library's profiler hooks do not count these kernels, so that derivation is the
-evidence of which kernel and which branch a case reaches.
+The derived quantities beside each shape are the planning of csrc/norm_pool_plan.h (bn_splits, bn_dxsum_splits, bn_vec,
+ew_grid, pool_launch, pool_lds_plan, pool_cover_2x2, bnpool_bwd_plan), which norm_pool.hip launches from; the library's
+profiler hooks do not count these kernels, so tests/norm_pool_plan_check.cpp (run by tests/test_norm_pool_plan_cpu.py, no
+GPU) asserts every one of them as a literal against that header: it is the evidence of which kernel and which branch a case
+reaches, and it fails when a constant of the planning moves a case off its branch.
 
 Kernel / template -> the case that reaches it, and through which condition:
   bn_stats_partial_kernel, bn_bwd_partial_kernel   S < N, uneven nper: (2,2,300,9) float4 arm, (3,1,300,9) scalar arm; run 2 and
@@ -126,7 +128,8 @@ def test_fused_bnorm_relu_pool_lds_geometries(gpu, name, train, unaligned):
     assert bad == 0, "table differs in %d windows that are no near-ties" % bad
 
 
-# pool_launch(rows, cols, planes): bx = pow2 >= rows (<= 256), by = pow2 >= cols (<= 256 / bx), bz = 256 / (bx by);
+# pool_launch(rows, cols, planes) of csrc/norm_pool_plan.h (the figures below are asserted in tests/norm_pool_plan_check.cpp):
+# bx = pow2 >= rows (<= 256), by = pow2 >= cols (<= 256 / bx), bz = 256 / (bx by);
 # gx = ceil(cols / by), gz = ceil(rows / bx), gy = min(max(1, 8192 / (gx gz)), ceil(planes / bz)): a block strides over planes
 # iff gy < ceil(planes / bz).  (301, 41) x 120 planes, stride 1 -- forward launch over the outputs, backward over the inputs:
 #   2 x 2: Ho x Wo = 300 x 40: bx 256, by 1, bz 1, gx 40, gz 2 -> gy = 102 < 120    pool_fwd_kernel<2, 2>, pool_bwd_kernel<true>
@@ -234,7 +237,8 @@ def test_pool_window_limit_and_refusals(gpu):
         vl.bnorm_relu_pool_backward(xb, gd, bd, mo, am, vl.from_numpy(rnd(rng, *yp.shape)), [5, 3], stride=[2, 1])
 
 
-# bnrelupool_backward: element kernels: bx = pow2 >= H, by = pow2 >= W (<= 256 / bx), S = min(N, 4096 / (C gx gz)); patch kernel
+# bnpool_bwd_plan of csrc/norm_pool_plan.h (the figures below are asserted in tests/norm_pool_plan_check.cpp):
+# element kernels: bx = pow2 >= H, by = pow2 >= W (<= 256 / bx), S = min(N, 4096 / (C gx gz)); patch kernel
 # (strides 2 x 2 and 3 x 2): KH = (H + pt + sy - 1) / sy, KW likewise, pS = min(N, 16384 / (C pgx pgz)); pooled sums (y_pool
 # given): S2 = bn_splits = min(N, 2048 / C).  All planes here fit one block (gx = gz = pgx = pgz = 1), N = 3:
 # (H, W, C, N, pool, stride, pad, with y_pool)
