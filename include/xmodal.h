@@ -57,7 +57,7 @@ enum { XM_FUSE_RELU = 1, XM_BN_BATCH_MOMENTS = 2, XM_FUSE_SIGMOID = 4 };
 
 /* ABI revision: 100 = round 1; 101 = xm_nnbnorm_relu_pool_backward gained `y_pool`, exchange entry points return
  * XM_EINVAL without a communicator; 102 = + xm_nnconv_forward_moments, xm_nnbnorm_backward_dxsum, xm_nnconv_forward_gated;
- * 103 = + xm_nnpool_global_avg_backward_accum; 104 = + xm_nnconv_backward_filter_bnrelupool, xm_nndropout_forward / _apply, xm_resample, xm_se_tail_backward_reduce / _apply, xm_se_squeeze_bn, xm_scale_axpy_bn; 105 = + xm_set_exec_hint / xm_get_exec_hint; 106 = + xm_nnconv_bnorm_relu_pool_forward, xm_stem_gram, xm_stem_gram_moments, xm_nnconv_backward_filter_bnrelupool_gram; 107 = + xm_nnaffinegrid / _backward, xm_nnbilinearsampler / _backward, xm_ferplus_batch; 108 = + XM_AGG_PEAK, xm_mnrfit, xm_mnrval; 109 = + xm_roc, xm_roc_launches, xm_label_hist; 110 = + xm_group_rows, xm_gather_rows, xm_scatter_rows, xm_track_peaks; 111 = + xm_wav_batch; 112 = + xm_spec_bucket_batch; 113 = + xm_jpeg_plan, xm_jpeg_decode_batch; 114 = + xm_wav_plan, xm_wav_decode_batch; 115 = + xm_jpeg_decode_batch_split, xm_jpeg_split_geometry; 116 = + xm_pixcsv_plan, xm_pixcsv_decode_batch, xm_pixcsv_geometry; 117 = + xm_nnconv_forward_strided_residual; 118 = + xm_solver_update; 119 = + xm_nnnormalize_forward / _backward, xm_nnnormalize_geometry (additions never change the revision's meaning for older bindings).  A binding checks xm_version() >= the revision it was written against. */
+ * 103 = + xm_nnpool_global_avg_backward_accum; 104 = + xm_nnconv_backward_filter_bnrelupool, xm_nndropout_forward / _apply, xm_resample, xm_se_tail_backward_reduce / _apply, xm_se_squeeze_bn, xm_scale_axpy_bn; 105 = + xm_set_exec_hint / xm_get_exec_hint; 106 = + xm_nnconv_bnorm_relu_pool_forward, xm_stem_gram, xm_stem_gram_moments, xm_nnconv_backward_filter_bnrelupool_gram; 107 = + xm_nnaffinegrid / _backward, xm_nnbilinearsampler / _backward, xm_ferplus_batch; 108 = + XM_AGG_PEAK, xm_mnrfit, xm_mnrval; 109 = + xm_roc, xm_roc_launches, xm_label_hist; 110 = + xm_group_rows, xm_gather_rows, xm_scatter_rows, xm_track_peaks; 111 = + xm_wav_batch; 112 = + xm_spec_bucket_batch; 113 = + xm_jpeg_plan, xm_jpeg_decode_batch; 114 = + xm_wav_plan, xm_wav_decode_batch; 115 = + xm_jpeg_decode_batch_split, xm_jpeg_split_geometry; 116 = + xm_pixcsv_plan, xm_pixcsv_decode_batch, xm_pixcsv_geometry; 117 = + xm_nnconv_forward_strided_residual; 118 = + xm_solver_update; 119 = + xm_nnnormalize_forward / _backward, xm_nnnormalize_geometry; 120 = + xm_jpeg_plan_prog, xm_jpeg_decode_batch_prog (additions never change the revision's meaning for older bindings).  A binding checks xm_version() >= the revision it was written against. */
 int xm_version(void);
 const char *xm_last_error(void);
 /* Device memory for hosts that have no device-array type of their own (MATLAB's gpuArray is CUDA-only: on an
@@ -765,6 +765,64 @@ int xm_jpeg_decode_batch_split(const unsigned char *bytes, long long nbytes, con
                                float *faces, float crop, int Ho, int Wo, const float *avg3, int *status, int seg_bytes,
                                int *rounds, void *stream);
 int xm_jpeg_split_geometry(int *segments_per_pass, int *launches);
+
+/* Progressive files in vl_imreadjpeg (ABI 120): MatConvNet's vl_imreadjpeg is libjpeg and reads a progressive file as it
+ * reads a baseline one; xm_jpeg_plan refuses it, and stays as it is.  This pair is the opt-in that accepts what
+ * xm_jpeg_plan accepts and, in addition, SOF2: 8-bit, Huffman, 1 or 3 components within the same sampling limits, any
+ * scan script that satisfies T.81 G.1.1.1.1 -- Ss <= Se <= 63; Ss == 0 implies Se == 0; an AC scan has one component;
+ * Ah == 0, or Ah == Al + 1 with Ah the Al of the previous scan of every coefficient of the band; Al <= 13 -- and sends
+ * no coefficient first twice.  A violation is XM_EINVAL with the file's index and the scan's number.  Deviation from
+ * libjpeg: libjpeg only warns about a bogus progression and decodes on; here the refinement of a coefficient that no
+ * earlier scan sent, and any other violation, refuses the batch.  Still XM_ENOTSUP, with the file's index: SOF1 and SOF3
+ * to SOF15 (extended, lossless, hierarchical, arithmetic), 12-bit samples, 4 components, multi-scan SOF0, more than
+ * XM_JPEG_MAX_SCANS scans in a file.  A file that ends after any of its scans (EOI, or the end of the bytes) is valid
+ * and decodes to what the coefficients sent so far give; a component's quantiser table is the one that stood at the
+ * file's first scan.  Such a file gets what libjpeg, and with it vl_imreadjpeg, gives it: while one of the first ten
+ * coefficients (zigzag order) of a component has not arrived in full, libjpeg's block smoothing estimates the ones
+ * that are still zero from the DC values of the 5 x 5 blocks around (jdcoefct.c, the form of libjpeg-turbo 2.1 and
+ * later), so the pixels equal libjpeg's there too.
+ *
+ * xm_jpeg_plan_prog: host only, no device call (usable without a GPU).  bytes, offsets, desc, tables as xm_jpeg_plan;
+ * for a baseline file the descriptor row and the table slots are those of xm_jpeg_plan; for SOF2 columns 13-18 mean
+ * nothing, 0 .. 1 span the entropy data of all scans, 7 is the restart interval at the first scan, 22, 23 the lanes
+ * of all scans -- but in a file that is smoothed column 13 + c is XM_JPEG_SMOOTH plus one nibble per coefficient 0 .. 9
+ * of component c, nibble z = 1 + the Al the coefficient stands at, 0 = never sent.
+ *   scans   XM_JPEG_SCAN int64 per (image, scan), in file order: 0 image; 1 components in the scan; 2-4 their index in
+ *           the frame (-1: none); 5 Ss; 6 Se; 7 Ah; 8 Al; 9-11 DC and 12-14 AC Huffman table slot per scan component, as
+ *           DHT stood at this scan (a progressive file redefines its tables between scans; 0 where the kind of scan
+ *           reads none); 15, 16 byte range of the entropy data; 17, 18 the raster, in MCUs, across and down: the
+ *           frame's MCUs for a scan of several components, else the component's own blocks ceil(ceil(W * h / hmax) /
+ *           8) x ceil(ceil(H * v / vmax) / 8), each block one MCU, not the MCU-padded count (the coefficient buffer
+ *           keeps its padded pitch); 19 level: 0 if no earlier scan of the image sends a (component, coefficient) it
+ *           sends, else 1 + the largest level among those that do -- scans of one level write disjoint coefficients;
+ *           20 first lane, 21 lanes; 22 restart interval in MCUs at this scan; 23 kind (XM_JPEG_SCAN_*)
+ *   lanes   XM_JPEG_LANE int64 per (scan, restart interval): scan row, byte range, first MCU
+ *   sizes   XM_JPEG_PROG_SIZES int64: the eight of xm_jpeg_plan, then 8 scans, 9 levels (at most XM_JPEG_MAX_LEVELS:
+ *           every scan of a coefficient lowers its Al by one), 10 whether a file of the batch is smoothed
+ * XM_ENOMEM: scans_cap / lanes_cap / tables_cap too small, `sizes` holds what is needed.
+ *
+ * xm_jpeg_decode_batch_prog: device.  The arguments up to `status` are those of xm_jpeg_decode_batch, from the plan
+ * above; scans (device, 8-byte aligned), nscans, levels and smooth are the plan's.  Launches: clear; the progressive entropy
+ * kernel once per level (one lane per (scan, restart interval), DC predictors and the end-of-band run zero at the
+ * start of each; DC first / refinement, AC first / refinement as T.81 G.1.2, the one scan of a baseline file as
+ * xm_jpeg_decode_batch decodes it); with `smooth` the two smoothing kernels; then IDCT, colour and faces exactly as
+ * xm_jpeg_decode_batch: 4 + levels launches, two more with smoothing, one more with faces, whatever N and the sizes
+ * are; no synchronisation.  Coefficients are read and written as int16
+ * only.  status as xm_jpeg_decode_batch, ORed over the image's lanes; XM_JPEG_BADCODE also covers a run or an
+ * end-of-band run that leaves the band or the restart interval.  Baseline files in the batch give pixels, faces and
+ * status bit for bit those of xm_jpeg_decode_batch. */
+enum { XM_JPEG_SCAN = 24, XM_JPEG_PROG_SIZES = 11, XM_JPEG_MAX_SCANS = 256, XM_JPEG_MAX_LEVELS = 14 };
+#define XM_JPEG_SMOOTH (1LL << 40)
+enum { XM_JPEG_SCAN_SEQ = 0, XM_JPEG_SCAN_DC_FIRST = 1, XM_JPEG_SCAN_DC_REFINE = 2, XM_JPEG_SCAN_AC_FIRST = 3,
+       XM_JPEG_SCAN_AC_REFINE = 4 };
+int xm_jpeg_plan_prog(const unsigned char *bytes, const long long *offsets, int N, long long *desc, long long *scans,
+                      long long scans_cap, long long *lanes, long long lanes_cap, unsigned char *tables, long long tables_cap,
+                      long long *sizes);
+int xm_jpeg_decode_batch_prog(const unsigned char *bytes, long long nbytes, const long long *desc, int N,
+                              const long long *lanes, int nlanes, const unsigned char *tables, int nq, int nh,
+                              long long coef_elems, long long plane_bytes, long long pixel_floats, float *pixels, float *faces,
+                              float crop, int Ho, int Wo, const float *avg3, int *status, const long long *scans, int nscans,
+                              int levels, int smooth, void *stream);
 
 /* audioinfo / audioread of a batch of WAV files, decoded on the device into the waveform bank that xm_wav_batch and
  * xm_spec_bucket_batch read (ABI 114): info = audioinfo(audfile) -> TotalSamples, SampleRate (getBatchEmoVoxCeleb.m:79),

@@ -135,6 +135,9 @@ SIGNATURES = {
     "xm_jpeg_decode_batch_split": [c_fp, C.c_longlong, c_fp, _i, c_fp, _i, c_fp, _i, _i, C.c_longlong, C.c_longlong,
                                    C.c_longlong, c_fp, c_fp, _f, _i, _i, C.POINTER(C.c_float), c_fp, _i, c_fp, _vp],
     "xm_jpeg_split_geometry": [C.POINTER(C.c_int), C.POINTER(C.c_int)],
+    "xm_jpeg_plan_prog": [_vp, _vp, _i, _vp, _vp, C.c_longlong, _vp, C.c_longlong, _vp, C.c_longlong, _vp],
+    "xm_jpeg_decode_batch_prog": [c_fp, C.c_longlong, c_fp, _i, c_fp, _i, c_fp, _i, _i, C.c_longlong, C.c_longlong,
+                                  C.c_longlong, c_fp, c_fp, _f, _i, _i, C.POINTER(C.c_float), c_fp, c_fp, _i, _i, _i, _vp],
     "xm_wav_plan": [_vp, _vp, _i, _vp, _i, C.c_longlong, _vp, _vp],
     "xm_wav_decode_batch": [c_fp, C.c_longlong, c_fp, _i, c_fp, C.c_longlong, _vp],
     "xm_pixcsv_plan": [_vp, C.c_longlong, _vp, C.c_longlong, _vp],

@@ -382,10 +382,12 @@ class JpegDenseFrames(SyntheticDenseFrames):
     """The dense face frames as JPEG files held in memory: the `lister` / `find` interface of SyntheticDenseFrames over a
     {path: bytes} table, and read(paths) -> list of bytes for buildImdb(read=...) / getImageBatch.  `files` is a list of
     JPEG files (bytes); frame j of the track with id i is files[(7 i + j) mod len(files)], so the frames of one track and
-    of one batch differ in size when the files do.  index(path) names the file behind a listed path."""
+    of one batch differ in size when the files do.  index(path) names the file behind a listed path.  progressive=True
+    says that some of the files are progressive: buildImdb(read=frames.read, progressive=frames.progressive)."""
 
-    def __init__(self, imdb, files, frameless=(), unclaimed=0):
+    def __init__(self, imdb, files, frameless=(), unclaimed=0, progressive=False):
         super().__init__(imdb, frameless=frameless, unclaimed=unclaimed)
+        self.progressive = bool(progressive)
         self.files = [bytes(f) for f in files]
         if not self.files:
             raise ValueError("JpegDenseFrames: no files")

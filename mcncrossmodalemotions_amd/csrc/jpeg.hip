@@ -23,29 +23,17 @@
 //   crop_resize_face_ragged_kernel (misc.hip, next to the kernel it must equal bit for bit)   the teacher's input
 // xm_jpeg_decode_batch_split enqueues the same launches with jpeg_entropy_split_kernel as the entropy stage: one block
 // per lane, one thread per segment of seg_bytes raw bytes, for files without restart markers (described at the kernel).
+// The byte reader, the Huffman lookup and the block decode live in jpeg_entropy.h and the layout constants and table
+// helpers in jpeg_scan_plan.h, shared with the progressive decode (csrc/jpeg_prog.hip), which also runs its entropy
+// stage between the launches of jpeg_decode_launch below.
 #include <algorithm>
 #include <vector>
 
+#include "jpeg_entropy.h"
 #include "prof.h"
 #include "xm_common.h"
 
 namespace xm {
-
-constexpr int kJpegDesc = XM_JPEG_DESC, kJpegLane = XM_JPEG_LANE;
-constexpr int kQtBytes = XM_JPEG_QT_BYTES, kHtBytes = XM_JPEG_HT_BYTES;
-constexpr int kJpegLanes = 4;        // lanes per 64-thread block of the entropy kernel
-constexpr int kJpegMaxSide = 4096;   // H, W <= 4096
-
-// descriptor columns
-enum { D_SCAN0 = 0, D_SCAN1, D_H, D_W, D_NCOMP, D_HS, D_VS, D_RI, D_MX, D_MY, D_QT, D_DC = 13, D_AC = 16, D_COEF = 19,
-       D_PLANE, D_PIX, D_LANE0, D_NLANES };
-
-static const unsigned char kNatural[64] = {0,  1,  8,  16, 9,  2,  3,  10, 17, 24, 32, 25, 18, 11, 4,  5,  12, 19, 26, 33, 40, 48,
-                                           41, 34, 27, 20, 13, 6,  7,  14, 21, 28, 35, 42, 49, 56, 57, 50, 43, 36, 29, 22, 15, 23,
-                                           30, 37, 44, 51, 58, 59, 52, 45, 38, 31, 39, 46, 53, 60, 61, 54, 47, 55, 62, 63};
-__constant__ unsigned char kNaturalDev[64] = {0,  1,  8,  16, 9,  2,  3,  10, 17, 24, 32, 25, 18, 11, 4,  5,  12, 19, 26, 33, 40, 48,
-                                              41, 34, 27, 20, 13, 6,  7,  14, 21, 28, 35, 42, 49, 56, 57, 50, 43, 36, 29, 22, 15, 23,
-                                              30, 37, 44, 51, 58, 59, 52, 45, 38, 31, 39, 46, 53, 60, 61, 54, 47, 55, 62, 63};
 
 // ---- jpeg_clear_kernel ---------------------------------------------------------------------------------------------
 __global__ void __launch_bounds__(256) jpeg_clear_kernel(uint4 *__restrict__ coef, size_t n16, int *__restrict__ status, int N) {
@@ -55,106 +43,6 @@ __global__ void __launch_bounds__(256) jpeg_clear_kernel(uint4 *__restrict__ coe
 }
 
 // ---- jpeg_entropy_kernel -------------------------------------------------------------------------------------------
-struct BitReader {
-  const uint4 *base;     // the batch's bytes, 16-byte pieces
-  long long pos, end;    // next byte and the end of the lane's range (absolute offsets, inside the buffer)
-  long long cidx;        // which piece `chunk` holds
-  uint4 chunk;
-  unsigned long long acc;   // next bit at the top
-  int nbits, fake;          // bits in acc; zero bits appended past the end of the range (they sit at the tail)
-
-  __device__ __forceinline__ unsigned byte_at(long long p) {
-    if ((p >> 4) != cidx) {
-      cidx = p >> 4;
-      chunk = base[cidx];
-    }
-    const int w = (int)(p >> 2) & 3;
-    const unsigned v = w == 0 ? chunk.x : (w == 1 ? chunk.y : (w == 2 ? chunk.z : chunk.w));
-    return (v >> (((int)p & 3) * 8)) & 255u;
-  }
-  __device__ __forceinline__ void refill() {
-    while (nbits <= 56) {
-      unsigned b = 0;
-      if (pos < end) {
-        b = byte_at(pos++);
-        if (b == 0xFFu && pos < end) {
-          if (byte_at(pos) == 0) {
-            ++pos;                 // FF 00: a stuffed zero
-          } else {                 // a marker inside the range: the entropy data ends here
-            end = pos - 1;
-            pos = end;
-            b = 0;
-            fake = min(fake + 8, 1 << 30);
-          }
-        }
-      } else {
-        fake = min(fake + 8, 1 << 30);
-      }
-      acc |= (unsigned long long)b << (56 - nbits);
-      nbits += 8;
-    }
-  }
-  __device__ __forceinline__ void drop(int n) {
-    acc <<= n;
-    nbits -= n;
-  }
-  __device__ __forceinline__ int take(int n) {   // n in 0 .. 16
-    refill();
-    const int v = n ? (int)(acc >> (64 - n)) : 0;
-    drop(n);
-    return v;
-  }
-  __device__ __forceinline__ bool starved() const { return nbits < fake; }
-};
-
-// one Huffman table in LDS: lut[256] of (nbits << 8 | symbol), huffval[256], maxcode[17], valoff[17]
-__device__ __forceinline__ int huff_decode(const unsigned char *t, BitReader &br) {
-  br.refill();
-  const unsigned w = (unsigned)(br.acc >> 48);
-  const unsigned e = ((const unsigned short *)t)[w >> 8];
-  if (e >> 8) {
-    br.drop((int)(e >> 8));
-    return (int)(e & 255u);
-  }
-  const int *maxcode = (const int *)(t + 768), *valoff = (const int *)(t + 836);
-  for (int l = 9; l <= 16; ++l) {
-    const int code = (int)(w >> (16 - l));
-    if (code <= maxcode[l]) {
-      br.drop(l);
-      return t[512 + ((code + valoff[l]) & 255)];
-    }
-  }
-  return -1;
-}
-
-__device__ __forceinline__ int huff_extend(int v, int s) { return (s && v < (1 << (s - 1))) ? v - (1 << s) + 1 : v; }
-
-// one block: 0 = fine, else XM_JPEG_BADCODE.  `out` holds 64 zeroed coefficients in row-major order.
-__device__ __forceinline__ int decode_block(BitReader &br, const unsigned char *dc, const unsigned char *ac,
-                                            const unsigned char *nat, int &pred, short *__restrict__ out) {
-  int s = huff_decode(dc, br);
-  if (s < 0 || s > 15) return XM_JPEG_BADCODE;
-  pred += huff_extend(br.take(s), s);
-  out[0] = (short)pred;
-  int k = 1;
-  while (k < 64) {
-    const int rs = huff_decode(ac, br);
-    if (rs < 0) return XM_JPEG_BADCODE;
-    const int r = rs >> 4;
-    s = rs & 15;
-    if (s == 0) {
-      if (r != 15) break;
-      k += 16;
-      continue;
-    }
-    k += r;
-    if (k > 63) return XM_JPEG_BADCODE;
-    out[nat[k & 63]] = (short)huff_extend(br.take(s), s);
-    ++k;
-  }
-  return 0;
-}
-
 __global__ void __launch_bounds__(64)
 jpeg_entropy_kernel(const uint4 *__restrict__ bytes, long long nbytes, const long long *__restrict__ desc, int N,
                     const long long *__restrict__ lanes, int nlanes, const unsigned char *__restrict__ huff,
@@ -575,16 +463,6 @@ jpeg_entropy_split_kernel(const uint4 *__restrict__ bytes, long long nbytes, con
 }
 
 // ---- jpeg_idct_kernel ----------------------------------------------------------------------------------------------
-// the image whose range [desc[i][col] / unit, desc[i + 1][col] / unit) holds g
-__device__ __forceinline__ int find_image(const long long *__restrict__ desc, int N, int col, long long unit, long long g) {
-  int lo = 0, hi = N - 1;
-  while (lo < hi) {
-    const int mid = (lo + hi + 1) >> 1;
-    if (desc[(long long)mid * kJpegDesc + col] / unit <= g) lo = mid; else hi = mid - 1;
-  }
-  return lo;
-}
-
 #define XM_IDCT_1D(x0, x1, x2, x3, x4, x5, x6, x7, SHIFT)                                                   \
   {                                                                                                         \
     int z2 = x2, z3 = x6;                                                                                   \
@@ -734,44 +612,6 @@ struct JpegTables {   // per file: what DQT / DHT defined
   unsigned char h[2][4][kHtBytes];
 };
 
-// jpeg_make_d_derived_tbl into the 1024-byte device form; false = invalid code lengths
-static bool derive_table(const unsigned char *counts, const unsigned char *vals, int nvals, unsigned char *out) {
-  memset(out, 0, kHtBytes);
-  unsigned short *lut = (unsigned short *)out;
-  unsigned char *hv = out + 512;
-  int *maxcode = (int *)(out + 768), *valoff = (int *)(out + 836);
-  int sizes[257], codes[257], n = 0;
-  for (int l = 1; l <= 16; ++l)
-    for (int i = 0; i < counts[l - 1]; ++i) sizes[n++] = l;
-  if (n != nvals || n > 256) return false;
-  int code = 0, si = n ? sizes[0] : 0, p = 0;
-  while (p < n) {
-    while (p < n && sizes[p] == si) codes[p++] = code++;
-    if (code > (1 << si)) return false;
-    code <<= 1;
-    ++si;
-  }
-  p = 0;
-  maxcode[0] = -1;
-  for (int l = 1; l <= 16; ++l) {
-    if (counts[l - 1]) {
-      valoff[l] = p - codes[p];
-      p += counts[l - 1];
-      maxcode[l] = codes[p - 1];
-    } else {
-      maxcode[l] = -1;
-    }
-  }
-  p = 0;
-  for (int l = 1; l <= 8; ++l)
-    for (int i = 0; i < counts[l - 1]; ++i, ++p) {
-      const int look = codes[p] << (8 - l);
-      for (int c = 0; c < (1 << (8 - l)); ++c) lut[look + c] = (unsigned short)((l << 8) | vals[p]);
-    }
-  memcpy(hv, vals, n);
-  return true;
-}
-
 static int parse_one(int idx, const unsigned char *d, long long n, JpegImage &im, JpegTables &tb,
                      std::vector<long long> &cuts) {
 #define JBAD(...) return fail(XM_EINVAL, __VA_ARGS__)
@@ -898,15 +738,6 @@ static int parse_one(int idx, const unsigned char *d, long long n, JpegImage &im
 #undef JNOT
 }
 
-template <int B>
-static int intern(std::vector<unsigned char> &pool, const unsigned char *t) {
-  const int n = (int)(pool.size() / B);
-  for (int i = 0; i < n; ++i)
-    if (!memcmp(&pool[(size_t)i * B], t, B)) return i;
-  pool.insert(pool.end(), t, t + B);
-  return n;
-}
-
 }  // namespace xm
 
 using namespace xm;
@@ -1001,16 +832,19 @@ int xm_jpeg_plan(const unsigned char *bytes, const long long *offsets, int N, lo
 
 }  // extern "C"
 
-// xm_jpeg_decode_batch (seg_bytes == 0) and xm_jpeg_decode_batch_split: the same launches but for the entropy stage
-static int jpeg_decode_launch(const unsigned char *bytes, long long nbytes, const long long *desc, int N, const long long *lanes,
-                              int nlanes, const unsigned char *tables, int nq, int nh, long long coef_elems,
-                              long long plane_bytes, long long pixel_floats, float *pixels, float *faces, float crop, int Ho,
-                              int Wo, const float *avg3, int *status, int seg_bytes, int *rounds, void *stream) {
+// The launches of a decode around its entropy stage (jpeg_entropy.h): xm_jpeg_decode_batch, xm_jpeg_decode_batch_split and
+// xm_jpeg_decode_batch_prog (csrc/jpeg_prog.hip) differ in that stage alone.
+namespace xm {
+
+int jpeg_decode_launch(const unsigned char *bytes, long long nbytes, const long long *desc, int N, const long long *lanes,
+                       int nlanes, const unsigned char *tables, int nq, int nh, long long coef_elems, long long plane_bytes,
+                       long long pixel_floats, float *pixels, float *faces, float crop, int Ho, int Wo, const float *avg3,
+                       int *status, const JpegEntropyStage &stage, void *stream) {
   if (N < 0 || nbytes < 0 || nlanes < 0 || nq < 0 || nh < 0 || coef_elems < 0 || plane_bytes < 0 || pixel_floats < 0)
     return fail(XM_EINVAL, "jpeg_decode_batch: negative size");
   if (N == 0) return XM_OK;
   if (!bytes || !desc || !lanes || !tables || !status) return fail(XM_EINVAL, "jpeg_decode_batch: NULL argument");
-  if (nlanes < N || nq < 1 || nh < 2 || coef_elems < 64 || (coef_elems & 63) || plane_bytes != coef_elems || pixel_floats < 3)
+  if (nlanes < N || nq < 1 || nh < stage.min_huff() || coef_elems < 64 || (coef_elems & 63) || plane_bytes != coef_elems || pixel_floats < 3)
     return fail(XM_EINVAL, "jpeg_decode_batch: sizes are not what xm_jpeg_plan reports");
   if (coef_elems >= (1LL << 31) || pixel_floats >= (1LL << 31)) return fail(XM_ETOOBIG, "jpeg_decode_batch: batch too large");
   if (((uintptr_t)bytes & 15) || ((uintptr_t)tables & 15) || ((uintptr_t)desc & 7) || ((uintptr_t)lanes & 7))
@@ -1037,15 +871,8 @@ static int jpeg_decode_launch(const unsigned char *bytes, long long nbytes, cons
                        (uint4 *)coef, n16, status, N);
   }
   XM_LAUNCH_CHECK();
-  {
-    ProfScope ps(prof_key(kProfJpeg, seg_bytes ? 5 : 1), 0, st);
-    if (seg_bytes)
-      hipLaunchKernelGGL(jpeg_entropy_split_kernel, dim3((unsigned)nlanes), dim3(kJpegSplitThreads), 0, st,
-                         (const uint4 *)bytes, nbytes, desc, N, lanes, nlanes, huff, nh, coef, status, seg_bytes, rounds);
-    else
-      hipLaunchKernelGGL(jpeg_entropy_kernel, dim3((unsigned)((nlanes + kJpegLanes - 1) / kJpegLanes)), dim3(64), 0, st,
-                         (const uint4 *)bytes, nbytes, desc, N, lanes, nlanes, huff, nh, coef, status);
-  }
+  rc = stage.launch(coef, huff, planes, st);
+  if (rc) return rc;
   XM_LAUNCH_CHECK();
   {
     ProfScope ps(prof_key(kProfJpeg, 2), 0, st);
@@ -1065,14 +892,58 @@ static int jpeg_decode_launch(const unsigned char *bytes, long long nbytes, cons
   return face_ragged_launch(pix, desc, kJpegDesc, D_H, D_W, D_PIX, N, crop, Ho, Wo, avg3, faces, st);
 }
 
+namespace {
+
+// seg_bytes == 0: one lane per restart interval; else the segment-parallel kernel, one block per lane
+struct BaselineStage : JpegEntropyStage {
+  const unsigned char *bytes;
+  long long nbytes;
+  const long long *desc, *lanes;
+  int N, nlanes, nh, *status, seg_bytes, *rounds;
+  int min_huff() const override { return 2; }   // a DC and an AC table
+  int launch(short *coef, const unsigned char *huff, unsigned char *, hipStream_t st) const override {
+    ProfScope ps(prof_key(kProfJpeg, seg_bytes ? 5 : 1), 0, st);
+    if (seg_bytes)
+      hipLaunchKernelGGL(jpeg_entropy_split_kernel, dim3((unsigned)nlanes), dim3(kJpegSplitThreads), 0, st,
+                         (const uint4 *)bytes, nbytes, desc, N, lanes, nlanes, huff, nh, coef, status, seg_bytes, rounds);
+    else
+      hipLaunchKernelGGL(jpeg_entropy_kernel, dim3((unsigned)((nlanes + kJpegLanes - 1) / kJpegLanes)), dim3(64), 0, st,
+                         (const uint4 *)bytes, nbytes, desc, N, lanes, nlanes, huff, nh, coef, status);
+    return XM_OK;
+  }
+};
+
+}  // namespace
+
+static int jpeg_decode_baseline(const unsigned char *bytes, long long nbytes, const long long *desc, int N, const long long *lanes,
+                                int nlanes, const unsigned char *tables, int nq, int nh, long long coef_elems,
+                                long long plane_bytes, long long pixel_floats, float *pixels, float *faces, float crop, int Ho,
+                                int Wo, const float *avg3, int *status, int seg_bytes, int *rounds, void *stream) {
+  BaselineStage stage;
+  stage.bytes = bytes;
+  stage.nbytes = nbytes;
+  stage.desc = desc;
+  stage.lanes = lanes;
+  stage.N = N;
+  stage.nlanes = nlanes;
+  stage.nh = nh;
+  stage.status = status;
+  stage.seg_bytes = seg_bytes;
+  stage.rounds = rounds;
+  return jpeg_decode_launch(bytes, nbytes, desc, N, lanes, nlanes, tables, nq, nh, coef_elems, plane_bytes, pixel_floats,
+                            pixels, faces, crop, Ho, Wo, avg3, status, stage, stream);
+}
+
+}  // namespace xm
+
 extern "C" {
 
 int xm_jpeg_decode_batch(const unsigned char *bytes, long long nbytes, const long long *desc, int N, const long long *lanes,
                          int nlanes, const unsigned char *tables, int nq, int nh, long long coef_elems,
                          long long plane_bytes, long long pixel_floats, float *pixels, float *faces, float crop, int Ho,
                          int Wo, const float *avg3, int *status, void *stream) {
-  return jpeg_decode_launch(bytes, nbytes, desc, N, lanes, nlanes, tables, nq, nh, coef_elems, plane_bytes, pixel_floats,
-                            pixels, faces, crop, Ho, Wo, avg3, status, 0, nullptr, stream);
+  return jpeg_decode_baseline(bytes, nbytes, desc, N, lanes, nlanes, tables, nq, nh, coef_elems, plane_bytes, pixel_floats,
+                              pixels, faces, crop, Ho, Wo, avg3, status, 0, nullptr, stream);
 }
 
 int xm_jpeg_decode_batch_split(const unsigned char *bytes, long long nbytes, const long long *desc, int N,
@@ -1082,8 +953,8 @@ int xm_jpeg_decode_batch_split(const unsigned char *bytes, long long nbytes, con
                                int *rounds, void *stream) {
   if (seg_bytes < 16 || seg_bytes > 65536 || (seg_bytes & 15))
     return fail(XM_EINVAL, "jpeg_decode_batch_split: seg_bytes must be a multiple of 16 in 16 .. 65536 (got %d)", seg_bytes);
-  return jpeg_decode_launch(bytes, nbytes, desc, N, lanes, nlanes, tables, nq, nh, coef_elems, plane_bytes, pixel_floats,
-                            pixels, faces, crop, Ho, Wo, avg3, status, seg_bytes, rounds, stream);
+  return jpeg_decode_baseline(bytes, nbytes, desc, N, lanes, nlanes, tables, nq, nh, coef_elems, plane_bytes, pixel_floats,
+                              pixels, faces, crop, Ho, Wo, avg3, status, seg_bytes, rounds, stream);
 }
 
 int xm_jpeg_split_geometry(int *segments_per_pass, int *launches) {

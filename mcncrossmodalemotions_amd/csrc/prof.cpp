@@ -59,6 +59,7 @@ static const ProfRow kProfRows[] = {
     // inexact (tests assert on this string): sub-key 4 is the family name, misc.hip picks the <false> / <true> instantiation
     {kProfJpeg, 6, {"jpeg_clear_kernel", "jpeg_entropy_kernel", "jpeg_idct_kernel", "jpeg_colour_kernel",
                     "crop_resize_face_ragged_kernel", "jpeg_entropy_split_kernel"}},
+    {kProfJpegProg, 3, {"jpeg_entropy_prog_kernel", "jpeg_smooth_kernel", "jpeg_smooth_dc_kernel"}},
     {kProfWav, 1, {"wav_decode_kernel"}},
     {kProfPixcsv, 1, {"pixcsv_decode_kernel"}},
     // inexact: the register-window rows name the N = 5 instantiation (the VGG-M family's) for every window width

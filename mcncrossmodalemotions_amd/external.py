@@ -248,13 +248,15 @@ def compute_audio_feats_files(dag, files, numEmotions=8, limit=float("inf"), max
 
 
 def compute_visual_feats(dag, track_frames, batchSize=128, numEmotions=8, limit=float("inf"), lanes=2, *, read=None,
-                         split=None, modelDir=None):
+                         split=None, progressive=False, modelDir=None):
     """faceLogits = compute_visual_feats(dag, track_frames): the frames of all tracks are flattened
     (:63-69), pushed through the frozen teacher `batchSize` at a time (:81-94) and the logits are split
     back per track (:104-109).  track_frames: list of 224 x 224 x 3 x F_i normalised face mats; with
     `read(paths) -> list of bytes` a list of frame-path lists instead, and every batch comes from
-    fetch_emovoxceleb_imdb.getImageBatch (:123-164: the JPEG files decoded on the device; `split` goes there).
+    fetch_emovoxceleb_imdb.getImageBatch (:123-164: the JPEG files decoded on the device; `split` and `progressive` go there).
     `dag` may be a model name, as upstream (:49 ferPlusZoo(opts.modelName)); `modelDir` then names the model files' directory."""
+    if progressive and split is not None:
+        raise ValueError("compute_visual_feats: progressive=True and split= exclude each other (vl.imreadjpeg)")
     if isinstance(dag, str):
         dag = zoo.ferPlusZoo(dag, modelDir=modelDir)
     _prepare(dag)
@@ -264,7 +266,8 @@ def compute_visual_feats(dag, track_frames, batchSize=128, numEmotions=8, limit=
         counts = [len(track_frames[i]) for i in first_ok]
         paths = [p for i in first_ok for p in track_frames[i]]
         teacher = zoo.FrozenTeacher(dag, lanes=lanes)
-        outs = [teacher.logits(fe.getImageBatch(paths[s:s + batchSize], dag, read=read, split=split))
+        outs = [teacher.logits(fe.getImageBatch(paths[s:s + batchSize], dag, read=read, split=split,
+                                                progressive=progressive))
                 for s in range(0, len(paths), batchSize)]
         logits = (np.concatenate([vl.to_numpy(o).reshape(-1, int(o.shape[3]), order="F").T for o in outs], 0)
                   if outs else np.zeros((0, numEmotions), np.float32))

@@ -143,12 +143,15 @@ def read_files(faceDir):
 
 
 def getImageBatch(imagePaths, dag, *, read=None, faceDir=os.path.join("data", "voxceleb", "faces"), device=None,
-                  split=None):
+                  split=None, progressive=False):
     """data = getImageBatch(imagePaths, dag) -- :152-193: vl_imreadjpeg with CropSize 1/1.6, CropLocation center,
     bilinear Resize to meta.normalization.imageSize (:160-172), rgb2gray, x3 and normalizeFace (:176-193), all on the
     device from the files' bytes (vl.imreadjpeg).  `read(paths) -> list of bytes` (default: the files under faceDir);
     `dag`: a network with meta.normalization, or an object with .imageSize / .averageImage.  Ho x Wo x 3 x n; nothing
-    is synchronised.  `split`: vl.imreadjpeg's seg_bytes (the segment-parallel entropy decode; the same faces)."""
+    is synchronised.  `split`: vl.imreadjpeg's seg_bytes (the segment-parallel entropy decode; the same faces).
+    `progressive`: vl.imreadjpeg's option of that name -- progressive files are read too, as vl_imreadjpeg reads them."""
+    if progressive and split is not None:
+        raise ValueError("getImageBatch: progressive=True and split= exclude each other (vl.imreadjpeg)")
     if hasattr(dag, "meta"):
         imageSize, avg = tuple(dag.meta["normalization"]["imageSize"][:2]), dag.meta["normalization"]["averageImage"]
     else:
@@ -156,7 +159,7 @@ def getImageBatch(imagePaths, dag, *, read=None, faceDir=os.path.join("data", "v
     read = read or read_files(faceDir)
     return vl.imreadjpeg(read(list(imagePaths)), resize=imageSize, crop_size=1 / 1.6, crop_location="center",
                          interpolation="bilinear", pack=True, num_threads=10, average_image=avg, device=device,
-                         split=split)
+                         split=split, progressive=progressive)
 
 
 class _Norm:
@@ -165,7 +168,7 @@ class _Norm:
 
 
 def buildImdb(teacher, imdb, frames=None, *, read=None, limit=math.inf, batchSize=128, lanes=2, device=None,
-              split=None):
+              split=None, progressive=False):
     """imdb = buildImdb(teacher) -- :54-149, for an imdb that went through addFramesToImdb.  `teacher`: a ferPlusZoo
     network (losses are stripped, test mode, one input: :101-110) or any object with .logits(faces) -> 1 x 1 x E x n;
     `frames(paths, device)` -> the decoded frames Hin x Win x 3 x n (0..255), what vl_imreadjpeg returns for
@@ -173,12 +176,14 @@ def buildImdb(teacher, imdb, frames=None, *, read=None, limit=math.inf, batchSiz
       wavLogits        host list, one F_i x E float32 array per wav (empty past `limit`), downloaded once;
       device_logits()  the same rows concatenated on the device, already in place.
     With `read(paths) -> list of bytes` instead of `frames` the batch comes from getImageBatch: the JPEG files are
-    decoded on the device (frames of any sizes in one batch); `split` goes to getImageBatch.
+    decoded on the device (frames of any sizes in one batch); `split` and `progressive` go to getImageBatch.
     The loop enqueues work only; it neither synchronises nor downloads."""
+    if progressive and split is not None:
+        raise ValueError("buildImdb: progressive=True and split= exclude each other (vl.imreadjpeg)")
     if (frames is None) == (read is None):
         raise ValueError("buildImdb: give either `frames` (decoded pixels) or `read` (JPEG bytes)")
-    if split is not None and read is None:
-        raise ValueError("buildImdb: `split` belongs to the device JPEG decode, which needs `read`")
+    if (split is not None or progressive) and read is None:
+        raise ValueError("buildImdb: `split` and `progressive` belong to the device JPEG decode, which needs `read`")
     if not torch.cuda.is_available():
         raise RuntimeError("buildImdb needs a GPU; this build has no CPU path")
     device = device or torch.device("cuda", torch.cuda.current_device())
@@ -197,7 +202,8 @@ def buildImdb(teacher, imdb, frames=None, *, read=None, limit=math.inf, batchSiz
         batch = range(start, min(start + int(batchSize), numIms))
         paths = [images["denseFrames"][i] for i in batch]
         if read is not None:
-            faces = getImageBatch(paths, _Norm(imageSize, avg), read=read, device=device, split=split)    # :152-193
+            faces = getImageBatch(paths, _Norm(imageSize, avg), read=read, device=device, split=split,
+                                  progressive=progressive)                               # :152-193
         else:
             data = frames(paths, device)                                                 # vl_imreadjpeg (:160-172)
             faces = vl.crop_resize_face(data, avg, imageSize)                            # getImageBatch (:152-193)
@@ -268,16 +274,19 @@ def load_imdb(path):
 
 
 def fetch_emovoxceleb_imdb(teacher="senet50-ferplus", imdbDir=os.path.join("data", "xEmo18", "storedFeats"), *,
-                           net=None, imdb=None, frames=None, read=None, split=None, verbose=True, modelDir=None,
+                           net=None, imdb=None, frames=None, read=None, split=None, progressive=False, verbose=True,
+                           modelDir=None,
                            **buildOpts):
     """loadedImdb = fetch_emovoxceleb_imdb(teacher, 'imdbDir', ..) -- :1-51: the cached imdb of (teacher, imdbDir), else
     <imdbDir>/<teacher>-logits.mat when it exists, else buildImdb and save.  Building needs (keyword-only) `net` (default
     zoo.ferPlusZoo(teacher, modelDir=modelDir): with `modelDir` the teacher's model file), `imdb` (an imdb that went through addFramesToImdb; default a 64-track synthetic one) and
-    `frames` or `read` (with `split`, as buildImdb); buildOpts go to buildImdb (limit, batchSize, lanes).  A loaded
+    `frames` or `read` (with `split` or `progressive`, as buildImdb); buildOpts go to buildImdb (limit, batchSize, lanes).  A loaded
     imdb uploads its logits on first use.
     The cache key and the file name hold the teacher's NAME and imdbDir, nothing else: a later call with another
     `net`, `imdb`, `frames` or `limit` under the same name and directory gets the first build back, from the module
     cache or from the file.  Use another imdbDir (or call buildImdb) for a different build."""
+    if progressive and split is not None:
+        raise ValueError("fetch_emovoxceleb_imdb: progressive=True and split= exclude each other (vl.imreadjpeg)")
     key = (str(teacher), os.path.abspath(imdbDir))
     if key in _CACHE:                                                                    # :19-20
         if verbose:
@@ -300,7 +309,7 @@ def fetch_emovoxceleb_imdb(teacher="senet50-ferplus", imdbDir=os.path.join("data
             raise ValueError("fetch_emovoxceleb_imdb: building needs `frames` for the given imdb")
         loaded = buildImdb(net if net is not None else zoo.ferPlusZoo(teacher, modelDir=modelDir), imdb,
                            frames if read is None else None,
-                           read=read, split=split, **buildOpts)
+                           read=read, split=split, progressive=progressive, **buildOpts)
         save_imdb(imdbPath, loaded)
     _CACHE[key] = loaded
     return loaded

@@ -1424,46 +1424,64 @@ def ferplus_batch(grey, transforms, flips, average_image, image_size=(224, 224))
 
 
 # --------------------------------------------------------------------------------------------
-# vl_imreadjpeg (fetch_emovoxceleb_imdb.m:160-172, compute_visual_feats.m:130-143): baseline JPEG decode on the device
+# vl_imreadjpeg (fetch_emovoxceleb_imdb.m:160-172, compute_visual_feats.m:130-143): baseline JPEG decode on the device,
+# progressive files too with progressive=True
 # --------------------------------------------------------------------------------------------
 JPEG_DESC, JPEG_LANE, JPEG_QT_BYTES, JPEG_HT_BYTES = 24, 4, 128, 1024          # include/xmodal.h XM_JPEG_*
 JPEG_OK, JPEG_TRUNCATED, JPEG_BADCODE = 0, 1, 2
+JPEG_SCAN = 24                                                                  # XM_JPEG_SCAN: int64 per scan row
 
 
-def jpeg_plan(files, stage=None):
+def jpeg_plan(files, stage=None, progressive=False):
     """The host side of imreadjpeg (xm_jpeg_plan; touches no device): `files` is a list of bytes.  Lays one staging
     buffer out as [file bytes | desc | lanes | tables] (16-byte aligned parts), parses every header into it and returns
     (stage, plan): `stage` a uint8 numpy array (`stage(nbytes)`, when given, allocates it -- imreadjpeg hands out
     pinned memory) and plan = dict(N, nbytes, desc, lanes, tables: (offset, used bytes) in the buffer, sizes: the
-    eight int64 of xm_jpeg_plan).  An unsupported or malformed file raises _lib.XmError naming its index."""
+    eight int64 of xm_jpeg_plan).  An unsupported or malformed file raises _lib.XmError naming its index.
+    progressive=True plans with xm_jpeg_plan_prog instead, which also accepts progressive (SOF2) files: the buffer is
+    [file bytes | desc | scans | lanes | tables], the plan has `scans` too and the eleven sizes of xm_jpeg_plan_prog, and
+    jpeg_decode runs it through xm_jpeg_decode_batch_prog."""
     N = len(files)
     lens = np.array([len(f) for f in files], np.int64)
     offsets = np.concatenate([[0], np.cumsum(lens)]).astype(np.int64)
     up = lambda v: (int(v) + 15) & ~15
     nbytes = int(offsets[-1])
     lanes_cap = N + 1024
+    scans_cap = 16 * N if progressive else 0
+    tab_cap = N * (3 * JPEG_QT_BYTES + (24 if progressive else 6) * JPEG_HT_BYTES)
     while True:
         o_desc = up(nbytes + 1)
-        o_lanes = up(o_desc + 8 * JPEG_DESC * N)
+        o_scans = up(o_desc + 8 * JPEG_DESC * N)
+        o_lanes = up(o_scans + 8 * JPEG_SCAN * scans_cap)
         o_tab = up(o_lanes + 8 * JPEG_LANE * lanes_cap)
-        tab_cap = N * (3 * JPEG_QT_BYTES + 6 * JPEG_HT_BYTES)
         total = up(o_tab + tab_cap)
         buf = stage(total) if stage is not None else np.empty(total, np.uint8)
         for f, o in zip(files, offsets):
             buf[o:o + len(f)] = np.frombuffer(f, np.uint8)
         buf[nbytes:o_desc] = 0
-        sizes = np.zeros(8, np.int64)
+        sizes = np.zeros(11 if progressive else 8, np.int64)
         base = buf.ctypes.data
-        rc = _L().xm_jpeg_plan(C.c_void_p(base), C.c_void_p(offsets.ctypes.data), N, C.c_void_p(base + o_desc),
-                               C.c_void_p(base + o_lanes), lanes_cap, C.c_void_p(base + o_tab), tab_cap,
-                               C.c_void_p(sizes.ctypes.data))
-        if rc == 2 and int(sizes[6]) > lanes_cap:          # XM_ENOMEM: more restart intervals than assumed
-            lanes_cap = int(sizes[6])
-            continue
+        if progressive:
+            rc = _L().xm_jpeg_plan_prog(C.c_void_p(base), C.c_void_p(offsets.ctypes.data), N, C.c_void_p(base + o_desc),
+                                        C.c_void_p(base + o_scans), scans_cap, C.c_void_p(base + o_lanes), lanes_cap,
+                                        C.c_void_p(base + o_tab), tab_cap, C.c_void_p(sizes.ctypes.data))
+            if rc == 2 and (int(sizes[8]) > scans_cap or int(sizes[6]) > lanes_cap or int(sizes[0]) > tab_cap):
+                scans_cap, lanes_cap, tab_cap = (max(scans_cap, int(sizes[8])), max(lanes_cap, int(sizes[6])),
+                                                 max(tab_cap, int(sizes[0])))          # XM_ENOMEM: the need is reported
+                continue
+        else:
+            rc = _L().xm_jpeg_plan(C.c_void_p(base), C.c_void_p(offsets.ctypes.data), N, C.c_void_p(base + o_desc),
+                                   C.c_void_p(base + o_lanes), lanes_cap, C.c_void_p(base + o_tab), tab_cap,
+                                   C.c_void_p(sizes.ctypes.data))
+            if rc == 2 and int(sizes[6]) > lanes_cap:          # XM_ENOMEM: more restart intervals than assumed
+                lanes_cap = int(sizes[6])
+                continue
         _lib.check(rc)
         break
     plan = dict(N=N, nbytes=nbytes, sizes=sizes, desc=(o_desc, 8 * JPEG_DESC * N),
                 lanes=(o_lanes, 8 * JPEG_LANE * int(sizes[6])), tables=(o_tab, int(sizes[0])), total=total)
+    if progressive:
+        plan["scans"] = (o_scans, 8 * JPEG_SCAN * int(sizes[8]))
     return buf, plan
 
 
@@ -1480,7 +1498,11 @@ def jpeg_decode(buf, plan, *, want_pixels=True, resize=None, crop=1.0, average_i
     xm_jpeg_decode_batch.  Returns (pixels ragged float32 | None, faces Ho x Wo x 3 x N | None, status int32[N], desc
     numpy N x 24).  Nothing is synchronised.  split=seg_bytes (a multiple of 16 in 16 .. 65536) decodes the entropy data
     segment-parallel (xm_jpeg_decode_batch_split): the same pixels, faces and status bit for bit; return_rounds=True then
-    appends the int32 device vector of decode rounds per lane."""
+    appends the int32 device vector of decode rounds per lane.  A plan made with progressive=True goes through
+    xm_jpeg_decode_batch_prog (one entropy launch per level of the batch's scans; no split)."""
+    prog = "scans" in plan
+    if prog and split is not None:
+        raise ValueError("jpeg_decode: split does not apply to a progressive plan")
     if split is None and return_rounds:
         raise ValueError("jpeg_decode: return_rounds needs split")
     if split is not None and (int(split) != split or not 16 <= split <= 65536 or split % 16):
@@ -1492,7 +1514,7 @@ def jpeg_decode(buf, plan, *, want_pixels=True, resize=None, crop=1.0, average_i
     head = plan["desc"][0] + plan["desc"][1]
     with torch.cuda.device(device):
         dev[:head].copy_(host[:head], non_blocking=True)
-        for o, n in (plan["lanes"], plan["tables"]):
+        for o, n in (plan["lanes"], plan["tables"]) + ((plan["scans"],) if prog else ()):
             dev[o:o + n].copy_(host[o:o + n], non_blocking=True)
         pixels = torch.empty(int(sizes[5]), dtype=torch.float32, device=device) if want_pixels else None
         faces, avg, Ho, Wo = None, None, 0, 0
@@ -1507,7 +1529,10 @@ def jpeg_decode(buf, plan, *, want_pixels=True, resize=None, crop=1.0, average_i
                 int(sizes[6]), C.c_void_p(p + plan["tables"][0]), int(sizes[1]), int(sizes[2]), int(sizes[3]), int(sizes[4]),
                 int(sizes[5]), _ptr(pixels), _ptr(faces), float(crop), Ho, Wo, avg, _ptr(status)]
         rounds = None
-        if split is None:
+        if prog:
+            _lib.check(_L().xm_jpeg_decode_batch_prog(*args, C.c_void_p(p + plan["scans"][0]), int(sizes[8]), int(sizes[9]),
+                                                      int(sizes[10]), _stream()))
+        elif split is None:
             _lib.check(_L().xm_jpeg_decode_batch(*args, _stream()))
         else:
             if return_rounds:
@@ -1522,7 +1547,8 @@ def _pinned(nbytes):
 
 
 def imreadjpeg(files, resize=None, crop_size=None, crop_location="center", interpolation="bilinear", pack=True,
-               num_threads=None, *, prefetch=False, average_image=None, device=None, return_status=False, split=None):
+               num_threads=None, *, prefetch=False, average_image=None, device=None, return_status=False, split=None,
+               progressive=False):
     """vl_imreadjpeg (fetch_emovoxceleb_imdb.m:160-172, compute_visual_feats.m:130-143) for baseline JPEG files, decoded
     on the device: `files` is a list of bytes or of paths.  Option names follow vl_imreadjpeg; `num_threads` is accepted
     and ignored (there are no decoder threads), only 'center' and 'bilinear' exist, `prefetch` raises.
@@ -1535,7 +1561,13 @@ def imreadjpeg(files, resize=None, crop_size=None, crop_location="center", inter
     not synchronise; return_status=True also returns the int32 device vector of JPEG_OK / JPEG_TRUNCATED / JPEG_BADCODE
     bits.  Progressive, arithmetic-coded, 12-bit, multi-scan, CMYK files and unusual sampling factors raise before
     anything is launched, with the index of the file; there is no host decode to fall back to.  split=seg_bytes: the
-    segment-parallel entropy decode of jpeg_decode, for files without restart markers; the same result bit for bit."""
+    segment-parallel entropy decode of jpeg_decode, for files without restart markers; the same result bit for bit.
+    progressive=True also reads progressive (SOF2) files, as vl_imreadjpeg does: every scan script T.81 allows, files that
+    end after any scan; a baseline file in such a batch gives what it gives without the option.  A scan script libjpeg
+    would only warn about raises.  The option excludes split=."""
+    if progressive and split is not None:
+        raise ValueError("imreadjpeg: progressive=True and split= exclude each other (progressive scans are not decoded "
+                         "segment-parallel)")
     if prefetch:
         raise ValueError("imreadjpeg: 'Prefetch' is not supported: the call already returns without waiting")
     if str(crop_location).lower() != "center":
@@ -1555,7 +1587,7 @@ def imreadjpeg(files, resize=None, crop_size=None, crop_location="center", inter
                 datas.append(fh.read())
     if not datas:
         return ([], None) if return_status else []
-    buf, plan = jpeg_plan(datas, stage=_pinned)
+    buf, plan = jpeg_plan(datas, stage=_pinned, progressive=progressive)
     pixels, faces, status, desc = jpeg_decode(buf, plan, want_pixels=resize is None, resize=resize,
                                               crop=1.0 if crop_size is None else float(crop_size),
                                               average_image=average_image, device=device, split=split)

@@ -1,6 +1,6 @@
 #!/usr/bin/env python
 """Timing of vl.imreadjpeg (xm_jpeg_plan / xm_jpeg_decode_batch) in front of the frozen teacher.
-usage: python tools/jpeg_bench.py [--teacher senet50-ferplus] [--batches 12] [--reps 10] [--split]
+usage: python tools/jpeg_bench.py [--teacher senet50-ferplus] [--batches 12] [--reps 10] [--split | --progressive]
 128 files of 256 x 256, 4:2:0, quality 90, smooth-plus-noise content (made with PIL when it is importable; otherwise the
 golden files of tests/golden/jpeg_small.npz repeated, and the PIL lines are left out).  Prints
  (a) ms per batch of each decode kernel (the library's profiler hook) and of the host parse and the enqueue;
@@ -9,7 +9,10 @@ golden files of tests/golden/jpeg_small.npz repeated, and the PIL lines are left
      teacher alone measured in the same process.
 --split prints instead, in one call on the same files, the table of the segment-parallel entropy decode (imreadjpeg's
 split=): the entropy kernel's time unsplit and at seg_bytes 64 / 128 / 256 / 512 with the mean and the maximum of the
-rounds per lane, the whole decode back to back, and buildImdb's loop unsplit, split and fed by PIL on 10 threads."""
+rounds per lane, the whole decode back to back, and buildImdb's loop unsplit, split and fed by PIL on 10 threads.
+--progressive prints, in one call, the same images encoded baseline and progressive (imreadjpeg's progressive=; needs
+PIL): the entropy stage per batch of each (the progressive one is a launch per level), the launches per call, the whole
+decode back to back, and buildImdb's loop fed each."""
 import argparse
 import io
 import os
@@ -37,7 +40,7 @@ def timeit(fn, reps):
     return s.elapsed_time(e) / reps * 1e-3
 
 
-def make_files(n):
+def make_files(n, progressive=False):
     try:
         from PIL import Image
     except ImportError:
@@ -49,7 +52,8 @@ def make_files(n):
     out = []
     for i in range(n):
         buf = io.BytesIO()
-        Image.fromarray(mk.smooth_noise(5000 + i, 256, 256, 3), "RGB").save(buf, "JPEG", quality=90, subsampling=2)
+        Image.fromarray(mk.smooth_noise(5000 + i, 256, 256, 3), "RGB").save(buf, "JPEG", quality=90, subsampling=2,
+                                                                            progressive=progressive)
         out.append(buf.getvalue())
     return out, True
 
@@ -148,6 +152,37 @@ def split_table(a, L, files, have_pil):
         print("    split=%d against the PIL-fed loop:           %.2f x" % (best, rates[keys[1]] / rates[keys[2]]))
 
 
+def progressive_table(a, L, files):
+    prog, _ = make_files(128, progressive=True)
+    print("the same images progressive: %.1f kB on average" % (sum(map(len, prog)) / 128e3))
+    face = dict(resize=(224, 224), crop_size=1 / 1.6, average_image=fe.AVERAGE_IMAGE)
+    want = vl.imreadjpeg(files, **face)
+    runs = [("baseline files, default path", lambda: vl.imreadjpeg(files, **face)),
+            ("baseline files, progressive=True", lambda: vl.imreadjpeg(files, progressive=True, **face)),
+            ("progressive files, progressive=True", lambda: vl.imreadjpeg(prog, progressive=True, **face))]
+    print("per batch of 128 (the library's profiler hook): the entropy stage, all launches of a call, the whole decode back to back")
+    print("    %-38s %12s %10s %10s %12s" % ("", "entropy ms", "launches", "calls ms", "decode ms"))
+    for label, fn in runs:
+        got = fn()
+        assert torch.equal(got.contiguous().view(torch.int32), want.contiguous().view(torch.int32)), label
+        with prof.recording(L):
+            for _ in range(a.reps):
+                fn()
+        rows = prof.collect(L)
+        entropy = sum(r.ms for r in rows if "entropy" in r.name) / a.reps
+        print("    %-38s %12.3f %10d %10.3f %12.3f" % (label, entropy, sum(r.launches for r in rows) // a.reps,
+                                                       sum(r.ms for r in rows) / a.reps, timeit(fn, a.reps) * 1e3))
+    teacher, imdb, n, alone = loop_setup(a, want)
+    print("buildImdb loop, %s, batch 128, %d frames" % (a.teacher, n))
+    print("    FrozenTeacher.logits alone (prepared faces)   %9.1f img/s  = %.3f ms per batch" % (alone, 128 / alone * 1e3))
+    for label, src in [("baseline files, default path", dict(read=lambda ps: [files[int(p)] for p in ps])),
+                       ("progressive files, progressive=True", dict(read=lambda ps: [prog[int(p)] for p in ps], progressive=True))]:
+        fe.buildImdb(teacher, imdb, batchSize=128, **src)
+        for rep in range(2):
+            r = loop_rate(teacher, imdb, n, **src)
+            print("    %-45s %9.1f img/s  (%+.1f %% vs alone)" % (label, r, 100 * (r / alone - 1)))
+
+
 def pil_frames_fn(files):
     """frames(paths, device) for buildImdb: PIL on 10 host threads, uploaded from pinned memory"""
     from PIL import Image
@@ -167,6 +202,7 @@ def main():
     ap.add_argument("--batches", type=int, default=12)
     ap.add_argument("--reps", type=int, default=10)
     ap.add_argument("--split", action="store_true", help="the table of the segment-parallel entropy decode")
+    ap.add_argument("--progressive", action="store_true", help="baseline against progressive encodings of the same images")
     a = ap.parse_args()
     dev = torch.device("cuda", 0)
     torch.cuda.set_device(0)
@@ -177,6 +213,10 @@ def main():
                                                   sum(map(len, files)) / 128e3))
     if a.split:
         return split_table(a, L, files, have_pil)
+    if a.progressive:
+        if not have_pil:
+            raise SystemExit("--progressive needs PIL to encode the files")
+        return progressive_table(a, L, files)
     full = lambda: vl.imreadjpeg(files, resize=(224, 224), crop_size=1 / 1.6, average_image=fe.AVERAGE_IMAGE)   # noqa: E731
     full()
     torch.cuda.synchronize()
