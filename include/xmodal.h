@@ -57,7 +57,7 @@ enum { XM_FUSE_RELU = 1, XM_BN_BATCH_MOMENTS = 2, XM_FUSE_SIGMOID = 4 };
 
 /* ABI revision: 100 = round 1; 101 = xm_nnbnorm_relu_pool_backward gained `y_pool`, exchange entry points return
  * XM_EINVAL without a communicator; 102 = + xm_nnconv_forward_moments, xm_nnbnorm_backward_dxsum, xm_nnconv_forward_gated;
- * 103 = + xm_nnpool_global_avg_backward_accum; 104 = + xm_nnconv_backward_filter_bnrelupool, xm_nndropout_forward / _apply, xm_resample, xm_se_tail_backward_reduce / _apply, xm_se_squeeze_bn, xm_scale_axpy_bn; 105 = + xm_set_exec_hint / xm_get_exec_hint; 106 = + xm_nnconv_bnorm_relu_pool_forward, xm_stem_gram, xm_stem_gram_moments, xm_nnconv_backward_filter_bnrelupool_gram; 107 = + xm_nnaffinegrid / _backward, xm_nnbilinearsampler / _backward, xm_ferplus_batch; 108 = + XM_AGG_PEAK, xm_mnrfit, xm_mnrval; 109 = + xm_roc, xm_roc_launches, xm_label_hist; 110 = + xm_group_rows, xm_gather_rows, xm_scatter_rows, xm_track_peaks; 111 = + xm_wav_batch; 112 = + xm_spec_bucket_batch; 113 = + xm_jpeg_plan, xm_jpeg_decode_batch; 114 = + xm_wav_plan, xm_wav_decode_batch; 115 = + xm_jpeg_decode_batch_split, xm_jpeg_split_geometry; 116 = + xm_pixcsv_plan, xm_pixcsv_decode_batch, xm_pixcsv_geometry; 117 = + xm_nnconv_forward_strided_residual; 118 = + xm_solver_update; 119 = + xm_nnnormalize_forward / _backward, xm_nnnormalize_geometry; 120 = + xm_jpeg_plan_prog, xm_jpeg_decode_batch_prog (additions never change the revision's meaning for older bindings).  A binding checks xm_version() >= the revision it was written against. */
+ * 103 = + xm_nnpool_global_avg_backward_accum; 104 = + xm_nnconv_backward_filter_bnrelupool, xm_nndropout_forward / _apply, xm_resample, xm_se_tail_backward_reduce / _apply, xm_se_squeeze_bn, xm_scale_axpy_bn; 105 = + xm_set_exec_hint / xm_get_exec_hint; 106 = + xm_nnconv_bnorm_relu_pool_forward, xm_stem_gram, xm_stem_gram_moments, xm_nnconv_backward_filter_bnrelupool_gram; 107 = + xm_nnaffinegrid / _backward, xm_nnbilinearsampler / _backward, xm_ferplus_batch; 108 = + XM_AGG_PEAK, xm_mnrfit, xm_mnrval; 109 = + xm_roc, xm_roc_launches, xm_label_hist; 110 = + xm_group_rows, xm_gather_rows, xm_scatter_rows, xm_track_peaks; 111 = + xm_wav_batch; 112 = + xm_spec_bucket_batch; 113 = + xm_jpeg_plan, xm_jpeg_decode_batch; 114 = + xm_wav_plan, xm_wav_decode_batch; 115 = + xm_jpeg_decode_batch_split, xm_jpeg_split_geometry; 116 = + xm_pixcsv_plan, xm_pixcsv_decode_batch, xm_pixcsv_geometry; 117 = + xm_nnconv_forward_strided_residual; 118 = + xm_solver_update; 119 = + xm_nnnormalize_forward / _backward, xm_nnnormalize_geometry; 120 = + xm_jpeg_plan_prog, xm_jpeg_decode_batch_prog; 121 = + xm_window_targets (additions never change the revision's meaning for older bindings).  A binding checks xm_version() >= the revision it was written against. */
 int xm_version(void);
 const char *xm_last_error(void);
 /* Device memory for hosts that have no device-array type of their own (MATLAB's gpuArray is CUDA-only: on an
@@ -529,6 +529,17 @@ int xm_aggregate_logits(const float *frame_logits, int F_total, int E, const int
                         void *stream);
 /* getBatchEmoVoxCeleb.m:32: [~, maxLabel] = max(lgo, [], 3); x is 1 x 1 x C x N, labels 1-based */
 int xm_max_label(const float *x, int C, int N, float *labels, void *stream);
+/* getBatchEmoVoxCeleb.m:30-32,145-158,179-188 in ONE launch, straight from the teacher's output (ABI 121): logits is
+ * 1 x 1 x E x n as the frozen teacher wrote it (frame f's E logits contiguous), first / last are 1-based inclusive rows
+ * into those n frames.  Pair j: the max or mean over its rows of emotions 1..P (lgo = lgo(:,:,1:numPredEmotions,:))
+ * -> out 1 x 1 x P x N, and max_label[j] = the first maximum of those P values, 1-based.  Bit for bit what
+ * xm_aggregate_logits on the transposed n x E copy, the channel cut and xm_max_label give: the mean is summed in
+ * ascending row order, a NaN is dropped by max, propagated by mean and never wins the label, an empty range gives -Inf
+ * (max) or 0 / (last - first + 1) (mean: NaN when first == last + 1) and label 1.  Rows are clamped to [0, n).
+ * XM_EINVAL: E outside 1..64, P outside 1..E, n < 0, N < 0, an unknown agg (XM_AGG_PEAK included), a NULL tensor with
+ * N > 0; N == 0: XM_OK. */
+int xm_window_targets(const float *logits, int E, int n, const int *first, const int *last, int N, int agg, int P,
+                      float *out, float *max_label, void *stream);
 /* mcnExtraLayers dagnn.ErrorStats bookkeeping (emoVoxZoo.m:165-169, read by extractStats,
  * run_distillation.m:186-207): for every sample n with label c = labels[n] (1-based):
  * population[c-1] += 1, correct[c-1] += (argmax_c x(:, n) == c).  ACCUMULATES into the two

@@ -112,6 +112,7 @@ SIGNATURES = {
     "xm_spec_bucket_batch": [c_fp, C.c_longlong, c_fp, _i, _i, c_fp, _i, _i, _i, c_fp, _vp],
     "xm_aggregate_logits": [c_fp, _i, _i, c_fp, c_fp, _i, _i, c_fp, c_fp, _vp],
     "xm_max_label": [c_fp, _i, _i, c_fp, _vp],
+    "xm_window_targets": [c_fp, _i, _i, c_fp, c_fp, _i, _i, _i, c_fp, c_fp, _vp],
     "xm_class_stats": [c_fp, c_fp, _i, _i, c_fp, c_fp, _vp],
     "xm_normalize_face": [c_fp, _i, _i, _i, C.POINTER(C.c_float), c_fp, _vp],
     "xm_crop_resize_face": [c_fp, _i, _i, _i, _f, _i, _i, C.POINTER(C.c_float), c_fp, _vp],

@@ -16,6 +16,9 @@ shapes the tensors the hot path consumes, fed from seeded synthetic sources:
     audioinfo / audioread        getBatchEmoVoxCeleb.m:79,97-117,126   -> WavFileEmoVoxImdb: the bank decoded from WAV files
                                                                        on the device (vl.audioread, xm_wav_decode_batch)
     target selection + maxLabel  getBatchEmoVoxCeleb.m:30-32
+    the teacher inside the batch fetch_emovoxceleb_imdb.m:98-136 per batch -> OnlineTeacher: the frames a batch's windows name
+                                 (online_frame_plan) decoded, evaluated and aggregated (HIP xm_window_targets) on a
+                                 stream of its own; no wavLogits cache
     face normalisation           fetch_emovoxceleb_imdb.m:176-193   -> HIP xm_normalize_face
     dense face frames            fetch_emovoxceleb_imdb.m:127,196-285 -> SyntheticDenseFrames (lister, find, decoded frames)
     FER+ batch (getBatchFerPlus) ferplus_baselines.m:153-268        -> HIP xm_ferplus_batch (grey -> flip -> x3 minus
@@ -429,6 +432,165 @@ def crop_window(total_samples, audSamp, fs, num_logit_rows, rng, fixedSegments=F
     return wr, s, min(e, int(num_logit_rows))
 
 
+def frame_index(imdb):
+    """(counts, order) of the frame lists of an imdb that went through addFramesToImdb: counts[ii] frames belong to
+    track ii (denseFramesWavIds == images.id[ii]) and order holds their positions in images.denseFrames, track after
+    track in imdb order, each track in list order -- the grouping buildImdb gets from vl.group_rows.  Host only; kept
+    with the imdb for as long as it holds the same `images`."""
+    images = imdb.images
+    held = imdb.__dict__.get("_frame_index")
+    if held is None or held[0] is not images:
+        ids = np.asarray(images["id"], np.int64)
+        wav = np.asarray(images["denseFramesWavIds"], np.int64)
+        by_id = np.argsort(wav, kind="stable")                  # frames grouped by wav id, list order inside a group
+        lo, hi = np.searchsorted(wav[by_id], ids, "left"), np.searchsorted(wav[by_id], ids, "right")
+        order = np.concatenate([by_id[a:b] for a, b in zip(lo, hi)] or [np.zeros(0, np.int64)])
+        held = imdb.__dict__["_frame_index"] = (images, (hi - lo).astype(np.int64), order.astype(np.int64))
+    return held[1], held[2]
+
+
+def logit_rows(imdb):
+    """(rows, offsets): the row count of every track's teacher logits and the row offsets of their concatenation
+    (num_tracks + 1 values).  From the cached imdb.wavLogits when there are any, else from the frame lists: a track has
+    one row per listed frame (frame_index).  Host only."""
+    if getattr(imdb, "wavLogits", None) is not None:
+        return np.array([l.shape[0] for l in imdb.wavLogits], np.int64), np.asarray(imdb.logit_offsets())
+    rows, _ = frame_index(imdb)
+    return rows, np.concatenate([[0], np.cumsum(rows)]).astype(np.int64)
+
+
+def online_frame_plan(imdb, first, last, framesPerPair="all", frame_rng=None):
+    """Which frame files the windows [first[k], last[k]] of wav_batch_plan name (1-based inclusive rows of the
+    concatenated per-track logits), for an imdb that went through addFramesToImdb; it needs no wavLogits.  Row r of
+    track ii is the r-th entry of images.denseFrames whose denseFramesWavIds equals images.id[ii], in list order.
+    Returns (paths, wfirst, wlast): the frames to decode, pair after pair, each window in ascending row order, and the
+    windows as 1-based inclusive int32 ranges into that compact list.
+      framesPerPair = k   keeps k rows of a window longer than k, drawn without replacement from `frame_rng` (a generator
+                          of its own: the audio crops of a run do not depend on it) and sorted; a window of at most k
+                          rows keeps them all and draws nothing
+      an empty window     (first > last) contributes no frames and keeps its length last - first + 1 <= 0, so that the
+                          mean over it is the cached mode's 0 / (last - first + 1).
+    Touches no device."""
+    if framesPerPair != "all" and (isinstance(framesPerPair, str) or int(framesPerPair) < 1):
+        raise ValueError("framesPerPair: 'all' or a positive number of frames, got %r" % (framesPerPair,))
+    first, last = np.asarray(first, np.int64).reshape(-1), np.asarray(last, np.int64).reshape(-1)
+    if first.shape != last.shape:
+        raise ValueError("online_frame_plan: first and last differ in length")
+    _, offs = logit_rows(imdb)
+    counts, order = frame_index(imdb)
+    foffs = np.concatenate([[0], np.cumsum(counts)])
+    frames = imdb.images["denseFrames"]
+    frame_rng = frame_rng if frame_rng is not None else np.random.default_rng(0)
+    paths = []
+    wfirst, wlast = np.zeros(len(first), np.int32), np.zeros(len(first), np.int32)
+    for k, (a, b) in enumerate(zip(first, last)):
+        wfirst[k] = len(paths) + 1
+        if a > b:
+            wlast[k] = len(paths) + (b - a + 1)
+            continue
+        if a < 1 or b > offs[-1]:
+            raise ValueError("online_frame_plan: window %d = [%d, %d] leaves the %d rows of the imdb" % (k, a, b, offs[-1]))
+        rows = np.arange(a - 1, b)                                      # 0-based rows of the concatenated logits
+        if framesPerPair != "all" and len(rows) > int(framesPerPair):
+            rows = rows[np.sort(frame_rng.choice(len(rows), int(framesPerPair), replace=False))]
+        ii = np.searchsorted(offs, rows, "right") - 1                   # the track of every row
+        r = rows - offs[ii]
+        if (r >= counts[ii]).any():
+            raise ValueError("online_frame_plan: window %d asks for a row its track lists no frame for" % k)
+        paths += [frames[j] for j in order[foffs[ii] + r]]
+        wlast[k] = len(paths)
+    return paths, wfirst, wlast
+
+
+class BatchInputs(list):
+    """the inputs list of a getBatch whose tensors are produced on another stream: `input_events` {input name:
+    torch.cuda.Event} goes to net.eval(..., input_events=...); a plain list has none"""
+    input_events = None
+
+
+class OnlineTeacher:
+    """The frozen teacher run inside the batch provider: the targets of a batch come from the face frames its windows
+    name instead of from imdb.wavLogits (fetch_emovoxceleb_imdb.m:98-136 per batch, not over the whole dataset).
+      teacher   a ferPlusZoo network (losses stripped, test mode, one input, wrapped in FrozenTeacher(lanes)) or any
+                object with .logits(faces) -> 1 x 1 x E x n
+      imdb      has been through addFramesToImdb; needs no wavLogits
+      read(paths) -> JPEG bytes (fetch_emovoxceleb_imdb.getImageBatch; `split`, `progressive` go there), or
+      frames(paths, device) -> decoded pixels (vl.crop_resize_face); exactly one of the two
+      chunk     at most that many faces per teacher call
+      framesPerPair, seed   online_frame_plan's option and the seed of its generator
+      overlap   the whole of targets() is enqueued on a stream of the object's own that first waits for the calling
+                stream; the returned event is recorded behind the targets.  False: the calling stream, event None.
+    Nothing synchronises the host."""
+
+    def __init__(self, teacher, imdb, *, read=None, frames=None, lanes=2, chunk=128, framesPerPair="all", overlap=True,
+                 split=None, progressive=False, seed=0):
+        from . import fetch_emovoxceleb_imdb as fe
+        if progressive and split is not None:
+            raise ValueError("OnlineTeacher: progressive=True and split= exclude each other (vl.imreadjpeg)")
+        if (frames is None) == (read is None):
+            raise ValueError("OnlineTeacher: give either `frames` (decoded pixels) or `read` (JPEG bytes)")
+        if (split is not None or progressive) and read is None:
+            raise ValueError("OnlineTeacher: `split` and `progressive` belong to the device JPEG decode, which needs `read`")
+        if int(chunk) < 1:
+            raise ValueError("OnlineTeacher: chunk must be at least one face")
+        online_frame_plan(imdb, [], [], framesPerPair)                   # refuses a bad framesPerPair before any device work
+        if not torch.cuda.is_available():
+            raise RuntimeError("OnlineTeacher needs a GPU; this build has no CPU path")
+        self.model, self.imageSize, self.averageImage = fe._as_teacher(teacher, lanes)
+        self._norm = fe._Norm(self.imageSize, self.averageImage)
+        self._getImageBatch = fe.getImageBatch
+        self.imdb, self.read, self.frames = imdb, read, frames
+        self.chunk, self.framesPerPair, self.split, self.progressive = int(chunk), framesPerPair, split, bool(progressive)
+        self.frame_rng = np.random.default_rng(seed)
+        self.device = getattr(teacher, "device", None) or torch.device("cuda", torch.cuda.current_device())
+        self.overlap = bool(overlap)
+        self.stream = torch.cuda.Stream(device=self.device) if self.overlap else None
+
+    def faces(self, paths):
+        """the normalised faces of a list of frames, imageSize x 3 x n"""
+        if self.read is not None:
+            return self._getImageBatch(paths, self._norm, read=self.read, device=self.device, split=self.split,
+                                       progressive=self.progressive)
+        return vl.crop_resize_face(self.frames(paths, self.device), self.averageImage, self.imageSize)
+
+    def logits(self, paths):
+        """1 x 1 x E x n teacher logits of the frames, evaluated `chunk` faces at a time"""
+        n, out = len(paths), None
+        for a in range(0, n, self.chunk):
+            lg = self.model.logits(self.faces(paths[a:a + self.chunk]))
+            if n <= self.chunk:
+                return lg
+            if out is None:
+                out = vl.mat_empty(1, 1, int(lg.shape[2]), n, device=self.device)
+            out[..., a:a + self.chunk].copy_(lg)
+        return out
+
+    def _targets(self, paths, wfirst, wlast, numPredEmotions, agg):
+        up = torch.from_numpy(np.stack([wfirst, wlast])).pin_memory().to(self.device, non_blocking=True)
+        # a batch of empty windows only: there is no frame to evaluate, the targets are those of empty ranges
+        lg = self.logits(paths) if paths else vl.mat_zeros(1, 1, int(numPredEmotions), 1, device=self.device)
+        if numPredEmotions > lg.shape[2]:
+            raise ValueError("numPredEmotions exceeds the number of the teacher's logits")
+        return vl.window_targets(lg, up[0], up[1], agg, numPredEmotions)
+
+    def targets(self, first, last, numPredEmotions=8, agg="max"):
+        """(lgo 1 x 1 x P x N, maxLabel 1 x 1 x 1 x N, event) of the windows [first, last] of wav_batch_plan"""
+        if agg not in ("max", "mean"):
+            raise ValueError("unreccognised aggregator %s" % agg)
+        paths, wfirst, wlast = online_frame_plan(self.imdb, first, last, self.framesPerPair, self.frame_rng)
+        if not self.overlap:
+            return self._targets(paths, wfirst, wlast, int(numPredEmotions), agg) + (None,)
+        main = torch.cuda.current_stream(self.device)
+        self.stream.wait_stream(main)
+        with torch.cuda.stream(self.stream):
+            lgo, lab = self._targets(paths, wfirst, wlast, int(numPredEmotions), agg)
+            ev = torch.cuda.Event()
+            ev.record(self.stream)
+        lgo.record_stream(main)        # made on the teacher stream, read (and freed) by the caller's
+        lab.record_stream(main)
+        return lgo, lab, ev
+
+
 def wav_batch_plan(imdb, batch, W, transformation, rng, fixedSegments=False, timeOffsets=None):
     """The host side of one batch of cnn_get_batch_wav_emo (getBatchEmoVoxCeleb.m:76-158): every random draw, in the
     reference's order per clip -- speedR (:103), the crop offset wr (:106 | :111), then Nir, Nwr, Nratio (:125-133) --
@@ -444,13 +606,14 @@ def wav_batch_plan(imdb, batch, W, transformation, rng, fixedSegments=False, tim
     audSamp = aud_samples(W)
     L = int(round(audSamp))
     chspeed, _, noisy = findSettings(transformation)
-    woffs, noffs, loffs = imdb.wav_offsets(), imdb.noise_offsets(), imdb.logit_offsets()
+    woffs, noffs = imdb.wav_offsets(), imdb.noise_offsets()
+    nrows, loffs = logit_rows(imdb)          # from the frame lists when the imdb has no cached logits (OnlineTeacher)
     desc = np.zeros((N, 6), np.int64)
     ratio = np.zeros(N, np.float32)
     first = np.zeros(N, np.int32)
     last = np.zeros(N, np.int32)
     for k, ii in enumerate(batch):
-        total, rows = int(imdb.num_samples[ii]), imdb.wavLogits[ii].shape[0]
+        total, rows = int(imdb.num_samples[ii]), int(nrows[ii])
         p = q = fs
         if chspeed and not fixedSegments:
             # :102-108 -- draw order as upstream: speed first, then the crop offset; the window read is audSampR long
@@ -511,7 +674,8 @@ def wav_clips(imdb, batch, desc, ratio, L, device):
 
 def getBatchEmoVoxCeleb(imdb, batch, imageSize=(512, 300), numPredEmotions=8, logitAggregator="max",
                         lossType="hot-cross-ent", transformation="I", rng=None, spec_source=None,
-                        device=None, use_wav=False, fixedSegments=False, timeOffsets=None, wavBatch=False):
+                        device=None, use_wav=False, fixedSegments=False, timeOffsets=None, wavBatch=False,
+                        onlineTeacher=None):
     """inputs = getBatchEmoVoxCeleb(imdb, batch, ...) -> ['data', im, 'logitTarget', lgo,
     'maxLabel', maxLabel] (getBatchEmoVoxCeleb.m:31-43).  Spectrogram magnitudes come from
     `spec_source` (H x W x 1 x N device tensor), from the imdb's waveforms through the device
@@ -523,7 +687,11 @@ def getBatchEmoVoxCeleb(imdb, batch, imageSize=(512, 300), numPredEmotions=8, lo
     `fixedSegments` (:91-101, :136-137; off upstream, run_distillation.m:86): the crop of clip k starts at
     timeOffsets[k] seconds, clips are not thresholded to DATASET_LIMIT, and ALL cached logit rows of the clip are
     aggregated.  (Upstream always passes timeOffsets = [] (:15), so the branch cannot run there; an offset list is
-    required here.)"""
+    required here.)
+    `onlineTeacher` (an OnlineTeacher over this imdb): the same draws and the same spectrogram path, but logitTarget and
+    maxLabel come from onlineTeacher.targets -- the teacher evaluated on the frames the windows name -- and the imdb needs
+    no wavLogits.  The returned list is a BatchInputs whose input_events {'logitTarget': ev, 'maxLabel': ev} belong to
+    net.eval(..., input_events=...) (None when the teacher ran on the calling stream)."""
     device = device or torch.device("cuda", torch.cuda.current_device())
     rng = rng or np.random.default_rng(0)
     batch = list(batch)
@@ -533,9 +701,15 @@ def getBatchEmoVoxCeleb(imdb, batch, imageSize=(512, 300), numPredEmotions=8, lo
     chspeed, _, noisy = findSettings(transformation)
     if (chspeed or noisy) and not (use_wav and spec_source is None):
         raise ValueError("transformations 'S' / 'N' act on the waveform: they need use_wav=True")
-    logits, _ = imdb.device_logits(device)
+    if onlineTeacher is None:
+        logits, _ = imdb.device_logits(device)
     from_wav = spec_source is None and use_wav
     desc, ratio, first, last = wav_batch_plan(imdb, batch, W, transformation, rng, fixedSegments, timeOffsets)
+    events = None
+    if onlineTeacher is not None:
+        # first of all, so that the teacher's stream works while this one makes the spectrograms
+        lgo, maxLabel, ev = onlineTeacher.targets(first, last, numPredEmotions, logitAggregator)
+        events = {"logitTarget": ev, "maxLabel": ev} if ev is not None else None
     if from_wav and wavBatch:
         wav, _ = imdb.device_wav_bank(device)
         noise = imdb.device_noise_bank(device)[0] if noisy else None
@@ -550,15 +724,18 @@ def getBatchEmoVoxCeleb(imdb, batch, imageSize=(512, 300), numPredEmotions=8, lo
         raw = torch.randn((N, 1, W, H), generator=g, device=device, dtype=torch.float32).abs_()
         spec_source = raw.permute(3, 2, 1, 0)
     im = vl.spec_rownorm(spec_source) if "I" in transformation else spec_source
-    lgo, maxLabel = vl.aggregate_logits(logits, torch.from_numpy(first).to(device),
-                                        torch.from_numpy(last).to(device), logitAggregator)
-    if numPredEmotions > lgo.shape[2]:
-        raise ValueError("numPredEmotions exceeds the number of cached logits")
-    if numPredEmotions != lgo.shape[2]:
-        # lgo = lgo(:,:,1:opts.numPredEmotions,:) ; [~, maxLabel] = max(lgo, [], 3)  (:30-32)
-        lgo = lgo[:, :, :numPredEmotions, :].permute(3, 2, 1, 0).contiguous().permute(3, 2, 1, 0)
-        maxLabel = vl.max_label(lgo)
-    inputs = ["data", im]
+    if onlineTeacher is None:
+        lgo, maxLabel = vl.aggregate_logits(logits, torch.from_numpy(first).to(device),
+                                            torch.from_numpy(last).to(device), logitAggregator)
+        if numPredEmotions > lgo.shape[2]:
+            raise ValueError("numPredEmotions exceeds the number of cached logits")
+        if numPredEmotions != lgo.shape[2]:
+            # lgo = lgo(:,:,1:opts.numPredEmotions,:) ; [~, maxLabel] = max(lgo, [], 3)  (:30-32)
+            lgo = lgo[:, :, :numPredEmotions, :].permute(3, 2, 1, 0).contiguous().permute(3, 2, 1, 0)
+            maxLabel = vl.max_label(lgo)
+    inputs = BatchInputs(["data", im]) if onlineTeacher is not None else ["data", im]
+    if events is not None:
+        inputs.input_events = events
     if lossType == "softmaxlog":
         inputs += ["maxLabel", maxLabel]
     elif lossType == "euclidean":

@@ -677,6 +677,43 @@ __global__ void max_label_kernel(const float *__restrict__ x, int C, int N, floa
   lab[n] = (float)(arg + 1);
 }
 
+// lgo = aggregate(logits(rows of pair n)) ; lgo = lgo(:,:,1:P,:) ; [~, maxLabel] = max(lgo, [], 3)
+// (getBatchEmoVoxCeleb.m:145-158,179-188,30-32) straight from the teacher's 1 x 1 x E x F output: no transposed copy.
+// One lane per (pair, emotion): G = the power of two >= P lanes of a wave form a pair's group (G <= 64 = blockDim, so a
+// group never straddles a wave), lane e walks the rows of emotion e in ascending order -- the summation order of
+// aggregate_logits_kernel, whose arithmetic this repeats expression for expression -- and the label is a scan of the
+// group's P values through __shfl in max_label_kernel's order.  Every lane reaches every __shfl; rows are clamped to
+// [0, F), the mean still divides by the caller's row count as aggregate_logits_kernel does.
+__global__ void __launch_bounds__(64)
+window_targets_kernel(const float *__restrict__ lg, int E, int F, const int *__restrict__ first,
+                      const int *__restrict__ last, int N, int agg, int P, int G, float *__restrict__ out,
+                      float *__restrict__ max_label) {
+  const int lane = threadIdx.x, e = lane % G, base = lane - e;
+  const int n = blockIdx.x * (64 / G) + lane / G;
+  const bool live = n < N && e < P;
+  float a = -INFINITY;
+  if (live) {
+    const int f0 = first[n] - 1, f1 = min(last[n], F);
+    a = agg == XM_AGG_MAX ? -INFINITY : 0.f;
+    for (int fr = max(f0, 0); fr < f1; ++fr) {
+      float v = lg[e + (size_t)E * fr];
+      a = agg == XM_AGG_MAX ? fmaxf(a, v) : a + v;
+    }
+    if (agg == XM_AGG_MEAN) a /= (float)(f1 - f0);
+    out[(size_t)P * n + e] = a;
+  }
+  float best = -INFINITY;
+  int arg = 0;
+  for (int c = 0; c < P; ++c) {
+    float v = __shfl(a, base + c, 64);
+    if (v > best) {
+      best = v;
+      arg = c;
+    }
+  }
+  if (live && e == 0) max_label[n] = (float)(arg + 1);
+}
+
 // one block; per-class counts through LDS atomics -- the addends are 0/1, so the float sums are
 // exact integers (< 2^24) whatever the order: deterministic
 __global__ void __launch_bounds__(256)
@@ -1214,6 +1251,23 @@ int xm_max_label(const float *x, int C, int N, float *labels, void *stream) {
   if (!x || !labels) return fail(XM_EINVAL, "max_label: NULL tensor");
   hipLaunchKernelGGL(max_label_kernel, dim3((N + 63) / 64), dim3(64), 0, (hipStream_t)stream, x, C, N,
                      labels);
+  XM_LAUNCH_CHECK();
+  return XM_OK;
+}
+
+int xm_window_targets(const float *logits, int E, int n, const int *first, const int *last, int N, int agg, int P,
+                      float *out, float *max_label, void *stream) {
+  if (E < 1 || E > 64) return fail(XM_EINVAL, "window_targets: E = %d, need 1 .. 64", E);
+  if (P < 1 || P > E) return fail(XM_EINVAL, "window_targets: numPredEmotions = %d, need 1 .. E = %d", P, E);
+  if (n < 0 || N < 0) return fail(XM_EINVAL, "window_targets: negative n or N");
+  if (agg != XM_AGG_MAX && agg != XM_AGG_MEAN) return fail(XM_EINVAL, "window_targets: unrecognised aggregator %d", agg);
+  if (N == 0) return XM_OK;
+  if (!first || !last || !out || !max_label || (n > 0 && !logits)) return fail(XM_EINVAL, "window_targets: NULL tensor");
+  int G = 1;
+  while (G < P) G *= 2;
+  const int per = 64 / G;
+  hipLaunchKernelGGL(window_targets_kernel, dim3((N + per - 1) / per), dim3(64), 0, (hipStream_t)stream, logits, E, n,
+                     first, last, N, agg, P, G, out, max_label);
   XM_LAUNCH_CHECK();
   return XM_OK;
 }

@@ -25,7 +25,9 @@ def run_distillation(gpus=(2,), cont=True, miniVal=0.2, numSeconds=4, batchSize=
                      parameterServer="tmove", wavDir=None,
                      *, imdb=None, dataDir="data/xEmo18", numTracks=256, widthMult=1.0, seed=0, verbose=False,
                      useWav=False, transformation="I", modelDir=None, solver=None, solverOpts=None,
-                     nesterovUpdate=False, momentum=0.9, weightDecay=5e-4):
+                     nesterovUpdate=False, momentum=0.9, weightDecay=5e-4,
+                     teacherMode="cached", teacherNet=None, read=None, frames=None, framesPerPair="all", teacherLanes=2,
+                     overlapTeacher=True, split=None, progressive=False):
     """Options as in run_distillation.m:72-90.  Extensions (keyword-only): `imdb` (a prepared imdb),
     `dataDir` (root of the experiment directories), `numTracks` / `seed` (synthetic imdb), `widthMult`
     (narrow student for tests), `useWav` (the batches come from the imdb's waveforms through the batched device
@@ -34,7 +36,24 @@ def run_distillation(gpus=(2,), cont=True, miniVal=0.2, numSeconds=4, batchSize=
     `modelDir` (emoVoxZoo's option: the student comes from <modelDir>/<student>.mat -- with fromScratch its architecture,
     without it the network as saved, loss heads included -- instead of the seeded stand-in); `solver`, `solverOpts`,
     `nesterovUpdate`, `momentum`, `weightDecay`: cnn_train_dag's options of those names (the defaults are the values the
-    call at :170-182 leaves to cnn_train_dag)."""
+    call at :170-182 leaves to cnn_train_dag).
+    `teacherMode` = 'online': the targets of every batch come from the frozen teacher run on the face frames the batch's
+    windows name (batch.OnlineTeacher) instead of from imdb.wavLogits; `imdb` is required, has been through
+    addFramesToImdb and needs no wavLogits.  The teacher is `teacherNet`, or zoo.ferPlusZoo(teacher, modelDir=modelDir);
+    the frames come from `read` (paths -> JPEG bytes, with `split` / `progressive`) or `frames` (paths, device -> decoded
+    pixels); `framesPerPair` ('all' | k frames drawn per window), `teacherLanes` and `overlapTeacher` are OnlineTeacher's
+    framesPerPair, lanes and overlap.  The experiment directory gains -online and -fppK.  Every data-parallel worker
+    runs its own replica of the teacher over its own shard."""
+    if teacherMode not in ("cached", "online"):
+        raise ValueError("teacherMode: 'cached' or 'online', got %r" % (teacherMode,))
+    online = teacherMode == "online"
+    if not online and (teacherNet is not None or read is not None or frames is not None or framesPerPair != "all"
+                       or split is not None or progressive):
+        raise ValueError("teacherNet, read, frames, framesPerPair, split and progressive belong to teacherMode='online'")
+    if online and imdb is None:
+        raise ValueError("teacherMode='online' needs an imdb with frame lists (fetch_emovoxceleb_imdb.addFramesToImdb)")
+    if online and (frames is None) == (read is None):
+        raise ValueError("teacherMode='online': give either `frames` (decoded pixels) or `read` (JPEG bytes)")
     gpus = list(np.atleast_1d(gpus))
     if miniEpochRatio is None:
         miniEpochRatio = 0.05 * len(gpus)                      # :77
@@ -50,6 +69,8 @@ def run_distillation(gpus=(2,), cont=True, miniVal=0.2, numSeconds=4, batchSize=
     expDir = os.path.join(dataDir, expName)
     if lossType == "hot-cross-ent":
         expDir += "-temp%d" % temperature
+    if online:      # other targets than the cached run's: its checkpoints are never resumed
+        expDir += "-online" + ("" if framesPerPair == "all" else "-fpp%d" % int(framesPerPair))
     # ParameterServer before the first device allocation / kernel of the process (xmodal.h "CALL ORDER": a communicator
     # created later slows every step); 'tmove' (run_distillation.m:88) = the library's communicator when there is
     # more than one worker and RCCL can carry it -- every worker of the node on its own device --, torch.distributed
@@ -78,6 +99,11 @@ def run_distillation(gpus=(2,), cont=True, miniVal=0.2, numSeconds=4, batchSize=
         valSamples = [valSamples[i] for i in sorted(pick)]
     epochSize = len(trainSamples) * miniEpochRatio                                    # :154
     brng = np.random.default_rng(seed + 17)
+    provider = None
+    if online:      # behind the communicator, like every device allocation
+        provider = xbatch.OnlineTeacher(teacherNet if teacherNet is not None else zoo.ferPlusZoo(teacher, modelDir=modelDir),
+                                        imdb, read=read, frames=frames, lanes=teacherLanes, framesPerPair=framesPerPair,
+                                        overlap=overlapTeacher, split=split, progressive=progressive, seed=seed + 23)
 
     def getBatch(imdb_, batch):                                                       # getBatchFn, :210-224
         tr = net.meta["augmentation"]["transformation"]
@@ -87,7 +113,7 @@ def run_distillation(gpus=(2,), cont=True, miniVal=0.2, numSeconds=4, batchSize=
                                           numPredEmotions=numPredEmotions, logitAggregator=logitAggregator,
                                           lossType=lossType, transformation=tr, rng=brng,
                                           fixedSegments=fixedSegments,             # bopts.fixedSegments, :220
-                                          use_wav=useWav, wavBatch=useWav)
+                                          use_wav=useWav, wavBatch=useWav, onlineTeacher=provider)
         # (fixedSegments = true fails upstream as well: getBatchEmoVoxCeleb.m:15 passes timeOffsets = [])
 
     return train.cnn_train_dag(net, imdb, getBatch, learningRate=learningRate, batchSize=batchSize,

@@ -582,10 +582,13 @@ def process_epoch(net, imdb, getBatch, subset, opts, epoch, mode, parserv=None, 
         shard = shard_batch(batch, rank, world)
         if mode == "train":
             inputs = getBatch(imdb, shard) if shard else None
-            train_step(net, inputs, opts, epoch, parserv, len(batch), local_batch=len(shard))
+            # (a getBatch whose targets are made on another stream says so: batch.BatchInputs.input_events)
+            train_step(net, inputs, opts, epoch, parserv, len(batch), local_batch=len(shard),
+                       input_events=getattr(inputs, "input_events", None))
         elif shard:
             net.mode = "test"
-            net.eval(getBatch(imdb, shard))
+            inputs = getBatch(imdb, shard)
+            net.eval(inputs, input_events=getattr(inputs, "input_events", None))
         num += len(batch)
         ahead.tick()
     merge_loss_stats(net, parserv)

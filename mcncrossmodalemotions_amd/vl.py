@@ -1019,6 +1019,31 @@ def aggregate_logits(frame_logits, first, last, agg="max"):
     return out, lab
 
 
+def window_targets(logits, first, last, agg="max", numPredEmotions=None):
+    """(logitTarget 1 x 1 x P x N, maxLabel 1 x 1 x 1 x N) of N windows straight from the teacher's 1 x 1 x E x n output
+    (getBatchEmoVoxCeleb.m:30-32,145-158,179-188; xm_window_targets): what aggregate_logits on the transposed n x E
+    copy, lgo(:,:,1:P,:) and max_label give, bit for bit, in one launch.  first / last: int32 device vectors, 1-based
+    inclusive rows into the n frames.  agg: "max" | "mean"; numPredEmotions P defaults to E."""
+    lg = _chk(logits, "LOGITS")
+    one, one_, E, n = _shape4(lg)
+    if one != 1 or one_ != 1:
+        raise ValueError("window_targets: expected the teacher's 1 x 1 x E x n logits")
+    if agg not in ("max", "mean"):
+        raise ValueError("unreccognised aggregator %s" % agg)
+    P = E if numPredEmotions is None else int(numPredEmotions)
+    N = int(first.numel())
+    for t, name in ((first, "first"), (last, "last")):
+        if t.dtype != torch.int32 or not t.is_cuda or not t.is_contiguous() or int(t.numel()) != N:
+            raise ValueError("window_targets: %s must be a contiguous int32 device vector of N entries" % name)
+    if not 1 <= P <= E:
+        raise ValueError("window_targets: numPredEmotions %d outside 1 .. %d" % (P, E))
+    out = mat_empty(1, 1, P, N, device=lg.device)
+    lab = mat_empty(1, 1, 1, N, device=lg.device)
+    _lib.check(_L().xm_window_targets(_ptr(lg), E, n, C.c_void_p(first.data_ptr()), C.c_void_p(last.data_ptr()), N,
+                                      _AGG[agg], P, _ptr(out), _ptr(lab), _stream()))
+    return out, lab
+
+
 # xm_mnrfit status codes (include/xmodal.h)
 MNR_CONVERGED, MNR_ITERLIMIT, MNR_NOTPD, MNR_BADINPUT = 0, 1, 2, 3
 
