@@ -174,8 +174,12 @@ int xm_nnconv_backward(const float *x, int H, int W, int C, int N, const float *
  * ~20 us per layer on the critical path of the backward pass.  xm_nnconv_prepare_backward builds it ahead of time
  * into a persistent buffer -- e.g. on a side stream while the forward pass of the same step runs -- and a later
  * xm_nnconv_backward with the same F pointer and geometry uses it (waiting on the device for it if it was built on
- * another stream).  Valid until the parameters change: xm_sgd_update / xm_average_update invalidate every prepared
- * operand; a host that updates parameters by other means calls xm_params_changed(). */
+ * another stream).  Valid until the parameters change: xm_sgd_update / xm_solver_update (every kind) / xm_average_update
+ * invalidate every prepared operand; a host that updates parameters by other means -- or frees a filter tensor, whose
+ * address the next allocation may reuse: the operands are keyed by F's address, the filter's size, the number of filter
+ * groups, stride, dilation, top / left padding and H, W (not N, nor bottom / right padding) -- calls xm_params_changed().
+ * From Python that is vl.params_changed(); dagnn calls it wherever DagNN.paramGeneration moves (pack_params, checkpoint
+ * loads, the training update) and when DagNN.move uploads parameters. */
 int xm_nnconv_prepare_backward(int H, int W, int C, int N, const float *f, int FH, int FW, int FC, int K,
                                int sy, int sx, int pt, int pb, int pl, int pr, int dy, int dx, void *stream);
 int xm_params_changed(void);

@@ -56,6 +56,9 @@ int xm_prof_kernel_name(int key, char *buf, int len);
  *                    0: the most recent forward with batch moments took them from a pass over Y instead
  *   "dgrad_last_transpose"  (read only) 1: the most recent dgrad filter operand came from transpose_filter_kernel, 0: from
  *                    prep_dgrad_filter_kernel (neither is profiled)
+ *   "dgrad_last_prepared"  (read only) where the most recent DZDX call (xm_nnconv_prepare_backward does not count) took its filter
+ *                    operand from: 1 = the operand xm_nnconv_prepare_backward had built, 0 = built inside the call, -1 = the call
+ *                    went a route without such an operand (conv_dgrad_s2_kernel, or no stride class that holds a tap)
  *   "conv_halo"      1 + v: halo-patch kernel variant v (0: 128-row tiles, 1: 96-row tiles, 2: 96-row tiles / tall patch) wherever it
  *                    can run, another runnable variant otherwise; 0: never; -1: measured choice (default)
  *   "conv_stem"      1: the single-channel stem kernels (conv_stem_kernel, conv_stem_wgrad_*; also gates the Gram route's kernels)

@@ -274,8 +274,11 @@ static int g_last_combine = 0;
 // launch_wgrad_patch / launch_wgrad_patch_s2 ("wgrad_last_splits"), S of the last bias-derivative launch
 // ("bias_grad_last_splits") and of the last forward_stats_reduce ("stats_last_splits": 0 when the most recent forward with
 // batch moments took them from a pass over Y instead); "dgrad_last_transpose": 1 when the
-// last dgrad filter operand was built by transpose_filter_kernel, 0 by prep_dgrad_filter_kernel
+// last dgrad filter operand was built by transpose_filter_kernel, 0 by prep_dgrad_filter_kernel; "dgrad_last_prepared": where
+// the last dgrad call (not a prepare) had its filter operand from -- 1 the prepared cache, 0 built in the call, -1 a route
+// without such an operand (conv_dgrad_s2_kernel, no stride class with taps)
 static int g_last_wgrad_splits = 0, g_last_bias_splits = 0, g_last_stats_splits = 0, g_last_dgrad_transpose = 0;
+static int g_last_dgrad_prepared = -1;
 
 // With few output tiles the reduction is split over grid.y; the split count fills ONE round of
 // 2 co-resident blocks per CU (no tail round).
@@ -1363,11 +1366,11 @@ static int conv_forward(const float *x, const float *f, const float *b, float *y
 // training step that is ~20 us per layer ON THE CRITICAL PATH of the backward pass.  xm_nnconv_prepare_backward
 // lets the host run the transposition early -- typically while the forward pass of the same step runs, on a
 // side stream -- into a persistent buffer; the backward call then finds it and skips the kernel.  An entry is
-// valid while the parameter version it was built at is current (xm_sgd_update / xm_average_update /
+// valid while the parameter version it was built at is current (xm_sgd_update / xm_solver_update / xm_average_update /
 // xm_params_changed bump the version) and the geometry matches.
 struct PrepKey {
   const float *f;
-  int FH, FW, FC, K, sy, sx, dy, dx, pt, pl, H, W, fold;
+  int FH, FW, FC, K, G, sy, sx, dy, dx, pt, pl, H, W, fold;   // (N, pb, pr do not shape the operand; C does through G)
   bool operator<(const PrepKey &o) const { return memcmp(this, &o, sizeof(PrepKey)) < 0; }
 };
 struct PrepEntry {
@@ -1382,7 +1385,7 @@ unsigned long long g_param_version = 1;   // bumped by every parameter update (m
 static PrepKey prep_key(const float *f, const Geo &g, bool fold) {
   PrepKey k;
   memset(&k, 0, sizeof k);
-  k.f = f, k.FH = g.FH, k.FW = g.FW, k.FC = g.FC, k.K = g.K, k.sy = g.sy, k.sx = g.sx, k.dy = g.dy, k.dx = g.dx;
+  k.f = f, k.FH = g.FH, k.FW = g.FW, k.FC = g.FC, k.K = g.K, k.G = g.G, k.sy = g.sy, k.sx = g.sx, k.dy = g.dy, k.dx = g.dx;
   k.pt = g.pt, k.pl = g.pl, k.H = g.H, k.W = g.W, k.fold = fold ? 1 : 0;
   return k;
 }
@@ -1512,6 +1515,7 @@ static int dgrad_filter_operand(const float *f, const Geo &g, const std::vector<
       have_prepared = true;
       if (pe->st != st) XM_HIP(hipStreamWaitEvent(st, pe->ev, 0));
     }
+    g_last_dgrad_prepared = have_prepared ? 1 : 0;
   }
   int rc = ws.init((pe ? 0 : abytes) + WsCarver::need(slab_floats, 4), st);
   if (rc) return rc;
@@ -1643,6 +1647,7 @@ static int dgrad_run_merged(const Geo &g, const std::vector<ConvGemmArgs> &merge
 // prepare_only: run just the filter transpositions into the persistent cache (xm_nnconv_prepare_backward)
 static int conv_dgrad(const float *f, const float *dzdy, float *dxo, const Geo &g, hipStream_t st,
                       const float *accum = nullptr, bool prepare_only = false) {
+  if (!prepare_only) g_last_dgrad_prepared = -1;   // until dgrad_filter_operand says where the operand came from
   if (dgrad_s2_ok(g, dzdy, dxo, accum)) {
     // the student's conv2: both row parities per wave, whole-line stores (conv_dgrad_s2_kernel); its filter operand is laid
     // out by a 3 MB pass inside the call, so there is nothing to prepare ahead
@@ -1997,6 +2002,7 @@ int xm_debug_get(const char *key) {
   if (key && strcmp(key, "bias_grad_last_splits") == 0) return g_last_bias_splits;
   if (key && strcmp(key, "stats_last_splits") == 0) return g_last_stats_splits;
   if (key && strcmp(key, "dgrad_last_transpose") == 0) return g_last_dgrad_transpose;
+  if (key && strcmp(key, "dgrad_last_prepared") == 0) return g_last_dgrad_prepared;
   const DebugSwitch *s = debug_switch(key);
   return s ? *s->value : INT_MIN;
 }

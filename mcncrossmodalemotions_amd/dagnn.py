@@ -532,6 +532,10 @@ class DagNN:
     @paramGeneration.setter
     def paramGeneration(self, v):
         self._gen[0] = int(v)
+        # the library's prepared dgrad operands (vl.conv_prepare_backward) are a cached view of the filters too, keyed by
+        # address: a checkpoint load writes new values at the old address, pack_params frees addresses for reuse
+        if self.device is not None:
+            vl.params_changed()
 
     # ---- construction -------------------------------------------------------------------
     def addLayer(self, name, block, inputs, outputs, params=()):
@@ -682,9 +686,13 @@ class DagNN:
         if device != "gpu":
             raise RuntimeError("this build has no CPU path (dag.move('cpu'))")
         self.device = torch.device("cuda", torch.cuda.current_device())
+        uploaded = False
         for p in self.params.values():
             if p.value is not None and not isinstance(p.value, torch.Tensor):
                 p.value = vl.from_numpy(p.value, self.device)
+                uploaded = True
+        if uploaded:
+            vl.params_changed()   # new device tensors may sit where a prepared filter of another net used to
         return self
 
     # ---- flat parameter storage -----------------------------------------------------------

@@ -258,6 +258,14 @@ def conv_prepare_backward(x, f, stride=1, pad=0, dilate=1):
                                                _stream()))
 
 
+def params_changed():
+    """Extension: xm_params_changed -- every operand conv_prepare_backward built so far is stale.  sgd_update,
+    solver_update and average_update say so themselves; call this after writing parameter values by any other means
+    (a torch copy_ into a filter tensor, a checkpoint load) and after giving parameters new storage (a freed filter's
+    address can be handed to the next tensor of its shape: the cache is keyed by address).  Host-side counter, no launch."""
+    _lib.check(_L().xm_params_changed())
+
+
 # --------------------------------------------------------------------------------------------
 # vl_nnpool
 # --------------------------------------------------------------------------------------------

@@ -555,6 +555,7 @@ def configureForRegression(net, lossType, numOutputs, dropout=0):
         # last layer are divided by 10
         p = net.params[net.layers[-1].params[0]]
         p.value = p.value / 10
+        net.paramGeneration += 1   # (on the device: new storage for the filters)
     elif lossType == "huber":
         layer, inputs = dagnn.HuberLoss(sigma=1), ["prediction", "logitTarget", "instanceWeights"]
     else:
