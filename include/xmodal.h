@@ -57,7 +57,7 @@ enum { XM_FUSE_RELU = 1, XM_BN_BATCH_MOMENTS = 2, XM_FUSE_SIGMOID = 4 };
 
 /* ABI revision: 100 = round 1; 101 = xm_nnbnorm_relu_pool_backward gained `y_pool`, exchange entry points return
  * XM_EINVAL without a communicator; 102 = + xm_nnconv_forward_moments, xm_nnbnorm_backward_dxsum, xm_nnconv_forward_gated;
- * 103 = + xm_nnpool_global_avg_backward_accum; 104 = + xm_nnconv_backward_filter_bnrelupool, xm_nndropout_forward / _apply, xm_resample, xm_se_tail_backward_reduce / _apply, xm_se_squeeze_bn, xm_scale_axpy_bn; 105 = + xm_set_exec_hint / xm_get_exec_hint; 106 = + xm_nnconv_bnorm_relu_pool_forward, xm_stem_gram, xm_stem_gram_moments, xm_nnconv_backward_filter_bnrelupool_gram; 107 = + xm_nnaffinegrid / _backward, xm_nnbilinearsampler / _backward, xm_ferplus_batch; 108 = + XM_AGG_PEAK, xm_mnrfit, xm_mnrval; 109 = + xm_roc, xm_roc_launches, xm_label_hist; 110 = + xm_group_rows, xm_gather_rows, xm_scatter_rows, xm_track_peaks; 111 = + xm_wav_batch; 112 = + xm_spec_bucket_batch; 113 = + xm_jpeg_plan, xm_jpeg_decode_batch; 114 = + xm_wav_plan, xm_wav_decode_batch; 115 = + xm_jpeg_decode_batch_split, xm_jpeg_split_geometry; 116 = + xm_pixcsv_plan, xm_pixcsv_decode_batch, xm_pixcsv_geometry; 117 = + xm_nnconv_forward_strided_residual; 118 = + xm_solver_update; 119 = + xm_nnnormalize_forward / _backward, xm_nnnormalize_geometry; 120 = + xm_jpeg_plan_prog, xm_jpeg_decode_batch_prog; 121 = + xm_window_targets (additions never change the revision's meaning for older bindings).  A binding checks xm_version() >= the revision it was written against. */
+ * 103 = + xm_nnpool_global_avg_backward_accum; 104 = + xm_nnconv_backward_filter_bnrelupool, xm_nndropout_forward / _apply, xm_resample, xm_se_tail_backward_reduce / _apply, xm_se_squeeze_bn, xm_scale_axpy_bn; 105 = + xm_set_exec_hint / xm_get_exec_hint; 106 = + xm_nnconv_bnorm_relu_pool_forward, xm_stem_gram, xm_stem_gram_moments, xm_nnconv_backward_filter_bnrelupool_gram; 107 = + xm_nnaffinegrid / _backward, xm_nnbilinearsampler / _backward, xm_ferplus_batch; 108 = + XM_AGG_PEAK, xm_mnrfit, xm_mnrval; 109 = + xm_roc, xm_roc_launches, xm_label_hist; 110 = + xm_group_rows, xm_gather_rows, xm_scatter_rows, xm_track_peaks; 111 = + xm_wav_batch; 112 = + xm_spec_bucket_batch; 113 = + xm_jpeg_plan, xm_jpeg_decode_batch; 114 = + xm_wav_plan, xm_wav_decode_batch; 115 = + xm_jpeg_decode_batch_split, xm_jpeg_split_geometry; 116 = + xm_pixcsv_plan, xm_pixcsv_decode_batch, xm_pixcsv_geometry; 117 = + xm_nnconv_forward_strided_residual; 118 = + xm_solver_update; 119 = + xm_nnnormalize_forward / _backward, xm_nnnormalize_geometry; 120 = + xm_jpeg_plan_prog, xm_jpeg_decode_batch_prog; 121 = + xm_window_targets; 122 = + xm_wav_plan_fs, xm_wav_decode_resample_batch, xm_wav_resample_geometry (additions never change the revision's meaning for older bindings).  A binding checks xm_version() >= the revision it was written against. */
 int xm_version(void);
 const char *xm_last_error(void);
 /* Device memory for hosts that have no device-array type of their own (MATLAB's gpuArray is CUDA-only: on an
@@ -852,7 +852,7 @@ int xm_jpeg_decode_batch_prog(const unsigned char *bytes, long long nbytes, cons
  *            3 NumChannels; 4 BitsPerSample; 5 format (XM_WAV_U8 .. XM_WAV_F64); 6 TotalSamples = floor(data bytes / block
  *            align) frames; 7 first frame decoded (0-based); 8 frames decoded; 9 channels written; 10 the channel
  *            selector; 11 first output float (out_base + the floats of the files before); 12 status (XM_WAV_TRUNCATED:
- *            the data chunk claimed more bytes than the file holds); 13 block align; 14, 15 zero
+ *            the data chunk claimed more bytes than the file holds); 13 block align; 14, 15 zero (xm_wav_plan_fs: p, q)
  *   sizes    XM_WAV_SIZES int64: output floats of the batch, N
  * Accepted: RIFF ... WAVE, chunks walked with the pad byte after odd sizes, unknown chunks (LIST, fact, bext ...) skipped
  * before and after `data`, `fmt ` before `data`, the first `data` chunk; format tag 1 (PCM 8 / 16 / 24 / 32 bits), 3
@@ -880,6 +880,39 @@ int xm_wav_plan(const unsigned char *bytes, const long long *offsets, int N, con
                 long long out_base, long long *desc, long long *sizes);
 int xm_wav_decode_batch(const unsigned char *bytes, long long nbytes, const long long *desc, int N, float *out,
                         long long out_floats, void *stream);
+
+/* WAV files of any rate resampled into the bank while they are decoded (ABI 122): [z, Fs] = audioread(f) followed by
+ * z = resample(z(:, c), fs, Fs), what compute_audio_feats.m:173-175 and emo_benchmarks need for RML / eNTERFACE / AFEW
+ * audio (22.05, 44.1, 48 kHz, often stereo) and upstream left to ffmpeg (getBatchEmoVoxCeleb.m:149).
+ *
+ * xm_wav_plan_fs: host only, no device call.  The parse, the refusals and the rows of xm_wav_plan, except that slots
+ *   14, 15 hold p, q = fs / SampleRate reduced by their gcd (1, 1 when the file is at fs already) and that slot 11 and
+ *   sizes[0] count OUTPUT floats: file i takes ceil(frames decoded * p / q) floats per channel written, a matrix of that
+ *   many rows in MATLAB layout (channel c at + c * rows).  Slot 8 stays the SOURCE frames decoded.  `ranges` are in source
+ *   frames, as in audioread(file, [a b]) followed by resample: samples outside the range count as zero, they are not the
+ *   file's neighbouring samples.  XM_ENOTSUP naming the file's index when, after the reduction, max(p, q) > 2^20 (the
+ *   limit of xm_wav_batch), q > 16 p or p > 16 q (these bound the tap loop, 20 max(p, q) / p + 1 taps per output, and
+ *   the window of source frames a tile keeps in LDS).  XM_EINVAL: fs < 1, and whatever xm_wav_plan refuses.
+ *
+ * xm_wav_decode_resample_batch: device, at most TWO launches whatever N, the formats, the rates and the lengths are --
+ *   one workgroup per file sums the filter's taps in fp64 for its gain, then one launch laid out by the output floats
+ *   decodes each tile's source window into LDS once and runs the taps from there.  No atomics, no tuning entries, no
+ *   synchronisation; the workspace holds the per-file gains only.  Arguments as xm_wav_decode_batch, with the rows of
+ *   xm_wav_plan_fs.  Output j of a channel is gain * sum_k u(j q - k p) x[k] over the decoded frames k, the taps, their
+ *   order (k descending) and the gain those of xm_wav_batch: the floats are bit for bit what xm_wav_batch returns for the
+ *   descriptor {src, frames, fs, SampleRate, 0, 0} on the bank xm_wav_decode_batch fills, and do not depend on what else
+ *   is in the batch or on where the tiles fall.  A file with p == q is copied: bit for bit xm_wav_decode_batch's floats.
+ *   Every float of the batch is written exactly once and nothing outside [0, out_floats); every byte read is clamped to
+ *   the file's data range, itself clamped to [0, nbytes); a row whose ratio is outside the plan's bounds is read as 1 / 1.
+ *   N == 0: XM_OK.  XM_EINVAL, before any device call: a negative argument, a NULL or misaligned pointer with N > 0.
+ *
+ * xm_wav_resample_geometry: host only.  tile: the output floats of one tile (at ratio 1 a tile is one run; at other
+ * ratios it is cut into runs whose source windows fit LDS); launches: what one decode-and-resample call enqueues. */
+int xm_wav_plan_fs(const unsigned char *bytes, const long long *offsets, int N, const long long *ranges, int channel,
+                   long long fs, long long out_base, long long *desc, long long *sizes);
+int xm_wav_decode_resample_batch(const unsigned char *bytes, long long nbytes, const long long *desc, int N, float *out,
+                                 long long out_floats, void *stream);
+int xm_wav_resample_geometry(int *tile, int *launches);
 
 /* The pixel column of the FER2013 CSV, decoded on the device into the image array of the FER+ imdb (ABI 116): what
  * imdb = getFerPlusImdb(opts.dataDir) (ferplus_baselines.m:103-110) reads before getBatchFerPlus gathers

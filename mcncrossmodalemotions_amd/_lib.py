@@ -141,6 +141,9 @@ SIGNATURES = {
                                   C.c_longlong, c_fp, c_fp, _f, _i, _i, C.POINTER(C.c_float), c_fp, c_fp, _i, _i, _i, _vp],
     "xm_wav_plan": [_vp, _vp, _i, _vp, _i, C.c_longlong, _vp, _vp],
     "xm_wav_decode_batch": [c_fp, C.c_longlong, c_fp, _i, c_fp, C.c_longlong, _vp],
+    "xm_wav_plan_fs": [_vp, _vp, _i, _vp, _i, C.c_longlong, C.c_longlong, _vp, _vp],
+    "xm_wav_decode_resample_batch": [c_fp, C.c_longlong, c_fp, _i, c_fp, C.c_longlong, _vp],
+    "xm_wav_resample_geometry": [C.POINTER(C.c_int), C.POINTER(C.c_int)],
     "xm_pixcsv_plan": [_vp, C.c_longlong, _vp, C.c_longlong, _vp],
     "xm_pixcsv_decode_batch": [c_fp, C.c_longlong, c_fp, _i, _i, _i, _i, c_fp, C.c_longlong, c_fp, _vp],
     "xm_pixcsv_geometry": [C.POINTER(C.c_int), C.POINTER(C.c_int)],

@@ -220,11 +220,17 @@ class WavFileEmoVoxImdb(SyntheticEmoVoxImdb):
                            `chunkBytes` of file bytes (out_base), so the staging buffer stays small next to the dataset
       device_wav(ii)       a view of the bank
       noisenum, noiselen   the number of noise files and the shortest of them (the reference has one `noiselen`);
-                           noise_offsets() are the real cumulative offsets"""
+                           noise_offsets() are the real cumulative offsets
+      resample=True        tracks and noise files of any rate vl.audioread(fs=) accepts are brought to `fs` while they
+                           are decoded (upstream converted such datasets with ffmpeg, :149); num_samples, noise_samples
+                           and noiselen are then the resampled lengths, from the plan alone
+      channel=c            files with several channels are read by that channel (compute_audio_feats.m:175 takes the
+                           left stream, c = 0); None keeps the refusal"""
 
     def __init__(self, files, wavLogits, set=None, names=None, fs=16000, noise=None, noiseNames=None, noisevol=0.3,
-                 chunkBytes=64 << 20, seed=0):
+                 chunkBytes=64 << 20, seed=0, resample=False, channel=None):
         self.fs, self.seed, self.noisevol, self.chunkBytes = int(fs), seed, noisevol, int(chunkBytes)
+        self.resample, self.channel = bool(resample), None if channel is None else int(channel)
         self._read, self.names = self._source(files, names)
         self.num_samples = self._lengths(self._read, self.names, "track")
         self.wavLogits = [np.asfortranarray(l, dtype=np.float32) for l in wavLogits]
@@ -275,13 +281,16 @@ class WavFileEmoVoxImdb(SyntheticEmoVoxImdb):
     def _lengths(self, read, names, what):
         total = np.zeros(len(names), np.int64)
         for s in range(0, len(names), 256):
-            info = vl.audioinfo(read(names[s:s + 256]))
+            info = vl.audioinfo(read(names[s:s + 256]), fs=self.fs if self.resample else None)
             for n, i in zip(names[s:s + 256], info):
-                if i["SampleRate"] != self.fs:
+                if i["SampleRate"] != self.fs and not self.resample:
                     raise ValueError("WavFileEmoVoxImdb: %s %r is sampled at %d Hz, the imdb at %d" % (what, n, i["SampleRate"], self.fs))
-                if i["NumChannels"] != 1:
+                if i["NumChannels"] != 1 and self.channel is None:
                     raise ValueError("WavFileEmoVoxImdb: %s %r has %d channels, one is required" % (what, n, i["NumChannels"]))
-            total[s:s + 256] = [i["TotalSamples"] for i in info]
+                if self.channel is not None and self.channel >= i["NumChannels"]:
+                    raise ValueError("WavFileEmoVoxImdb: %s %r has %d channels, channel %d was asked for" %
+                                     (what, n, i["NumChannels"], self.channel))
+            total[s:s + 256] = [i["ResampledSamples" if self.resample else "TotalSamples"] for i in info]
         return total
 
     def _bank(self, key, read, names, lengths, device):
@@ -297,7 +306,8 @@ class WavFileEmoVoxImdb(SyntheticEmoVoxImdb):
                         break
                     datas.append(d)
                     used += len(d)
-                _, got = vl.audioread(datas, out=bank, out_base=int(offs[s]))
+                _, got = vl.audioread(datas, out=bank, out_base=int(offs[s]), channel=self.channel,
+                                      fs=self.fs if self.resample else None)
                 if int(got[-1]) != int(offs[s + len(datas)]):
                     raise RuntimeError("WavFileEmoVoxImdb: the files changed since their lengths were read")
                 s += len(datas)

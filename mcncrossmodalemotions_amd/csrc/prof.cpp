@@ -61,6 +61,7 @@ static const ProfRow kProfRows[] = {
                     "crop_resize_face_ragged_kernel", "jpeg_entropy_split_kernel"}},
     {kProfJpegProg, 3, {"jpeg_entropy_prog_kernel", "jpeg_smooth_kernel", "jpeg_smooth_dc_kernel"}},
     {kProfWav, 1, {"wav_decode_kernel"}},
+    {kProfWavRate, 2, {"wav_rate_gain_kernel", "wav_resample_kernel"}},
     {kProfPixcsv, 1, {"pixcsv_decode_kernel"}},
     // inexact: the register-window rows name the N = 5 instantiation (the VGG-M family's) for every window width
     {kProfLrn, 6, {"lrn_forward_kernel<5, false>", "lrn_forward_kernel<5, true>", "lrn_backward_kernel<5, false>",

@@ -28,6 +28,7 @@ enum ProfKind {
   kProfPixcsv = 23,         // pixcsv.hip
   kProfLrn = 25,            // lrn.hip, sub = 2 * backward + 16-byte arm; 4 / 5: the general arm, forward / backward
   kProfJpegProg = 26,       // jpeg_prog.hip: the entropy launch of a level, the two smoothing launches
+  kProfWavRate = 27,        // wav.hip, decode + resample: sub = 0 the gains, 1 the data
 };
 constexpr int prof_key(ProfKind kind, int sub = 0) { return kind * 100 + sub; }
 

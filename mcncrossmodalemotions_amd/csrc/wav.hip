@@ -15,10 +15,18 @@
 //                        A dword index is clamped to the dwords that hold the file's data range, itself clamped to the
 //                        buffer; an output index is compared against the batch's range and out_floats before the store.
 //                        No atomics, no workspace; every output float has exactly one writer.
+//
+// xm_wav_plan_fs / xm_wav_decode_resample_batch (ABI 122) bring files of any rate to one: [z, Fs] = audioread(f);
+// z = resample(z(:, c), fs, Fs) for a whole batch in one pass, no native-rate bank in between.  TWO launches:
+//   wav_rate_gain_kernel  one workgroup per file: the fp64 sum of the filter's taps (wav_resample.h, shared with misc.hip)
+//   wav_resample_kernel   laid out by the output like the kernel above; a tile's (file, channel) pieces are cut into
+//                         runs whose source window fits LDS, the window is decoded once and the taps run from there.
+//                         Documented in front of the kernel, further down.
 #include <algorithm>
 
 #include "prof.h"
 #include "wav_plan.h"
+#include "wav_resample.h"
 #include "xm_common.h"
 
 namespace xm {
@@ -226,11 +234,174 @@ wav_decode_kernel(const uint32_t *__restrict__ words, long long nbytes, const lo
   }
 }
 
+// ---- decode and resample in one pass (xm_wav_decode_resample_batch) -----------------------------------------------
+// The plan's slots 14, 15 hold p, q = fs / SampleRate reduced; file i takes ceil(frames p / q) floats per channel written
+// and output j of a channel is gain sum_k u(j q - k p) x[k] over the decoded frames 0 <= k < frames (wav_resample.h; the
+// tap loop is wav_batch_kernel's, k descending, so the bits are those of xm_wav_batch on the decoded bank).  The work is
+// laid out by the OUTPUT as above: tiles of kWavRateTile output floats, the files of a tile found by bisection.  Inside a
+// tile the block walks the pieces (file, channel) and cuts each into runs of outputs whose source window -- at most
+// (n - 1) q / p + 20 max(p, q) / p + 1 frames for n outputs -- fits the kWavRateWin frames of LDS: the window is decoded
+// into LDS once and every tap reads it there.  p == q copies the decoded sample.  Every loop bound around a barrier is
+// block-uniform; a ratio outside the plan's bounds is treated as 1 / 1, so a forged descriptor cannot widen the window.
+constexpr int kWavRateTile = 2048;                  // output floats per tile
+constexpr int kWavRateWin = 4096;                   // source frames of one channel held in LDS (16 KB)
+static_assert(kWavPlanMaxRatio == kWavMaxRatio, "the plan refuses what xm_wav_batch's taps cannot take");
+static_assert(kWavRateWin - 1 >= 20 * kWavPlanMaxStep, "the window of a run of one output fits LDS at the steepest ratio");
+
+// wav_file with the resampled counts: p, q of the plan (1, 1 when unusable), frames per channel written at the new rate
+__device__ __forceinline__ WavFile wav_rate_file(const long long *__restrict__ desc, int i, long long nbytes, int &p, int &q,
+                                                 long long &oframes) {
+  WavFile f = wav_file(desc, i, nbytes);
+  const long long *d = desc + (long long)i * kWavDesc;
+  long long pp = d[WD_P], qq = d[WD_Q];
+  if (pp < 1 || qq < 1 || pp > kWavPlanMaxRatio || qq > kWavPlanMaxRatio || qq > kWavPlanMaxStep * pp || pp > kWavPlanMaxStep * qq)
+    pp = qq = 1;
+  f.frames = min(f.frames, 1LL << 32);
+  p = (int)pp;
+  q = (int)qq;
+  oframes = (f.frames * pp + qq - 1) / qq;
+  f.count = oframes * f.cw;
+  return f;
+}
+
+__global__ void __launch_bounds__(1024)
+wav_rate_gain_kernel(const long long *__restrict__ desc, WavClip *__restrict__ clip) {
+  const int n = blockIdx.x;
+  const long long *d = desc + (long long)n * kWavDesc;
+  wav_gain_block(d[WD_P], d[WD_Q], clip, n);
+}
+
+__global__ void __launch_bounds__(256)
+wav_resample_kernel(const uint32_t *__restrict__ words, long long nbytes, const long long *__restrict__ desc, int N,
+                    const WavClip *__restrict__ clip, uint32_t *__restrict__ out, long long out_floats) {
+  __shared__ uint32_t win[kWavRateWin];
+  const int tid = threadIdx.x;
+  // the batch's output range, inside [0, out_floats)
+  const long long lo = min(max(desc[WD_OUT], 0LL), out_floats);
+  long long hi;
+  {
+    int pl, ql;
+    long long ol;
+    const WavFile fl = wav_rate_file(desc, N - 1, nbytes, pl, ql, ol);
+    hi = min(max(fl.out + fl.count, lo), out_floats);
+  }
+  if (hi <= lo) return;
+  const long long ntiles = (hi - lo + kWavRateTile - 1) / kWavRateTile;
+  for (long long t = blockIdx.x; t < ntiles; t += gridDim.x) {
+    const long long ta = lo + t * kWavRateTile, tb = min(ta + kWavRateTile, hi);
+    const int i0 = wav_find(desc, 0, N - 1, ta), i1 = wav_find(desc, i0, N - 1, tb - 1);
+    for (int i = i0; i <= i1; ++i) {
+      int p, q;
+      long long oframes;
+      const WavFile f = wav_rate_file(desc, i, nbytes, p, q, oframes);
+      const long long a0 = max(ta, f.out), a1 = min(tb, f.out + f.count);
+      if (f.count <= 0 || a0 >= a1) continue;                 // a file of 0 frames, or one outside this tile
+      const float gain = p != q ? clip[i].gain : 1.f;
+      const int P = p > q ? p : q, half = 10 * P;
+      // outputs per run: (n - 1) q + 2 half <= (kWavRateWin - 1) p, whole passes of the block where it can be
+      long long run = ((long long)(kWavRateWin - 1) * p - 2LL * half) / q + 1;
+      run = min(max(run, 1LL), (long long)kWavRateTile);
+      if (run >= 256) run &= ~255LL;
+      const long long step = (long long)f.nch * f.bps;
+      const long long c0 = (a0 - f.out) / oframes, c1 = (a1 - 1 - f.out) / oframes;
+      for (long long c = c0; c <= c1; ++c) {
+        const long long cbase = f.out + c * oframes;
+        const long long jA = max(a0, cbase) - cbase, jB = min(a1, cbase + oframes) - cbase;
+        const long long pbase = f.begin + (f.sel >= 0 ? f.sel : c) * f.bps;
+        if (p == q) {                                          // the file's own rate: a copy of the decoded samples
+          for (long long j = jA + tid; j < jB; j += 256) out[cbase + j] = wav_sample(words, f, pbase + j * step);
+          continue;
+        }
+        for (long long j0 = jA; j0 < jB; j0 += run) {
+          const long long n = min(run, jB - j0);
+          // the window of the run: from the first tap of its first output to the last tap of its last, inside the file
+          const unsigned long long top0 = (unsigned long long)j0 * (unsigned)q + (unsigned)half;
+          const long long khi0 = (long long)(top0 / (unsigned)p);
+          const long long kbase = max(khi0 - (2 * half - (int)(top0 - (unsigned long long)khi0 * (unsigned)p)) / p, 0LL);
+          long long ktop = (long long)(((unsigned long long)(j0 + n - 1) * (unsigned)q + (unsigned)half) / (unsigned)p);
+          ktop = min(min(ktop, f.frames - 1), kbase + kWavRateWin - 1);
+          __syncthreads();                                     // the run before has been read
+          for (long long k = kbase + tid; k <= ktop; k += 256) win[k - kbase] = wav_sample(words, f, pbase + k * step);
+          __syncthreads();
+          for (long long j = j0 + tid; j < j0 + n; j += 256) {
+            const unsigned long long top = (unsigned long long)j * (unsigned)q + (unsigned)half;
+            const long long khi = (long long)(top / (unsigned)p);      // largest k with j q - k p >= -half
+            const int rem = (int)(top - (unsigned long long)khi * (unsigned)p);
+            const long long klo = khi - (2 * half - rem) / p;          // smallest k with j q - k p <= half
+            const long long k1 = khi < ktop ? khi : ktop, k0 = klo > kbase ? klo : kbase;
+            float v = 0.f;
+            if (k1 >= k0) {
+              int m = rem - half + (int)((khi - k1) * p);              // j q - k1 p
+              const int qd = (m + half) / P;                           // floor(m / P) + 10
+              int r = m + half - qd * P, odd = qd & 1;
+              const float invP = 1.f / (float)P, P_over_pi = (float)P * 0.318309886f,
+                          kb = kWavBeta2Over4 / ((float)half * (float)half);
+              float acc = 0.f;
+              for (int k = (int)(k1 - kbase); k >= (int)(k0 - kbase); --k) {
+                acc = fmaf(wav_tap(m, r, odd, P, invP, P_over_pi, half, kb), __uint_as_float(win[k]), acc);
+                m += p;
+                r += p;
+                if (r >= P) {
+                  r -= P;
+                  odd ^= 1;
+                }
+              }
+              v = acc * gain;
+            }
+            out[cbase + j] = __float_as_uint(v);
+          }
+        }
+      }
+    }
+  }
+}
+
 }  // namespace xm
 
 using namespace xm;
 
 extern "C" {
+
+int xm_wav_plan_fs(const unsigned char *bytes, const long long *offsets, int N, const long long *ranges, int channel,
+                   long long fs, long long out_base, long long *desc, long long *sizes) {
+  char msg[256];
+  msg[0] = 0;
+  const int rc = wav_plan_batch_fs(bytes, offsets, N, ranges, channel, fs, out_base, desc, sizes, msg, (int)sizeof msg);
+  return rc ? fail(rc, "%s", msg) : XM_OK;
+}
+
+int xm_wav_resample_geometry(int *tile, int *launches) {
+  if (tile) *tile = kWavRateTile;
+  if (launches) *launches = 2;
+  return XM_OK;
+}
+
+int xm_wav_decode_resample_batch(const unsigned char *bytes, long long nbytes, const long long *desc, int N, float *out,
+                                 long long out_floats, void *stream) {
+  if (N < 0 || nbytes < 0 || out_floats < 0)
+    return fail(XM_EINVAL, "wav_decode_resample_batch: need N >= 0, nbytes >= 0, out_floats >= 0 (got N=%d nbytes=%lld out_floats=%lld)",
+                N, nbytes, out_floats);
+  if (N == 0) return XM_OK;
+  if (!bytes || !desc || !out) return fail(XM_EINVAL, "wav_decode_resample_batch: NULL argument");
+  if (((uintptr_t)bytes & 15) || ((uintptr_t)desc & 7) || ((uintptr_t)out & 3))
+    return fail(XM_EINVAL, "wav_decode_resample_batch: bytes must be 16-byte aligned, desc 8-byte and out 4-byte aligned");
+  if (nbytes == 0 || out_floats == 0) return XM_OK;   // no data chunk holds a byte: nothing to write
+  hipStream_t st = (hipStream_t)stream;
+  void *ws = nullptr;
+  const int rc = ws_get((size_t)N * sizeof(WavClip), &ws, st);
+  if (rc != XM_OK) return rc;
+  {
+    ProfScope ps(prof_key(kProfWavRate, 0), 0, st);
+    hipLaunchKernelGGL(wav_rate_gain_kernel, dim3((unsigned)N), dim3(1024), 0, st, desc, (WavClip *)ws);
+    XM_LAUNCH_CHECK();
+  }
+  const long long tiles = (out_floats + kWavRateTile - 1) / kWavRateTile;   // an upper bound of the kernel's tile count
+  ProfScope ps(prof_key(kProfWavRate, 1), 0, st);
+  hipLaunchKernelGGL(wav_resample_kernel, dim3((unsigned)std::min<long long>(tiles, kWavMaxBlocks)), dim3(256), 0, st,
+                     (const uint32_t *)bytes, nbytes, desc, N, (const WavClip *)ws, (uint32_t *)out, out_floats);
+  XM_LAUNCH_CHECK();
+  return XM_OK;
+}
 
 int xm_wav_plan(const unsigned char *bytes, const long long *offsets, int N, const long long *ranges, int channel,
                 long long out_base, long long *desc, long long *sizes) {

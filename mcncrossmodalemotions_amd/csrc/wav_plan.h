@@ -3,6 +3,8 @@
 // only, nothing from HIP (compiles with g++ -std=c++17; tests/wav_plan_check.cpp parses every truncation and
 // single-byte mutation of a valid file per format under the address and undefined-behaviour sanitizers).
 // include/xmodal.h documents the descriptor row; csrc/wav.hip holds the C entry point and the device decode.
+// wav_plan_batch_fs is the same plan towards one sample rate (xm_wav_plan_fs: p / q = fs / SampleRate per file, output
+// offsets at that rate); tests/wav_rate_plan_check.cpp does for it what wav_plan_check.cpp does for wav_plan_batch.
 #pragma once
 #include <cstdarg>
 #include <cstdint>
@@ -14,7 +16,13 @@ namespace xm {
 
 // descriptor columns (XM_WAV_DESC int64 per file)
 enum { WD_BEGIN = 0, WD_END, WD_RATE, WD_NCH, WD_BITS, WD_FMT, WD_TOTAL, WD_FIRST, WD_FRAMES, WD_CW, WD_SEL, WD_OUT,
-       WD_STATUS, WD_ALIGN };
+       WD_STATUS, WD_ALIGN, WD_P, WD_Q };
+
+// xm_wav_plan_fs: the reduced ratio p / q = fs / SampleRate a file may have.  kWavPlanMaxRatio is xm_wav_batch's limit
+// (kWavMaxRatio, wav_resample.h); kWavPlanMaxStep bounds the tap loop (20 max(p, q) / p + 1 taps per output) and the
+// window of source frames a tile of the decode-and-resample kernel holds in LDS.
+constexpr long long kWavPlanMaxRatio = 1 << 20;
+constexpr long long kWavPlanMaxStep = 16;
 
 struct WavInfo {
   long long begin = 0, end = 0;   // byte range of the sample data inside the file, clamped to it
@@ -113,8 +121,11 @@ static inline int wav_parse_one(int idx, const unsigned char *d, long long n, Wa
 // the batch: file i is bytes[offsets[i] .. offsets[i + 1]); ranges (optional) N x 2 1-based inclusive [first last],
 // last == -1: to the end; channel -1: all channels, c >= 0: that one; out_base: first float of the batch in the bank.
 // Writes N rows of XM_WAV_DESC int64 and sizes = {output floats, N}.
-static inline int wav_plan_batch(const unsigned char *bytes, const long long *offsets, int N, const long long *ranges, int channel,
-                                 long long out_base, long long *desc, long long *sizes, char *err, int errlen) {
+// fs == 0: the files' own rates (xm_wav_plan).  fs >= 1 (xm_wav_plan_fs): every file resampled to fs -- p, q = fs /
+// SampleRate reduced go to slots 14, 15 and a file takes ceil(frames p / q) output floats per channel written.
+static inline int wav_plan_batch_rate(const unsigned char *bytes, const long long *offsets, int N, const long long *ranges,
+                                      int channel, long long fs, long long out_base, long long *desc, long long *sizes, char *err,
+                                      int errlen) {
   if (N < 0 || out_base < 0 || channel < -1)
     return wav_fail(err, errlen, XM_EINVAL, "wav_plan: need N >= 0, out_base >= 0, channel >= -1 (got N=%d out_base=%lld channel=%d)", N,
                     out_base, channel);
@@ -158,11 +169,42 @@ static inline int wav_plan_batch(const unsigned char *bytes, const long long *of
     d[WD_OUT] = out;
     d[WD_STATUS] = w.status;
     d[WD_ALIGN] = w.align;
-    out += frames * cw;
+    long long oframes = frames;
+    if (fs > 0) {
+      long long a = fs, b = w.rate;
+      while (b) {
+        const long long t = a % b;
+        a = b;
+        b = t;
+      }
+      const long long p = fs / a, q = w.rate / a;
+      if (p > kWavPlanMaxRatio || q > kWavPlanMaxRatio)
+        return wav_fail(err, errlen, XM_ENOTSUP, "wav_plan: file %d: %lld Hz to %lld Hz is the ratio %lld / %lld, terms above 2^20 are not supported",
+                        i, w.rate, fs, p, q);
+      if (q > kWavPlanMaxStep * p)
+        return wav_fail(err, errlen, XM_ENOTSUP, "wav_plan: file %d: %lld Hz to %lld Hz is below 1 / 16 of the file's rate", i, w.rate, fs);
+      if (p > kWavPlanMaxStep * q)
+        return wav_fail(err, errlen, XM_ENOTSUP, "wav_plan: file %d: %lld Hz to %lld Hz is above 16 times the file's rate", i, w.rate, fs);
+      d[WD_P] = p;
+      d[WD_Q] = q;
+      oframes = (frames * p + q - 1) / q;     // frames < 2^32 and p <= 2^20
+    }
+    out += oframes * cw;
   }
   sizes[0] = out - out_base;
   sizes[1] = N;
   return XM_OK;
+}
+
+static inline int wav_plan_batch(const unsigned char *bytes, const long long *offsets, int N, const long long *ranges, int channel,
+                                 long long out_base, long long *desc, long long *sizes, char *err, int errlen) {
+  return wav_plan_batch_rate(bytes, offsets, N, ranges, channel, 0, out_base, desc, sizes, err, errlen);
+}
+
+static inline int wav_plan_batch_fs(const unsigned char *bytes, const long long *offsets, int N, const long long *ranges, int channel,
+                                    long long fs, long long out_base, long long *desc, long long *sizes, char *err, int errlen) {
+  if (fs < 1) return wav_fail(err, errlen, XM_EINVAL, "wav_plan: need fs >= 1 (got %lld)", fs);
+  return wav_plan_batch_rate(bytes, offsets, N, ranges, channel, fs, out_base, desc, sizes, err, errlen);
 }
 
 }  // namespace xm

@@ -231,19 +231,20 @@ def compute_audio_feats_wav(dag, wav, offsets, numEmotions=8, limit=float("inf")
     return logits
 
 
-def compute_audio_feats_files(dag, files, numEmotions=8, limit=float("inf"), maxBatch=64, *, modelDir=None):
+def compute_audio_feats_files(dag, files, numEmotions=8, limit=float("inf"), maxBatch=64, *, modelDir=None, fs=None):
     """logits = compute_audio_feats from the WAV files themselves (compute_audio_feats.m:116-136,172-176): `files` is a
     list of bytes or of paths.  [z, fs] = audioread(path); assert(size(z,2) <= 2, 'unexpected number of streams');
     z = z(:,1): vl.audioread with channel=0 (the left stream) decodes every file on the device into one bank, then
-    compute_audio_feats_wav runs on it.  As upstream there is no check of the sample rate.  `limit` as there: only the
-    first limit + 1 files are read."""
+    compute_audio_feats_wav runs on it.  As upstream there is no check of the sample rate: with fs=None a file at another
+    rate is read as if it were at the student's; fs=16000 resamples every file to it while it is decoded
+    (vl.audioread(fs=)).  `limit` as there: only the first limit + 1 files are read."""
     files = list(files)
     if limit != float("inf"):
         files = files[:max(0, min(len(files), int(limit) + 1))]
     for k, i in enumerate(vl.audioinfo(files)):
         if i["NumChannels"] > 2:
             raise ValueError("unexpected number of streams: file %d has %d channels" % (k, i["NumChannels"]))   # :174
-    bank, offsets = vl.audioread(files, channel=0)
+    bank, offsets = vl.audioread(files, channel=0, fs=fs)
     return compute_audio_feats_wav(dag, bank, offsets, numEmotions=numEmotions, maxBatch=maxBatch, modelDir=modelDir)
 
 

@@ -1653,14 +1653,17 @@ def _file_bytes(files):
     return datas
 
 
-def wav_plan(files, ranges=None, channel=None, out_base=0, stage=None):
+def wav_plan(files, ranges=None, channel=None, out_base=0, stage=None, fs=None):
     """The host side of audioread (xm_wav_plan; touches no device): `files` is a list of bytes.  Lays one staging buffer
     out as [file bytes | desc] (16-byte aligned parts), parses every header into it and returns (stage, plan): `stage` a
     uint8 numpy array (`stage(nbytes)`, when given, allocates it -- audioread hands out pinned memory) and plan =
     dict(N, nbytes, desc: (offset, bytes) in the buffer, rows: the N x 16 int64 view of it, floats, total).
     ranges: None, one [first last] pair for every file, or N pairs (1-based inclusive, last = -1 or inf: to the end);
     channel: None for all channels or the 0-based channel to keep; out_base: first float of the batch in the bank.
-    An unsupported or malformed file raises _lib.XmError naming its index."""
+    An unsupported or malformed file raises _lib.XmError naming its index.
+    fs: None, or the rate every file is resampled to (xm_wav_plan_fs): rows[:, 14:16] then hold p, q = fs / SampleRate
+    reduced, rows[:, 11], `floats` and plan["out_frames"] (per file and channel written) count floats at rate fs, and
+    plan["fs"] records the rate; such rows go to xm_wav_decode_resample_batch.  A ratio beyond 16 either way raises too."""
     N = len(files)
     lens = np.array([len(f) for f in files], np.int64)
     offsets = np.concatenate([[0], np.cumsum(lens)]).astype(np.int64)
@@ -1683,31 +1686,54 @@ def wav_plan(files, ranges=None, channel=None, out_base=0, stage=None):
         rng = np.ascontiguousarray(r, np.int64)
     sizes = np.zeros(2, np.int64)
     base = buf.ctypes.data
-    _lib.check(_L().xm_wav_plan(C.c_void_p(base), C.c_void_p(offsets.ctypes.data), N,
-                                C.c_void_p(rng.ctypes.data) if rng is not None else None,
-                                -1 if channel is None else int(channel), int(out_base), C.c_void_p(base + o_desc),
-                                C.c_void_p(sizes.ctypes.data)))
+    args = (C.c_void_p(base), C.c_void_p(offsets.ctypes.data), N, C.c_void_p(rng.ctypes.data) if rng is not None else None,
+            -1 if channel is None else int(channel))
+    tail = (int(out_base), C.c_void_p(base + o_desc), C.c_void_p(sizes.ctypes.data))
+    if fs is None:
+        _lib.check(_L().xm_wav_plan(*args, *tail))
+    else:
+        _lib.check(_L().xm_wav_plan_fs(*args, int(fs), *tail))
     rows = buf[o_desc:o_desc + 8 * WAV_DESC * N].view(np.int64).reshape(N, WAV_DESC)
-    return buf, dict(N=N, nbytes=nbytes, desc=(o_desc, 8 * WAV_DESC * N), rows=rows, floats=int(sizes[0]), total=total,
-                     out_base=int(out_base))
+    plan = dict(N=N, nbytes=nbytes, desc=(o_desc, 8 * WAV_DESC * N), rows=rows, floats=int(sizes[0]), total=total,
+                out_base=int(out_base))
+    if fs is not None:
+        plan.update(fs=int(fs), out_frames=_wav_out_frames(rows))
+    return buf, plan
 
 
-def _wav_info(rows):
-    return [dict(SampleRate=int(d[2]), TotalSamples=int(d[6]), NumChannels=int(d[3]), BitsPerSample=int(d[4]),
+def _wav_out_frames(rows):
+    """ceil(frames decoded * p / q) of every row of xm_wav_plan_fs"""
+    return -(-rows[:, 8] * rows[:, 14] // rows[:, 15])
+
+
+def wav_resample_geometry():
+    """(tile, launches) of xm_wav_decode_resample_batch: the output floats of one tile, the launches of one call."""
+    t, n = C.c_int(), C.c_int()
+    _lib.check(_L().xm_wav_resample_geometry(C.byref(t), C.byref(n)))
+    return t.value, n.value
+
+
+def _wav_info(rows, resampled=False):
+    info = [dict(SampleRate=int(d[2]), TotalSamples=int(d[6]), NumChannels=int(d[3]), BitsPerSample=int(d[4]),
                  Duration=float(d[6]) / float(d[2]), Truncated=bool(int(d[12]) & WAV_TRUNCATED)) for d in rows]
+    if resampled:
+        for i, n in zip(info, _wav_out_frames(rows)):
+            i["ResampledSamples"] = int(n)
+    return info
 
 
-def audioinfo(files):
+def audioinfo(files, fs=None):
     """info = audioinfo(file) for a list of WAV files (bytes or paths): a list of dicts with SampleRate, TotalSamples
     (frames), NumChannels, BitsPerSample, Duration (and Truncated: the data chunk claimed more than the file holds).
-    Host only -- the parse of xm_wav_plan; no device call."""
+    With fs, ResampledSamples = ceil(TotalSamples fs / SampleRate) is added: the length audioread(fs=fs) gives the file.
+    Host only -- the parse of xm_wav_plan / xm_wav_plan_fs; no device call."""
     datas = _file_bytes(files)
     if not datas:
         return []
-    return _wav_info(wav_plan(datas)[1]["rows"])
+    return _wav_info(wav_plan(datas, fs=fs)[1]["rows"], fs is not None)
 
 
-def audioread(files, ranges=None, *, channel=None, out=None, out_base=0, device=None, return_info=False):
+def audioread(files, ranges=None, *, channel=None, out=None, out_base=0, device=None, return_info=False, fs=None):
     """[y, Fs] = audioread(file) / audioread(file, [first last]) for a batch of WAV files (bytes or paths), decoded on
     the device into one waveform bank: returns (bank, offsets), `bank` a 1-D float32 device tensor and `offsets` int64
     numpy with N + 1 entries -- file i is bank[offsets[i]:offsets[i + 1]], a frames x channels matrix in MATLAB layout
@@ -1715,7 +1741,11 @@ def audioread(files, ranges=None, *, channel=None, out=None, out_base=0, device=
     as WAVE_FORMAT_EXTENSIBLE; values are single(audioread's double), bit for bit.  `out` / `out_base` decode into a
     slice of an existing bank starting at float out_base.  One pinned staging buffer, one non-blocking upload, one
     launch, no wait.  return_info=True appends the audioinfo dicts.  Anything else (companded, compressed, RF64 ...)
-    raises before anything is launched, with the index of the file; there is no host decode to fall back to."""
+    raises before anything is launched, with the index of the file; there is no host decode to fall back to.
+    fs: None, or the rate of the bank -- every file is decoded and resampled in one pass (xm_wav_decode_resample_batch,
+    two launches), file i becoming resample(audioread(file_i, range_i), fs, SampleRate_i) column by column: `offsets`
+    then count floats at rate fs, a file at fs already is copied bit for bit, and the info dicts keep the file's own
+    SampleRate and TotalSamples and gain ResampledSamples.  A range is cut from the file BEFORE resampling."""
     if not torch.cuda.is_available():
         raise RuntimeError("audioread needs a GPU; this build has no CPU path")
     datas = _file_bytes(files)
@@ -1738,7 +1768,7 @@ def audioread(files, ranges=None, *, channel=None, out=None, out_base=0, device=
         held.append(torch.empty(int(n), dtype=torch.uint8, pin_memory=True))
         return held[-1].numpy()
 
-    buf, plan = wav_plan(datas, ranges, channel, out_base, stage=stage)
+    buf, plan = wav_plan(datas, ranges, channel, out_base, stage=stage, fs=fs)
     rows, floats = plan["rows"], plan["floats"]
     if out is None:
         out = torch.empty(floats, dtype=torch.float32, device=device)
@@ -1750,10 +1780,11 @@ def audioread(files, ranges=None, *, channel=None, out=None, out_base=0, device=
             dev = torch.empty(plan["total"], dtype=torch.uint8, device=device)
             dev.copy_(held[-1], non_blocking=True)
             p = dev.data_ptr()
-            _lib.check(_L().xm_wav_decode_batch(C.c_void_p(p), plan["nbytes"], C.c_void_p(p + plan["desc"][0]), plan["N"],
-                                                _ptr(out), out.numel(), _stream()))
+            decode = _L().xm_wav_decode_batch if fs is None else _L().xm_wav_decode_resample_batch
+            _lib.check(decode(C.c_void_p(p), plan["nbytes"], C.c_void_p(p + plan["desc"][0]), plan["N"], _ptr(out), out.numel(),
+                              _stream()))
     res = (out, offsets)
-    return res + (_wav_info(rows),) if return_info else res
+    return res + (_wav_info(rows, fs is not None),) if return_info else res
 
 
 # --------------------------------------------------------------------------------------------
