@@ -57,7 +57,7 @@ enum { XM_FUSE_RELU = 1, XM_BN_BATCH_MOMENTS = 2, XM_FUSE_SIGMOID = 4 };
 
 /* ABI revision: 100 = round 1; 101 = xm_nnbnorm_relu_pool_backward gained `y_pool`, exchange entry points return
  * XM_EINVAL without a communicator; 102 = + xm_nnconv_forward_moments, xm_nnbnorm_backward_dxsum, xm_nnconv_forward_gated;
- * 103 = + xm_nnpool_global_avg_backward_accum; 104 = + xm_nnconv_backward_filter_bnrelupool, xm_nndropout_forward / _apply, xm_resample, xm_se_tail_backward_reduce / _apply, xm_se_squeeze_bn, xm_scale_axpy_bn; 105 = + xm_set_exec_hint / xm_get_exec_hint; 106 = + xm_nnconv_bnorm_relu_pool_forward, xm_stem_gram, xm_stem_gram_moments, xm_nnconv_backward_filter_bnrelupool_gram; 107 = + xm_nnaffinegrid / _backward, xm_nnbilinearsampler / _backward, xm_ferplus_batch; 108 = + XM_AGG_PEAK, xm_mnrfit, xm_mnrval; 109 = + xm_roc, xm_roc_launches, xm_label_hist; 110 = + xm_group_rows, xm_gather_rows, xm_scatter_rows, xm_track_peaks; 111 = + xm_wav_batch; 112 = + xm_spec_bucket_batch; 113 = + xm_jpeg_plan, xm_jpeg_decode_batch; 114 = + xm_wav_plan, xm_wav_decode_batch; 115 = + xm_jpeg_decode_batch_split, xm_jpeg_split_geometry; 116 = + xm_pixcsv_plan, xm_pixcsv_decode_batch, xm_pixcsv_geometry; 117 = + xm_nnconv_forward_strided_residual; 118 = + xm_solver_update; 119 = + xm_nnnormalize_forward / _backward, xm_nnnormalize_geometry; 120 = + xm_jpeg_plan_prog, xm_jpeg_decode_batch_prog; 121 = + xm_window_targets; 122 = + xm_wav_plan_fs, xm_wav_decode_resample_batch, xm_wav_resample_geometry (additions never change the revision's meaning for older bindings).  A binding checks xm_version() >= the revision it was written against. */
+ * 103 = + xm_nnpool_global_avg_backward_accum; 104 = + xm_nnconv_backward_filter_bnrelupool, xm_nndropout_forward / _apply, xm_resample, xm_se_tail_backward_reduce / _apply, xm_se_squeeze_bn, xm_scale_axpy_bn; 105 = + xm_set_exec_hint / xm_get_exec_hint; 106 = + xm_nnconv_bnorm_relu_pool_forward, xm_stem_gram, xm_stem_gram_moments, xm_nnconv_backward_filter_bnrelupool_gram; 107 = + xm_nnaffinegrid / _backward, xm_nnbilinearsampler / _backward, xm_ferplus_batch; 108 = + XM_AGG_PEAK, xm_mnrfit, xm_mnrval; 109 = + xm_roc, xm_roc_launches, xm_label_hist; 110 = + xm_group_rows, xm_gather_rows, xm_scatter_rows, xm_track_peaks; 111 = + xm_wav_batch; 112 = + xm_spec_bucket_batch; 113 = + xm_jpeg_plan, xm_jpeg_decode_batch; 114 = + xm_wav_plan, xm_wav_decode_batch; 115 = + xm_jpeg_decode_batch_split, xm_jpeg_split_geometry; 116 = + xm_pixcsv_plan, xm_pixcsv_decode_batch, xm_pixcsv_geometry; 117 = + xm_nnconv_forward_strided_residual; 118 = + xm_solver_update; 119 = + xm_nnnormalize_forward / _backward, xm_nnnormalize_geometry; 120 = + xm_jpeg_plan_prog, xm_jpeg_decode_batch_prog; 121 = + xm_window_targets; 122 = + xm_wav_plan_fs, xm_wav_decode_resample_batch, xm_wav_resample_geometry; 123 = + xm_nnconv_forward_lattice (additions never change the revision's meaning for older bindings).  A binding checks xm_version() >= the revision it was written against. */
 int xm_version(void);
 const char *xm_last_error(void);
 /* Device memory for hosts that have no device-array type of their own (MATLAB's gpuArray is CUDA-only: on an
@@ -155,6 +155,24 @@ int xm_nnconv_forward_strided_residual(const float *x, int H, int W, int C, int 
                                        int pl, int pr, int dy, int dx, const float *scale, const float *shift,
                                        const float *gate, const float *residual, int res_H, int res_W, int res_sy,
                                        int res_sx, int flags, void *stream);
+/* Extension (ABI 123): xm_nnconv_forward_fused on an OUTPUT LATTICE, written in place.  The layer is computed only at the
+ * output pixels (lat_y * i, lat_x * j), i < floor((Ho - 1) / lat_y) + 1, j likewise, and stored at those positions of the
+ * full-extent Ho x Wo x K x N tensor y; every other element of y is left untouched (its content is whatever the caller had
+ * there).  What it is for: a 3 x 3 layer whose only reader is a stage-end 1 x 1 expansion that runs with stride s (above):
+ * the reader looks at one pixel in s * s, the others need not be computed, and y keeps the extent the reader expects.
+ * The same bits: every lattice pixel gets the bits a full-extent call (xm_nnconv_forward_fused, same operands) gives it.  The
+ * launch takes the tile configuration of the FULL-EXTENT layer (table entry or modelled choice under the full-extent key), its
+ * split-K cut points (an LDS-DMA selection runs as a register-staged configuration with ONE accumulator chain, which is how
+ * the LDS-DMA kernels sum), and, where that launch runs a hybrid remainder, computes the lattice pixels below the hybrid cut
+ * unsplit and the others as a split launch with the hybrid's cut points.  Where that is not possible -- the full-extent
+ * selection is not known without a measurement (find mode on, shape not in the table: the call measures it like any first
+ * call), or it is not an implicit-GEMM launch (skinny, stem or halo-patch kernels), or the layer has filter groups -- the call runs the layer at FULL
+ * EXTENT and writes all of y: bits come before FLOPs.  lat_y == lat_x == 1 is xm_nnconv_forward_fused.
+ * XM_ENOTSUP: a residual operand, XM_FUSE_SIGMOID. */
+int xm_nnconv_forward_lattice(const float *x, int H, int W, int C, int N, const float *f, int FH, int FW, int FC, int K,
+                              const float *b, float *y, int sy, int sx, int pt, int pb, int pl, int pr, int dy, int dx,
+                              const float *scale, const float *shift, const float *residual, int flags, int lat_y,
+                              int lat_x, void *stream);
 /* Extension: Y = vl_nnconv(X, F, B, ...) AND the batch moments of Y that a train-mode vl_nnbnorm(Y, G, B) would
  * compute first -- moments_out (K x 2, column-major) = [mean_k, sqrt(var_k + epsilon)] over H x W x N, biased
  * variance (emoVoxZoo.m:118-123: every dagnn.Conv of the student is followed by dagnn.BatchNorm).  Hand them to

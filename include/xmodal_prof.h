@@ -49,6 +49,9 @@ int xm_prof_kernel_name(int key, char *buf, int len);
  *   "conv_splits"    split-K factor of the implicit-GEMM launches (0 = automatic)
  *   "conv_last_combine"  (read only) what the most recent implicit-GEMM launch left to conv_splitk_epilogue_kernel: 0 = nothing,
  *                    z > 0 = z partial slabs combined by its 16-byte form, z < 0 = |z| slabs by its scalar form
+ *   "conv_last_lattice"  (read only) 1: the most recent xm_nnconv_forward_lattice call computed the lattice pixels only; 0: it ran
+ *                    the layer at full extent (the full-extent selection of the shape was not known without a measurement, or
+ *                    was no implicit-GEMM launch, or the layer has filter groups)
  *   "wgrad_last_splits"  (read only) the final split count of the most recent filter-derivative launch (generic or patch kernel):
  *                    the number of partial slabs reduce_splits_kernel added, 1 = none
  *   "bias_grad_last_splits"  (read only) sample splits S of the most recent bias-derivative launch

@@ -1295,6 +1295,12 @@ static int forward_run(const Geo &g, const ConvGemmArgs &a, const float *x, cons
   return arm(select_arm(4, key, st, 4, hok, kHaloMargin, halo_forced(hok), arm));
 }
 
+static bool fwd_dma_ok(const Geo &g, const float *x, const float *f, bool need_pad, int mode) {
+  return !need_pad && mode == 0 && g.FH == 1 && g.FW == 1 && g.sy == 1 && g.sx == 1 && g.dy == 1 &&
+         g.dx == 1 && (g.H * g.W) % 4 == 0 && ((uintptr_t)x & 15) == 0 && ((uintptr_t)f & 15) == 0 &&
+         g.R % kBK == 0 && path_on(kPathDma);
+}
+
 // moments_out != NULL: also the batch moments [mean, sqrt(var + eps)] of Y (the statistics half of the train-mode
 // vl_nnbnorm that follows the convolution), from per-wave partial sums of the GEMM epilogue when the launch allows it
 // (16-byte-store epilogue, no split-K, no filter groups), else by a pass over Y.
@@ -1316,9 +1322,7 @@ static int conv_forward(const float *x, const float *f, const float *b, float *y
   const size_t slabf = slab_floats(g.Kg, NP, Rp, kNumCfg, g.FH, g.FW, g.R);
   // LDS-DMA eligibility: a plain GEMM in memory (1x1, unit stride, no padding), pixel quads inside one sample,
   // 16-byte aligned operands
-  const bool dma_ok = !need_pad && mode == 0 && g.FH == 1 && g.FW == 1 && g.sy == 1 && g.sx == 1 && g.dy == 1 &&
-                      g.dx == 1 && (g.H * g.W) % 4 == 0 && ((uintptr_t)x & 15) == 0 && ((uintptr_t)f & 15) == 0 &&
-                      g.R % kBK == 0 && path_on(kPathDma);
+  const bool dma_ok = fwd_dma_ok(g, x, f, need_pad, mode);
   const bool want_stats = moments_out != nullptr && g.G == 1 && path_on(kPathFusedStats);
   // partial sums: one {sum, sum sq} pair per row and per pixel tile (>= 32 pixels), + 64 fp64 slabs for the reduction
   // (the persistent stem kernel leaves one row per block: stem_grid(NP) can exceed NP / 32 on small problems)
@@ -1358,6 +1362,177 @@ static int conv_forward(const float *x, const float *f, const float *b, float *y
     }
   }
   if (moments_out && !stats_done) return bn_batch_moments(y, g.Ho, g.Wo, g.K, g.N, eps, moments_out, st);
+  return XM_OK;
+}
+
+// ---- forward on an output lattice (xm_nnconv_forward_lattice) -------------------------------------------------------------
+// The layer computed only at the output pixels (ly i, lx j) and stored at those positions of the full-extent Y: the same
+// implicit GEMM over N * PI * PJ lattice pixels, the gather walking X with step (ly sy, lx sx), the scalar-store epilogue
+// with the output strides (ly, lx).  Every lattice pixel has to get the BITS the full-extent launch gives it, and the bits
+// follow the structure of the reduction: the launch therefore takes the tile configuration, the split-K
+// cut points and the hybrid cut of the FULL-EXTENT layer, looked up under the full-extent key -- never its own.
+struct FullExtentPlan {
+  int ci;      // register-staged configuration with the chain structure of the full-extent launch
+  int tps;     // reduction stages per split-K slab (nkt: unsplit)
+  int hyS, hyTps, hyP0;   // hybrid remainder: the full-extent pixels from hyP0 on are hyS-way sums of hyTps stages
+};
+// 1 while the most recent xm_nnconv_forward_lattice call computed the lattice only, 0 when it ran the layer at full extent
+// (xm_debug_get("conv_last_lattice"): tests)
+static int g_last_lattice = 0;
+
+// What forward_run does with the full-extent problem `a` of a group, WITHOUT launching.  false: not known without a
+// measurement (find mode on, shape not in the table), or not an implicit-GEMM launch (a stem or halo-patch kernel: another
+// summation order) -- the caller then runs the layer at full extent, which also records the measurement.
+static bool full_extent_plan(const Geo &g, const ConvGemmArgs &a, const float *x, int mode, bool have_slab, hipStream_t st,
+                             FullExtentPlan &p) {
+  if (stem_ok(a, g, x, false) || stem3_ok(a, g, x, false)) return false;
+  const TuneKey key = tune_key_forward(0, g, a.M, a.NP, a.Rp, mode);
+  int ci = pick_cfg(a.M, a.NP, a.Rp / kBK);
+  const int ncfg = a.dmaOk ? kNumCfg : kNumBaseCfg;
+  if (g_force_cfg >= 0) ci = g_force_cfg < ncfg ? g_force_cfg : base_cfg(g_force_cfg);
+  else if (tune_must_measure(key, st, &ci)) return false;
+  ConvGemmArgs ah = a;
+  const int hneed = forced_tiling() ? 0 : halo_setup(ah, g.N);
+  const bool hok[4] = {true, halo_var_ok(ah, hneed, 0), halo_var_ok(ah, hneed, 1), halo_var_ok(ah, hneed, 2)};
+  if (hok[1] || hok[2] || hok[3]) {
+    int arm = halo_forced(hok);
+    if (arm < 0) {
+      TuneKey k4 = key;
+      k4.kind = 4;
+      arm = 0;
+      if (tune_must_measure(k4, st, &arm)) return false;
+      if (arm < 0 || arm >= 4 || !hok[arm]) arm = 0;
+    }
+    if (arm != 0) return false;
+  }
+  // forward_run's gemm(ci), then launch_gemm
+  ci = a.dmaOk ? ci : base_cfg(ci);
+  int sp;
+  gemm_slab_floats(a, ci, &sp);
+  if (ci == kCfgW8 && !path_on(kPathW8)) ci = 0;
+  const Cfg &c = kCfgs[ci];
+  ConvGemmArgs t = a;
+  t.nbm = (a.M + c.bm() - 1) / c.bm(), t.nbn = (a.NP + c.bn() - 1) / c.bn(), t.nkt = a.Rp / kBK;
+  t.statPart = nullptr;
+  p.tps = (t.nkt + sp - 1) / sp;
+  p.hyS = 1, p.hyTps = 0, p.hyP0 = 0;
+  if (p.tps >= t.nkt && have_slab) {
+    int full;
+    const int hyS = hybrid_plan(t, ci, &full);
+    if (hyS > 1) {
+      p.hyTps = (t.nkt + hyS - 1) / hyS;
+      p.hyS = (t.nkt + p.hyTps - 1) / p.hyTps;
+      p.hyP0 = full / t.nbm * c.bn();
+    }
+  }
+  // Every LDS-DMA kernel sums each output in ONE accumulator chain, in k order -- also 11, whose register-staged base
+  // <1,1,2,2> has the two chains of the 1 x 1 wave tiles: that one maps to the one-chain <1,2,2,2>, the others to their bases
+  p.ci = !is_dma_cfg(ci) ? ci : (kCfgs[ci].tm * kCfgs[ci].tn == 1 ? 3 : base_cfg(ci));
+  return true;
+}
+
+// One implicit-GEMM launch of lattice problem `a` with a GIVEN split of the reduction (tps stages per slab); the slabs are
+// combined over the pixels [p0, NP) only (p0 > 0: the launch began at a sample boundary below the hybrid cut).
+static int launch_gemm_lattice(ConvGemmArgs a, int mode, int ci, int tps, float *slab, int p0, hipStream_t st) {
+  const Cfg &c = kCfgs[ci];
+  a.nbm = (a.M + c.bm() - 1) / c.bm();
+  a.nbn = (a.NP + c.bn() - 1) / c.bn();
+  a.nkt = a.Rp / kBK;
+  a.tilesPerSplit = std::min(tps, a.nkt);
+  const int splits = (a.nkt + a.tilesPerSplit - 1) / a.tilesPerSplit;
+  a.NPs = (a.NP + 3) & ~3;
+  a.slab = splits > 1 ? slab : nullptr;
+  a.dbgCycles = g_dbg_cycles;
+  a.hyS = 1, a.hyFull = 0, a.hyTps = 0, a.hyP0 = 0;
+  if (splits > 1 && !slab) return fail(XM_EINVAL, "vl_nnconv(lattice): split launch without a slab");
+  {
+    const double abytes = (double)a.xBytes + 4.0 * a.M * a.Rtrue + 4.0 * a.M * (double)a.NP;
+    ProfScope ps(prof_key(kProfGemm, ci * 2 + mode), 2.0 * a.M * (double)a.NP * a.Rtrue, st, abytes);
+    const dim3 grid(a.nbm * a.nbn, splits);
+    if (mode) launch_gemm_cfg<1>(ci, a, grid, st);
+    else launch_gemm_cfg<0>(ci, a, grid, st);
+  }
+  XM_LAUNCH_CHECK();
+  g_last_combine = 0;
+  if (splits > 1) {
+    a.slab += p0, a.hyP0 = p0;       // the combine kernel reads the slabs relative to hyP0
+    launch_splitk_epilogue(a, splits, a.NP - p0, false, st);
+    g_last_combine = -splits;
+    XM_LAUNCH_CHECK();
+  }
+  return XM_OK;
+}
+
+// *ran = 0: the layer's full-extent bits cannot be reproduced on the lattice (full_extent_plan); nothing was launched
+static int conv_forward_lattice(const float *x, const float *f, const float *b, float *y, const Geo &g, const float *scale,
+                                const float *shift, int relu, int ly, int lx, hipStream_t st, int *ran) {
+  *ran = 0;
+  const bool padded = (g.pt | g.pb | g.pl | g.pr) != 0;
+  const bool bigTaps = g.FH * g.FW > 63;
+  if (bigTaps && padded) return XM_OK;          // (the full-extent call reports it)
+  // filter groups: forward_run selects per group (the alignment of a group's slice of Y decides its candidates); not
+  // worth a plan per group -- such a layer stays at full extent
+  if (g.G != 1) return XM_OK;
+  const int Rp = (g.R + kBK - 1) / kBK * kBK;
+  const bool need_pad = (g.R % kBK) != 0 || ((uintptr_t)f & 15);
+  const int mode = (padded || Rp != g.R) ? 1 : 0;
+  const int NP = g.Ho * g.Wo * g.N;
+  const bool have_slab = slab_floats(g.Kg, NP, Rp, kNumCfg, g.FH, g.FW, g.R) > 0;
+  const int PI = lattice_extent(g.Ho, ly), PJ = lattice_extent(g.Wo, lx), NPl = PI * PJ * g.N;
+  FwdOperands o{x, f, b, scale, shift, nullptr, nullptr, y, nullptr, g.R, Rp, relu, bigTaps, fwd_dma_ok(g, x, f, need_pad, mode)};
+  FullExtentPlan p;
+  if (!full_extent_plan(g, forward_args(g, 0, o), x, mode, have_slab, st, p)) return XM_OK;
+  const int nkt = Rp / kBK;
+  const int z = p.hyS > 1 ? p.hyS : (nkt + p.tps - 1) / p.tps;       // slabs of the split launch (1: none)
+  const long long cut = p.hyS > 1 ? lattice_pixels_below(p.hyP0, g.Ho, g.Wo, ly, lx) : 0;   // lattice pixels of the unsplit prefix
+  const int n0 = (int)(cut / (PI * PJ));                // the split launch of a hybrid plan starts at this sample
+  const int NPz = NPl - n0 * PI * PJ;                   // ... and covers this many lattice pixels
+  const size_t slabf = z > 1 ? (size_t)z * g.Kg * ((NPz + 3) & ~3) : 0;
+  WsCarver ws;
+  int rc = ws.init(WsCarver::need(need_pad ? (size_t)g.K * Rp : 0, 4) + WsCarver::need(slabf, 4), st);
+  if (rc) return rc;
+  o.taps = device_taps(fwd_tap_table(g, Rp, bigTaps));
+  if (!o.taps) return fail(XM_ENOMEM, "vl_nnconv: tap table allocation failed");
+  if (need_pad) {
+    float *Ap = ws.take<float>((size_t)g.K * Rp);
+    const size_t n = (size_t)g.K * Rp;
+    hipLaunchKernelGGL(pad_filter_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, f, Ap, g.K, g.R, Rp);
+    XM_LAUNCH_CHECK();
+    o.A = Ap;
+    o.lda = Rp;
+  }
+  float *slab = slabf ? ws.take<float>(slabf) : nullptr;
+  for (int grp = 0; grp < g.G; ++grp) {
+    ConvGemmArgs a = forward_args(g, grp, o);
+    a.PI = PI, a.PJ = PJ, a.NP = NPl;
+    a.divPIJ = make_fastdiv((uint32_t)(PI * PJ)), a.divPI = make_fastdiv((uint32_t)PI);
+    a.gsy = g.sy * ly, a.gsx = g.sx * lx;       // the gather origin of lattice pixel (i, j) is that of output pixel (ly i, lx j)
+    a.osy = ly, a.osx = lx;                     // ... and that is where it is stored (OH, channel and sample strides: full extent)
+    a.vecStore = 0, a.dmaOk = 0;                // lattice neighbours are never adjacent in Y
+    if (p.hyS <= 1) {
+      rc = launch_gemm_lattice(a, mode, p.ci, p.tps, slab, 0, st);
+      if (rc) return rc;
+      continue;
+    }
+    // hybrid plan: the lattice pixels below the cut are one chain each, the others hyS-way sums with the hybrid's cut points
+    if (cut > 0) {
+      ConvGemmArgs a1 = a;
+      a1.NP = (int)cut;
+      rc = launch_gemm_lattice(a1, mode, p.ci, nkt, nullptr, 0, st);
+      if (rc) return rc;
+    }
+    if (cut < NPl) {
+      // the kernels enumerate pixels from 0: the split launch starts at the sample that holds the cut and its combine
+      // skips the pixels below it (they are computed twice, less than one sample)
+      ConvGemmArgs a2 = a;
+      const size_t xskip = (size_t)n0 * g.H * g.W * g.C;
+      a2.X += xskip, a2.xBytes -= (unsigned)(xskip * 4), a2.Y += (size_t)n0 * a.oSampleStride;
+      a2.NP = NPz;
+      rc = launch_gemm_lattice(a2, mode, p.ci, p.hyTps, slab, (int)(cut - (long long)n0 * PI * PJ), st);
+      if (rc) return rc;
+    }
+  }
+  *ran = 1;
   return XM_OK;
 }
 
@@ -1998,6 +2173,7 @@ int xm_debug_set(const char *key, int value) {
 int xm_debug_get(const char *key) {
   if (key && strcmp(key, "num_conv_cfgs") == 0) return kNumCfg;
   if (key && strcmp(key, "conv_last_combine") == 0) return g_last_combine;
+  if (key && strcmp(key, "conv_last_lattice") == 0) return g_last_lattice;
   if (key && strcmp(key, "wgrad_last_splits") == 0) return g_last_wgrad_splits;
   if (key && strcmp(key, "bias_grad_last_splits") == 0) return g_last_bias_splits;
   if (key && strcmp(key, "stats_last_splits") == 0) return g_last_stats_splits;
@@ -2104,6 +2280,32 @@ int xm_nnconv_forward_strided_residual(const float *x, int H, int W, int C, int 
   if (residual && res_H < 1) return fail(XM_EINVAL, "vl_nnconv(fused): residual extent must be positive");
   return fused_forward(x, H, W, C, N, f, FH, FW, FC, K, b, y, sy, sx, pt, pb, pl, pr, dy, dx, scale, shift, gate, residual,
                        residual ? res_H : 0, res_W, res_sy, res_sx, flags, stream);
+}
+
+int xm_nnconv_forward_lattice(const float *x, int H, int W, int C, int N, const float *f, int FH, int FW, int FC, int K,
+                              const float *b, float *y, int sy, int sx, int pt, int pb, int pl, int pr, int dy, int dx,
+                              const float *scale, const float *shift, const float *residual, int flags, int lat_y,
+                              int lat_x, void *stream) {
+  Geo g;
+  int rc = make_geo(g, H, W, C, N, FH, FW, FC, K, sy, sx, pt, pb, pl, pr, dy, dx);
+  if (rc) return rc;
+  if (!x || !f || !y) return fail(XM_EINVAL, "vl_nnconv: NULL tensor");
+  if (lat_y < 1 || lat_x < 1) return fail(XM_EINVAL, "vl_nnconv(lattice): the lattice steps must be >= 1, got [%d %d]", lat_y, lat_x);
+  if ((scale == nullptr) != (shift == nullptr))
+    return fail(XM_EINVAL, "vl_nnconv(fused): scale and shift must be given together");
+  if (residual) return fail(XM_ENOTSUP, "vl_nnconv(lattice): a residual operand is not built");
+  if (flags & ~XM_FUSE_RELU) return fail(XM_ENOTSUP, "vl_nnconv(lattice): only the ReLU epilogue is built");
+  g_last_lattice = 0;
+  int ran = 0;
+  if ((lat_y > 1 || lat_x > 1) && !fc_skinny_ok(g)) {
+    rc = conv_forward_lattice(x, f, b, y, g, scale, shift, (flags & XM_FUSE_RELU) ? 1 : 0, lat_y, lat_x, (hipStream_t)stream, &ran);
+    if (rc) return rc;
+  }
+  g_last_lattice = ran;
+  if (ran) return XM_OK;
+  // bits before FLOPs: the layer at full extent (every lattice pixel is among its pixels)
+  return fused_forward(x, H, W, C, N, f, FH, FW, FC, K, b, y, sy, sx, pt, pb, pl, pr, dy, dx, scale, shift, nullptr, nullptr, 0, 0,
+                       1, 1, flags, stream);
 }
 
 int xm_nnconv_forward_moments(const float *x, int H, int W, int C, int N, const float *f, int FH, int FW,

@@ -63,6 +63,20 @@ inline std::vector<Tap4> wgrad_tap_table(const Geo &g, int count) {
   return t;
 }
 
+// ---- forward on an output lattice (xm_nnconv_forward_lattice) -------------------------------------------------------
+// The lattice holds the output pixels (ly i, lx j): PI x PJ of them per sample, enumerated like the full-extent pixels
+// (i fastest, then j, then the sample), so the map from a full-extent pixel index to its lattice index is monotone.
+inline int lattice_extent(int full, int step) { return (full - 1) / step + 1; }
+// the number of lattice pixels whose FULL-EXTENT index i + Ho (j + Wo n) lies below p0: what a cut of the full-extent
+// pixel range at p0 (the start of a hybrid launch's split remainder) becomes in lattice indices
+inline long long lattice_pixels_below(long long p0, int Ho, int Wo, int ly, int lx) {
+  const int PI = lattice_extent(Ho, ly), PJ = lattice_extent(Wo, lx);
+  const long long n = p0 / ((long long)Ho * Wo);
+  const int q = (int)(p0 - n * Ho * Wo), j = q / Ho, i = q % Ho;
+  // whole samples, whole lattice columns left of column j, and the lattice rows above row i when j is a lattice column
+  return n * PI * PJ + (long long)((j + lx - 1) / lx) * PI + (j % lx == 0 ? (i + ly - 1) / ly : 0);
+}
+
 // ---- dgrad: one implicit GEMM per stride-parity class (a, b) of the input pixels ------------------------------------
 // Class (a, b) holds the input pixels (hi, wi) with (hi + pt) % sy == a, (wi + pl) % sx == b: hi = hi0 + sy i (i < PI),
 // wi = wi0 + sx j (j < PJ).  Only the taps with (u dy) % sy == a, (v dx) % sx == b reach them: u = u0 + ustep iu

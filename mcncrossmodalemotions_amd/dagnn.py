@@ -507,6 +507,9 @@ class DagNN:
         # test-mode plans: a 1 x 1 expansion whose output is read only by 1 x 1 / stride-s convolutions (the end of a
         # Caffe-style ResNet stage) computes the pixels those readers look at and nothing else (_prune_strided_boundaries)
         self.stridePrune = os.environ.get("XM_STRIDE_PRUNE", "1") != "0"
+        # ... and a convolution whose only reader is such a pruned expansion computes the lattice of pixels the expansion
+        # samples, in place in its full-extent output (_prune_reader_lattices; off with stridePrune too)
+        self.latticePrune = os.environ.get("XM_LATTICE_PRUNE", "1") != "0"
         self.wgradStream = None  # optional side HIP stream for the filter / bias derivatives
         self.gradHook = None     # callable(layer name): called right after a conv layer's parameter
                                  # derivatives were enqueued, on the stream they were enqueued on
@@ -613,7 +616,7 @@ class DagNN:
         import copy
         r = DagNN()
         r.meta, r.mode, r.fuse, r.device = self.meta, self.mode, self.fuse, self.device
-        r.conserveMemory, r.stridePrune = self.conserveMemory, self.stridePrune
+        r.conserveMemory, r.stridePrune, r.latticePrune = self.conserveMemory, self.stridePrune, self.latticePrune
         for l in self.layers:
             r.layers.append(_LayerRec(l.name, copy.copy(l.block), l.inputs, l.outputs, l.params))
         r.params = self.params
@@ -833,7 +836,7 @@ class DagNN:
     def _plan(self, training):
         # the set of precious variables is part of the key: a fused step never materialises the intermediate
         # variables it swallows, so marking one precious after a plan was built must rebuild the plan
-        key = (training, self.mode, self.fuse, self.stridePrune, len(self.layers),
+        key = (training, self.mode, self.fuse, self.stridePrune, self.latticePrune, len(self.layers),
                tuple(n for n, v in self.vars.items() if v.precious))
         layers = [id(l) for l in self.layers]
         if self._plan_key != key or self._plan_layers != layers:
@@ -889,6 +892,10 @@ class _Step:
         # block's -- (s, s) on a pruned stage-end expansion (its shortcut operand is then sampled with the same stride),
         # (1, 1) on the stride-s readers of its output
         self.run_stride = None
+        # forward-only test-mode plans (_prune_reader_lattices): (s, s) on a folded convolution step whose only reader is a
+        # pruned expansion with run_stride (s, s) -- the step computes the output pixels (s i, s j), in place in its
+        # full-extent output; the other elements of that variable are unspecified and nothing reads them
+        self.out_lattice = None
 
     def _stride(self):
         return self.rec.block.stride if self.run_stride is None else self.run_stride
@@ -1413,7 +1420,7 @@ class _ConvFoldStep(_Step):
         pruned = self.run_stride if (resid is not None and self.run_stride != (1, 1)) else None
         return [vl.vl_nnconv(ins[0], prm[0], prm[1] if blk.hasBias else None, stride=self._stride(), pad=blk.pad,
                              dilate=blk.dilate, scale=sc, shift=sh, residual=resid, residual_stride=pruned,
-                             relu=self.relu_rec is not None)]
+                             relu=self.relu_rec is not None, out_lattice=self.out_lattice)]
 
     def backward(self, net):
         raise RuntimeError("folded conv+bn steps exist only in forward-only test-mode plans")
@@ -1670,6 +1677,29 @@ def _prune_strided_boundaries(w, steps):
             q.run_stride = (1, 1)
 
 
+def _prune_reader_lattices(w, steps):
+    """forward-only test-mode plans, after _prune_strided_boundaries: skip the pixels a pruned expansion never samples.
+
+    A plain folded convolution step (Conv -> BatchNorm [-> ReLU]: no shortcut add, no SE tail) with unit stride whose output
+    variable is not precious and whose ONLY reader is a step that _prune_strided_boundaries gave run_stride (s, s), s > 1
+    (it reads its input through its head convolution alone, 1 x 1 / pad 0, at the pixels (s i, s j)) computes exactly those
+    pixels: out_lattice = (s, s).  The variable keeps its extent and the reader its run_stride, so no step gains or loses a
+    layer; the library gives every lattice pixel the bits of the full-extent launch (vl_nnconv out_lattice).  In the SE teacher
+    the reader's squeeze is a mean over ALL pixels of its input (_SEFoldStep.reads_through_conv is False): no lattice there."""
+    head = {id(st.rec): st for st in steps}
+    for st in steps:
+        if type(st) is not _ConvFoldStep or st.sum_rec is not None or st.run_stride is not None or \
+                tuple(vl._pair(st.rec.block.stride, "STRIDE")) != (1, 1) or w.net.vars[st.outputs[0]].precious:
+            continue
+        readers = [head.get(id(c)) for c in w.consumers.get(st.outputs[0], [])]
+        if len(readers) != 1 or readers[0] is None or not readers[0].reads_through_conv:
+            continue
+        s = readers[0].run_stride
+        if s is None or s[0] != s[1] or s[0] <= 1 or not _conv_1x1(readers[0].rec.block, unit_stride=True):
+            continue
+        st.out_lattice = tuple(s)
+
+
 def build_plan(net, training):
     w = _Wiring(net)
     fold = net.fuse and not training and net.mode == "test"
@@ -1686,4 +1716,6 @@ def build_plan(net, training):
         _link_training(w, steps)
     if fold and net.stridePrune:
         _prune_strided_boundaries(w, steps)
+        if net.latticePrune:
+            _prune_reader_lattices(w, steps)
     return steps

@@ -151,7 +151,7 @@ def out_size(n, pa, pb, f, d, s):
 def vl_nnconv(x, f, b=None, dzdy=None, stride=1, pad=0, dilate=1, no_der_data=False,
               no_der_filters=False, no_der_biases=False, scale=None, shift=None, residual=None,
               relu=False, df_out=None, db_out=None, dx_accum=None, sigmoid=False, moments_out=None, epsilon=1e-4,
-              gate=None, residual_stride=None):
+              gate=None, residual_stride=None, out_lattice=None):
     """Y = VL_NNCONV(X, F, B) / [DX, DF, DB] = VL_NNCONV(X, F, B, DZDY).
 
     `gate` (forward, extension; 1 x 1 x K x N): per-(channel, sample) multiplier between scale / shift and the residual --
@@ -161,6 +161,9 @@ def vl_nnconv(x, f, b=None, dzdy=None, stride=1, pad=0, dilate=1, no_der_data=Fa
     `scale/shift/residual/relu/sigmoid` select the fused forward epilogue (extension; see xmodal.h);
     `residual_stride=(sy, sx)` (forward, extension): RESIDUAL has an extent of its own, RH x RW x K x N, and is sampled at
     (oy * sy, ox * sx); Ho must equal floor((RH - 1) / sy) + 1, likewise Wo (xm_nnconv_forward_strided_residual);
+    `out_lattice=(ly, lx)` (forward, extension; with scale / shift / relu only): Y keeps its full extent but only the pixels
+    (ly * i, lx * j) are computed, with the bits of the full-extent call; the other elements of Y are unspecified
+    (xm_nnconv_forward_lattice: what a layer whose only reader has stride (ly, lx) needs);
     `dx_accum` (backward, extension): DX = dgrad + dx_accum in the dgrad epilogue."""
     x, f = _chk(x, "X"), _chk(f, "F")
     H, W, Cc, N = _shape4(x)
@@ -179,7 +182,14 @@ def vl_nnconv(x, f, b=None, dzdy=None, stride=1, pad=0, dilate=1, no_der_data=Fa
     if dzdy is None:
         y = mat_empty(max(Ho, 0), max(Wo, 0), K, N, device=x.device)
         fused = scale is not None or residual is not None or relu or sigmoid
-        if residual_stride is not None:
+        if out_lattice is not None:
+            if residual is not None or gate is not None or sigmoid or moments_out is not None or residual_stride is not None:
+                raise ValueError("vl_nnconv: out_lattice takes the scale / shift / relu epilogue only")
+            lty, ltx = _pair(out_lattice, "OUT_LATTICE")
+            _lib.check(L.xm_nnconv_forward_lattice(
+                _ptr(x), H, W, Cc, N, _ptr(f), FH, FW, FC, K, _ptr(bb), _ptr(y), sy, sx, pt, pb, pl, pr, dy, dx,
+                _ptr(scale), _ptr(shift), None, 1 if relu else 0, lty, ltx, _stream()))
+        elif residual_stride is not None:
             if residual is None:
                 raise ValueError("vl_nnconv: residual_stride without a residual")
             if moments_out is not None or sigmoid:
