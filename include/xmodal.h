@@ -27,6 +27,10 @@
  *     Gram route): an Inf or NaN just OUTSIDE an output's receptive field can turn that output into NaN there, where
  *     MatConvNet -- and this library's generic implicit-GEMM arm -- would stay finite.  Results are specified for finite
  *     X, F, DZDY; which arm runs is a function of (shape, tuning table, exec hint), see xm_set_exec_hint.
+ *     The bf16x3 arm (xm_nnconv_forward_split) narrows this further: its derived error bound holds for operands whose
+ *     magnitude is 0 or within [2^-100, 2^100].  Outside that range the hi half can overflow to Inf or the lo half
+ *     underflow to 0 (the result is then NaN / Inf, or carries a plain bf16 rounding of that operand); the kernel faults on
+ *     no finite input.
  */
 #ifndef XMODAL_H
 #define XMODAL_H
@@ -57,7 +61,7 @@ enum { XM_FUSE_RELU = 1, XM_BN_BATCH_MOMENTS = 2, XM_FUSE_SIGMOID = 4 };
 
 /* ABI revision: 100 = round 1; 101 = xm_nnbnorm_relu_pool_backward gained `y_pool`, exchange entry points return
  * XM_EINVAL without a communicator; 102 = + xm_nnconv_forward_moments, xm_nnbnorm_backward_dxsum, xm_nnconv_forward_gated;
- * 103 = + xm_nnpool_global_avg_backward_accum; 104 = + xm_nnconv_backward_filter_bnrelupool, xm_nndropout_forward / _apply, xm_resample, xm_se_tail_backward_reduce / _apply, xm_se_squeeze_bn, xm_scale_axpy_bn; 105 = + xm_set_exec_hint / xm_get_exec_hint; 106 = + xm_nnconv_bnorm_relu_pool_forward, xm_stem_gram, xm_stem_gram_moments, xm_nnconv_backward_filter_bnrelupool_gram; 107 = + xm_nnaffinegrid / _backward, xm_nnbilinearsampler / _backward, xm_ferplus_batch; 108 = + XM_AGG_PEAK, xm_mnrfit, xm_mnrval; 109 = + xm_roc, xm_roc_launches, xm_label_hist; 110 = + xm_group_rows, xm_gather_rows, xm_scatter_rows, xm_track_peaks; 111 = + xm_wav_batch; 112 = + xm_spec_bucket_batch; 113 = + xm_jpeg_plan, xm_jpeg_decode_batch; 114 = + xm_wav_plan, xm_wav_decode_batch; 115 = + xm_jpeg_decode_batch_split, xm_jpeg_split_geometry; 116 = + xm_pixcsv_plan, xm_pixcsv_decode_batch, xm_pixcsv_geometry; 117 = + xm_nnconv_forward_strided_residual; 118 = + xm_solver_update; 119 = + xm_nnnormalize_forward / _backward, xm_nnnormalize_geometry; 120 = + xm_jpeg_plan_prog, xm_jpeg_decode_batch_prog; 121 = + xm_window_targets; 122 = + xm_wav_plan_fs, xm_wav_decode_resample_batch, xm_wav_resample_geometry; 123 = + xm_nnconv_forward_lattice (additions never change the revision's meaning for older bindings).  A binding checks xm_version() >= the revision it was written against. */
+ * 103 = + xm_nnpool_global_avg_backward_accum; 104 = + xm_nnconv_backward_filter_bnrelupool, xm_nndropout_forward / _apply, xm_resample, xm_se_tail_backward_reduce / _apply, xm_se_squeeze_bn, xm_scale_axpy_bn; 105 = + xm_set_exec_hint / xm_get_exec_hint; 106 = + xm_nnconv_bnorm_relu_pool_forward, xm_stem_gram, xm_stem_gram_moments, xm_nnconv_backward_filter_bnrelupool_gram; 107 = + xm_nnaffinegrid / _backward, xm_nnbilinearsampler / _backward, xm_ferplus_batch; 108 = + XM_AGG_PEAK, xm_mnrfit, xm_mnrval; 109 = + xm_roc, xm_roc_launches, xm_label_hist; 110 = + xm_group_rows, xm_gather_rows, xm_scatter_rows, xm_track_peaks; 111 = + xm_wav_batch; 112 = + xm_spec_bucket_batch; 113 = + xm_jpeg_plan, xm_jpeg_decode_batch; 114 = + xm_wav_plan, xm_wav_decode_batch; 115 = + xm_jpeg_decode_batch_split, xm_jpeg_split_geometry; 116 = + xm_pixcsv_plan, xm_pixcsv_decode_batch, xm_pixcsv_geometry; 117 = + xm_nnconv_forward_strided_residual; 118 = + xm_solver_update; 119 = + xm_nnnormalize_forward / _backward, xm_nnnormalize_geometry; 120 = + xm_jpeg_plan_prog, xm_jpeg_decode_batch_prog; 121 = + xm_window_targets; 122 = + xm_wav_plan_fs, xm_wav_decode_resample_batch, xm_wav_resample_geometry; 123 = + xm_nnconv_forward_lattice; 124 = + xm_nnconv_forward_split, xm_nnconv_split_geometry, XM_CONV_F32 / XM_CONV_BF16X3 (additions never change the revision's meaning for older bindings).  A binding checks xm_version() >= the revision it was written against. */
 int xm_version(void);
 const char *xm_last_error(void);
 /* Device memory for hosts that have no device-array type of their own (MATLAB's gpuArray is CUDA-only: on an
@@ -173,6 +177,38 @@ int xm_nnconv_forward_lattice(const float *x, int H, int W, int C, int N, const 
                               const float *b, float *y, int sy, int sx, int pt, int pb, int pl, int pr, int dy, int dx,
                               const float *scale, const float *shift, const float *residual, int flags, int lat_y,
                               int lat_x, void *stream);
+/* Extension (ABI 124): the bf16x3 arm of 1 x 1 layers -- an opt-in fast mode with a stated error, for forward-only
+ * (frozen teacher) use.  Operands, optional NULLs, extent checks and XM_FUSE_RELU are those of
+ * xm_nnconv_forward_strided_residual:
+ *   y(oy, ox, k, n) = act( ((sum_c x(oy sy, ox sx, c, n) f(c, k) + b_k) scale_k + shift_k) gate(k, n)
+ *                          + residual(oy res_sy, ox res_sx, k, n) )
+ * with the epilogue in fp32, in the order of operations of the fp32 kernels; only the dot product differs.  Each fp32
+ * operand is written v = hi + lo + r, hi = bf16(v) (round to nearest even), lo = bf16(v - hi) (v - hi is exact), so
+ * |v - hi| <= 2^-8 |v| and |r| <= 2^-16 |v|.  Per 16 reduction steps three v_mfma_f32_32x32x16_bf16 add into ONE fp32
+ * accumulator in this fixed order, small terms first:  x_lo f_hi,  x_hi f_lo,  x_hi f_hi  (each bf16 x bf16 product is exact
+ * in fp32); c ascends, the C tail is zero-filled.  Dropped per product: x_lo f_lo + r_x f + x r_f, so
+ *   | dot - exact | <= 3 * 2^-16 * sum_c |x| |f|  (+ second-order terms, + the fp32 accumulation of C products)
+ * -- a DERIVED bound, for operands of magnitude 0 or within [2^-100, 2^100] (FINITE INPUTS above).
+ * DETERMINISM: one accumulation chain per output, never split-K, no atomics, one fixed tile configuration and no tuning-table
+ * entry: the bits of an output element depend on its own operands only -- not on N, not on which other pixels the call
+ * computes (a strided call gives the bits of the unit-stride call on the pre-sampled input), not on what the process ran
+ * before.
+ * precision: XM_CONV_BF16X3.  XM_CONV_F32 names the other entry points' arithmetic and is XM_EINVAL here, like an unknown
+ * value, a NULL tensor with work to do, and residual extents that do not match.  XM_ENOTSUP, with a message, for what the
+ * kernel is not built for: a filter larger than 1 x 1, padding, filter groups (FC != C), XM_FUSE_SIGMOID, a tensor of 2^31
+ * elements or more.  Dilation is accepted and ignored (a 1 x 1 filter has one tap).  Both kinds are raised before anything
+ * touches the device.
+ * xm_nnconv_split_geometry: host only, no device call, usable without a GPU.  can: the call above would run; want: a
+ * forward-only plan should send this layer to it (a pure function of the shape: the measured rule of conv_split_plan.h;
+ * can == 0 implies want == 0); blocks / launches: the launch geometry (128 pixels x 64 output channels per block, pixels
+ * numbered across samples; one launch), 0 when can == 0.  Always XM_OK; NULL outputs are skipped. */
+enum { XM_CONV_F32 = 0, XM_CONV_BF16X3 = 1 };
+int xm_nnconv_forward_split(const float *x, int H, int W, int C, int N, const float *f, int FH, int FW, int FC, int K,
+                            const float *b, float *y, int sy, int sx, int pt, int pb, int pl, int pr, int dy, int dx,
+                            const float *scale, const float *shift, const float *gate, const float *residual, int res_H,
+                            int res_W, int res_sy, int res_sx, int flags, int precision, void *stream);
+int xm_nnconv_split_geometry(int H, int W, int C, int N, int FH, int FW, int FC, int K, int sy, int sx, int pt, int pb,
+                             int pl, int pr, int dy, int dx, int flags, int *can, int *want, int *blocks, int *launches);
 /* Extension: Y = vl_nnconv(X, F, B, ...) AND the batch moments of Y that a train-mode vl_nnbnorm(Y, G, B) would
  * compute first -- moments_out (K x 2, column-major) = [mean_k, sqrt(var_k + epsilon)] over H x W x N, biased
  * variance (emoVoxZoo.m:118-123: every dagnn.Conv of the student is followed by dagnn.BatchNorm).  Hand them to

@@ -73,6 +73,8 @@ int xm_prof_kernel_name(int key, char *buf, int len);
  *   "spec_blocks"    v >= 1: xm_spec_bucket_batch launches spec_gemm_kernel with min(v, 65535) blocks (and sizes the partial
  *                    slots from it), so that a small input gives every block many tiles; 0 or negative: CUs x 2 (default).
  *                    Only the grouping of the fp64 merges of a clip's statistics follows it (tests/test_gpu_spec_edges.py)
+ *   "conv_split_want"  what xm_nnconv_split_geometry reports as WANT: 1 wherever the bf16x3 kernel can run, 0 nowhere, -1 the
+ *                    measured rule of conv_split_plan.h (default).  The kernel itself runs whenever it is called
  *   "comm_single"    1: xm_comm_init with one worker creates a real one-rank RCCL communicator (tests of the exchange path)
  * (xm_debug_conv_cycles -- per-block shader-clock records for tools/conv_bench.py --cycles -- exists only in a library
  * built with XM_DEBUG_CYCLES=1.) */

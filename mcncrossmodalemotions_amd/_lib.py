@@ -45,6 +45,9 @@ SIGNATURES = {
                                [c_fp, c_fp, c_fp, c_fp, _i, _vp],
     "xm_nnconv_forward_strided_residual": [c_fp] + [_i] * 4 + [c_fp] + [_i] * 4 + [c_fp, c_fp] + [_i] * 8 +
                                           [c_fp, c_fp, c_fp, c_fp] + [_i] * 5 + [_vp],
+    "xm_nnconv_forward_split": [c_fp] + [_i] * 4 + [c_fp] + [_i] * 4 + [c_fp, c_fp] + [_i] * 8 +
+                               [c_fp, c_fp, c_fp, c_fp] + [_i] * 6 + [_vp],
+    "xm_nnconv_split_geometry": [_i] * 17 + [C.POINTER(C.c_int)] * 4,
     "xm_nnconv_forward_lattice": [c_fp] + [_i] * 4 + [c_fp] + [_i] * 4 + [c_fp, c_fp] + [_i] * 8 +
                                  [c_fp, c_fp, c_fp, _i, _i, _i, _vp],
     "xm_nnconv_forward_fused": [c_fp] + [_i] * 4 + [c_fp] + [_i] * 4 + [c_fp, c_fp] + [_i] * 8 +

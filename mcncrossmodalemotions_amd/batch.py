@@ -528,13 +528,15 @@ class OnlineTeacher:
       frames(paths, device) -> decoded pixels (vl.crop_resize_face); exactly one of the two
       chunk     at most that many faces per teacher call
       framesPerPair, seed   online_frame_plan's option and the seed of its generator
+      precision zoo.FrozenTeacher's (None | 'fp32' | 'bf16x3'); .precision is what the teacher runs at
       overlap   the whole of targets() is enqueued on a stream of the object's own that first waits for the calling
                 stream; the returned event is recorded behind the targets.  False: the calling stream, event None.
     Nothing synchronises the host."""
 
     def __init__(self, teacher, imdb, *, read=None, frames=None, lanes=2, chunk=128, framesPerPair="all", overlap=True,
-                 split=None, progressive=False, seed=0):
+                 split=None, progressive=False, seed=0, precision=None):
         from . import fetch_emovoxceleb_imdb as fe
+        fe.check_precision(precision, "OnlineTeacher")
         if progressive and split is not None:
             raise ValueError("OnlineTeacher: progressive=True and split= exclude each other (vl.imreadjpeg)")
         if (frames is None) == (read is None):
@@ -546,7 +548,8 @@ class OnlineTeacher:
         online_frame_plan(imdb, [], [], framesPerPair)                   # refuses a bad framesPerPair before any device work
         if not torch.cuda.is_available():
             raise RuntimeError("OnlineTeacher needs a GPU; this build has no CPU path")
-        self.model, self.imageSize, self.averageImage = fe._as_teacher(teacher, lanes)
+        self.model, self.imageSize, self.averageImage = fe._as_teacher(teacher, lanes, precision)
+        self.precision = getattr(self.model, "precision", "fp32")
         self._norm = fe._Norm(self.imageSize, self.averageImage)
         self._getImageBatch = fe.getImageBatch
         self.imdb, self.read, self.frames = imdb, read, frames

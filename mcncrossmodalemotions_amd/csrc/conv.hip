@@ -2150,6 +2150,7 @@ static const struct DebugSwitch {
     {"wgrad_patch", &g_force_wgrad_patch, norm_tri}, {"wgrad_patch_s2", &g_force_wgrad_patch_s2, norm_tri},
     {"dgrad_s2", &g_force_dgrad_s2, norm_tri},
     {"spec_blocks", &g_spec_blocks, [](int v) { return v > 0 ? v : 0; }},
+    {"conv_split_want", &g_conv_split_want, norm_tri},
 };
 static const DebugSwitch *debug_switch(const char *key) {
   for (const DebugSwitch &s : kDebugSwitches)

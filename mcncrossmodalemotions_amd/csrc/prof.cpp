@@ -63,6 +63,7 @@ static const ProfRow kProfRows[] = {
     {kProfWav, 1, {"wav_decode_kernel"}},
     {kProfWavRate, 2, {"wav_rate_gain_kernel", "wav_resample_kernel"}},
     {kProfPixcsv, 1, {"pixcsv_decode_kernel"}},
+    {kProfConvSplit, 1, {"conv_split_kernel"}},
     // inexact: the register-window rows name the N = 5 instantiation (the VGG-M family's) for every window width
     {kProfLrn, 6, {"lrn_forward_kernel<5, false>", "lrn_forward_kernel<5, true>", "lrn_backward_kernel<5, false>",
                    "lrn_backward_kernel<5, true>", "lrn_general_kernel<false>", "lrn_general_kernel<true>"}},

@@ -29,6 +29,7 @@ enum ProfKind {
   kProfLrn = 25,            // lrn.hip, sub = 2 * backward + 16-byte arm; 4 / 5: the general arm, forward / backward
   kProfJpegProg = 26,       // jpeg_prog.hip: the entropy launch of a level, the two smoothing launches
   kProfWavRate = 27,        // wav.hip, decode + resample: sub = 0 the gains, 1 the data
+  kProfConvSplit = 28,      // conv_split.hip: the bf16x3 arm of 1 x 1 layers
 };
 constexpr int prof_key(ProfKind kind, int sub = 0) { return kind * 100 + sub; }
 

@@ -93,6 +93,8 @@ double env_double(const char *name, double dflt);
 int comm_force_single(int on);
 // spec.hip: test switch behind xm_debug_set("spec_blocks", v)
 extern int g_spec_blocks;
+// conv_split.hip: test switch behind xm_debug_set("conv_split_want", v)
+extern int g_conv_split_want;
 // conv.hip: test switch behind xm_debug_set("conv_stem", v), and the checked geometry of a vl_nnconv call (struct Geo:
 // conv_plan.h) -- stem_pool.hip needs both
 extern int g_force_stem;

@@ -510,6 +510,10 @@ class DagNN:
         # ... and a convolution whose only reader is such a pruned expansion computes the lattice of pixels the expansion
         # samples, in place in its full-extent output (_prune_reader_lattices; off with stridePrune too)
         self.latticePrune = os.environ.get("XM_LATTICE_PRUNE", "1") != "0"
+        # forward-only test-mode plans: 'bf16x3' sends the 1 x 1 layers for which xm_nnconv_split_geometry says can && want
+        # to the split-bf16 matrix-core kernel (vl_nnconv precision=; error <= 3 * 2^-16 * sum |x||f| per product sum).
+        # 'fp32' (default): the plan and every bit are what they are without the option.  Training plans never look at it.
+        self.convPrecision = "fp32"
         self.wgradStream = None  # optional side HIP stream for the filter / bias derivatives
         self.gradHook = None     # callable(layer name): called right after a conv layer's parameter
                                  # derivatives were enqueued, on the stream they were enqueued on
@@ -617,6 +621,7 @@ class DagNN:
         r = DagNN()
         r.meta, r.mode, r.fuse, r.device = self.meta, self.mode, self.fuse, self.device
         r.conserveMemory, r.stridePrune, r.latticePrune = self.conserveMemory, self.stridePrune, self.latticePrune
+        r.convPrecision = self.convPrecision
         for l in self.layers:
             r.layers.append(_LayerRec(l.name, copy.copy(l.block), l.inputs, l.outputs, l.params))
         r.params = self.params
@@ -836,7 +841,9 @@ class DagNN:
     def _plan(self, training):
         # the set of precious variables is part of the key: a fused step never materialises the intermediate
         # variables it swallows, so marking one precious after a plan was built must rebuild the plan
-        key = (training, self.mode, self.fuse, self.stridePrune, self.latticePrune, len(self.layers),
+        if self.convPrecision not in ("fp32", "bf16x3"):
+            raise ValueError("dagnn: convPrecision is %r, expected 'fp32' or 'bf16x3'" % (self.convPrecision,))
+        key = (training, self.mode, self.fuse, self.stridePrune, self.latticePrune, self.convPrecision, len(self.layers),
                tuple(n for n, v in self.vars.items() if v.precious))
         layers = [id(l) for l in self.layers]
         if self._plan_key != key or self._plan_layers != layers:
@@ -896,6 +903,10 @@ class _Step:
         # pruned expansion with run_stride (s, s) -- the step computes the output pixels (s i, s j), in place in its
         # full-extent output; the other elements of that variable are unspecified and nothing reads them
         self.out_lattice = None
+        # forward-only test-mode plans of a net with convPrecision = 'bf16x3' (build_plan): 'bf16x3' on every step that
+        # issues a forward vl_nnconv; _forward_conv then asks the library per shape
+        self.precision = None
+        self._split_ok = {}
 
     def _stride(self):
         return self.rec.block.stride if self.run_stride is None else self.run_stride
@@ -964,6 +975,9 @@ class _ConvStep(_Step):
                              dilate=blk.dilate, moments_out=mo, epsilon=bn.block.epsilon)
             bn.block._pre_moments = mo
             return [y]
+        if self.precision is not None:
+            return [_forward_conv(self, ins[0], prm[0], prm[1] if blk.hasBias else None, stride=self._stride(), pad=blk.pad,
+                                  dilate=blk.dilate)]
         if self.run_stride is not None:
             return [vl.vl_nnconv(ins[0], prm[0], prm[1] if blk.hasBias else None, stride=self.run_stride, pad=blk.pad,
                                  dilate=blk.dilate)]
@@ -1367,6 +1381,23 @@ class _BnReluPoolStep(_BnStep):
         return True
 
 
+def _forward_conv(step, x, f, b, **kw):
+    """the forward vl_nnconv of a forward-only test-mode plan step.  step.precision None (net.convPrecision 'fp32'): the call
+    as written.  'bf16x3': the library is asked per shape (xm_nnconv_split_geometry, host only) and the layers it says
+    can && want for run on the split-bf16 kernel; a sigmoid epilogue and a lattice-pruned 3 x 3 stay fp32 by `can`."""
+    if step.precision == "bf16x3" and kw.get("out_lattice") is None:
+        key = (tuple(x.shape), tuple(f.shape), tuple(vl._pair(kw.get("stride", 1), "STRIDE")))
+        ok = step._split_ok.get(key)
+        if ok is None:
+            g = vl.conv_split_geometry(x.shape, f.shape, stride=kw.get("stride", 1), pad=kw.get("pad", 0),
+                                       dilate=kw.get("dilate", 1), relu=bool(kw.get("relu")), sigmoid=bool(kw.get("sigmoid")))
+            ok = step._split_ok[key] = g["can"] and g["want"]
+        if ok:
+            kw.pop("out_lattice", None)
+            return vl.vl_nnconv(x, f, b, precision="bf16x3", **kw)
+    return vl.vl_nnconv(x, f, b, **kw)
+
+
 class _ConvActStep(_Step):
     """forward-only plans: Conv -> ReLU / Sigmoid with the activation in the producing kernel (the SE gate's
     fc1 -> relu and fc2 -> sigmoid: four launches become two skinny-FC kernels, see xm_nnconv_forward_fused)."""
@@ -1380,8 +1411,8 @@ class _ConvActStep(_Step):
     def _values(self, net, ins):
         blk, par = self.rec.block, self._params(net)
         sig = isinstance(self.act_rec.block, Sigmoid)
-        return [vl.vl_nnconv(ins[0], par[0], par[1] if blk.hasBias else None, stride=self._stride(),
-                             pad=blk.pad, dilate=blk.dilate, relu=not sig, sigmoid=sig)]
+        return [_forward_conv(self, ins[0], par[0], par[1] if blk.hasBias else None, stride=self._stride(),
+                              pad=blk.pad, dilate=blk.dilate, relu=not sig, sigmoid=sig)]
 
     def backward(self, net):
         raise RuntimeError("dagnn: a forward-only plan was asked for derivatives")
@@ -1418,9 +1449,9 @@ class _ConvFoldStep(_Step):
             other = [v for v in self.sum_rec.inputs if v != self.bn_rec.outputs[0]][0]
             resid = net.vars[other].value
         pruned = self.run_stride if (resid is not None and self.run_stride != (1, 1)) else None
-        return [vl.vl_nnconv(ins[0], prm[0], prm[1] if blk.hasBias else None, stride=self._stride(), pad=blk.pad,
-                             dilate=blk.dilate, scale=sc, shift=sh, residual=resid, residual_stride=pruned,
-                             relu=self.relu_rec is not None, out_lattice=self.out_lattice)]
+        return [_forward_conv(self, ins[0], prm[0], prm[1] if blk.hasBias else None, stride=self._stride(), pad=blk.pad,
+                              dilate=blk.dilate, scale=sc, shift=sh, residual=resid, residual_stride=pruned,
+                              relu=self.relu_rec is not None, out_lattice=self.out_lattice)]
 
     def backward(self, net):
         raise RuntimeError("folded conv+bn steps exist only in forward-only test-mode plans")
@@ -1487,9 +1518,10 @@ class _SEFoldStep(_ConvFoldStep):
             h = vl.vl_nnconv(z, f1[0], b1, relu=True)
         a = vl.vl_nnconv(h, f2[0], f2[1] if se["fc2"].block.hasBias else None, sigmoid=True)
         # (a pruned step samples only the excite's write: the squeeze above is a mean over ALL pixels of u)
-        return [vl.vl_nnconv(u, prm[0], bias, stride=self._stride(), pad=blk.pad, dilate=blk.dilate, scale=sc, shift=sh,
-                             gate=a, residual=net.vars[se["shortcut"]].value, residual_stride=self.run_stride,
-                             relu=se["relu"] is not None)]
+        # (the squeeze and the two gate layers above stay fp32; only the wide projection may take the bf16x3 arm)
+        return [_forward_conv(self, u, prm[0], bias, stride=self._stride(), pad=blk.pad, dilate=blk.dilate, scale=sc, shift=sh,
+                              gate=a, residual=net.vars[se["shortcut"]].value, residual_stride=self.run_stride,
+                              relu=se["relu"] is not None)]
 
 
 # ---- building a plan: who reads and writes what, the fusions by kind of plan, the links, the pruning --------------------
@@ -1718,4 +1750,8 @@ def build_plan(net, training):
         _prune_strided_boundaries(w, steps)
         if net.latticePrune:
             _prune_reader_lattices(w, steps)
+    if not training and net.mode == "test" and net.convPrecision == "bf16x3":
+        for st in steps:
+            if isinstance(st, (_ConvStep, _ConvActStep, _ConvFoldStep)):
+                st.precision = "bf16x3"
     return steps

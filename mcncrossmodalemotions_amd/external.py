@@ -249,13 +249,14 @@ def compute_audio_feats_files(dag, files, numEmotions=8, limit=float("inf"), max
 
 
 def compute_visual_feats(dag, track_frames, batchSize=128, numEmotions=8, limit=float("inf"), lanes=2, *, read=None,
-                         split=None, progressive=False, modelDir=None):
+                         split=None, progressive=False, modelDir=None, precision=None):
     """faceLogits = compute_visual_feats(dag, track_frames): the frames of all tracks are flattened
     (:63-69), pushed through the frozen teacher `batchSize` at a time (:81-94) and the logits are split
     back per track (:104-109).  track_frames: list of 224 x 224 x 3 x F_i normalised face mats; with
     `read(paths) -> list of bytes` a list of frame-path lists instead, and every batch comes from
     fetch_emovoxceleb_imdb.getImageBatch (:123-164: the JPEG files decoded on the device; `split` and `progressive` go there).
-    `dag` may be a model name, as upstream (:49 ferPlusZoo(opts.modelName)); `modelDir` then names the model files' directory."""
+    `dag` may be a model name, as upstream (:49 ferPlusZoo(opts.modelName)); `modelDir` then names the model files' directory.
+    `precision`: zoo.FrozenTeacher's (None | 'fp32' | 'bf16x3': the split-bf16 arm of the teacher's 1 x 1 layers)."""
     if progressive and split is not None:
         raise ValueError("compute_visual_feats: progressive=True and split= exclude each other (vl.imreadjpeg)")
     if isinstance(dag, str):
@@ -266,7 +267,7 @@ def compute_visual_feats(dag, track_frames, batchSize=128, numEmotions=8, limit=
         from . import fetch_emovoxceleb_imdb as fe
         counts = [len(track_frames[i]) for i in first_ok]
         paths = [p for i in first_ok for p in track_frames[i]]
-        teacher = zoo.FrozenTeacher(dag, lanes=lanes)
+        teacher = zoo.FrozenTeacher(dag, lanes=lanes, precision=precision)
         outs = [teacher.logits(fe.getImageBatch(paths[s:s + batchSize], dag, read=read, split=split,
                                                 progressive=progressive))
                 for s in range(0, len(paths), batchSize)]
@@ -278,7 +279,7 @@ def compute_visual_feats(dag, track_frames, batchSize=128, numEmotions=8, limit=
             off += c
         return faceLogits
     counts = [int(track_frames[i].shape[3]) for i in first_ok]
-    teacher = zoo.FrozenTeacher(dag, lanes=lanes)
+    teacher = zoo.FrozenTeacher(dag, lanes=lanes, precision=precision)
     flat = []
     for i in first_ok:
         t = track_frames[i]

@@ -49,9 +49,10 @@ class EmoVoxImdb(xbatch.SyntheticEmoVoxImdb):
 
     PER_FRAME = ("denseFrames", "denseFramesWavIds")
 
-    def __init__(self, images, fs=16000, seed=0, wavLogits=None):
+    def __init__(self, images, fs=16000, seed=0, wavLogits=None, precision="fp32"):
         self.images, self.fs, self.seed = images, int(fs), int(seed)
         self.wavLogits = wavLogits
+        self.precision = precision       # the arithmetic of the teacher that wrote wavLogits (buildImdb teacherPrecision)
         self._dev = None
 
     set = property(lambda self: np.asarray(self.images["set"]))
@@ -116,9 +117,21 @@ def addFramesToImdb(imdb, lister, *, find=None, expectFrames=None):
     return new
 
 
-def _as_teacher(teacher, lanes):
-    """:98-110: strip the losses, test mode, a single input, on the device -> (object with .logits, imageSize, avg)"""
+def check_precision(precision, who):
+    if precision not in (None, "fp32", "bf16x3"):
+        raise ValueError("%s: teacher precision is %r, expected None, 'fp32' or 'bf16x3'" % (who, precision))
+    return precision
+
+
+def _as_teacher(teacher, lanes, precision=None):
+    """:98-110: strip the losses, test mode, a single input, on the device -> (object with .logits, imageSize, avg).
+    `precision` (None: as the teacher stands) goes to zoo.FrozenTeacher; an object that already has .logits keeps its own
+    and must not contradict the one asked for."""
+    check_precision(precision, "teacher")
     if hasattr(teacher, "logits"):
+        own = getattr(teacher, "precision", "fp32")
+        if precision is not None and precision != own:
+            raise ValueError("the teacher object runs at precision %r, %r was asked for" % (own, precision))
         return (teacher, tuple(getattr(teacher, "imageSize", (224, 224)))[:2],
                 getattr(teacher, "averageImage", AVERAGE_IMAGE))
     zoo.strip_losses(teacher)                                                            # :101-106
@@ -128,7 +141,7 @@ def _as_teacher(teacher, lanes):
     if teacher.device is None:
         teacher.move("gpu")                                                              # :108
     norm = teacher.meta["normalization"]
-    return zoo.FrozenTeacher(teacher, lanes=lanes), tuple(norm["imageSize"][:2]), norm["averageImage"]
+    return zoo.FrozenTeacher(teacher, lanes=lanes, precision=precision), tuple(norm["imageSize"][:2]), norm["averageImage"]
 
 
 def read_files(faceDir):
@@ -168,7 +181,7 @@ class _Norm:
 
 
 def buildImdb(teacher, imdb, frames=None, *, read=None, limit=math.inf, batchSize=128, lanes=2, device=None,
-              split=None, progressive=False):
+              split=None, progressive=False, teacherPrecision=None):
     """imdb = buildImdb(teacher) -- :54-149, for an imdb that went through addFramesToImdb.  `teacher`: a ferPlusZoo
     network (losses are stripped, test mode, one input: :101-110) or any object with .logits(faces) -> 1 x 1 x E x n;
     `frames(paths, device)` -> the decoded frames Hin x Win x 3 x n (0..255), what vl_imreadjpeg returns for
@@ -177,9 +190,11 @@ def buildImdb(teacher, imdb, frames=None, *, read=None, limit=math.inf, batchSiz
       device_logits()  the same rows concatenated on the device, already in place.
     With `read(paths) -> list of bytes` instead of `frames` the batch comes from getImageBatch: the JPEG files are
     decoded on the device (frames of any sizes in one batch); `split` and `progressive` go to getImageBatch.
+    `teacherPrecision` (None | 'fp32' | 'bf16x3'): zoo.FrozenTeacher's precision; the imdb records what ran (.precision).
     The loop enqueues work only; it neither synchronises nor downloads."""
     if progressive and split is not None:
         raise ValueError("buildImdb: progressive=True and split= exclude each other (vl.imreadjpeg)")
+    check_precision(teacherPrecision, "buildImdb")
     if (frames is None) == (read is None):
         raise ValueError("buildImdb: give either `frames` (decoded pixels) or `read` (JPEG bytes)")
     if (split is not None or progressive) and read is None:
@@ -188,7 +203,7 @@ def buildImdb(teacher, imdb, frames=None, *, read=None, limit=math.inf, batchSiz
         raise RuntimeError("buildImdb needs a GPU; this build has no CPU path")
     device = device or torch.device("cuda", torch.cuda.current_device())
     images = imdb.images
-    model, imageSize, avg = _as_teacher(teacher, lanes)
+    model, imageSize, avg = _as_teacher(teacher, lanes, teacherPrecision)
     wavIds = np.asarray(images["denseFramesWavIds"], dtype=np.int64)
     ids = np.asarray(images["id"], dtype=np.int64)
     # compute for the first `limit` tracks (:112-115).  The reference is asymmetric and this keeps it: the frames of the
@@ -231,6 +246,7 @@ def buildImdb(teacher, imdb, frames=None, *, read=None, limit=math.inf, batchSiz
     cells += [np.zeros((0, E), np.float32, order="F") for _ in range(numWavs - numLogits)]   # [] cells past limit (:141)
     new = copy.copy(imdb)
     new.wavLogits = cells
+    new.precision = getattr(model, "precision", "fp32")
     new._dev = (grouped, np.concatenate([h_off, np.full(numWavs - numLogits, kept, np.int64)]))
     return new
 
@@ -254,7 +270,8 @@ def save_imdb(path, imdb):
     cell = np.empty((1, len(imdb.wavLogits)), dtype=object)
     for i, l in enumerate(imdb.wavLogits):
         cell[0, i] = np.asarray(l, dtype=np.float32)
-    savemat(path, {"images": images, "wavLogits": cell, "fs": imdb.fs, "seed": imdb.seed})
+    savemat(path, {"images": images, "wavLogits": cell, "fs": imdb.fs, "seed": imdb.seed,
+                   "precision": getattr(imdb, "precision", "fp32")})
 
 
 def load_imdb(path):
@@ -270,12 +287,24 @@ def load_imdb(path):
     cells = [np.asarray(c, dtype=np.float32) for c in m["wavLogits"].reshape(-1)]
     E = next((int(c.shape[1]) for c in cells if c.ndim == 2 and c.size), E)          # the width the teacher wrote
     wav = [np.asfortranarray(c.reshape(-1, E)) for c in cells]
-    return EmoVoxImdb(images, fs=int(m["fs"].ravel()[0]), seed=int(m["seed"].ravel()[0]), wavLogits=wav)
+    # (a file from before the field existed was written by the fp32 teacher)
+    precision = str(np.asarray(m["precision"]).reshape(-1)[0]).strip() if "precision" in m else "fp32"
+    return EmoVoxImdb(images, fs=int(m["fs"].ravel()[0]), seed=int(m["seed"].ravel()[0]), wavLogits=wav,
+                      precision=precision)
+
+
+def require_precision(imdb, wanted, where):
+    """a cache of teacher logits is good for ONE arithmetic: mixing the targets of two silently is what this refuses"""
+    have = getattr(imdb, "precision", "fp32")
+    if have != wanted:
+        raise ValueError("%s holds teacher logits computed at precision %r, but %r was asked for: use another imdbDir, "
+                         "or ask for teacherPrecision=%r" % (where, have, wanted, have))
+    return imdb
 
 
 def fetch_emovoxceleb_imdb(teacher="senet50-ferplus", imdbDir=os.path.join("data", "xEmo18", "storedFeats"), *,
                            net=None, imdb=None, frames=None, read=None, split=None, progressive=False, verbose=True,
-                           modelDir=None,
+                           modelDir=None, teacherPrecision=None,
                            **buildOpts):
     """loadedImdb = fetch_emovoxceleb_imdb(teacher, 'imdbDir', ..) -- :1-51: the cached imdb of (teacher, imdbDir), else
     <imdbDir>/<teacher>-logits.mat when it exists, else buildImdb and save.  Building needs (keyword-only) `net` (default
@@ -284,19 +313,23 @@ def fetch_emovoxceleb_imdb(teacher="senet50-ferplus", imdbDir=os.path.join("data
     imdb uploads its logits on first use.
     The cache key and the file name hold the teacher's NAME and imdbDir, nothing else: a later call with another
     `net`, `imdb`, `frames` or `limit` under the same name and directory gets the first build back, from the module
-    cache or from the file.  Use another imdbDir (or call buildImdb) for a different build."""
+    cache or from the file.  Use another imdbDir (or call buildImdb) for a different build.
+    `teacherPrecision` (None = 'fp32' | 'bf16x3'): the arithmetic of the teacher's 1 x 1 layers (buildImdb).  The file
+    records it in a `precision` field (a file without the field counts as 'fp32'); a cached or stored imdb written at
+    another precision than the one asked for raises ValueError naming both."""
     if progressive and split is not None:
         raise ValueError("fetch_emovoxceleb_imdb: progressive=True and split= exclude each other (vl.imreadjpeg)")
+    wanted = check_precision(teacherPrecision, "fetch_emovoxceleb_imdb") or "fp32"
     key = (str(teacher), os.path.abspath(imdbDir))
     if key in _CACHE:                                                                    # :19-20
         if verbose:
             print("found imdb in cache, re-using..", flush=True)
-        return _CACHE[key]
+        return require_precision(_CACHE[key], wanted, "the imdb cached for %s" % (key,))
     imdbPath = getImdbPath(imdbDir, teacher)
     if os.path.exists(imdbPath):                                                         # :24-27
         if verbose:
             print("loading imdb ...", flush=True)
-        loaded = load_imdb(imdbPath)
+        loaded = require_precision(load_imdb(imdbPath), wanted, imdbPath)
     else:                                                                                # :28-34
         if verbose:
             print("generating imdb (this will take a long time)...", flush=True)
@@ -309,7 +342,7 @@ def fetch_emovoxceleb_imdb(teacher="senet50-ferplus", imdbDir=os.path.join("data
             raise ValueError("fetch_emovoxceleb_imdb: building needs `frames` for the given imdb")
         loaded = buildImdb(net if net is not None else zoo.ferPlusZoo(teacher, modelDir=modelDir), imdb,
                            frames if read is None else None,
-                           read=read, split=split, progressive=progressive, **buildOpts)
+                           read=read, split=split, progressive=progressive, teacherPrecision=wanted, **buildOpts)
         save_imdb(imdbPath, loaded)
     _CACHE[key] = loaded
     return loaded

@@ -27,7 +27,7 @@ def run_distillation(gpus=(2,), cont=True, miniVal=0.2, numSeconds=4, batchSize=
                      useWav=False, transformation="I", modelDir=None, solver=None, solverOpts=None,
                      nesterovUpdate=False, momentum=0.9, weightDecay=5e-4,
                      teacherMode="cached", teacherNet=None, read=None, frames=None, framesPerPair="all", teacherLanes=2,
-                     overlapTeacher=True, split=None, progressive=False):
+                     overlapTeacher=True, split=None, progressive=False, teacherPrecision=None):
     """Options as in run_distillation.m:72-90.  Extensions (keyword-only): `imdb` (a prepared imdb),
     `dataDir` (root of the experiment directories), `numTracks` / `seed` (synthetic imdb), `widthMult`
     (narrow student for tests), `useWav` (the batches come from the imdb's waveforms through the batched device
@@ -42,14 +42,18 @@ def run_distillation(gpus=(2,), cont=True, miniVal=0.2, numSeconds=4, batchSize=
     addFramesToImdb and needs no wavLogits.  The teacher is `teacherNet`, or zoo.ferPlusZoo(teacher, modelDir=modelDir);
     the frames come from `read` (paths -> JPEG bytes, with `split` / `progressive`) or `frames` (paths, device -> decoded
     pixels); `framesPerPair` ('all' | k frames drawn per window), `teacherLanes` and `overlapTeacher` are OnlineTeacher's
-    framesPerPair, lanes and overlap.  The experiment directory gains -online and -fppK.  Every data-parallel worker
+    framesPerPair, lanes and overlap; `teacherPrecision` (None | 'fp32' | 'bf16x3') is its precision.  The experiment
+    directory gains -online, -fppK and, at 'bf16x3', -bf16x3.  Every data-parallel worker
     runs its own replica of the teacher over its own shard."""
     if teacherMode not in ("cached", "online"):
         raise ValueError("teacherMode: 'cached' or 'online', got %r" % (teacherMode,))
     online = teacherMode == "online"
+    if teacherPrecision not in (None, "fp32", "bf16x3"):
+        raise ValueError("teacherPrecision: None, 'fp32' or 'bf16x3', got %r" % (teacherPrecision,))
     if not online and (teacherNet is not None or read is not None or frames is not None or framesPerPair != "all"
-                       or split is not None or progressive):
-        raise ValueError("teacherNet, read, frames, framesPerPair, split and progressive belong to teacherMode='online'")
+                       or split is not None or progressive or teacherPrecision is not None):
+        raise ValueError("teacherNet, read, frames, framesPerPair, split, progressive and teacherPrecision belong to "
+                         "teacherMode='online'")
     if online and imdb is None:
         raise ValueError("teacherMode='online' needs an imdb with frame lists (fetch_emovoxceleb_imdb.addFramesToImdb)")
     if online and (frames is None) == (read is None):
@@ -71,6 +75,7 @@ def run_distillation(gpus=(2,), cont=True, miniVal=0.2, numSeconds=4, batchSize=
         expDir += "-temp%d" % temperature
     if online:      # other targets than the cached run's: its checkpoints are never resumed
         expDir += "-online" + ("" if framesPerPair == "all" else "-fpp%d" % int(framesPerPair))
+        expDir += "-bf16x3" if teacherPrecision == "bf16x3" else ""
     # ParameterServer before the first device allocation / kernel of the process (xmodal.h "CALL ORDER": a communicator
     # created later slows every step); 'tmove' (run_distillation.m:88) = the library's communicator when there is
     # more than one worker and RCCL can carry it -- every worker of the node on its own device --, torch.distributed
@@ -103,7 +108,8 @@ def run_distillation(gpus=(2,), cont=True, miniVal=0.2, numSeconds=4, batchSize=
     if online:      # behind the communicator, like every device allocation
         provider = xbatch.OnlineTeacher(teacherNet if teacherNet is not None else zoo.ferPlusZoo(teacher, modelDir=modelDir),
                                         imdb, read=read, frames=frames, lanes=teacherLanes, framesPerPair=framesPerPair,
-                                        overlap=overlapTeacher, split=split, progressive=progressive, seed=seed + 23)
+                                        overlap=overlapTeacher, split=split, progressive=progressive, seed=seed + 23,
+                                        precision=teacherPrecision)
 
     def getBatch(imdb_, batch):                                                       # getBatchFn, :210-224
         tr = net.meta["augmentation"]["transformation"]

@@ -151,7 +151,7 @@ def out_size(n, pa, pb, f, d, s):
 def vl_nnconv(x, f, b=None, dzdy=None, stride=1, pad=0, dilate=1, no_der_data=False,
               no_der_filters=False, no_der_biases=False, scale=None, shift=None, residual=None,
               relu=False, df_out=None, db_out=None, dx_accum=None, sigmoid=False, moments_out=None, epsilon=1e-4,
-              gate=None, residual_stride=None, out_lattice=None):
+              gate=None, residual_stride=None, out_lattice=None, precision=None):
     """Y = VL_NNCONV(X, F, B) / [DX, DF, DB] = VL_NNCONV(X, F, B, DZDY).
 
     `gate` (forward, extension; 1 x 1 x K x N): per-(channel, sample) multiplier between scale / shift and the residual --
@@ -164,7 +164,16 @@ def vl_nnconv(x, f, b=None, dzdy=None, stride=1, pad=0, dilate=1, no_der_data=Fa
     `out_lattice=(ly, lx)` (forward, extension; with scale / shift / relu only): Y keeps its full extent but only the pixels
     (ly * i, lx * j) are computed, with the bits of the full-extent call; the other elements of Y are unspecified
     (xm_nnconv_forward_lattice: what a layer whose only reader has stride (ly, lx) needs);
-    `dx_accum` (backward, extension): DX = dgrad + dx_accum in the dgrad epilogue."""
+    `dx_accum` (backward, extension): DX = dgrad + dx_accum in the dgrad epilogue;
+    `precision` (forward, extension): None / 'fp32' is the library's fp32 arithmetic; 'bf16x3' runs an unpadded, ungrouped
+    1 x 1 layer on the bf16 matrix cores with both operands split in two bf16 halves (xm_nnconv_forward_split: error at
+    most 3 * 2^-16 * sum |x||f| per output, bits independent of the batch) -- with scale / shift / gate / residual /
+    residual_stride / relu, never with dzdy, moments_out, out_lattice or sigmoid."""
+    if precision not in (None, "fp32", "bf16x3"):
+        raise ValueError("vl_nnconv: unknown precision %r (None, 'fp32' or 'bf16x3')" % (precision,))
+    if precision == "bf16x3":
+        return _nnconv_split(x, f, b, dzdy, stride, pad, dilate, scale, shift, residual, relu, sigmoid, moments_out, gate,
+                             residual_stride, out_lattice)
     x, f = _chk(x, "X"), _chk(f, "F")
     H, W, Cc, N = _shape4(x)
     FH, FW, FC, K = _shape4(f)
@@ -254,6 +263,66 @@ def vl_nnconv(x, f, b=None, dzdy=None, stride=1, pad=0, dilate=1, no_der_data=Fa
                                           _ptr(dxo), _ptr(dfo), _ptr(dbo), sy, sx, pt, pb, pl, pr, dy, dx,
                                           _ptr(acc), _stream()))
     return dxo, dfo, dbo
+
+
+CONV_BF16X3 = 1    # include/xmodal.h XM_CONV_BF16X3
+
+
+def conv_split_geometry(xshape, fshape, stride=1, pad=0, dilate=1, relu=False, sigmoid=False):
+    """xm_nnconv_split_geometry (host only, no device call): dict(can, want, blocks, launches) of the bf16x3 arm for a
+    layer of these shapes -- `can`: vl_nnconv(precision='bf16x3') would run it; `want`: a forward-only plan sends it there."""
+    H, W, Cc, N = [int(v) for v in tuple(xshape) + (1,) * (4 - len(xshape))]
+    FH, FW, FC, K = [int(v) for v in tuple(fshape) + (1,) * (4 - len(fshape))]
+    sy, sx = _pair(stride, "STRIDE")
+    dy, dx = _pair(dilate, "DILATE")
+    pt, pb, pl, pr = _pad4(pad)
+    out = [C.c_int(0) for _ in range(4)]
+    _lib.check(_L().xm_nnconv_split_geometry(H, W, Cc, N, FH, FW, FC, K, sy, sx, pt, pb, pl, pr, dy, dx,
+                                             (1 if relu else 0) | (4 if sigmoid else 0), *[C.byref(o) for o in out]))
+    return dict(can=bool(out[0].value), want=bool(out[1].value), blocks=out[2].value, launches=out[3].value)
+
+
+def _nnconv_split(x, f, b, dzdy, stride, pad, dilate, scale, shift, residual, relu, sigmoid, moments_out, gate,
+                  residual_stride, out_lattice):
+    """vl_nnconv(precision='bf16x3'): the forward direction of an unpadded 1 x 1 layer through xm_nnconv_forward_split"""
+    for name, v in (("dzdy", dzdy), ("moments_out", moments_out), ("out_lattice", out_lattice), ("sigmoid", sigmoid or None)):
+        if v is not None:
+            raise ValueError("vl_nnconv: precision='bf16x3' is a forward mode and cannot be combined with %s" % name)
+    x, f = _chk(x, "X"), _chk(f, "F")
+    H, W, Cc, N = _shape4(x)
+    FH, FW, FC, K = _shape4(f)
+    sy, sx = _pair(stride, "STRIDE")
+    dy, dx = _pair(dilate, "DILATE")
+    pt, pb, pl, pr = _pad4(pad)
+    bb = None
+    if b is not None and b.numel() > 0:
+        bb = _chk(b, "B")
+        if bb.numel() != K:
+            raise ValueError("vl_nnconv: B has %d elements, expected %d" % (bb.numel(), K))
+    L = _L()
+    Ho, Wo = L.xm_out_size(H, pt, pb, FH, dy, sy), L.xm_out_size(W, pl, pr, FW, dx, sx)
+    for name, v in (("SCALE", scale), ("SHIFT", shift)):
+        if v is not None and _chk(v, name).numel() != K:
+            raise ValueError("vl_nnconv: %s has %d elements, expected %d" % (name, v.numel(), K))
+    gt = None
+    if gate is not None:
+        gt = _chk(gate, "GATE")
+        if gt.numel() != K * N:
+            raise ValueError("vl_nnconv: GATE must be 1 x 1 x %d x %d" % (K, N))
+    RH, RW, rsy, rsx = 0, 0, 1, 1
+    if residual_stride is not None and residual is None:
+        raise ValueError("vl_nnconv: residual_stride without a residual")
+    if residual is not None:
+        RH, RW, RK, RN = _shape4(_chk(residual, "RESIDUAL"))
+        if residual_stride is not None:
+            rsy, rsx = _pair(residual_stride, "RESIDUAL_STRIDE")
+        if [RK, RN] != [K, N] or (residual_stride is None and [RH, RW] != [Ho, Wo]):
+            raise ValueError("vl_nnconv: residual shape mismatch")
+    y = mat_empty(max(Ho, 0), max(Wo, 0), K, N, device=x.device)
+    _lib.check(L.xm_nnconv_forward_split(
+        _ptr(x), H, W, Cc, N, _ptr(f), FH, FW, FC, K, _ptr(bb), _ptr(y), sy, sx, pt, pb, pl, pr, dy, dx,
+        _ptr(scale), _ptr(shift), _ptr(gt), _ptr(residual), RH, RW, rsy, rsx, 1 if relu else 0, CONV_BF16X3, _stream()))
+    return y
 
 
 def conv_prepare_backward(x, f, stride=1, pad=0, dilate=1):

@@ -461,11 +461,18 @@ class FrozenTeacher:
     A ResNet forward is a chain of ~55 dependent launches; with a single stream every launch pays its
     ramp-up and tail alone, two lanes fill each other's gaps (measured on MI355X: -7 % time at batch
     128, no gain at 32).  Samples are independent in test mode, so the logits are those of the
-    single-lane evaluation up to the summation order of the tile configuration chosen per shape."""
+    single-lane evaluation up to the summation order of the tile configuration chosen per shape.
+    `precision`: None leaves net.convPrecision as it is; 'fp32' / 'bf16x3' set it on the network and every lane's replica
+    (dagnn.DagNN.convPrecision: the opt-in split-bf16 arm of the 1 x 1 layers).  self.precision is what the lanes run."""
 
-    def __init__(self, net, lanes=2, output=None):
+    def __init__(self, net, lanes=2, output=None, precision=None):
         if net.mode != "test":
             raise ValueError("FrozenTeacher needs a test-mode network (fetch_emovoxceleb_imdb.m:107)")
+        if precision not in (None, "fp32", "bf16x3"):
+            raise ValueError("FrozenTeacher: precision is %r, expected None, 'fp32' or 'bf16x3'" % (precision,))
+        if precision is not None:
+            net.convPrecision = precision
+        self.precision = net.convPrecision
         self.output = output or net.getOutputs()[-1]
         net.vars[self.output].precious = True
         self.nets = [net] + [net.replica() for _ in range(max(1, int(lanes)) - 1)]
