@@ -10,25 +10,22 @@ namespace xm {
 
 static bool stem_pool_ok(const Geo &g, const float *x) { return path_on(kPathStem) && stem_pool_can(g, (uintptr_t)x); }
 
-static int stem_pool_units(const Geo &g) { return g.N * ((g.Wo + 1) / 2) * ((g.Ho + 255) / 256); }
 static void stem_pool_args(StemPoolArgs &a, const float *x, const Geo &g) {
   a.X = x, a.M = g.Kg, a.R = g.R, a.nU = g.FH, a.nV = g.FW, a.PI = g.Ho, a.PJ = g.Wo;
-  const int G = (g.Ho + 255) / 256;
-  a.divJG = make_fastdiv((uint32_t)(((g.Wo + 1) / 2) * G)), a.divG = make_fastdiv((uint32_t)G);
+  const int G = sp_row_groups(g.Ho);
+  a.divJG = make_fastdiv((uint32_t)(sp_col_pairs(g.Wo) * G)), a.divG = make_fastdiv((uint32_t)G);
   a.gsx = g.sx, a.gh0 = -g.pt, a.gw0 = -g.pl, a.LimH = g.H, a.LimW = g.W, a.xSampleStride = g.H * g.W;
 }
 
-static int stem_pool_grid(int nunits, int occ) { return std::min(256 * occ, (nunits + 7) / 8 * 8); }
-static size_t stem_gram_need(const Geo &g) {
-  return WsCarver::need((size_t)stem_pool_grid(stem_pool_units(g), 3) * 64 * 64, 4);
-}
+// (units, grids and unit -> work maps of all three kernels: stem_pool_plan.h)
+static size_t stem_gram_need(const Geo &g) { return WsCarver::need(stem_gram_part_floats(g.N, g.Ho, g.Wo), 4); }
 
 // G (fp64 [64][64]) of the patches of x; scratch from the caller's carver
 static int launch_stem_gram(WsCarver &ws, const float *x, const Geo &g, double *gram, hipStream_t st) {
   StemPoolArgs a{};
   stem_pool_args(a, x, g);
-  const int nunits = stem_pool_units(g), grid = stem_pool_grid(nunits, 3);
-  a.part = ws.take<float>((size_t)grid * 64 * 64);
+  const int nunits = stem_pool_units(g.N, g.Ho, g.Wo), grid = stem_pool_grid(nunits, kSpGramOcc);
+  a.part = ws.take<float>(stem_gram_part_floats(g.N, g.Ho, g.Wo));
   static bool attr_done = false;
   if (!attr_done) {
     XM_HIP(hipFuncSetAttribute((const void *)stem_gram_kernel<2>, hipFuncAttributeMaxDynamicSharedMemorySize, kSpGramSmem));
@@ -118,23 +115,8 @@ int xm_nnconv_bnorm_relu_pool_forward(const float *x, int H, int W, int C, int N
   a.Y = y_pool, a.amax = argmax;
   a.M = g.K, a.R = g.R, a.nU = g.FH, a.nV = g.FW;
   a.PI = g.Ho, a.PJ = g.Wo, a.pHo = pHo, a.pWo = pWo;
-  a.NS = (pHo + 62) / 63;
-  const int slots = 256 * XM_SF_OCC * 4;
-  // segments of window columns per (sample, strip, row tile): the count that minimises (rounds of the resident waves) x
-  // (output columns of a unit, one of them computed twice per segment).  A partly filled last round costs a whole one:
-  // 11 segments at 32 spectrograms = 2112 units for 2048 waves ran 285 us, 10 segments 206 us; at 256 spectrograms one
-  // segment leaves a quarter of the waves idle and two make 1.5 rounds, four make exactly three.
-  {
-    const long long base = (long long)g.N * a.NS * 3;
-    long long best = -1;
-    a.SG = 1;
-    for (int sg = 1; sg <= std::min(16, pWo); ++sg) {
-      const long long rounds = (base * sg + slots - 1) / slots;
-      const long long cost = rounds * (2 * ((pWo + sg - 1) / sg) + 1);
-      if (best < 0 || cost < best) best = cost, a.SG = sg;
-    }
-  }
-  a.nunits = g.N * a.NS * a.SG * 3;
+  const SfPlan fp = stem_fwd_plan(g.N, pHo, pWo, XM_SF_OCC);      // strips, segments of window columns, wave units
+  a.NS = fp.NS, a.SG = fp.SG, a.nunits = fp.nunits;
   a.div3 = make_fastdiv(3u), a.divSG = make_fastdiv((uint32_t)a.SG), a.divNS = make_fastdiv((uint32_t)a.NS);
   a.gh0 = -g.pt, a.gw0 = -g.pl, a.LimH = g.H, a.LimW = g.W, a.xSampleStride = g.H * g.W;
   a.yBytes = (unsigned)(pooled * 4), a.amBytes = (unsigned)pooled;
@@ -143,7 +125,7 @@ int xm_nnconv_bnorm_relu_pool_forward(const float *x, int H, int W, int C, int N
     XM_HIP(hipFuncSetAttribute((const void *)conv_stem_bnpool_fwd_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, kSfSmem));
     attr_done = true;
   }
-  const int grid = std::min(256 * XM_SF_OCC, (a.nunits + 3) / 4);
+  const int grid = fp.grid;
   {
     ProfScope ps(prof_key(kProfStemBnpoolFwd), 2.0 * g.K * (double)g.Ho * g.Wo * g.N * g.R, st, 4.0 * g.H * g.W * g.N + 5.0 * (double)pooled);
     hipLaunchKernelGGL(conv_stem_bnpool_fwd_kernel, dim3(grid), dim3(256), kSfSmem, st, a);
@@ -176,14 +158,11 @@ int xm_nnconv_backward_filter_bnrelupool_gram(const float *x, int H, int W, int 
     return fail(XM_ENOTSUP, "vl_nnconv(filter derivative through bnorm+relu+pool, gram): geometry not covered by the fused kernel");
   StemPoolArgs a{};
   stem_pool_args(a, x, g);
-  // wave units (sample, column pair, 64-row chunk pair) x 3 row tiles of filters; grid: whole XCD rows of blocks whose
-  // waves split evenly over the row tiles (a multiple of 24 blocks), two blocks per CU
-  const int ncp = (g.Ho + 63) / 64, npair = (g.Wo + 1) / 2;
-  const int nunits = g.N * npair * ncp;
-  a.divJG = make_fastdiv((uint32_t)npair);
-  a.divG = make_fastdiv((uint32_t)ncp);
-  const int grid = std::min(504, ((nunits * 3 + 3) / 4 + 23) / 24 * 24);      // two blocks per CU, 63 per XCD
-  const int nwc = grid * 4 / 3;
+  // wave units (sample, column pair, 64-row chunk pair) x 3 row tiles of filters
+  const SpBwdPlan bp = stem_bwd_plan(g.N, g.Ho, g.Wo);
+  const int nunits = bp.nunits, grid = bp.grid, nwc = bp.nwc;
+  a.divJG = make_fastdiv((uint32_t)bp.npair);
+  a.divG = make_fastdiv((uint32_t)bp.ncp);
   WsCarver ws;
   rc = ws.init(WsCarver::need((size_t)grid * 4 * 32 * 64, 4) + WsCarver::need(64 * 64, 8) + stem_gram_need(g), st);
   if (rc) return rc;

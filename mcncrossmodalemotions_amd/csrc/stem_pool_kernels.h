@@ -25,6 +25,7 @@
 // (conv_stem_bnpool_fwd_kernel, second part of this file) writes the pooled output and the table without writing x either.
 #pragma once
 #include "conv_plan.h"
+#include "stem_pool_plan.h"
 #include "xm_common.h"
 
 namespace xm {
@@ -59,30 +60,13 @@ constexpr int kSpTP = 36;                     // row pitch (floats) of a dz regi
 constexpr int kSpCst = 64;                    // 32 ones + 32 zeros: what the B lanes of the ones column / the padding columns read
 constexpr int kSpGramSmem = (4 * kSpPatch + kSpCst > 64 * 64 ? 4 * kSpPatch + kSpCst : 64 * 64) * 4;   // bytes per block of stem_gram_kernel
 
-struct SpUnit {
-  int n, jp, cp;         // sample, column pair, 64-row chunk pair of this wave
-  bool live;             // the unit exists and the wave's rows exist
-  bool col1, chunk1;     // the second column / the second 32-row chunk exist
-};
-
 #define XM_SP_COMMON(a)                                                                                              \
   const int t = threadIdx.x, lane = t & 63, wave = t >> 6, half = lane >> 5, l31 = lane & 31;                        \
   const int lc = lane >> 3, lk = lane & 7;                                                                           \
-  const int per = (nunits + 7) >> 3, tbase = (blockIdx.x & 7) * per, tstep = gridDim.x >> 3;                         \
-  const int tend = min(per, nunits - tbase);                                                                         \
+  const SpGramWalk walk = sp_gram_walk((int)blockIdx.x, (int)gridDim.x, nunits);                                     \
+  const int tbase = walk.tbase, tstep = walk.tstep, tend = walk.tend;                                                \
   const int wv = __builtin_amdgcn_readfirstlane(wave);                                                               \
-  auto wave_unit = [&](int unit) {                                                                                   \
-    SpUnit c;                                                                                                        \
-    const uint32_t u = (uint32_t)unit;                                                                               \
-    c.n = (int)xm_div(u, a.divJG);                                                                                   \
-    const uint32_t rem = u - (uint32_t)c.n * a.divJG.d;                                                              \
-    c.jp = (int)xm_div(rem, a.divG);                                                                                 \
-    c.cp = 4 * ((int)rem - c.jp * (int)a.divG.d) + wv;                                                               \
-    c.live = 64 * c.cp < a.PI;                                                                                       \
-    c.col1 = 2 * c.jp + 1 < a.PJ;                                                                                    \
-    c.chunk1 = 64 * c.cp + 32 < a.PI;                                                                                \
-    return c;                                                                                                        \
-  };                                                                                                                 \
+  auto wave_unit = [&](int unit) { return sp_gram_unit(unit, wv, a.divJG, a.divG, a.PI, a.PJ); };                    \
   f32x4 ld[6];                                                                                                       \
   int ldst[6];                                                                                                       \
   bool ldz[6];                                                                                                       \
@@ -143,7 +127,7 @@ stem_gram_kernel(const StemPoolArgs a, const int nunits) {
   for (int i = 0; i < 3; ++i)
 #pragma unroll
     for (int r = 0; r < 16; ++r) acc[i][r] = 0.f;
-  int q = blockIdx.x >> 3;
+  int q = walk.q0;
   __syncthreads();
   SpUnit cur = wave_unit(tbase + min(q, max(tend, 1) - 1));
   if (q < tend) {
@@ -249,7 +233,10 @@ stem_gram_reduce_kernel(const float *__restrict__ part, double *__restrict__ gra
 // 16-byte quads (lane -> filter lane / 4 (+ 16), quad lane % 4 of chunk h) -- pooled derivative, routing codes and (GATE)
 // the pooled forward output -- plus the single window row 32 cp - 1 in front (lanes with lane % 4 == 0: p = 0, == 1: p = 1).
 // A quad that would reach past its pooled column reads the head of the next one (masked); in the last column of the tensor
-// it is shifted back (no load leaves the tensor) and re-aligned after the load.  The derivatives are gated once and stay in
+// it is shifted back and re-aligned after the load.  No load is issued for a filter >= M (the plane offset travels in the
+// load's scalar offset, which the hardware does not range-check): a missing group of 16 is skipped, a lane of a missing filter
+// is out of range by its own offset -- stem_pool_plan.h, checked for every geometry by tests/stem_pool_plan_check.cpp.
+// The derivatives are gated once and stay in
 // registers for the four (column, chunk) steps of the unit; each step composes the wave's dz region [32 filters][32 pixels]
 // in registers (compose_slice below), stores it with two 16-byte LDS stores per filter and multiplies: 32 MFMAs per step.
 // Output column 2 jp takes dw = 0 of window column jp and dw = 2 of jp - 1; column 2 jp + 1 takes dw = 1 of jp.  The next
@@ -262,7 +249,7 @@ stem_gram_reduce_kernel(const float *__restrict__ part, double *__restrict__ gra
 // Logical wave index: XCD x (blocks b % 8 == x) holds a contiguous range, so that the waves that work on neighbouring
 // units at the same time -- and share pooled lines and source columns -- share an L2.
 constexpr int kSp3Wave = kSpPatch + 32 * kSpTP;          // a wave's source patch + its dz region
-constexpr int kSp3Smem = (4 * kSp3Wave + kSpCst) * 4;    // 43 KB per block (two blocks per CU: 229 registers per lane)
+constexpr int kSp3Smem = (4 * kSp3Wave + kSpCst) * 4;    // 43 KB per block (two blocks per CU: 225 registers per lane, GATE: 256)
 template <int SY, bool GATE>
 __global__ void __launch_bounds__(256, 2)
 conv_stem_wgrad_pool_kernel(const StemPoolArgs a, const int nunits) {
@@ -271,9 +258,8 @@ conv_stem_wgrad_pool_kernel(const StemPoolArgs a, const int nunits) {
   const int t = threadIdx.x, lane = t & 63, wave = t >> 6, half = lane >> 5, l31 = lane & 31;
   const int lc = lane >> 3, lk = lane & 7;
   const int wv = __builtin_amdgcn_readfirstlane(wave);
-  const int nb8 = gridDim.x >> 3;                                            // blocks per XCD (grid % 24 == 0)
-  const int wl = ((blockIdx.x & 7) * nb8 + (blockIdx.x >> 3)) * 4 + wv;      // logical wave
-  const int rt = wl % 3, wc = wl / 3, nwc = (gridDim.x * 4) / 3;
+  const SpWave lw = sp_bwd_wave((int)blockIdx.x, (int)gridDim.x, wv);        // logical wave (stem_pool_plan.h)
+  const int wl = lw.wl, rt = lw.rt, wc = lw.wc, nwc = (gridDim.x * 4) / 3;
   for (int i = t; i < 4 * kSp3Wave / 4; i += 256) reinterpret_cast<f32x4 *>(smem)[i] = f32x4{0.f, 0.f, 0.f, 0.f};
   float *const sW = smem + wave * kSp3Wave;           // this wave's source patch
   float *const reg = sW + kSpPatch;                   // this wave's dz region [32][TP]
@@ -282,22 +268,10 @@ conv_stem_wgrad_pool_kernel(const StemPoolArgs a, const int nunits) {
   const __amdgpu_buffer_rsrc_t dprsrc = __builtin_amdgcn_make_buffer_rsrc((void *)a.dP, 0, a.dpBytes, 0x00020000);
   const __amdgpu_buffer_rsrc_t yprsrc = __builtin_amdgcn_make_buffer_rsrc((void *)a.yP, 0, a.dpBytes, 0x00020000);
   const __amdgpu_buffer_rsrc_t amrsrc = __builtin_amdgcn_make_buffer_rsrc((void *)a.amax, 0, a.amBytes, 0x00020000);
-  const int pHW = a.pHo * a.pWo;
   const int cl = lane >> 2, qd = lane & 3;
-  const bool mok[2] = {32 * rt + cl < a.M, 32 * rt + 16 + cl < a.M};      // filters that do not exist: nothing is routed
+  const bool mok[2] = {sp_filter_ok(rt, 0, lane, a.M), sp_filter_ok(rt, 1, lane, a.M)};      // filters that do not exist: nothing is routed
 
-  auto unit_of = [&](int u) {
-    SpUnit c;
-    const uint32_t uu = (uint32_t)min(u, nunits - 1);
-    const uint32_t q = xm_div(uu, a.divG);                // divG here: chunk pairs per column
-    c.cp = (int)(uu - q * a.divG.d);
-    c.n = (int)xm_div(q, a.divJG);                        // divJG here: column pairs per sample
-    c.jp = (int)(q - (uint32_t)c.n * a.divJG.d);
-    c.live = u < nunits;
-    c.col1 = 2 * c.jp + 1 < a.PJ;
-    c.chunk1 = 64 * c.cp + 32 < a.PI;
-    return c;
-  };
+  auto unit_of = [&](int u) { return sp_bwd_unit(u, nunits, a.divG, a.divJG, a.PI, a.PJ); };
   f32x4 ld[6];
   int ldst[6];
   bool ldz[6];
@@ -333,41 +307,10 @@ conv_stem_wgrad_pool_kernel(const StemPoolArgs a, const int nunits) {
   }
 
   // ---- per-unit lane geometry of the candidates ---------------------------------------------------------------------------
-  struct Cand {
-    unsigned voff[2];     // per chunk h: element offset of the lane's quad inside a (sample, 16-filter group, window column 0) block
-    unsigned vmask;       // bit 4 h + e: element e of the chunk-h quad is a window row of this column (< pHo)
-    int shift[2];         // != 0 only for the LAST pooled column of the tensor: the quad was loaded `shift` rows early
-    bool anyshift;        // (wave-uniform) some lane of this unit has a shifted quad
-    unsigned exoff;       // the window row 32 cp - 1 (lanes with qd < 2: window column p = qd): element offset inside a
-                          // (sample, 16-filter group) block, or out of range
-    bool ok[2];           // window column p exists (wave-uniform)
-    int sbase;            // element offset of (sample, filter 32 rt, window column 0, window row 0)
-    int jp;
-  };
-  auto cand_of = [&](const SpUnit &c) {
-    Cand k;
-    k.jp = c.jp;
-    k.ok[1] = c.live && c.jp < a.pWo;
-    k.ok[0] = c.live && c.jp >= 1 && c.jp - 1 < a.pWo;
-    // a quad that reaches past its pooled column reads the head of the next one (ignored: vmask) -- except in the very last
-    // column of the tensor, where it would leave the buffer: there it is loaded early and re-aligned after the load
-    const bool lastplane = c.n * a.M + 32 * rt + 32 >= (a.dpBytes >> 2) / (unsigned)pHW;      // (wave-uniform)
-    k.anyshift = lastplane && c.jp >= a.pWo - 1 && 32 * c.cp + 32 > a.pHo;
-    k.vmask = 0;
-#pragma unroll
-    for (int h = 0; h < 2; ++h) {
-      const int ph0 = 32 * c.cp + 16 * h + 4 * qd;        // first window row of the lane's quad
-      const int phs = k.anyshift ? min(ph0, a.pHo - 4) : ph0;
-      k.shift[h] = ph0 - phs;
-      k.voff[h] = (unsigned)(cl * pHW + phs);
-#pragma unroll
-      for (int e = 0; e < 4; ++e) k.vmask |= (ph0 + e < a.pHo ? 1u : 0u) << (4 * h + e);
-    }
-    const bool exok = c.cp > 0 && qd < 2 && (qd ? k.ok[1] : k.ok[0]);
-    k.exoff = exok ? (unsigned)((cl * a.pWo + c.jp - 1 + qd) * a.pHo + 32 * c.cp - 1) : 0x3FFFFFFFu;
-    k.sbase = (c.n * a.M + 32 * rt) * pHW;
-    return k;
-  };
+  // (SpCand, stem_pool_plan.h: no load is issued for a filter that does not exist, none leaves the pooled tensors)
+  typedef SpCand Cand;
+  const unsigned pooledElems = a.dpBytes >> 2;
+  auto cand_of = [&](const SpUnit &c) { return sp_cand_of(c, rt, lane, a.M, a.pHo, a.pWo, pooledElems); };
   // pooled operands of a unit: [window column p][group of 16 filters][chunk].  n*: as loaded, for the NEXT unit (requested a
   // whole unit ahead); c*: gated, the unit being multiplied.  e*: the window row in front of the unit's first one
   f32x4 cdp[2][2][2], ndp[2][2][2], nyp[2][2][2];
@@ -379,21 +322,24 @@ conv_stem_wgrad_pool_kernel(const StemPoolArgs a, const int nunits) {
     for (int it = 0; it < 2; ++it) {
 #pragma unroll
       for (int p = 0; p < 2; ++p) {
-        if (k.ok[p]) {
+        if (sp_cand_issued(k, it, p)) {                                        // (wave-uniform) the column and the group's filters exist
           typedef unsigned u4 __attribute__((ext_vector_type(4)));
-          const int so = k.sbase + 16 * it * pHW + (k.jp - 1 + p) * a.pHo;     // scalar part (elements)
+          const int so = sp_cand_so(k, it, p, a.pHo, a.pWo);                   // scalar part (elements)
 #pragma unroll
           for (int h = 0; h < 2; ++h) {
-            ndp[p][it][h] = __builtin_bit_cast(f32x4, (u4)__builtin_amdgcn_raw_buffer_load_b128(dprsrc, (int)(k.voff[h] * 4u), so * 4, 0));
-            if (GATE) nyp[p][it][h] = __builtin_bit_cast(f32x4, (u4)__builtin_amdgcn_raw_buffer_load_b128(yprsrc, (int)(k.voff[h] * 4u), so * 4, 0));
-            ncd[p][it][h] = __builtin_amdgcn_raw_buffer_load_b32(amrsrc, (int)k.voff[h], so, 0);
+            const unsigned vo = sp_cand_voff(k, h, mok[it]);
+            ndp[p][it][h] = __builtin_bit_cast(f32x4, (u4)__builtin_amdgcn_raw_buffer_load_b128(dprsrc, (int)(vo * 4u), so * 4, 0));
+            if (GATE) nyp[p][it][h] = __builtin_bit_cast(f32x4, (u4)__builtin_amdgcn_raw_buffer_load_b128(yprsrc, (int)(vo * 4u), so * 4, 0));
+            ncd[p][it][h] = __builtin_amdgcn_raw_buffer_load_b32(amrsrc, (int)vo, so, 0);
           }
         }
       }
-      const int so = k.sbase + 16 * it * pHW;
-      nedp[it] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(dprsrc, (int)(k.exoff * 4u), so * 4, 0));
-      if (GATE) neyp[it] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(yprsrc, (int)(k.exoff * 4u), so * 4, 0));
-      necd[it] = __builtin_amdgcn_raw_buffer_load_b8(amrsrc, (int)k.exoff, so, 0);
+      // (a row, column or filter that does not exist: the offset is out of range, the load returns zero without an access)
+      const int so = sp_cand_exso(k, it, a.pHo, a.pWo);
+      const unsigned xo = sp_cand_exoff(k, mok[it]);
+      nedp[it] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(dprsrc, (int)(xo * 4u), so * 4, 0));
+      if (GATE) neyp[it] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(yprsrc, (int)(xo * 4u), so * 4, 0));
+      necd[it] = __builtin_amdgcn_raw_buffer_load_b8(amrsrc, (int)xo, so, 0);
     }
   };
   // gate, once per unit: the derivative of a window whose maximum did not pass the ReLU, of a filter or a window row that
@@ -493,7 +439,6 @@ conv_stem_wgrad_pool_kernel(const StemPoolArgs a, const int nunits) {
   __syncthreads();                       // zero fill and constants complete
   int u = wc;
   SpUnit cur = unit_of(u), nxt = unit_of(u + nwc);
-  Cand kn = cand_of(nxt);                               // geometry of the unit whose operands are in flight (n*)
   if (u < nunits) {
     const Cand k0 = cand_of(cur);
     issue_patch(cur);
@@ -501,7 +446,7 @@ conv_stem_wgrad_pool_kernel(const StemPoolArgs a, const int nunits) {
     write_patch();
     gate_cand(k0);
     __builtin_amdgcn_sched_barrier(0);
-    issue_cand(kn);                                     // the next unit's operands and patch: a whole unit ahead
+    issue_cand(cand_of(nxt));                           // the next unit's operands and patch: a whole unit ahead
     if (!GATE) issue_patch(nxt);                        // (GATE: y_pool's quads leave no registers for a patch in flight)
   }
   const float *tr = reg + l31 * TP + 16 * half;        // A operand: row l31, pixels 16 half + 4 c .. + 3
@@ -536,13 +481,18 @@ conv_stem_wgrad_pool_kernel(const StemPoolArgs a, const int nunits) {
     // this unit's operands are dead: gate the next unit's (requested a unit ago), request the ones after them, park the
     // next unit's patch behind this unit's last B reads (LDS operations of a wave execute in order)
     if (GATE) issue_patch(nxt);
-    gate_cand(kn);
+    {
+      // (the lane geometry of the unit in flight is formed AGAIN rather than kept in registers across the MFMA steps: the
+      // opaque copy of the lane index keeps the compiler from carrying it over)
+      int lane2 = lane;
+      asm volatile("" : "+v"(lane2));
+      gate_cand(sp_cand_of(nxt, rt, lane2, a.M, a.pHo, a.pWo, pooledElems));
+    }
     write_patch();
     __builtin_amdgcn_sched_barrier(0);
     cur = nxt;
     nxt = unit_of(u + 2 * nwc);
-    kn = cand_of(nxt);
-    issue_cand(kn);
+    issue_cand(cand_of(nxt));
     if (!GATE) issue_patch(nxt);
   }
   // the wave's partial [32][64]
@@ -705,13 +655,8 @@ conv_stem_bnpool_fwd_kernel(const StemFwdArgs a) {
 
   for (int unit = blockIdx.x * 4 + wv; unit < a.nunits; unit += gridDim.x * 4) {
     // ---- unit -> (sample, strip, segment, row tile) --------------------------------------------------------------------
-    uint32_t uu = (uint32_t)unit;
-    const uint32_t q3 = xm_div(uu, a.div3);
-    const int rt = (int)(uu - q3 * 3u);
-    const uint32_t qs = xm_div(q3, a.divSG);
-    const int seg = (int)(q3 - qs * a.divSG.d);
-    const int n = (int)xm_div(qs, a.divNS), strip = (int)(qs - (uint32_t)n * a.divNS.d);
-    const int pw0 = seg * a.pWo / a.SG, pw1 = (seg + 1) * a.pWo / a.SG;
+    const SfUnit su = sf_unit(unit, a.div3, a.divSG, a.divNS, a.pWo, a.SG);
+    const int rt = su.rt, n = su.n, strip = su.strip, pw0 = su.pw0, pw1 = su.pw1;
     const int ncol = 2 * (pw1 - pw0) + 1;                  // output columns 2 pw0 .. 2 pw1
     // source rows: tile a, lane q, tap u: 2 (126 strip + 2 q) + gh0 + u = 4 q + b0 + u; units of 4 rows from U0
     const int b0 = 252 * strip + a.gh0;

@@ -8,6 +8,7 @@
 #include <cstring>
 
 #include "../../include/xmodal.h"
+#include "fastdiv.h"   // FastDiv, make_fastdiv, fast_div: magic division by a runtime divisor
 
 namespace xm {
 
@@ -133,22 +134,6 @@ static inline bool too_big(long long a, long long b = 1, long long c = 1, long l
   return a * b * c * d >= (1LL << 31);
 }
 
-// magic division of a 31-bit numerator by a runtime divisor: q = (n * m) >> s
-struct FastDiv {
-  uint32_t m;
-  uint32_t s;
-  uint32_t d;
-};
-static inline FastDiv make_fastdiv(uint32_t d) {
-  FastDiv f;
-  f.d = d;
-  uint32_t l = 0;
-  while ((1ull << l) < d) ++l;
-  f.s = 31 + l;
-  f.m = (uint32_t)(((1ull << f.s) + d - 1) / d);
-  return f;
-}
-
 #ifdef __HIPCC__
 // MFMA accumulator and 16-byte access vectors of the kernel headers (conv_kernels.h, stem_pool_kernels.h)
 typedef float f32x16 __attribute__((ext_vector_type(16)));
@@ -159,7 +144,7 @@ typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 #ifdef __HIPCC__
 __device__ __forceinline__ uint32_t xm_div(uint32_t n, const xm::FastDiv f) {
-  return (uint32_t)(((uint64_t)n * f.m) >> f.s);
+  return xm::fast_div(n, f);
 }
 __device__ __forceinline__ float xm_wave_sum(float v) {
 #pragma unroll
