@@ -61,7 +61,7 @@ enum { XM_FUSE_RELU = 1, XM_BN_BATCH_MOMENTS = 2, XM_FUSE_SIGMOID = 4 };
 
 /* ABI revision: 100 = round 1; 101 = xm_nnbnorm_relu_pool_backward gained `y_pool`, exchange entry points return
  * XM_EINVAL without a communicator; 102 = + xm_nnconv_forward_moments, xm_nnbnorm_backward_dxsum, xm_nnconv_forward_gated;
- * 103 = + xm_nnpool_global_avg_backward_accum; 104 = + xm_nnconv_backward_filter_bnrelupool, xm_nndropout_forward / _apply, xm_resample, xm_se_tail_backward_reduce / _apply, xm_se_squeeze_bn, xm_scale_axpy_bn; 105 = + xm_set_exec_hint / xm_get_exec_hint; 106 = + xm_nnconv_bnorm_relu_pool_forward, xm_stem_gram, xm_stem_gram_moments, xm_nnconv_backward_filter_bnrelupool_gram; 107 = + xm_nnaffinegrid / _backward, xm_nnbilinearsampler / _backward, xm_ferplus_batch; 108 = + XM_AGG_PEAK, xm_mnrfit, xm_mnrval; 109 = + xm_roc, xm_roc_launches, xm_label_hist; 110 = + xm_group_rows, xm_gather_rows, xm_scatter_rows, xm_track_peaks; 111 = + xm_wav_batch; 112 = + xm_spec_bucket_batch; 113 = + xm_jpeg_plan, xm_jpeg_decode_batch; 114 = + xm_wav_plan, xm_wav_decode_batch; 115 = + xm_jpeg_decode_batch_split, xm_jpeg_split_geometry; 116 = + xm_pixcsv_plan, xm_pixcsv_decode_batch, xm_pixcsv_geometry; 117 = + xm_nnconv_forward_strided_residual; 118 = + xm_solver_update; 119 = + xm_nnnormalize_forward / _backward, xm_nnnormalize_geometry; 120 = + xm_jpeg_plan_prog, xm_jpeg_decode_batch_prog; 121 = + xm_window_targets; 122 = + xm_wav_plan_fs, xm_wav_decode_resample_batch, xm_wav_resample_geometry; 123 = + xm_nnconv_forward_lattice; 124 = + xm_nnconv_forward_split, xm_nnconv_split_geometry, XM_CONV_F32 / XM_CONV_BF16X3 (additions never change the revision's meaning for older bindings).  A binding checks xm_version() >= the revision it was written against. */
+ * 103 = + xm_nnpool_global_avg_backward_accum; 104 = + xm_nnconv_backward_filter_bnrelupool, xm_nndropout_forward / _apply, xm_resample, xm_se_tail_backward_reduce / _apply, xm_se_squeeze_bn, xm_scale_axpy_bn; 105 = + xm_set_exec_hint / xm_get_exec_hint; 106 = + xm_nnconv_bnorm_relu_pool_forward, xm_stem_gram, xm_stem_gram_moments, xm_nnconv_backward_filter_bnrelupool_gram; 107 = + xm_nnaffinegrid / _backward, xm_nnbilinearsampler / _backward, xm_ferplus_batch; 108 = + XM_AGG_PEAK, xm_mnrfit, xm_mnrval; 109 = + xm_roc, xm_roc_launches, xm_label_hist; 110 = + xm_group_rows, xm_gather_rows, xm_scatter_rows, xm_track_peaks; 111 = + xm_wav_batch; 112 = + xm_spec_bucket_batch; 113 = + xm_jpeg_plan, xm_jpeg_decode_batch; 114 = + xm_wav_plan, xm_wav_decode_batch; 115 = + xm_jpeg_decode_batch_split, xm_jpeg_split_geometry; 116 = + xm_pixcsv_plan, xm_pixcsv_decode_batch, xm_pixcsv_geometry; 117 = + xm_nnconv_forward_strided_residual; 118 = + xm_solver_update; 119 = + xm_nnnormalize_forward / _backward, xm_nnnormalize_geometry; 120 = + xm_jpeg_plan_prog, xm_jpeg_decode_batch_prog; 121 = + xm_window_targets; 122 = + xm_wav_plan_fs, xm_wav_decode_resample_batch, xm_wav_resample_geometry; 123 = + xm_nnconv_forward_lattice; 124 = + xm_nnconv_forward_split, xm_nnconv_split_geometry, XM_CONV_F32 / XM_CONV_BF16X3; 125 = + xm_imread_plan, xm_imread_transform_batch, xm_imread_geometry, xm_imread_round_u8 (additions never change the revision's meaning for older bindings).  A binding checks xm_version() >= the revision it was written against. */
 int xm_version(void);
 const char *xm_last_error(void);
 /* Device memory for hosts that have no device-array type of their own (MATLAB's gpuArray is CUDA-only: on an
@@ -1036,6 +1036,53 @@ int xm_nnnormalize_forward(const float *x, int H, int W, int C, int S, int N, fl
 int xm_nnnormalize_backward(const float *x, const float *dzdy, int H, int W, int C, int S, int N, float kappa,
                             float alpha, float beta, float *dx, void *stream);
 int xm_nnnormalize_geometry(int *pixels_per_block, int *channels_per_pass, int *window_in_registers);
+
+/* ---- vl_imreadjpeg's crop, flip, filter and colour options (ABI 125) [EXT: vl_imreadjpeg; its sources are not at hand, so
+ * the definitions of DESIGN section 24 are the specification] ----
+ * One stage behind the JPEG decoders: it reads the ragged `pixels` buffer they write (image n: H x W x 3, 0..255, MATLAB
+ * layout) and writes single outputs, never rounded to uint8.
+ *
+ * xm_imread_plan: host only, no device call (usable without a GPU).
+ *   hw      N x 3 int64: H, W, offset of the image's pixels in `pixels` (floats)
+ *   opts    XM_IMREAD_OPTS doubles: 0 Resize mode (0 none: the output has the image's size; 1 [Ho Wo]; 2 scalar S: the
+ *           shorter side becomes S, the other max(1, floor(S long / short + 0.5))); 1, 2 Ho (or S), Wo; 3, 4
+ *           CropAnisotropy [amin amax] ([0 0]: the window has the image's aspect ratio); 5, 6 CropSize [smin smax] in
+ *           (0, 1]; 7 CropLocation (0 center, 1 random); 8 Flip; 9 filter (XM_IMREAD_BOX / _BILINEAR / _BICUBIC: Keys,
+ *           a = -1/2); 10 antialias (widen the kernel by max(r, 1)); 11 Contrast C; 12 Saturation S; 13-21 Brightness B,
+ *           3 x 3 row-major; 22 SubtractAverage (0 none, 1 three values, 2 an Ho x Wo x 3 image)
+ *   draws   N x XM_IMREAD_DRAWS doubles: u0 anisotropy, u1 size, u2 y, u3 x, u4 flip (mirrored when < 0.5), u5 contrast, u6
+ *           saturation in [0, 1], then g0..g2 ~ N(0, 1) for Brightness; NULL when no option is random
+ *   rows    N rows of XM_IMREAD_ROW doubles: 0 H; 1 W; 2 pixel offset; 3 Ho; 4 Wo; 5 offset of the Ho x Wo x 3 output in
+ *           `out` (floats); 6-9 the window y0, x0, ch, cw; 10 flip; 11 filter; 12 antialias; 13, 14 taps Ty, Tx; 15-23 the
+ *           colour matrix sigma gamma I + (1 - sigma) gamma / 3 11' (row-major); 24-26 its product with b = B g; 27 gamma;
+ *           28 sigma; 29-31 b; 32 offset of the image's tap tables in the stage's scratch (4-byte words: Ty x Ho and
+ *           Wo x Tx weights, Ho and Wo first taps); 33 output rows per LDS chunk; 34, 35 the ratios ch / Ho, cw / Wo;
+ *           36, 37 the kernel widening per axis; 38 column tiles; 39 offset of its partial sums; 40 SubtractAverage kind;
+ *           41 Contrast on; 42, 43 zero
+ *   sizes   XM_IMREAD_SIZES int64: output floats, table words, partial sums, most column tiles of an image, Contrast on,
+ *           all outputs of one size, longest output side, N
+ * XM_EINVAL with a message: CropSize outside (0, 1], amin > amax, a random option without draws, an average image with
+ * ragged outputs ...; XM_ENOTSUP naming the image: a window reduced by more than 64 on an axis; XM_ETOOBIG: a side above
+ * 32768.
+ * xm_imread_transform_batch: device.  desc: the rows on the device; rows: the same rows on the host, from which the launch
+ * geometry is read and which are checked against what the plan writes; avg: three floats or an Ho x Wo x 3 image on the
+ * device (NULL without SubtractAverage); out: sizes[0] floats.  Output sample o of an axis with n inputs, m outputs and
+ * window (c0, len) reads at u = c0 + (o' + 1/2) len / m - 1/2 (o' = m - 1 - o on the mirrored horizontal axis) the taps
+ * floor(u - S s / 2) + 1 ... with weights k((t - u) / s) divided by their sum, indices clamped to [0, n - 1]; weights in
+ * double rounded once to float, sums in fp32, horizontal pass first.  Then p - a + b, contrast towards the channel means
+ * of that, saturation towards the pixel's grey.  The same bits on every run, and for an image alone
+ * or in any batch.  xm_imread_geometry's launches (2, with Contrast 3) whatever N and the sizes; scratch from the
+ * stream's workspace; no synchronisation.
+ * xm_imread_geometry: host only.  tile_rows x tile_cols x 3 floats is the LDS tile of the resampling kernel.
+ * xm_imread_round_u8: y = min(max(floor(x + 1/2), 0), 255) over n values (y may be x), one launch: the uint8 conversion
+ * of the narrow path for a caller that hands the stage's unrounded outputs to a consumer of uint8 values. */
+enum { XM_IMREAD_ROW = 44, XM_IMREAD_OPTS = 24, XM_IMREAD_DRAWS = 10, XM_IMREAD_SIZES = 8 };
+enum { XM_IMREAD_BOX = 0, XM_IMREAD_BILINEAR = 1, XM_IMREAD_BICUBIC = 2 };
+int xm_imread_plan(const long long *hw, int N, const double *opts, const double *draws, double *rows, long long *sizes);
+int xm_imread_transform_batch(const float *pixels, const double *desc, int N, const double *rows, const float *avg,
+                              float *out, void *stream);
+int xm_imread_geometry(int *launches, int *launches_contrast, int *tile_rows, int *tile_cols);
+int xm_imread_round_u8(const float *x, long long n, float *y, void *stream);
 
 #ifdef __cplusplus
 }

@@ -152,6 +152,10 @@ SIGNATURES = {
     "xm_pixcsv_plan": [_vp, C.c_longlong, _vp, C.c_longlong, _vp],
     "xm_pixcsv_decode_batch": [c_fp, C.c_longlong, c_fp, _i, _i, _i, _i, c_fp, C.c_longlong, c_fp, _vp],
     "xm_pixcsv_geometry": [C.POINTER(C.c_int), C.POINTER(C.c_int)],
+    "xm_imread_plan": [c_fp, _i, c_fp, c_fp, c_fp, c_fp],
+    "xm_imread_transform_batch": [c_fp, c_fp, _i, c_fp, c_fp, c_fp, _vp],
+    "xm_imread_geometry": [C.POINTER(C.c_int)] * 4,
+    "xm_imread_round_u8": [c_fp, C.c_longlong, c_fp, _vp],
     "xm_nnnormalize_forward": [c_fp] + [_i] * 5 + [_f, _f, _f, c_fp, _vp],
     "xm_nnnormalize_backward": [c_fp, c_fp] + [_i] * 5 + [_f, _f, _f, c_fp, _vp],
     "xm_nnnormalize_geometry": [C.POINTER(C.c_int)] * 3,

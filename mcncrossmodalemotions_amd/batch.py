@@ -25,6 +25,8 @@ shapes the tensors the hot path consumes, fed from seeded synthetic sources:
                                                                        averageImage -> affine grid -> bilinear sampler)
     FER+ imdb (getFerPlusImdb)   ferplus_baselines.m:103-110        -> FerPlusImdb: fer2013.csv's pixel column parsed on the
                                                                        device (vl.pixcsv_decode, xm_pixcsv_decode_batch)
+    JPEG face folder (getBatch)  vl_imreadjpeg's options [EXT]      -> getBatchJpegFaces: random crop, flip and jitter on the
+                                                                       device (vl.vl_imreadjpeg, xm_imread_transform_batch)
 """
 import math
 import os
@@ -1106,3 +1108,45 @@ def getBatchFerPlus(imdb, batch, dataType="CNTK", lossType="distributions", data
     if lossType == "softmaxlog":
         return ["data", data, "label", hardlabel]
     raise ValueError("unknown loss type: %s" % lossType)
+
+
+def getBatchJpegFaces(files, labels, batch, dag, train, rng, *, read=None, interpolation="bilinear", antialias=False,
+                      device=None, split=None, progressive=False, **aug):
+    """inputs = getBatch(imdb, batch) over a folder of JPEG faces, the way every MatConvNet getBatch builds one (random
+    crop, flip and colour jitter through vl_imreadjpeg's options [EXT]): bind it for train.cnn_train_dag as
+        lambda imdb, batch: getBatchJpegFaces(files, labels, batch, dag, imdb.images["set"][batch[0]] == 1, rng, **aug)
+    `files`: bytes or paths (with `read(paths) -> list of bytes`, names), `labels`: one class index per file (1-based, as
+    vl_nnloss takes them), `batch`: indices into both.  `aug`: vl_imreadjpeg options by name -- CropSize=[0.35, 1],
+    CropAnisotropy=[3 / 4, 4 / 3], Flip=True, Brightness=..., Contrast=..., Saturation=....  In train mode they apply
+    with CropLocation 'random' and draws from `rng`; otherwise the crop is centred, of the largest CropSize, and nothing is
+    drawn.  Both modes resize to meta.normalization.imageSize and, unless meta.normalization says grey=False, go through
+    vl.normalize_face (grey -> x3 -> minus averageImage, the FER+ teachers' input); with grey=False averageImage is
+    subtracted from the colour image instead.  Returns ['data', Ho x Wo x 3 x N, 'label', 1 x 1 x 1 x N]; no
+    synchronisation."""
+    norm = dag.meta["normalization"]
+    imageSize, avg = [int(v) for v in norm["imageSize"][:2]], norm["averageImage"]
+    grey = bool(norm.get("grey", True))
+    batch = [int(b) for b in batch]
+    datas = [files[b] for b in batch]
+    if read is not None:
+        datas = read(datas)
+    aug = {str(k).lower(): v for k, v in aug.items()}
+    unknown = sorted(set(aug) - {"cropsize", "cropanisotropy", "flip", "brightness", "contrast", "saturation"})
+    if unknown:
+        raise ValueError("getBatchJpegFaces: unknown augmentation %r" % (unknown[0],))
+    options = ["Pack", "Resize", imageSize, "Interpolation", interpolation]
+    if train:
+        options += ["CropLocation", "random"]
+        for k, v in aug.items():
+            options += [k, bool(v)] if k == "flip" else [k, v]
+    else:
+        options += ["CropLocation", "center", "CropSize", float(np.max(aug.get("cropsize", 1.0)))]
+    if not grey:
+        options += ["SubtractAverage", avg]
+    data = vl.vl_imreadjpeg(datas, *options, rng=rng if train else None, antialias=antialias, device=device, split=split,
+                            progressive=progressive)
+    if grey:
+        data = vl.normalize_face(data, avg)
+    lab = np.asarray(labels, np.float32)[batch]
+    label = torch.from_numpy(lab).to(data.device).reshape(len(batch), 1, 1, 1).permute(3, 2, 1, 0)
+    return ["data", data, "label", label]

@@ -11,8 +11,8 @@ CSRC = os.path.join(HERE, "csrc")
 # gpurun call).  The product build uses neither.
 TAG = os.environ.get("XM_BUILD_TAG", "")
 OUT = os.path.join(HERE, "libxmodal_hip%s.so" % ("_" + TAG if TAG else ""))
-SOURCES = ["context.cpp", "prof.cpp", "conv.hip", "conv_split.hip", "stem_pool.hip", "norm_pool.hip", "lrn.hip", "misc.hip", "spec.hip", "sampler.hip", "eval.hip", "roc.hip", "imdb.hip", "jpeg.hip", "jpeg_prog.hip", "wav.hip", "pixcsv.hip", "comm.cpp"]
-HEADERS = ["xm_common.h", "fastdiv.h", "prof.h", "conv_plan.h", "stem_pool_plan.h", "conv_split_plan.h", "norm_pool_plan.h", "conv_tune.h", "wav_plan.h", "wav_resample.h", "pixcsv_plan.h", "jpeg_scan_plan.h", "jpeg_entropy.h", "conv_kernels.h", "stem_pool_kernels.h", os.path.join("..", "..", "include", "xmodal.h")]
+SOURCES = ["context.cpp", "prof.cpp", "conv.hip", "conv_split.hip", "stem_pool.hip", "norm_pool.hip", "lrn.hip", "misc.hip", "spec.hip", "sampler.hip", "eval.hip", "roc.hip", "imdb.hip", "jpeg.hip", "jpeg_prog.hip", "wav.hip", "pixcsv.hip", "imread_xform.hip", "comm.cpp"]
+HEADERS = ["xm_common.h", "fastdiv.h", "prof.h", "conv_plan.h", "stem_pool_plan.h", "conv_split_plan.h", "norm_pool_plan.h", "conv_tune.h", "wav_plan.h", "wav_resample.h", "pixcsv_plan.h", "imread_plan.h", "jpeg_scan_plan.h", "jpeg_entropy.h", "conv_kernels.h", "stem_pool_kernels.h", os.path.join("..", "..", "include", "xmodal.h")]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-unused-function"]
 if os.environ.get("XM_DEBUG_CYCLES"):   # per-block clock trace in the conv kernels (tools/conv_bench.py --cycles)
     FLAGS.append("-DXM_DEBUG_CYCLES")

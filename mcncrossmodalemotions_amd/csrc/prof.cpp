@@ -64,6 +64,8 @@ static const ProfRow kProfRows[] = {
     {kProfWavRate, 2, {"wav_rate_gain_kernel", "wav_resample_kernel"}},
     {kProfPixcsv, 1, {"pixcsv_decode_kernel"}},
     {kProfConvSplit, 1, {"conv_split_kernel"}},
+    {kProfImread, 5, {"imread_table_kernel", "imread_resample_kernel<false>", "imread_resample_kernel<true>", "imread_colour_kernel",
+                     "imread_round_kernel"}},
     // inexact: the register-window rows name the N = 5 instantiation (the VGG-M family's) for every window width
     {kProfLrn, 6, {"lrn_forward_kernel<5, false>", "lrn_forward_kernel<5, true>", "lrn_backward_kernel<5, false>",
                    "lrn_backward_kernel<5, true>", "lrn_general_kernel<false>", "lrn_general_kernel<true>"}},

@@ -30,6 +30,7 @@ enum ProfKind {
   kProfJpegProg = 26,       // jpeg_prog.hip: the entropy launch of a level, the two smoothing launches
   kProfWavRate = 27,        // wav.hip, decode + resample: sub = 0 the gains, 1 the data
   kProfConvSplit = 28,      // conv_split.hip: the bf16x3 arm of 1 x 1 layers
+  kProfImread = 29,         // imread_xform.hip: sub = 0 the tap tables, 1 / 2 resampling without / with Contrast, 3 its colour pass, 4 uint8 rounding
 };
 constexpr int prof_key(ProfKind kind, int sub = 0) { return kind * 100 + sub; }
 

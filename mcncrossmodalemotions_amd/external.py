@@ -249,14 +249,17 @@ def compute_audio_feats_files(dag, files, numEmotions=8, limit=float("inf"), max
 
 
 def compute_visual_feats(dag, track_frames, batchSize=128, numEmotions=8, limit=float("inf"), lanes=2, *, read=None,
-                         split=None, progressive=False, modelDir=None, precision=None):
+                         split=None, progressive=False, modelDir=None, precision=None, interpolation=None, antialias=False,
+                         crop_size=1 / 1.6):
     """faceLogits = compute_visual_feats(dag, track_frames): the frames of all tracks are flattened
     (:63-69), pushed through the frozen teacher `batchSize` at a time (:81-94) and the logits are split
     back per track (:104-109).  track_frames: list of 224 x 224 x 3 x F_i normalised face mats; with
     `read(paths) -> list of bytes` a list of frame-path lists instead, and every batch comes from
     fetch_emovoxceleb_imdb.getImageBatch (:123-164: the JPEG files decoded on the device; `split` and `progressive` go there).
     `dag` may be a model name, as upstream (:49 ferPlusZoo(opts.modelName)); `modelDir` then names the model files' directory.
-    `precision`: zoo.FrozenTeacher's (None | 'fp32' | 'bf16x3': the split-bf16 arm of the teacher's 1 x 1 layers)."""
+    `precision`: zoo.FrozenTeacher's (None | 'fp32' | 'bf16x3': the split-bf16 arm of the teacher's 1 x 1 layers).
+    `interpolation`, `antialias`, `crop_size`: getImageBatch's (with `read`): the filter for frames that are reduced to the
+    network's input, as :129-135 reduces AFEW's; None leaves the path as it is."""
     if progressive and split is not None:
         raise ValueError("compute_visual_feats: progressive=True and split= exclude each other (vl.imreadjpeg)")
     if isinstance(dag, str):
@@ -269,7 +272,8 @@ def compute_visual_feats(dag, track_frames, batchSize=128, numEmotions=8, limit=
         paths = [p for i in first_ok for p in track_frames[i]]
         teacher = zoo.FrozenTeacher(dag, lanes=lanes, precision=precision)
         outs = [teacher.logits(fe.getImageBatch(paths[s:s + batchSize], dag, read=read, split=split,
-                                                progressive=progressive))
+                                                progressive=progressive, interpolation=interpolation, antialias=antialias,
+                                                crop_size=crop_size))
                 for s in range(0, len(paths), batchSize)]
         logits = (np.concatenate([vl.to_numpy(o).reshape(-1, int(o.shape[3]), order="F").T for o in outs], 0)
                   if outs else np.zeros((0, numEmotions), np.float32))

@@ -156,13 +156,17 @@ def read_files(faceDir):
 
 
 def getImageBatch(imagePaths, dag, *, read=None, faceDir=os.path.join("data", "voxceleb", "faces"), device=None,
-                  split=None, progressive=False):
+                  split=None, progressive=False, interpolation=None, antialias=False, crop_size=1 / 1.6):
     """data = getImageBatch(imagePaths, dag) -- :152-193: vl_imreadjpeg with CropSize 1/1.6, CropLocation center,
     bilinear Resize to meta.normalization.imageSize (:160-172), rgb2gray, x3 and normalizeFace (:176-193), all on the
     device from the files' bytes (vl.imreadjpeg).  `read(paths) -> list of bytes` (default: the files under faceDir);
     `dag`: a network with meta.normalization, or an object with .imageSize / .averageImage.  Ho x Wo x 3 x n; nothing
     is synchronised.  `split`: vl.imreadjpeg's seg_bytes (the segment-parallel entropy decode; the same faces).
-    `progressive`: vl.imreadjpeg's option of that name -- progressive files are read too, as vl_imreadjpeg reads them."""
+    `progressive`: vl.imreadjpeg's option of that name -- progressive files are read too, as vl_imreadjpeg reads them.
+    `interpolation` ('box' | 'bilinear' | 'bicubic'; None: the path above, unchanged) picks the filter: the frames then go
+    through vl.vl_imreadjpeg(..., 'Resize', imageSize, 'CropLocation', 'center', 'CropSize', crop_size) with `antialias`
+    as given, are rounded to uint8 values as the path above rounds them, and vl.normalize_face does the rest -- the path
+    for frames larger than the network's input (AFEW-sized frames, which are already tightly cropped: crop_size=1)."""
     if progressive and split is not None:
         raise ValueError("getImageBatch: progressive=True and split= exclude each other (vl.imreadjpeg)")
     if hasattr(dag, "meta"):
@@ -170,6 +174,11 @@ def getImageBatch(imagePaths, dag, *, read=None, faceDir=os.path.join("data", "v
     else:
         imageSize, avg = tuple(getattr(dag, "imageSize", (224, 224)))[:2], getattr(dag, "averageImage", AVERAGE_IMAGE)
     read = read or read_files(faceDir)
+    if interpolation is not None:
+        rgb = vl.vl_imreadjpeg(read(list(imagePaths)), "Pack", "Resize", list(imageSize), "CropLocation", "center", "CropSize",
+                               crop_size, "Interpolation", interpolation, "NumThreads", 10, antialias=antialias,
+                               device=device, split=split, progressive=progressive)
+        return vl.normalize_face(vl.uint8_round(rgb), avg)
     return vl.imreadjpeg(read(list(imagePaths)), resize=imageSize, crop_size=1 / 1.6, crop_location="center",
                          interpolation="bilinear", pack=True, num_threads=10, average_image=avg, device=device,
                          split=split, progressive=progressive)

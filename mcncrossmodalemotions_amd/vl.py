@@ -1714,6 +1714,212 @@ def imreadjpeg(files, resize=None, crop_size=None, crop_location="center", inter
 
 
 # --------------------------------------------------------------------------------------------
+# vl_imreadjpeg with MatConvNet's crop, flip, filter and colour options [EXT; DESIGN section 24 is the specification]: one
+# device stage (xm_imread_transform_batch) behind the decoders above.  imreadjpeg itself stays the narrow path.
+# --------------------------------------------------------------------------------------------
+IMREAD_ROW, IMREAD_OPTS, IMREAD_DRAWS, IMREAD_SIZES = 44, 24, 10, 8             # include/xmodal.h XM_IMREAD_*
+IMREAD_FILTERS = {"box": 0, "bilinear": 1, "bicubic": 2}
+_IMREAD_FLAGS = ("pack", "flip", "gpu", "verbose", "prefetch")
+_IMREAD_VALUED = ("resize", "cropsize", "cropanisotropy", "croplocation", "interpolation", "subtractaverage", "brightness",
+                  "contrast", "saturation", "numthreads")
+
+
+def imread_options(options):
+    """MatConvNet's option list ('Pack', 'Resize', [224 224], 'Flip', 'CropSize', [0.35 1] ...) -> dict keyed by the
+    lower-case names; names are matched without regard to case (vl_argparse).  'Pack', 'Flip', 'Gpu', 'Verbose' and
+    'Prefetch' are flags (a bool may follow); 'Prefetch' raises; an unknown option raises with its name."""
+    out, i, options = {}, 0, list(options)
+    while i < len(options):
+        name = options[i]
+        if not isinstance(name, str):
+            raise ValueError("vl_imreadjpeg: expected an option name at position %d, got %r" % (i, name))
+        key = name.lower()
+        i += 1
+        if key in _IMREAD_FLAGS:
+            val = True
+            if i < len(options) and isinstance(options[i], (bool, np.bool_)):
+                val = bool(options[i])
+                i += 1
+        elif key in _IMREAD_VALUED:
+            if i >= len(options):
+                raise ValueError("vl_imreadjpeg: option '%s' needs a value" % name)
+            val = options[i]
+            i += 1
+        else:
+            raise ValueError("vl_imreadjpeg: unknown option '%s'" % name)
+        out[key] = val
+    if out.get("prefetch"):
+        raise ValueError("vl_imreadjpeg: 'Prefetch' is not supported: the call already returns without waiting")
+    return out
+
+
+def imread_opts_vector(opt, antialias=False):
+    """the XM_IMREAD_OPTS doubles of xm_imread_plan from a dict of imread_options, and the SubtractAverage array or None"""
+    v = np.zeros(IMREAD_OPTS, np.float64)
+    if opt.get("resize") is not None:
+        r = np.ravel(np.asarray(opt["resize"], np.float64))
+        if r.size == 1:
+            v[0], v[1] = 2, r[0]
+        elif r.size == 2:
+            v[0], v[1], v[2] = 1, r[0], r[1]
+        else:
+            raise ValueError("vl_imreadjpeg: 'Resize' takes S or [Ho Wo]")
+    a = np.ravel(np.asarray(opt.get("cropanisotropy", [0, 0]), np.float64))
+    v[3], v[4] = (a[0], a[0]) if a.size == 1 else (a[0], a[1])
+    s = np.ravel(np.asarray(opt.get("cropsize", 1.0), np.float64))
+    v[5], v[6] = (s[0], s[0]) if s.size == 1 else (s[0], s[1])
+    loc = str(opt.get("croplocation", "center")).lower()
+    if loc not in ("center", "random"):
+        raise ValueError("vl_imreadjpeg: CropLocation must be 'center' or 'random' (got %r)" % (opt["croplocation"],))
+    v[7] = loc == "random"
+    v[8] = bool(opt.get("flip", False))
+    name = str(opt.get("interpolation", "bilinear")).lower()
+    if name not in IMREAD_FILTERS:
+        raise ValueError("vl_imreadjpeg: Interpolation must be 'box', 'bilinear' or 'bicubic' (got %r)" % (opt["interpolation"],))
+    v[9] = IMREAD_FILTERS[name]
+    v[10] = bool(antialias)
+    v[11] = float(opt.get("contrast", 0.0))
+    v[12] = float(opt.get("saturation", 0.0))
+    B = np.asarray(opt.get("brightness", 0.0), np.float64)
+    if B.size == 1:
+        B = np.eye(3) * float(B.ravel()[0])
+    elif B.size == 3:
+        B = np.diag(B.ravel())
+    elif B.shape != (3, 3):
+        raise ValueError("vl_imreadjpeg: 'Brightness' takes a scalar, 3 values or a 3 x 3 matrix")
+    v[13:22] = B.reshape(-1)
+    avg = opt.get("subtractaverage")
+    if avg is not None:
+        if isinstance(avg, torch.Tensor):
+            avg = to_numpy(avg) if avg.dim() > 1 else avg.detach().cpu().numpy()
+        avg = np.asarray(avg, np.float32)
+        if avg.size == 3:
+            avg, v[22] = avg.reshape(3), 1
+        elif avg.ndim == 3 and avg.shape[2] == 3:
+            v[22] = 2
+        else:
+            raise ValueError("vl_imreadjpeg: 'SubtractAverage' takes 3 values or an Ho x Wo x 3 array")
+    return v, avg
+
+
+def imread_random(v):
+    """whether the options vector asks for anything drawn"""
+    return bool(v[3] != v[4] or v[5] != v[6] or v[7] or v[8] or v[11] > 0 or v[12] > 0 or np.any(v[13:22] != 0))
+
+
+def imread_draws(rng, N):
+    """the draws of a batch: U = rng.random((N, 7)) and then G = rng.standard_normal((N, 3)), always both and in that order"""
+    U = rng.random((N, 7))
+    G = rng.standard_normal((N, 3))
+    return np.ascontiguousarray(np.concatenate([U, G], 1))
+
+
+def imread_plan(hw, opts, draws=None):
+    """xm_imread_plan (host only): hw N x 3 (H, W, pixel offset), opts from imread_opts_vector, draws N x 10 or None ->
+    (rows N x 44 float64, sizes int64[8]); a refusal raises _lib.XmError"""
+    hw = np.ascontiguousarray(hw, np.int64).reshape(-1, 3)
+    N = int(hw.shape[0])
+    opts = np.ascontiguousarray(opts, np.float64)
+    rows = np.zeros((max(N, 1), IMREAD_ROW), np.float64)
+    sizes = np.zeros(IMREAD_SIZES, np.int64)
+    d = None if draws is None else np.ascontiguousarray(draws, np.float64)
+    if d is not None and d.shape != (N, IMREAD_DRAWS):
+        raise ValueError("imread_plan: draws must be N x %d" % IMREAD_DRAWS)
+    _lib.check(_L().xm_imread_plan(C.c_void_p(hw.ctypes.data), N, C.c_void_p(opts.ctypes.data),
+                                   None if d is None else C.c_void_p(d.ctypes.data), C.c_void_p(rows.ctypes.data),
+                                   C.c_void_p(sizes.ctypes.data)))
+    return rows[:N], sizes
+
+
+def imread_geometry():
+    """(launches, launches with Contrast, LDS tile rows, LDS tile columns) of the stage (xm_imread_geometry; no device call)"""
+    g = [C.c_int(0) for _ in range(4)]
+    _lib.check(_L().xm_imread_geometry(*[C.byref(x) for x in g]))
+    return tuple(x.value for x in g)
+
+
+def imread_transform(pixels, rows, sizes, avg=None, device=None):
+    """enqueues xm_imread_transform_batch on decoded `pixels` (the ragged float32 buffer of jpeg_decode): returns the flat
+    float32 output of sizes[0] values; image n is Ho x Wo x 3 (MATLAB layout) at rows[n, 5].  No synchronisation."""
+    device = device or pixels.device
+    N = int(rows.shape[0])
+    rows = np.ascontiguousarray(rows, np.float64)
+    kind = int(rows[0, 40]) if N else 0
+    want = {0: None, 1: (3,), 2: (int(rows[0, 3]), int(rows[0, 4]), 3) if N else None}[kind]
+    if (None if avg is None else tuple(np.shape(avg))) != want:
+        raise ValueError("imread_transform: the rows were planned for an average of shape %r, got %r"
+                         % (want, None if avg is None else tuple(np.shape(avg))))
+    with torch.cuda.device(device):
+        host = torch.empty(rows.shape, dtype=torch.float64, pin_memory=True)
+        host.numpy()[...] = rows
+        desc = host.to(device, non_blocking=True)
+        avg_dev = None
+        if avg is not None:
+            avg_dev = from_numpy(avg, device) if np.ndim(avg) == 3 else torch.from_numpy(np.asarray(avg, np.float32)).to(device)
+        out = torch.empty(int(sizes[0]), dtype=torch.float32, device=device)
+        _lib.check(_L().xm_imread_transform_batch(_ptr(pixels), _ptr(desc), N, C.c_void_p(rows.ctypes.data), _ptr(avg_dev),
+                                                  _ptr(out), _stream()))
+    return out
+
+
+def uint8_round(x):
+    """min(max(floor(x + 1/2), 0), 255) on the device (xm_imread_round_u8): the uint8 values imreadjpeg's resampler rounds
+    to, from vl_imreadjpeg's unrounded ones; same shape and layout"""
+    x = _chk(x, "X")
+    y = torch.empty_like(x)
+    _lib.check(_L().xm_imread_round_u8(_ptr(x), int(x.numel()), _ptr(y), _stream()))
+    return y
+
+
+def vl_imreadjpeg(files, *options, rng=None, antialias=False, device=None, split=None, progressive=False,
+                  return_status=False):
+    """vl_imreadjpeg(files, 'Pack', 'Resize', [224 224], 'Flip', 'CropSize', [0.35 1], ...) with MatConvNet's option list
+    [EXT], decoded, cropped, mirrored, resampled and colour-jittered on the device (DESIGN section 24 holds the
+    definitions).  `files`: bytes or paths.  Options: Resize (S | [Ho Wo]), CropSize, CropAnisotropy, CropLocation
+    ('center' | 'random'), Flip, Interpolation ('box' | 'bilinear' | 'bicubic'), SubtractAverage (3 values | Ho x Wo x 3),
+    Brightness, Contrast, Saturation, Pack; NumThreads, Gpu and Verbose are accepted and ignored, Prefetch raises.
+    `antialias` (ours): widen the kernel by the reduction ratio.  `rng`: the numpy Generator every random option draws
+    from (rng.random((N, 7)), then rng.standard_normal((N, 3)), whatever options are on).  Returns single values that are
+    never rounded to uint8: with Pack an Ho x Wo x 3 x N tensor (all outputs must have one size), otherwise a list of
+    Ho x Wo x 3 tensors.  split / progressive: imreadjpeg's; return_status as there.  The call does not synchronise."""
+    if progressive and split is not None:
+        raise ValueError("vl_imreadjpeg: progressive=True and split= exclude each other (progressive scans are not decoded "
+                         "segment-parallel)")
+    opt = imread_options(options)
+    v, avg = imread_opts_vector(opt, antialias)
+    if rng is None and imread_random(v):
+        raise ValueError("vl_imreadjpeg: a random option (CropSize or CropAnisotropy range, CropLocation 'random', Flip, "
+                         "Brightness, Contrast, Saturation) needs rng")
+    datas = _file_bytes(files)
+    N = len(datas)
+    pack = bool(opt.get("pack", False))
+    if not datas:
+        return ([], None) if return_status else []
+    buf, plan = jpeg_plan(datas, stage=_pinned if torch.cuda.is_available() else None, progressive=progressive)
+    jdesc = np.array(buf[plan["desc"][0]:plan["desc"][0] + plan["desc"][1]]).view(np.int64).reshape(N, JPEG_DESC)
+    draws = imread_draws(rng, N) if rng is not None else None
+    rows, sizes = imread_plan(jdesc[:, [2, 3, 21]], v, draws)
+    if pack and not sizes[5]:
+        raise ValueError("vl_imreadjpeg: 'Pack' needs outputs of one size; these are ragged (give 'Resize' [Ho Wo])")
+    if avg is not None and v[22] == 2 and tuple(avg.shape[:2]) != (int(rows[0, 3]), int(rows[0, 4])):
+        raise ValueError("vl_imreadjpeg: 'SubtractAverage' is %d x %d, the outputs are %d x %d"
+                         % (avg.shape[0], avg.shape[1], rows[0, 3], rows[0, 4]))
+    if not torch.cuda.is_available():
+        raise RuntimeError("vl_imreadjpeg needs a GPU; this build has no CPU path")
+    pixels, _, status, _ = jpeg_decode(buf, plan, want_pixels=True, device=device, split=split)
+    flat = imread_transform(pixels, rows, sizes, avg)
+    if pack:
+        Ho, Wo = int(rows[0, 3]), int(rows[0, 4])
+        out = flat.view(N, 3, Wo, Ho).permute(3, 2, 1, 0)
+    else:
+        out = []
+        for r in rows:
+            Ho, Wo, o = int(r[3]), int(r[4]), int(r[5])
+            out.append(flat[o:o + 3 * Ho * Wo].view(3, Wo, Ho).permute(2, 1, 0))
+    return (out, status) if return_status else out
+
+
+# --------------------------------------------------------------------------------------------
 # audioinfo / audioread (getBatchEmoVoxCeleb.m:79,97-117,126, compute_audio_feats.m:173-175): WAV decode on the device
 # --------------------------------------------------------------------------------------------
 WAV_DESC = 16                                                                   # include/xmodal.h XM_WAV_*
