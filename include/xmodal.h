@@ -61,7 +61,7 @@ enum { XM_FUSE_RELU = 1, XM_BN_BATCH_MOMENTS = 2, XM_FUSE_SIGMOID = 4 };
 
 /* ABI revision: 100 = round 1; 101 = xm_nnbnorm_relu_pool_backward gained `y_pool`, exchange entry points return
  * XM_EINVAL without a communicator; 102 = + xm_nnconv_forward_moments, xm_nnbnorm_backward_dxsum, xm_nnconv_forward_gated;
- * 103 = + xm_nnpool_global_avg_backward_accum; 104 = + xm_nnconv_backward_filter_bnrelupool, xm_nndropout_forward / _apply, xm_resample, xm_se_tail_backward_reduce / _apply, xm_se_squeeze_bn, xm_scale_axpy_bn; 105 = + xm_set_exec_hint / xm_get_exec_hint; 106 = + xm_nnconv_bnorm_relu_pool_forward, xm_stem_gram, xm_stem_gram_moments, xm_nnconv_backward_filter_bnrelupool_gram; 107 = + xm_nnaffinegrid / _backward, xm_nnbilinearsampler / _backward, xm_ferplus_batch; 108 = + XM_AGG_PEAK, xm_mnrfit, xm_mnrval; 109 = + xm_roc, xm_roc_launches, xm_label_hist; 110 = + xm_group_rows, xm_gather_rows, xm_scatter_rows, xm_track_peaks; 111 = + xm_wav_batch; 112 = + xm_spec_bucket_batch; 113 = + xm_jpeg_plan, xm_jpeg_decode_batch; 114 = + xm_wav_plan, xm_wav_decode_batch; 115 = + xm_jpeg_decode_batch_split, xm_jpeg_split_geometry; 116 = + xm_pixcsv_plan, xm_pixcsv_decode_batch, xm_pixcsv_geometry; 117 = + xm_nnconv_forward_strided_residual; 118 = + xm_solver_update; 119 = + xm_nnnormalize_forward / _backward, xm_nnnormalize_geometry; 120 = + xm_jpeg_plan_prog, xm_jpeg_decode_batch_prog; 121 = + xm_window_targets; 122 = + xm_wav_plan_fs, xm_wav_decode_resample_batch, xm_wav_resample_geometry; 123 = + xm_nnconv_forward_lattice; 124 = + xm_nnconv_forward_split, xm_nnconv_split_geometry, XM_CONV_F32 / XM_CONV_BF16X3; 125 = + xm_imread_plan, xm_imread_transform_batch, xm_imread_geometry, xm_imread_round_u8 (additions never change the revision's meaning for older bindings).  A binding checks xm_version() >= the revision it was written against. */
+ * 103 = + xm_nnpool_global_avg_backward_accum; 104 = + xm_nnconv_backward_filter_bnrelupool, xm_nndropout_forward / _apply, xm_resample, xm_se_tail_backward_reduce / _apply, xm_se_squeeze_bn, xm_scale_axpy_bn; 105 = + xm_set_exec_hint / xm_get_exec_hint; 106 = + xm_nnconv_bnorm_relu_pool_forward, xm_stem_gram, xm_stem_gram_moments, xm_nnconv_backward_filter_bnrelupool_gram; 107 = + xm_nnaffinegrid / _backward, xm_nnbilinearsampler / _backward, xm_ferplus_batch; 108 = + XM_AGG_PEAK, xm_mnrfit, xm_mnrval; 109 = + xm_roc, xm_roc_launches, xm_label_hist; 110 = + xm_group_rows, xm_gather_rows, xm_scatter_rows, xm_track_peaks; 111 = + xm_wav_batch; 112 = + xm_spec_bucket_batch; 113 = + xm_jpeg_plan, xm_jpeg_decode_batch; 114 = + xm_wav_plan, xm_wav_decode_batch; 115 = + xm_jpeg_decode_batch_split, xm_jpeg_split_geometry; 116 = + xm_pixcsv_plan, xm_pixcsv_decode_batch, xm_pixcsv_geometry; 117 = + xm_nnconv_forward_strided_residual; 118 = + xm_solver_update; 119 = + xm_nnnormalize_forward / _backward, xm_nnnormalize_geometry; 120 = + xm_jpeg_plan_prog, xm_jpeg_decode_batch_prog; 121 = + xm_window_targets; 122 = + xm_wav_plan_fs, xm_wav_decode_resample_batch, xm_wav_resample_geometry; 123 = + xm_nnconv_forward_lattice; 124 = + xm_nnconv_forward_split, xm_nnconv_split_geometry, XM_CONV_F32 / XM_CONV_BF16X3; 125 = + xm_imread_plan, xm_imread_transform_batch, xm_imread_geometry, xm_imread_round_u8; 126 = + xm_roc_geometry (additions never change the revision's meaning for older bindings).  A binding checks xm_version() >= the revision it was written against. */
 int xm_version(void);
 const char *xm_last_error(void);
 /* Device memory for hosts that have no device-array type of their own (MATLAB's gpuArray is CUDA-only: on an
@@ -678,6 +678,11 @@ int xm_mnrval(const double *b, const float *x, int p, int n, int k, const int *o
 int xm_roc(const float *scores, int n, int E, const int *cls, const int *offsets, const int *rows, int nnz, int G,
            double *auc, long long *area, int *counts, int *status, int *perm_out, int *tp_out, void *stream);
 int xm_roc_launches(void);
+/* xm_roc_geometry (ABI 126): host only, the constants of the kernels; a NULL pointer is skipped.  tile: entries of a
+ * problem one workgroup owns; wave_span: consecutive entries of a tile one wave ranks and scans (tile / wave_span waves);
+ * threads: the workgroup size, which is also the number of threads that share the per-call set loop and the per-problem
+ * tile scan; hist_classes_max: the largest E xm_label_hist takes. */
+int xm_roc_geometry(int *tile, int *wave_span, int *threads, int *hist_classes_max);
 /* histcounts(labels, 0.5:E+0.5) of [~, labels] = max(x, [], 2): the first maximum per sample (as xm_max_label) counted
  * into E 64-bit integer bins, one launch, exact in any order.  x holds N samples of E logits: sample_major = 0 is
  * E x N (a sample's logits contiguous, the 1 x 1 x E x N layout of xm_max_label), sample_major = 1 is N x E column-major

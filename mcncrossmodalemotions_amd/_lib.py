@@ -130,6 +130,7 @@ SIGNATURES = {
     "xm_mnrval": [c_fp, c_fp, _i, _i, _i, c_fp, c_fp, _i, _i, c_fp, c_fp, c_fp, c_fp, _vp],
     "xm_roc": [c_fp, _i, _i, c_fp, c_fp, c_fp, _i, _i, c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, _vp],
     "xm_roc_launches": [],
+    "xm_roc_geometry": [C.POINTER(C.c_int)] * 4,
     "xm_label_hist": [c_fp, _i, _i, _i, c_fp, _vp],
     "xm_group_rows": [c_fp, _i, c_fp, _i, _i, c_fp, c_fp, c_fp, _vp],
     "xm_gather_rows": [c_fp, _i, _i, _i, c_fp, _i, c_fp, _vp],

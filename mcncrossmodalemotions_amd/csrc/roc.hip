@@ -28,6 +28,7 @@ constexpr int kRocWaveSpan = 64 * kRocItems;              // consecutive entries
 constexpr int kTile = kRocThreads * kRocItems;            // 2048
 constexpr unsigned kNegInfKey = 0xFF800000u;              // the key of -Inf: larger than the key of every score > -Inf
 constexpr int kRocNanBit = 1, kRocBadBit = 2;             // raw per-problem flags, turned into XM_ROC_* by the last kernel
+constexpr int kHistClassesMax = 4096;                     // xm_label_hist: one LDS counter per class, 16 KiB at the limit
 
 // descending order of the scores = ascending order of the keys; -0.0 and +0.0 share a key
 __device__ __forceinline__ unsigned roc_key(float s) {
@@ -470,6 +471,14 @@ extern "C" {
 
 int xm_roc_launches(void) { return 18; }
 
+int xm_roc_geometry(int *tile, int *wave_span, int *threads, int *hist_classes_max) {
+  if (tile) *tile = kTile;
+  if (wave_span) *wave_span = kRocWaveSpan;
+  if (threads) *threads = kRocThreads;
+  if (hist_classes_max) *hist_classes_max = kHistClassesMax;
+  return XM_OK;
+}
+
 int xm_roc(const float *scores, int n, int E, const int *cls, const int *offsets, const int *rows, int nnz, int G,
            double *auc, long long *area, int *counts, int *status, int *perm_out, int *tp_out, void *stream) {
   if (E < 1 || G < 0 || n < 1 || nnz < 0)
@@ -519,7 +528,7 @@ int xm_roc(const float *scores, int n, int E, const int *cls, const int *offsets
 
 int xm_label_hist(const float *x, int N, int E, int sample_major, long long *bins, void *stream) {
   if (N < 0 || E < 1) return fail(XM_EINVAL, "label_hist: need N >= 0 and E >= 1 (got N=%d E=%d)", N, E);
-  if (E > 4096) return fail(XM_ENOTSUP, "label_hist: more than 4096 classes");
+  if (E > kHistClassesMax) return fail(XM_ENOTSUP, "label_hist: more than %d classes", kHistClassesMax);
   if (N == 0) return XM_OK;
   if (!x || !bins) return fail(XM_EINVAL, "label_hist: NULL tensor");
   const int blocks = (int)(((size_t)N + 255) / 256 < 2048 ? ((size_t)N + 255) / 256 : 2048);

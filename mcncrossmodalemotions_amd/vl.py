@@ -1225,6 +1225,13 @@ def roc_sets(sets, n, device):
     return _csr(sets, device)
 
 
+def roc_geometry():
+    """(tile, wave_span, threads, hist_classes_max) of the xm_roc / xm_label_hist kernels (xm_roc_geometry; no device call)"""
+    v = [C.c_int(0) for _ in range(4)]
+    _lib.check(_L().xm_roc_geometry(*[C.byref(t) for t in v]))
+    return tuple(int(t.value) for t in v)
+
+
 def roc(scores, cls, sets, want_curve=False):
     """[~, ~, info] = vl_roc(labels, scores) (vlfeat, default options; student_stats.m:109-115) for every index set of
     `sets` (1-based rows, or the tuple roc_sets() made of them) and every column of `scores`, one call of xm_roc.

@@ -90,6 +90,25 @@ def test_roc_abi_declared_typed_and_exported():
     assert L.xm_roc_launches() > 0
 
 
+def test_roc_geometry_is_host_only_and_matches_the_case_table():
+    """xm_roc_geometry (ABI 126): declared, typed, exported, NULL pointers skipped; its numbers are the literals the edge
+    cases of tests/roc_cases.py stand on, and the class limit is the one xm_label_hist enforces"""
+    import roc_cases
+    from mcncrossmodalemotions_amd import _lib, vl
+    hdr = open(os.path.join(ROOT, "include", "xmodal.h")).read()
+    L = _lib.load()
+    assert L.xm_version() >= 126 and "126 = + xm_roc_geometry" in hdr
+    proto = re.search(r"\bint xm_roc_geometry\(([^;]*)\);", hdr).group(1)
+    assert len(proto.split(",")) == len(_lib.SIGNATURES["xm_roc_geometry"]) == 4
+    assert L.xm_roc_geometry.argtypes == _lib.SIGNATURES["xm_roc_geometry"]
+    assert L.xm_roc_geometry(None, None, None, None) == 0
+    tile, span, threads, classes = vl.roc_geometry()
+    assert (tile, span, threads, classes) == roc_cases.GEOMETRY
+    assert tile == threads * (span // 64) and tile % span == 0
+    assert L.xm_label_hist(None, 0, classes, 0, None, None) == 0
+    assert L.xm_label_hist(None, 0, classes + 1, 0, None, None) == 5 and b"more than %d classes" % classes in L.xm_last_error()
+
+
 def test_roc_arguments_are_rejected_without_a_device():
     from mcncrossmodalemotions_amd import _lib
     L = _lib.load()
